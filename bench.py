@@ -367,6 +367,44 @@ def lib_md5():
     return hashlib.md5(open(lib.LIBPATH, "rb").read()).hexdigest()[:12]
 
 
+DUMP_SAMPLE = 1 << 21            # elements of the seeded parameter / gradient samples --dump-outputs writes (8 MB each in float32)
+DUMP_LIMIT = 64 << 20            # bytes --dump-outputs may write in all
+
+
+def snapshot_outputs(loss, loss_dict, store):
+    """What the timed path computed in its last step, copied to the host: the total loss, every loss-dict entry, and a fixed sample
+    (numpy default_rng(0), sorted element indices over the trainable parameters in the engine's flat order) of the parameters after the
+    optimizer update and of the gradients the step produced.  Called right after the timed region, before anything else runs on the
+    model: the captured step's loss buffers and the flat parameter / gradient buffers are overwritten by the next step."""
+    import numpy as np
+    out = {"loss": loss.detach().double().cpu().numpy()}
+    for k, v in loss_dict.items():
+        assert k not in out, k
+        out[k] = v.detach().double().cpu().numpy() if torch.is_tensor(v) else np.asarray(v, dtype=np.float64)
+    # the flat buffers pad every parameter to an alignment: sample element positions of the parameters, then map them to flat offsets
+    numels = np.array([p.numel() for p in store.params], dtype=np.int64)
+    starts = np.array([store.offsets[n] for n in store.names], dtype=np.int64)
+    total = int(numels.sum())
+    pos = np.sort(np.random.default_rng(0).choice(total, size=min(DUMP_SAMPLE, total), replace=False))
+    which = np.searchsorted(np.cumsum(numels), pos, side="right")
+    flat_idx = torch.from_numpy(starts[which] + pos - (np.cumsum(numels) - numels)[which]).to(store.flat.device)
+    out["parameters_sample"] = store.flat[flat_idx].cpu().numpy()
+    out["gradients_sample"] = store.gflat[flat_idx].cpu().numpy()
+    return out
+
+
+def dump_outputs(outputs, path):
+    """``outputs`` ({name: float32 / float64 array}) -> path/<name>.npy"""
+    import numpy as np
+    size = sum(a.nbytes for a in outputs.values())
+    assert size <= DUMP_LIMIT, "--dump-outputs: %d bytes > %d" % (size, DUMP_LIMIT)
+    os.makedirs(path, exist_ok=True)
+    for name, a in outputs.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(path, name + ".npy"), a)
+    print("bench.py: wrote %d arrays (%.1f MB) of the last timed step to %s" % (len(outputs), size / 1e6, path), file=sys.stderr, flush=True)
+
+
 def spawn_ranks(n):
     """``python bench.py --gpus N`` without a launcher (WORLD_SIZE / RANK unset): start the N ranks here, one process per GPU, the way
     the reference's ``pipelines/launch.py:20-50`` spawns its own workers -- the same command line re-executed with the torchrun environment
@@ -420,7 +458,11 @@ def main():
     ap.add_argument("--with-input-pipeline", action="store_true", help="after the headline measurement, time the same steps again with every "
                     "batch fed as uint8 frames through input_pipeline.ClipBatch.to(device) (H2D + resize + flip/crop/jitter/normalise/collate "
                     "on a side stream, double-buffered) and report both figures")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps write what the last of them computed to DIR/<name>.npy: "
+                    "the loss and its terms, and a fixed seeded sample of the updated parameters and of the step's gradients (rank 0)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.gpus > 1 and "RANK" not in os.environ and int(os.environ.get("WORLD_SIZE", "1")) == 1:
         raise SystemExit(spawn_ranks(args.gpus))      # the driver's `python bench.py --gpus N`: no launcher needed
 
@@ -524,9 +566,10 @@ def main():
     t0 = time.perf_counter()
     loss = None
     for _ in range(args.steps):
-        loss, _ = step()
+        loss, loss_dict = step()
     fence()
     dt = time.perf_counter() - t0
+    outputs = snapshot_outputs(loss, loss_dict, model.engine()[0]) if args.dump_outputs and rank == 0 else None
     # HIP-event timing of the dominant kernel family: the same launches, same stream, same inputs, issued eagerly right after the
     # timed region (launches replayed from a hipGraph cannot be bracketed by events individually)
     timer = LaunchTimer(only=dominant) if dominant else None
@@ -577,6 +620,8 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t)
     model.engine()[0].check_coop()            # a timed-out barrier of the cooperative decoder launch would have invalidated the steps
+    if outputs is not None:
+        dump_outputs(outputs, args.dump_outputs)
     ms = 1e3 * dt / args.steps
     total_clips = args.batch * world * args.steps
     headline = args.config == "TubeR_CSN152_AVA21.yaml" and hw == (256, 340)
