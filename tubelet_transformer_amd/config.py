@@ -140,7 +140,8 @@ def get_cfg_defaults():
     cfg.USE_LOCATION = False
     cfg.TRAIN = CfgNode(dict(
         START_EPOCH=0, EPOCH_NUM=20, BATCH_SIZE=2, LR=1e-4, MIN_LR=1e-5, LR_BACKBONE=1e-5,
-        W_DECAY=1e-4, LR_POLICY="step", AUX_LOSS=True), new_allowed=True)
+        W_DECAY=1e-4, LR_POLICY="step", AUX_LOSS=True,
+        ACCUM_STEPS=1), new_allowed=True)      # micro-batches per optimizer step (accum.py; not a reference key)
     cfg.VAL = CfgNode(dict(FREQ=2, BATCH_SIZE=1), new_allowed=True)
     cfg.DATA = CfgNode(dict(
         DATASET_NAME="ava", NUM_CLASSES=80, IMG_SIZE=256, TEMP_LEN=32, FRAME_RATE=2), new_allowed=True)

@@ -258,6 +258,13 @@ DOC = {
                                  "non-finite loss (video_action_recognition.py:195-198).",
     "tuber_adamw_segment": "AdamW update (torch.optim.AdamW semantics: decoupled decay, bias correction) of one contiguous flat segment with the "
                            "clip coefficient applied to the gradient on the fly (video_action_recognition.py:154; groups train_tuber_ava.py:41-58).",
+    "tuber_grad_accum": "gradient accumulation over m micro-batches (DistributedDataParallel's mean over ranks reproduced on fewer GPUs: the mean of "
+                        "independent per-rank backward passes, utils/model_utils.py:47-49) over a DEVICE table of nwin [begin, end) int64 windows of the flat "
+                        "fp32 gradient buffer, in ONE launch: mode 0 acc = g, mode 1 acc += g, mode 2 g = (acc + g) * scale (scale_dev[0] when given). "
+                        "Fixed order: sequential fp32 sum, then one multiply. g and acc 16-byte aligned.",
+    "tuber_bn_stats_copy": "snapshot (restore = 0: arena <- buffers) or restore (restore = 1: buffers <- arena) of BatchNorm running statistics "
+                           "(running_mean, running_var, num_batches_tracked of nn.BatchNorm3d, models/backbones/ir_CSN_152.py:46,56,64,154) in ONE launch over a "
+                           "DEVICE table of nrows {address, arena offset in 32-bit words, words} int64 rows; max_words = the largest row.",
     "tuber_scale_f32": "x *= coef: gradient averaging after the RCCL all-reduce (DistributedDataParallel's mean, utils/model_utils.py:47-49).",
     "tuber_criterion_cost": "Hungarian matching cost C = w_bbox*L1 - w_giou*GIoU - w_class*p of every decoder layer at once, [L,B,Q,Tmax] fp32 "
                             "(HungarianMatcher.forward, models/detr/matcher.py:61-76 / matcher_ucf.py:61-78; generalized_box_iou utils/box_ops.py:41-65).",

@@ -155,6 +155,7 @@ class FlatGradReducer:
         self.compress = bool(os.environ.get("TUBER_DDP_BF16")) if compress is None else bool(compress)
         self.stage = None                     # bf16 staging buffer of the compressed path (allocated on first use)
         self.dry = False                      # hooks fire but nothing is sent (capture warm-up)
+        self.pre_reduce = None                # fn(windows) run on the current stream before a window is handed to the transport (accum.py)
         self._joined = True
         self.handles = []
         self.issued = 0                       # elements handed to the transport since begin() (tests / logging)
@@ -230,11 +231,14 @@ class FlatGradReducer:
     def reduce(self, lo, hi, edge=True):
         """all-reduce (and average) the trainable part of gflat[lo:hi); returns immediately.  ``edge``: order the transport's stream behind the
         current stream with an event first (False: the caller has already ordered it -- wait_for(), or an earlier window of the same issue point)."""
-        if hi <= lo or (self.world <= 1 and self.comm is None):
+        if hi <= lo:
             return
         wins = [(max(a, lo), min(b, hi)) for a, b in self.ranges]
         wins = [(a, b) for a, b in wins if b > a]
-        if not wins or self.dry:
+        if wins and self.pre_reduce is not None:
+            self.pre_reduce(wins)              # accum.py: the last micro-batch folds these windows on the backward stream first ...
+            edge = True                        # ... so the transport must wait for THIS point: a flag wait or an earlier window's event precedes the fold
+        if not wins or self.dry or (self.world <= 1 and self.comm is None):
             return
         st = self.store
         if self.comm is None:

@@ -53,33 +53,57 @@ def build_optimizer(model, cfg):
     return FusedClipAdamW(build_param_groups(model, cfg), lr=T.LR, weight_decay=T.W_DECAY, model=model)
 
 
-def train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=0, cfg=None):
+def train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=0, cfg=None, accum=None, last=False):
     """One eager optimisation step.  ``optimizer``: a ``FusedClipAdamW``, or the object the reference script builds --
     ``torch.optim.AdamW(param_dicts, lr=..., weight_decay=...)`` (train_tuber_ava.py:58), adopted transparently (optim.adopt: shared
     ``param_groups``, state exposed as views) -- or any other ``torch.optim.Optimizer``, driven by the reference's literal sequence
     ``clip_grad_norm_`` + ``optimizer.step()`` on the gradient views (video_action_recognition.py:152-154).
+    ``accum``: an accum.GradAccumulator -- this call is one micro-batch of its group (``last``: it ends the group early); only the
+    group's last micro-batch folds the mean gradient and steps the optimizer, clipping applies to the mean.
     Returns (total loss tensor, loss dict) -- all on the device, nothing synchronised."""
     store, _ = model.engine()
     reducer = getattr(store, "reducer", None)
     fused = adopt(optimizer, model)
+    role = accum.begin_micro(last) if accum is not None else None
     outputs = model(samples)
+    if role is not None:
+        accum.after_forward(role)          # BatchNorm running statistics: only micro-batch 0 of a group updates them
     loss_dict = criterion(outputs, targets)
     weight_dict = criterion.weight_dict
     if cfg is not None and epoch > cfg.CONFIG.LOSS_COFS.WEIGHT_CHANGE:          # video_action_recognition.py:145-146
         weight_dict["loss_ce"] = cfg.CONFIG.LOSS_COFS.LOSS_CHANGE_COF
     losses = criterion.weighted_total(loss_dict, weight_dict)
     store.zero_grad()                      # optimizer.zero_grad() of a stock optimizer would drop the views into the flat buffer
+    if role in ("first", "middle"):
+        store.reducer = None               # no collective before the group's last micro-batch (DDP's no_sync)
+        try:
+            losses.backward()
+        finally:
+            store.reducer = reducer
+        accum.after_backward(role)
+        accum.end_micro()
+        return losses.detach(), loss_dict
     if reducer is not None:
         reducer.begin()
-    losses.backward()
-    if reducer is not None:
-        reducer.finish()
+        if role == "last":
+            reducer.pre_reduce = accum.fold    # each window folded right before its all-reduce is issued
+    try:
+        losses.backward()
+        if reducer is not None:
+            reducer.finish()
+    finally:
+        if reducer is not None:
+            reducer.pre_reduce = None
+    if role == "last" and reducer is None:
+        accum.fold()
     if fused is not None:
         fused.step(max_norm=max_norm if max_norm and max_norm > 0 else None)
     else:
         if max_norm and max_norm > 0:
             torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
         optimizer.step()
+    if accum is not None:
+        accum.end_micro()
     return losses.detach(), loss_dict
 
 
@@ -87,10 +111,11 @@ class _Snapshot:
     """Everything a training step mutates: parameters, BatchNorm buffers, Adam moments + step count, dropout seed.  The captured
     step needs eager warm-up passes (workspace sizing, reduce tables); they must not count as optimisation steps."""
 
-    def __init__(self, model, store, opt):
+    def __init__(self, model, store, opt, extra=()):
         self.items = [(store.flat, store.flat.clone()), (store.seed, store.seed.clone()), (opt.exp_avg, opt.exp_avg.clone()),
                       (opt.exp_avg_sq, opt.exp_avg_sq.clone()), (opt.t_dev, opt.t_dev.clone())]
         self.items += [(b, b.clone()) for b in model.buffers()]
+        self.items += [(t, t.clone()) for t in extra if t is not None]       # gradient accumulation: acc, BatchNorm snapshot, fold scale
 
     def restore(self):
         with torch.no_grad():
@@ -122,9 +147,14 @@ class GraphedTrainStep:
     graph A2 (layer2 / layer1 / stem backward) -> all-reduce of the remainder -> graph B2 (clip + AdamW), which waits for the side
     stream by event.  ``TUBER_DDP_CUTS=3`` restores the single cut of rounds 2-5 (97 % under layer2 / layer1 / stem); with
     ``TUBER_RCCL_IN_GRAPH=1`` the collectives are captured into ONE graph as a forked branch instead.
+
+    ``accum_steps = k > 1`` (accum.py): every call is one micro-batch; its role in the group is part of the graph key.  "first":
+    zero_grad, forward, BatchNorm snapshot, backward, acc = g; "middle": forward, BatchNorm restore, backward, acc += g (no collective);
+    "last": forward, BatchNorm restore, backward, g = (acc + g) / m -- per window right before its all-reduce when a reducer is attached --
+    then clip + AdamW + the bf16 refresh of the next forward.  ``last=True`` ends a group early (1/m is read from the device).
     """
 
-    def __init__(self, model, criterion, optimizer, max_norm, tmax=16, max_graphs=4):
+    def __init__(self, model, criterion, optimizer, max_norm, tmax=16, max_graphs=4, accum_steps=1):
         fused = adopt(optimizer, model)
         if fused is None:
             raise TypeError("GraphedTrainStep needs AdamW (FusedClipAdamW or a stock torch.optim.AdamW); got %s" % type(optimizer).__name__)
@@ -132,9 +162,14 @@ class GraphedTrainStep:
         self.max_norm, self.tmax, self.max_graphs = max_norm, tmax, max_graphs
         self.graphs = collections.OrderedDict()
         self.part_marks = None
+        self.accum = None
+        if int(accum_steps) != 1:
+            from .accum import GradAccumulator
+            self.accum = GradAccumulator(model.engine()[0], accum_steps)
+            self.max_graphs = 4 * max_graphs          # per clip shape: the first / middle / last graphs and the group-of-one graph
 
     # -- capture -------------------------------------------------------------------------------------------------------------
-    def _capture(self, clips, mask, targets, tmax):
+    def _capture(self, clips, mask, targets, tmax, role=None):
         """capture with the cyclic garbage collector parked: a collection that runs INSIDE a stream capture may destroy the hipGraph /
         device tensors of an earlier step object (reference cycles through autograd nodes keep them until the collector runs), and the
         runtime aborts the process on such a call while a capture is open (seen in the GPU suite: "Fatal Python error: Aborted",
@@ -144,18 +179,21 @@ class GraphedTrainStep:
         was_enabled = gc.isenabled()
         gc.disable()
         try:
-            return self._capture_impl(clips, mask, targets, tmax)
+            return self._capture_impl(clips, mask, targets, tmax, role)
         finally:
             if was_enabled:
                 gc.enable()
 
-    def _capture_impl(self, clips, mask, targets, tmax):
+    def _capture_impl(self, clips, mask, targets, tmax, role=None):
         from .criterion import PaddedTargets
         from .misc import NestedTensor
         model, crit, opt = self.model, self.criterion, self.optimizer
         store, _ = model.engine()
         dev = store.device
-        red = getattr(store, "reducer", None)
+        acc = self.accum
+        keep = getattr(store, "reducer", None)
+        red = None if role in ("first", "middle") else keep       # no collective before a group's last micro-batch
+        stepping = role not in ("first", "middle")
         ddp = red is not None                        # N > 1 ranks (or a forced one-rank communicator): gradients are all-reduced
         in_graph = ddp and red.comm is not None and bool(os.environ.get("TUBER_RCCL_IN_GRAPH"))
         g = type("Captured", (), {})()
@@ -167,6 +205,8 @@ class GraphedTrainStep:
 
         def head():
             outputs = model(NestedTensor(g.clips, g.mask))
+            if role is not None:
+                acc.after_forward(role)              # BatchNorm running statistics: snapshot (first) / restore (middle, last)
             logits, logits_b, boxes = crit.stacked(outputs)
             g.logits_s, g.boxes_s = crit.select(logits, boxes, g.pt)
             g.logits_b = logits_b
@@ -181,13 +221,17 @@ class GraphedTrainStep:
             g.loss = crit.weighted_total(g.loss_dict)
             opt.zero_grad()
             g.loss.backward()
+            if role in ("first", "middle"):
+                acc.after_backward(role)
+            elif role == "last" and not ddp:
+                acc.fold()                           # (with a reducer: per window, right before its all-reduce -- pre_reduce)
             if step:
                 opt.step(max_norm=max_norm)
 
         # eager warm-up with the reducer detached (its hooks must not fire inside a stream capture, and it flushes the deferred
         # reductions per bottleneck where the captured backward flushes twice): sizes every workspace, builds the reduce tables and
         # the loss-weight / hyper-parameter device tables.  Rolled back afterwards -- a capture is not an optimisation step.
-        snap = _Snapshot(model, store, opt)
+        snap = _Snapshot(model, store, opt, () if acc is None else (acc.acc, acc.bn_arena, acc.scale_dev))
         store.reducer = red if in_graph else None
         split = ddp and not in_graph and not os.environ.get("TUBER_NO_SPLIT_GRAPH")
         split = split or bool(os.environ.get("TUBER_FORCE_SPLIT_GRAPH"))
@@ -197,6 +241,8 @@ class GraphedTrainStep:
         runner.cut_stages = tuple(int(x) for x in os.environ.get("TUBER_DDP_CUTS", "4,3").split(",") if x) if split else (3,)
         if in_graph:
             red.dry = True                           # hooks fire (same deferred-reduce flush points as the capture), nothing is sent
+            if role == "last":
+                red.pre_reduce = acc.fold            # captured with the collectives: the fold of each window goes in front of it
         try:
             for _ in range(2):
                 head()
@@ -204,7 +250,7 @@ class GraphedTrainStep:
                 g.match = crit.assign(g.cost, g.pt)
                 if in_graph:
                     red.begin()
-                tail(not in_graph)
+                tail(not in_graph and stepping)
                 if in_graph:
                     red.finish()
                     opt.step(max_norm=max_norm)
@@ -227,6 +273,7 @@ class GraphedTrainStep:
                 red.begin()
                 tail(False)
                 red.finish()
+                red.pre_reduce = None
                 opt.step(max_norm=max_norm)
         elif split and g.on_device:
             # DDP: the graph is CUT inside the backward pass where a gradient window becomes final, so that window's RCCL all-reduce runs
@@ -257,7 +304,7 @@ class GraphedTrainStep:
                 try:
                     head()
                     g.match = crit.assign(g.cost, g.pt)
-                    tail(own_step)
+                    tail(own_step and stepping)
                 finally:
                     runner.split_hook = None
                 if len(cut) in flag_edges and not own_step and cut:  # (no cut -- a frozen body: one event-ordered window after the graph)
@@ -271,7 +318,7 @@ class GraphedTrainStep:
             with torch.cuda.graph(g.A):
                 head()
                 g.match = crit.assign(g.cost, g.pt)
-                tail(own_step)
+                tail(own_step and stepping)
         else:
             # assignment problems beyond the device solver's 128 x 128 bound: graph A / host tuber_lsap / graph B1
             with torch.cuda.graph(g.A):
@@ -282,8 +329,8 @@ class GraphedTrainStep:
             g.cost_host = torch.empty(g.cost.shape, dtype=torch.float32).pin_memory()
             g.B1 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g.B1, pool=g.A.pool()):
-                tail(own_step)
-        store.reducer = red
+                tail(own_step and stepping)
+        store.reducer = keep
         if not own_step:
             g.B2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g.B2, pool=g.A.pool()):
@@ -301,9 +348,12 @@ class GraphedTrainStep:
         return None
 
     # -- replay --------------------------------------------------------------------------------------------------------------
-    def __call__(self, samples, targets):
-        """``samples``: NestedTensor (clips + padding mask) or a plain [B,3,T,H,W] tensor (no padding)."""
+    def __call__(self, samples, targets, last=False):
+        """``samples``: NestedTensor (clips + padding mask) or a plain [B,3,T,H,W] tensor (no padding).  ``last`` (accum_steps > 1): this
+        micro-batch ends its group whatever its index."""
         store, _ = self.model.engine()
+        acc = self.accum
+        role = acc.begin_micro(last) if acc is not None else None
         if hasattr(samples, "tensors"):
             clips, mask = samples.tensors, samples.mask
         else:
@@ -320,12 +370,14 @@ class GraphedTrainStep:
                 break
         # (a captured step bakes the decoder's launch form in: after a timed-out cooperative launch -- engine.coop_failed -- a new one is captured)
         key = (tuple(clips.shape), store.trainable_signature(), self.criterion.training, tmax, store.coop_off)
+        if role is not None:
+            key = key + (role,)
         g = self.graphs.get(key)
         if g is None:
             while len(self.graphs) >= self.max_graphs:            # LRU: a graph holds its own memory pool
                 self.graphs.popitem(last=False)
             try:
-                g = self._capture(clips.to(store.device, torch.float32), mask.to(store.device), targets, tmax)
+                g = self._capture(clips.to(store.device, torch.float32), mask.to(store.device), targets, tmax, role)
             except (RuntimeError, ValueError) as e:
                 raise CaptureFailed("%s: %s" % (type(e).__name__, e)) from e
             self.graphs[key] = g
@@ -339,12 +391,15 @@ class GraphedTrainStep:
             g.mask.copy_(mask, non_blocking=True)
         g.pt.refill(targets)
         self.optimizer.sync_hyper()
-        self.optimizer.mark_stepped()
+        if role in (None, "last"):
+            self.optimizer.mark_stepped()
         self.criterion.sync_weights(store.device)
         sizes = g.pt.sizes
         red = g.red
         if red is not None and not g.in_graph:
             red.begin()
+            if role == "last":
+                red.pre_reduce = acc.fold                     # each cut's windows folded on this stream right before their all-reduce
         marks = self.part_marks                               # bench.py: HIP-event stamps between the graph parts of the measured steps
         if marks is not None:
             marks.append([])
@@ -389,10 +444,13 @@ class GraphedTrainStep:
             red.reduce(0, store.total)
         if red is not None and not g.in_graph:
             red.finish(rest=False)                            # the optimizer graph waits for the side stream (events only)
+            red.pre_reduce = None
         if g.B2 is not None:
             g.B2.replay()
             if marks is not None:
                 self._mark()
+        if acc is not None:
+            acc.end_micro()
         return g.loss, g.loss_dict
 
     def _mark(self):
@@ -434,18 +492,37 @@ class _DeviceMeters:
         return dict(zip(self.KEYS, host))
 
 
-def _graphed_for(model, criterion, optimizer, max_norm):
-    """the cached GraphedTrainStep of (model, criterion, optimizer, max_norm), or None when the optimizer is not AdamW"""
+def _graphed_for(model, criterion, optimizer, max_norm, accum_steps=1):
+    """the cached GraphedTrainStep of (model, criterion, optimizer, max_norm[, accum_steps]), or None when the optimizer is not AdamW"""
     fused = adopt(optimizer, model)
     if fused is None:
         return None
     cache = model.__dict__.setdefault("_tuber_graphed", {})
     key = (id(criterion), id(fused), float(max_norm or 0.0))
+    if accum_steps != 1:
+        key = key + (int(accum_steps),)
     g = cache.get(key)
     if g is None:
         cache.clear()                       # one live training configuration per model: a graph owns its memory pool
-        g = cache[key] = GraphedTrainStep(model, criterion, fused, max_norm)
+        g = cache[key] = GraphedTrainStep(model, criterion, fused, max_norm, accum_steps=accum_steps)
     return g
+
+
+def _accum_for(model, k):
+    """the cached accum.GradAccumulator of the eager step for k micro-batches per optimizer step"""
+    from .accum import GradAccumulator
+    a = model.__dict__.get("_tuber_accum")
+    if a is None or a.k != k or a.store is not model.engine()[0]:
+        a = model.__dict__["_tuber_accum"] = GradAccumulator(model.engine()[0], k)
+    return a
+
+
+def accum_steps(cfg):
+    """CONFIG.TRAIN.ACCUM_STEPS (micro-batches per optimizer step; 1 = off), validated"""
+    k = int(getattr(cfg.CONFIG.TRAIN, "ACCUM_STEPS", 1))
+    if k < 1:
+        raise ValueError("CONFIG.TRAIN.ACCUM_STEPS must be >= 1, got %d" % k)
+    return k
 
 
 def train_tuber_detection(cfg, model, criterion, data_loader, optimizer, epoch, max_norm, lr_scheduler=None, writer=None,
@@ -459,8 +536,14 @@ def train_tuber_detection(cfg, model, criterion, data_loader, optimizer, epoch, 
     the optimizer is not AdamW).  The six scalars the reference logs -- ``train/{class_error,totall_loss,loss_bbox,loss_giou,
     loss_ce,loss_ce_b}`` (:215-220), running averages weighted by ``len(targets)`` -- are accumulated on the device for EVERY
     iteration and read back every ``print_freq`` iterations, so the GPU queue stays full; a non-finite loss stops training like
-    the reference (:195-198).  ``epoch > LOSS_COFS.WEIGHT_CHANGE`` switches ``loss_ce``'s weight (:145-146)."""
+    the reference (:195-198).  ``epoch > LOSS_COFS.WEIGHT_CHANGE`` switches ``loss_ce``'s weight (:145-146).
+
+    ``CONFIG.TRAIN.ACCUM_STEPS = k > 1`` (accum.py): the optimizer steps every k batches on the mean gradient of the group -- an
+    8-rank x 2-clip step on one GPU with k = 8 -- and once more on the trailing partial group (1/m) at the end of the epoch; the
+    cosine ``lr_scheduler.step_update`` is called per optimizer step with the optimizer-step index.  Meters and the non-finite check
+    stay per batch."""
     import time
+    k = accum_steps(cfg)
     model.train()
     criterion.train()
     dev = next(model.parameters()).device
@@ -468,7 +551,7 @@ def train_tuber_detection(cfg, model, criterion, data_loader, optimizer, epoch, 
     if epoch > cfg.CONFIG.LOSS_COFS.WEIGHT_CHANGE:
         criterion.weight_dict["loss_ce"] = cfg.CONFIG.LOSS_COFS.LOSS_CHANGE_COF
     if graphed is None and not ab.on("eager_step"):
-        graphed = _graphed_for(model, criterion, optimizer, max_norm)
+        graphed = _graphed_for(model, criterion, optimizer, max_norm, accum_steps=k)
     elif graphed is False or graphed is None:
         graphed = None
     meters = _DeviceMeters(dev)
@@ -479,13 +562,31 @@ def train_tuber_detection(cfg, model, criterion, data_loader, optimizer, epoch, 
     import torch.distributed as _dist
     world = _dist.get_world_size() if _dist.is_available() and _dist.is_initialized() else 1
     n_iter = len(data_loader)
+    if k > 1:
+        from .accum import steps_per_epoch
+        n_steps = steps_per_epoch(n_iter, k)
+        if graphed is not None and getattr(graphed, "accum", None) is None:
+            raise ValueError("ACCUM_STEPS = %d needs a GraphedTrainStep built with accum_steps=%d" % (k, k))
+        accum = graphed.accum if graphed is not None else _accum_for(model, k)
+        if accum.k != k:
+            raise ValueError("ACCUM_STEPS = %d, but the step accumulates over %d micro-batches" % (k, accum.k))
+        opt_step = accum.steps
+        acc_kw = dict(accum=accum, last=False)
+    else:
+        n_steps, accum, acc_kw = n_iter, None, {}
     for idx, data in enumerate(data_loader):
         samples, targets = data[0], data[1]
         samples = samples.to(dev)            # reference :121; for an input_pipeline.ClipBatch this IS the HIP pre-pass (uint8 frames -> fp32 batch)
         targets = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in t.items() if k != "image_id"} for t in targets]
+        if accum is not None:
+            acc_kw["last"] = idx + 1 == n_iter                    # the trailing partial group steps at the end of the epoch
+            steps_before = accum.steps
         if graphed is not None:
             try:
-                loss, loss_dict = graphed(samples, targets)       # NestedTensor: clips AND padding mask go to the captured buffers
+                if accum is not None:
+                    loss, loss_dict = graphed(samples, targets, last=acc_kw["last"])
+                else:
+                    loss, loss_dict = graphed(samples, targets)   # NestedTensor: clips AND padding mask go to the captured buffers
             except CaptureFailed as e:                            # a failed capture must not end the epoch
                 if getattr(model.engine()[0], "reducer", None) is not None:
                     raise                                         # N > 1: every rank must stay on the same collective sequence
@@ -493,11 +594,16 @@ def train_tuber_detection(cfg, model, criterion, data_loader, optimizer, epoch, 
                 print("[tuber] hipGraph step unavailable (%s: %s); continuing with the eager step" % (type(e).__name__, e), file=sys.stderr, flush=True)
                 graphed = None
                 model.__dict__.pop("_tuber_graphed", None)
-                loss, loss_dict = train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=epoch, cfg=cfg)
+                loss, loss_dict = train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=epoch, cfg=cfg, **acc_kw)
         else:
-            loss, loss_dict = train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=epoch, cfg=cfg)
-        if lr_scheduler is not None and cfg.CONFIG.TRAIN.LR_POLICY == "cosine":
-            lr_scheduler.step_update(epoch * n_iter + idx)
+            loss, loss_dict = train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=epoch, cfg=cfg, **acc_kw)
+        if accum is None:
+            stepped, opt_idx = True, idx
+        else:
+            stepped = accum.steps != steps_before
+            opt_idx = accum.steps - 1 - opt_step
+        if stepped and lr_scheduler is not None and cfg.CONFIG.TRAIN.LR_POLICY == "cosine":
+            lr_scheduler.step_update(epoch * n_steps + opt_idx)
         if rank == 0:
             meters.update(loss, loss_dict, len(targets))
         # non-finite loss (reference :195-198 checks the rank-reduced loss on every rank, every iteration, BEFORE optimizer.step()): here the
