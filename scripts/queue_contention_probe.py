@@ -1,7 +1,7 @@
 """Round 6: what does a SECOND HIP stream cost a launch-bound captured graph on this runtime?
 
 The one-rank forced-DDP line is +0.55 - 0.8 ms although the one-rank in-place ncclAllReduce does nothing on the device (5 us of stream
-time) -- and the same with the call skipped, with device-scope events, with fence-free events (scripts/r06_ddp_probe.sh, r06_ddp_edge.sh).
+time) -- and the same with the call skipped, with device-scope events, with fence-free events (profiles/r06_ddp_edges.txt sections 2 - 3).
 What is left is the pair of stream edges itself.  This probe replays a captured graph of N tiny dependent kernels on stream `main` and
 times the replay (mean over rounds, GPU fully queued) for:
   alone            nothing else

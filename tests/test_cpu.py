@@ -283,6 +283,44 @@ def test_flat_gradient_reducer_gloo_world2():
     assert np.allclose(g0, mean, atol=1e-6) and np.allclose(g1, mean, atol=1e-6)   # every slice reduced exactly once
 
 
+@pytest.mark.parametrize("cuts,body_begin,total", [
+    ([700], 100, 1000),                 # one cut
+    ([700, 400], 100, 1000),            # two cuts (the default TUBER_DDP_CUTS=4,3)
+    ([900, 600, 300], 100, 1000),       # three cuts
+    ([700, 400], 0, 1000),              # nothing laid out in front of the body
+    ([700, 400], 400, 1000),            # the body ends at the last cut: nothing pending after it
+])
+def test_cut_windows_cover_the_flat_buffer_once_in_issue_order(cuts, body_begin, total):
+    from tubelet_transformer_amd.ddp import cut_windows
+    w = cut_windows(cuts, body_begin, total)
+    assert len(w) == len(cuts) + 1
+    assert w[0] == [(cuts[0], total), (0, body_begin)]
+    assert w[1:-1] == [[(cuts[i], cuts[i - 1])] for i in range(1, len(cuts))]
+    assert w[-1] == [(body_begin, cuts[-1])]
+    seen = np.zeros(total, dtype=np.int64)
+    for lo, hi in (x for point in w for x in point):
+        assert 0 <= lo <= hi <= total
+        seen[lo:hi] += 1
+    assert (seen == 1).all()                                     # disjoint, and together exactly [0, total)
+
+
+def test_unknown_ddp_edge_mode_is_refused(monkeypatch):
+    from tubelet_transformer_amd.ddp import FlatGradReducer
+    m = torch.nn.Linear(8, 4)
+    store = type("S", (), {})()
+    store.module, store.names, store.params = m, ["weight", "bias"], [m.weight, m.bias]
+    store.offsets, store.total = {"weight": 0, "bias": 64}, 128
+    for mode in ("event", "flag", "hybrid"):
+        monkeypatch.setenv("TUBER_DDP_EDGE", mode)
+        assert FlatGradReducer(store, world_size=2, comm=None).edge_mode == mode
+    monkeypatch.delenv("TUBER_DDP_EDGE")
+    assert FlatGradReducer(store, world_size=2, comm=None).edge_mode == "hybrid"
+    for mode in ("device", "nofence", "plain", ""):
+        monkeypatch.setenv("TUBER_DDP_EDGE", mode)
+        with pytest.raises(ValueError, match="TUBER_DDP_EDGE"):
+            FlatGradReducer(store, world_size=2, comm=None)
+
+
 # ---------------------------------------------------------------- checkpoints -----------------------
 def test_checkpoint_roundtrip_with_ddp_prefix(tmp_path):
     from tubelet_transformer_amd import checkpoint as ck

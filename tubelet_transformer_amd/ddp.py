@@ -12,8 +12,8 @@ final and overlapped with the remaining backward kernels:
     end of backward                 the rest: stem, and the transformer / head window laid out before the body
 
 Transport (``RcclComm``): RCCL bound directly through the C ABI (``csrc/collective.cpp``: ``ncclAllReduce`` from the librccl the
-process already has), on a communicator and a HIP stream this module owns.  Ordering is by events only: the side stream waits for
-the backward stream at each issue point, the optimizer waits for the side stream once; the host never blocks.  The averaging
+process already has), on a communicator and a HIP stream this module owns.  The side stream waits for the backward stream at each
+issue point (an event, or a device-memory counter: flag_points), the optimizer waits for the side stream once; the host never blocks.  The averaging
 (x 1/world) runs on the side stream right behind each window's all-reduce, so it is overlapped too.  Windows of frozen parameters
 (``requires_grad = False``) hold no gradient and are never sent.  Optional bf16 compression (``TUBER_DDP_BF16=1`` or
 ``compress=True``): a window is cast to bf16 into a staging buffer, summed in bf16, and expanded + averaged back into the fp32
@@ -21,15 +21,17 @@ buffer -- half the xGMI bytes (xGMI is point-to-point, 7 links x ~153 GB/s per G
 precision.  Without a GPU / with the gloo backend (CPU tests, two ranks sharing one GPU) the same windows go through
 ``torch.distributed.all_reduce``.
 
-The hipGraph step (training.GraphedTrainStep) does not use the backward hooks: it cuts its graph once, where layer3's backward
-ends, and calls ``reduce()`` for the final windows before replaying the rest (layer2 / layer1 / stem backward) -- or, with
+The hipGraph step (training.GraphedTrainStep) does not use the backward hooks: it cuts its graph where layer4's and layer3's backward
+end and, at each cut, hands the windows final there (``cut_windows``) to ``issue()`` before replaying the rest -- or, with
 ``TUBER_RCCL_IN_GRAPH=1``, keeps the hooks and captures the collectives INTO the graph as a forked branch.
 
 No bucket copies, no unused-parameter bitmap (C2), no per-step buffer broadcast (C3): BatchNorm statistics stay local like the
 reference's non-synchronised BatchNorm3d; rank 0's running statistics are what a checkpoint holds.
 """
+import contextlib
 import ctypes
 import os
+import time
 
 import torch
 import torch.distributed as dist
@@ -48,6 +50,20 @@ def trainable_ranges(store):
         else:
             out.append([o, e])
     return [(a, b) for a, b in out]
+
+
+def cut_windows(cuts, body_begin, total):
+    """windows of the flat gradient buffer that are final at each issue point of the cut-graph step, in issue order.  The backward
+    fills the buffer from its high end down to ``body_begin`` (the CSN body) and cuts the graph at the descending offsets ``cuts``;
+    what lies in front of the body (transformer, heads) is final by the first cut:
+
+        point 0          [cuts[0], total), then [0, body_begin)
+        point i          [cuts[i], cuts[i-1])
+        point len(cuts)  [body_begin, cuts[-1])     (after the last graph part: stem, layer1, layer2)"""
+    out = [[(cuts[0], total), (0, body_begin)]]
+    out += [[(cuts[i], cuts[i - 1])] for i in range(1, len(cuts))]
+    out.append([(body_begin, cuts[-1])])
+    return out
 
 
 class RcclComm:
@@ -106,42 +122,6 @@ class RcclComm:
             self.comm = None
 
 
-class StreamEdge:
-    """One-directional ordering edge between two HIP streams of this device: what was enqueued on ``src`` so far happens before what is
-    enqueued on ``dst`` afterwards (hipEventRecord + hipStreamWaitEvent on a reusable event).
-
-    torch's ``dst.wait_stream(src)`` records a DEFAULT event, and a default HIP event performs a SYSTEM-scope release when it completes
-    (cache write-back + invalidate: /opt/rocm/include/hip/hip_runtime_api.h, hipEventDisableSystemFence).  Round 6 measured what that costs
-    the captured step (scripts/r06_ddp_probe.sh): the pair of edges around the gradient exchange -- with NO collective enqueued between
-    them -- slows the step by 0.7 - 0.8 ms, the same as with the one-rank ncclAllReduce (which is a no-op on the device: 5 us of stream
-    time).  ``mode``: 'torch' = wait_stream; 'device' = own event with hipEventReleaseToDevice (an agent-scope release is all another
-    stream of the SAME device needs); 'nofence' = hipEventDisableSystemFence."""
-    _hip = None
-    FLAGS = {"device": 0x2 | 0x40000000, "nofence": 0x2 | 0x20000000, "plain": 0x2}
-
-    def __init__(self, mode):
-        self.mode = mode
-        self.ev = None
-        if mode != "torch":
-            if StreamEdge._hip is None:
-                StreamEdge._hip = ctypes.CDLL("libamdhip64.so")
-            ev = ctypes.c_void_p()
-            rc = StreamEdge._hip.hipEventCreateWithFlags(ctypes.byref(ev), ctypes.c_uint(self.FLAGS[mode]))
-            if rc != 0:
-                raise RuntimeError("hipEventCreateWithFlags(%s) failed: %d" % (mode, rc))
-            self.ev = ev
-
-    def __call__(self, src, dst):
-        if self.ev is None:
-            dst.wait_stream(src)
-            return
-        h = StreamEdge._hip
-        rc = h.hipEventRecord(self.ev, ctypes.c_void_p(src.cuda_stream))
-        rc = rc or h.hipStreamWaitEvent(ctypes.c_void_p(dst.cuda_stream), self.ev, ctypes.c_uint(0))
-        if rc != 0:
-            raise RuntimeError("stream edge failed: %d" % rc)
-
-
 class RcclBootstrapTimeout(RuntimeError):
     """ncclCommInitRank did not complete before TUBER_RCCL_INIT_TIMEOUT_S: a rank is missing.  Not recoverable in-process."""
 
@@ -173,13 +153,12 @@ class FlatGradReducer:
         self.ranges = trainable_ranges(store)
         # how the transport's stream learns that a window is final on the backward stream (see flag_points): 'flag' = a counter in device
         # memory, bumped by a one-thread kernel that is the last node of a graph part and polled by a one-wave kernel in front of the
-        # collective (csrc/stream_flag.hip); 'event' = hipEventRecord + hipStreamWaitEvent as until round 5 ('device' / 'nofence' /
-        # 'plain': the same with other event flags -- measured identical); 'hybrid' (default) = counter at the first cut, events after.
+        # collective (csrc/stream_flag.hip); 'event' = ``wait_stream`` (hipEventRecord + hipStreamWaitEvent); 'hybrid' (default) =
+        # counter at the first cut, events after.  Events with other flags (agent-scope release, no system fence) measured the same as
+        # the default event and were removed (profiles/r06_ddp_edges.txt).
         self.edge_mode = os.environ.get("TUBER_DDP_EDGE", "hybrid")
-        ev_mode = "torch" if self.edge_mode in ("flag", "event", "hybrid") else self.edge_mode
-        self.edge_out = [StreamEdge(ev_mode) for _ in range(8)]  # backward stream -> transport stream, one reusable event per issue point of a step
-        self.edge_back = StreamEdge(ev_mode)                      # transport stream -> optimizer's stream (few kernels behind it: cheap)
-        self.edge_k = 0
+        if self.edge_mode not in ("event", "flag", "hybrid"):
+            raise ValueError("TUBER_DDP_EDGE must be event, flag or hybrid; got %r" % self.edge_mode)
         self.flags = torch.zeros(16, dtype=torch.int32, device=store.device) if comm is not None else None      # [0..7] counters, [15] error word
         self.expect = [0] * 8
 
@@ -189,13 +168,32 @@ class FlatGradReducer:
         self.issued = 0
         self.windows = 0
         self.done_from = self.store.total
-        self.edge_k = 0
         self.ranges = trainable_ranges(self.store)       # windows of frozen parameters hold no gradient: never sent
         self._joined = True
         if self.measure and self.comm is not None and not torch.cuda.is_current_stream_capturing():
             e = torch.cuda.Event(enable_timing=True)
             e.record(torch.cuda.current_stream())
             self.win_events.append((e, []))
+
+    @contextlib.contextmanager
+    def step(self, fold=None):
+        """one step's gradient exchange: ``begin()``, then ``fold`` (accum.GradAccumulator.fold on a group's last micro-batch) runs on
+        every window right before the transport sees it, until the block ends -- exceptions included.  ``finish()`` is the caller's."""
+        self.begin()
+        self.pre_reduce = fold
+        try:
+            yield self
+        finally:
+            self.pre_reduce = None
+
+    def issue(self, i, windows, counter=False):
+        """issue point ``i`` of the captured cut-graph step: hand ``windows`` (cut_windows) to the transport.  ``counter``: the transport's
+        stream is ordered by the device counter the graph part in front bumped (``signal(i)``, see flag_points); else the first window
+        orders it by an event and the later ones ride on that edge."""
+        if counter:
+            self.wait_for(i)
+        for k, (lo, hi) in enumerate(windows):
+            self.reduce(lo, hi, edge=k == 0 and not counter)
 
     def flag_points(self):
         """issue points of the captured step (0 = the first cut) that are ordered by a device-memory counter instead of an event.
@@ -254,16 +252,13 @@ class FlatGradReducer:
             issue = torch.cuda.Event(enable_timing=True)
             issue.record(torch.cuda.current_stream())           # when the backward stream reaches this issue point
         if edge:
-            self.edge_out[self.edge_k % len(self.edge_out)](torch.cuda.current_stream(), cs)      # the windows are final on the backward stream up to here
-            self.edge_k += 1
+            cs.wait_stream(torch.cuda.current_stream())         # the windows are final on the backward stream up to here
         self._joined = False
         inv = 1.0 / self.world
         base = st.gflat.data_ptr()
-        skip_call = bool(os.environ.get("TUBER_DDP_SKIP_CALL"))      # diagnostic: everything but the ncclAllReduce call itself (stream edges only)
-        import time as _time
-        h0 = _time.perf_counter()
         with torch.cuda.stream(cs):
             if timed:
+                h0 = time.perf_counter()
                 w0 = torch.cuda.Event(enable_timing=True)
                 w0.record(cs)
             for a, b in wins:
@@ -276,8 +271,7 @@ class FlatGradReducer:
                     self.comm.all_reduce(sp, n, bf16=True)
                     lib.call("tuber_cast_bf16_f32_scale", sp, base + 4 * a, n, inv)
                 else:
-                    if not skip_call:
-                        self.comm.all_reduce(base + 4 * a, n)
+                    self.comm.all_reduce(base + 4 * a, n)
                     if self.world > 1:
                         lib.call("tuber_scale_f32", base + 4 * a, n, None, inv)
                 self.issued += n
@@ -285,7 +279,7 @@ class FlatGradReducer:
             if timed:
                 w1 = torch.cuda.Event(enable_timing=True)
                 w1.record(cs)
-                self.win_events[-1][1].append((issue, w0, w1, sum(b - a for a, b in wins) * (2 if self.compress else 4), _time.perf_counter() - h0))
+                self.win_events[-1][1].append((issue, w0, w1, sum(b - a for a, b in wins) * (2 if self.compress else 4), time.perf_counter() - h0))
 
     def _reduce_excluding_late(self, lo, hi):
         cur = lo
@@ -319,7 +313,7 @@ class FlatGradReducer:
                 if timed:
                     e0 = torch.cuda.Event(enable_timing=True)
                     e0.record(cur)
-                self.edge_back(self.comm.stream, cur)
+                cur.wait_stream(self.comm.stream)
                 if timed:
                     e1 = torch.cuda.Event(enable_timing=True)
                     e1.record(cur)

@@ -9,12 +9,13 @@ times on rank 0 (:182-193); here a step has no device->host transfer at all (the
 logging reads the (still on-device) loss tensors only when asked to.
 """
 import collections
+import contextlib
 import os
 
 import torch
 
 from . import ab
-from .ddp import attach_reducer, broadcast_parameters
+from .ddp import attach_reducer, broadcast_parameters, cut_windows
 from .optim import FusedClipAdamW, adopt, build_param_groups
 
 
@@ -84,18 +85,13 @@ def train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=0,
         accum.end_micro()
         return losses.detach(), loss_dict
     if reducer is not None:
-        reducer.begin()
-        if role == "last":
-            reducer.pre_reduce = accum.fold    # each window folded right before its all-reduce is issued
-    try:
-        losses.backward()
-        if reducer is not None:
+        with reducer.step(fold=accum.fold if role == "last" else None):    # each window folded right before its all-reduce is issued
+            losses.backward()
             reducer.finish()
-    finally:
-        if reducer is not None:
-            reducer.pre_reduce = None
-    if role == "last" and reducer is None:
-        accum.fold()
+    else:
+        losses.backward()
+        if role == "last":
+            accum.fold()
     if fused is not None:
         fused.step(max_norm=max_norm if max_norm and max_norm > 0 else None)
     else:
@@ -121,6 +117,45 @@ class _Snapshot:
         with torch.no_grad():
             for live, saved in self.items:
                 live.copy_(saved)
+
+
+def _capture_plan(red):
+    """(in_graph, split, cut_stages) of a capture, from the environment at capture time.  ``red``: the reducer the step all-reduces
+    through, or None.
+      TUBER_RCCL_IN_GRAPH=1      the collectives are captured into the one graph as a forked branch (own RCCL communicator only)
+      TUBER_NO_SPLIT_GRAPH=1     a reducer without in-graph collectives: one graph, the all-reduce after it (else the graph is cut)
+      TUBER_FORCE_SPLIT_GRAPH=1  cut the graph even without a reducer (tests: the cut graphs equal the single graph)
+      TUBER_DDP_CUTS=4,3         the CSN stages whose backward ends at a cut (backbone.CSNRunner.cut_stages; (3,) when not cut)"""
+    env = os.environ.get
+    in_graph = red is not None and red.comm is not None and bool(env("TUBER_RCCL_IN_GRAPH"))
+    split = (red is not None and not in_graph and not env("TUBER_NO_SPLIT_GRAPH")) or bool(env("TUBER_FORCE_SPLIT_GRAPH"))
+    cut_stages = tuple(int(x) for x in env("TUBER_DDP_CUTS", "4,3").split(",") if x) if split else (3,)
+    return in_graph, split, cut_stages
+
+
+class _Captured:
+    """One captured step of GraphedTrainStep: its graphs, the device buffers they read and write, and how its replay drives the reducer."""
+
+    def __init__(self, red, in_graph, clips, mask, pt):
+        self.red = red                  # ddp.FlatGradReducer the step all-reduces through (None: no reducer, or not a group's last micro-batch)
+        self.in_graph = in_graph        # the collectives are part of graph A (TUBER_RCCL_IN_GRAPH); else the replay issues them
+        self.clips = clips              # [B,3,T,H,W] fp32 input buffer the graphs read (GraphedTrainStep.input_buffers)
+        self.mask = mask                # [B,H,W] bool padding mask buffer
+        self.pt = pt                    # criterion.PaddedTargets: the padded [B, Tmax] targets, refilled before every replay
+        self.A = None                   # first (or only) graph: weight refresh, forward, matching cost, ...
+        self.B1 = None                  # host assignment only: criterion + backward (+ clip + AdamW), replayed after the host solve
+        self.B2 = None                  # clip + AdamW behind the all-reduce (a reducer without in-graph collectives)
+        self.parts = []                 # cut step: the graph parts after each cut, in replay order
+        self.A2 = None                  # cut step: the last of ``parts`` (None: not cut)
+        self.cuts = []                  # cut step: flat gradient offset of each cut, descending
+        self.windows = None             # per issue point, the [lo, hi) windows of the flat gradient final there (ddp.cut_windows)
+        self.flag_edges = frozenset()   # issue points ordered by a device counter instead of an event (FlatGradReducer.flag_points)
+        self.on_device = True           # the Hungarian assignment runs on the device (cost within tuber_lsap_device's 128 x 128)
+        self.logits_s = self.logits_b = self.boxes_s = self.cost = None     # forward outputs the criterion and matcher read
+        self.match = None               # int32 [L, B, Tmax]: query matched to each target (-1: none)
+        self.match_host = self.cost_host = None                            # host assignment only: pinned staging buffers
+        self.loss = None                # total loss of the last replay (device)
+        self.loss_dict = None           # its terms (device)
 
 
 class CaptureFailed(RuntimeError):
@@ -188,19 +223,18 @@ class GraphedTrainStep:
         from .criterion import PaddedTargets
         from .misc import NestedTensor
         model, crit, opt = self.model, self.criterion, self.optimizer
-        store, _ = model.engine()
+        store, runner = model.engine()
         dev = store.device
         acc = self.accum
         keep = getattr(store, "reducer", None)
-        red = None if role in ("first", "middle") else keep       # no collective before a group's last micro-batch
         stepping = role not in ("first", "middle")
+        red = keep if stepping else None             # no collective before a group's last micro-batch
         ddp = red is not None                        # N > 1 ranks (or a forced one-rank communicator): gradients are all-reduced
-        in_graph = ddp and red.comm is not None and bool(os.environ.get("TUBER_RCCL_IN_GRAPH"))
-        g = type("Captured", (), {})()
-        g.red, g.in_graph = red, in_graph
-        g.clips = clips.clone()
-        g.mask = mask.clone()
-        g.pt = PaddedTargets(targets, crit.ava, crit.num_classes if crit.ava else crit.num_classes + 1, dev, tmax=tmax)
+        in_graph, split, cut_stages = _capture_plan(red)
+        own_step = not ddp or in_graph               # clip + AdamW inside the main graph (else graph B2, behind the all-reduce)
+        fold = acc.fold if role == "last" else None  # with a reducer: each window folded right before its all-reduce (pre_reduce)
+        g = _Captured(red, in_graph, clips.clone(), mask.clone(),
+                      PaddedTargets(targets, crit.ava, crit.num_classes if crit.ava else crit.num_classes + 1, dev, tmax=tmax))
         max_norm = self.max_norm if self.max_norm and self.max_norm > 0 else None
 
         def head():
@@ -220,40 +254,39 @@ class GraphedTrainStep:
             g.loss_dict["class_error"] = crit.class_error(g.logits_s[-1], g.pt, g.match[-1])
             g.loss = crit.weighted_total(g.loss_dict)
             opt.zero_grad()
-            g.loss.backward()
+            if in_graph:
+                # the reducer's hooks fork its side stream off this stream inside the backward: the all-reduces (+ averaging) become a
+                # parallel branch that joins before clip + AdamW
+                with red.step(fold=fold):
+                    g.loss.backward()
+                    red.finish()
+            else:
+                g.loss.backward()
             if role in ("first", "middle"):
                 acc.after_backward(role)
             elif role == "last" and not ddp:
-                acc.fold()                           # (with a reducer: per window, right before its all-reduce -- pre_reduce)
+                acc.fold()
             if step:
                 opt.step(max_norm=max_norm)
+
+        def step_body(step):
+            head()
+            g.match = crit.assign(g.cost, g.pt)
+            tail(step)
 
         # eager warm-up with the reducer detached (its hooks must not fire inside a stream capture, and it flushes the deferred
         # reductions per bottleneck where the captured backward flushes twice): sizes every workspace, builds the reduce tables and
         # the loss-weight / hyper-parameter device tables.  Rolled back afterwards -- a capture is not an optimisation step.
         snap = _Snapshot(model, store, opt, () if acc is None else (acc.acc, acc.bn_arena, acc.scale_dev))
         store.reducer = red if in_graph else None
-        split = ddp and not in_graph and not os.environ.get("TUBER_NO_SPLIT_GRAPH")
-        split = split or bool(os.environ.get("TUBER_FORCE_SPLIT_GRAPH"))
-        _, runner = model.engine()
         # where the backward makes its gradient windows final (backbone.CSNRunner._backward_blocks): fixed BEFORE the warm-up passes so
         # that they and the capture issue the same weight-gradient groups and deferred-reduce tables
-        runner.cut_stages = tuple(int(x) for x in os.environ.get("TUBER_DDP_CUTS", "4,3").split(",") if x) if split else (3,)
+        runner.cut_stages = cut_stages
         if in_graph:
             red.dry = True                           # hooks fire (same deferred-reduce flush points as the capture), nothing is sent
-            if role == "last":
-                red.pre_reduce = acc.fold            # captured with the collectives: the fold of each window goes in front of it
         try:
             for _ in range(2):
-                head()
-                g.on_device = g.cost.shape[2] <= 128 and g.cost.shape[3] <= 128      # the bound of tuber_lsap_device (criterion.assign)
-                g.match = crit.assign(g.cost, g.pt)
-                if in_graph:
-                    red.begin()
-                tail(not in_graph and stepping)
-                if in_graph:
-                    red.finish()
-                    opt.step(max_norm=max_norm)
+                step_body(stepping)
             torch.cuda.synchronize()
         finally:
             snap.restore()
@@ -261,20 +294,11 @@ class GraphedTrainStep:
                 red.dry = False
         opt.sync_hyper()
         crit.sync_weights(dev)
-        g.A, g.A2, g.B1, g.B2, g.split, g.parts, g.cuts, g.flag_edges = torch.cuda.CUDAGraph(), None, None, None, None, [], [], frozenset()
-        split = split and g.on_device
-        own_step = not ddp or in_graph               # clip + AdamW inside the main graph (else graph B2, behind the all-reduce)
+        g.on_device = g.cost.shape[2] <= 128 and g.cost.shape[3] <= 128      # the bound of tuber_lsap_device (criterion.assign)
+        g.A = torch.cuda.CUDAGraph()
         if in_graph:
-            # ONE graph: the reducer's hooks fork its side stream off the capture stream inside the backward pass, so the RCCL
-            # all-reduces (+ averaging) are captured as a parallel branch that joins before clip + AdamW
             with torch.cuda.graph(g.A, capture_error_mode="relaxed"):      # RCCL may touch the runtime while enqueuing
-                head()
-                g.match = crit.assign(g.cost, g.pt)
-                red.begin()
-                tail(False)
-                red.finish()
-                red.pre_reduce = None
-                opt.step(max_norm=max_norm)
+                step_body(own_step and stepping)
         elif split and g.on_device:
             # DDP: the graph is CUT inside the backward pass where a gradient window becomes final, so that window's RCCL all-reduce runs
             # on the reducer's stream under the backward of the stages below it.  Default cuts (TUBER_DDP_CUTS=4,3): (1) where layer4's
@@ -285,7 +309,7 @@ class GraphedTrainStep:
             cut = []
             graphs = [g.A]
             # issue points ordered by a device-memory counter instead of an event (ddp.FlatGradReducer.flag_points): by default the FIRST
-            flag_edges = g.flag_edges = red.flag_points() if red is not None else frozenset()
+            flag_edges = red.flag_points() if red is not None else frozenset()
             torch.cuda.synchronize()
             cs = torch.cuda.Stream()
             cs.wait_stream(torch.cuda.current_stream())
@@ -302,25 +326,21 @@ class GraphedTrainStep:
                     graphs.append(nxt)
                 runner.split_hook = hook
                 try:
-                    head()
-                    g.match = crit.assign(g.cost, g.pt)
-                    tail(own_step and stepping)
+                    step_body(own_step and stepping)
                 finally:
                     runner.split_hook = None
                 if len(cut) in flag_edges and not own_step and cut:  # (no cut -- a frozen body: one event-ordered window after the graph)
                     red.signal(len(cut))                             # end of backward: the remainder is final
                 graphs[-1].capture_end()
-                g.parts, g.cuts, g.body_begin = graphs[1:], cut, int(runner.body_begin)
-                g.A2 = graphs[-1] if cut else None
-                g.split = cut[-1] if cut else None
             torch.cuda.current_stream().wait_stream(cs)
+            g.parts, g.cuts = graphs[1:], cut
+            g.A2 = graphs[-1] if cut else None
+            g.flag_edges = flag_edges if cut else frozenset()
         elif g.on_device:
             with torch.cuda.graph(g.A):
-                head()
-                g.match = crit.assign(g.cost, g.pt)
-                tail(own_step and stepping)
+                step_body(own_step and stepping)
         else:
-            # assignment problems beyond the device solver's 128 x 128 bound: graph A / host tuber_lsap / graph B1
+            # assignment problems beyond the device solver's 128 x 128 bound: graph A (head) / tuber_lsap on the host / graph B1 (tail)
             with torch.cuda.graph(g.A):
                 head()
             L, B = g.cost.shape[:2]
@@ -335,17 +355,26 @@ class GraphedTrainStep:
             g.B2 = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g.B2, pool=g.A.pool()):
                 opt.step(max_norm=max_norm)
-        g.ranges = store.trainable_ranges()
+        g.windows = cut_windows(g.cuts, runner.body_begin, store.total) if g.cuts else [[(0, store.total)]]
         return g
+
+    def _key(self, shape, tmax, role=None):
+        """graph key: clip shape, set of trainable tensors, train / eval criterion, padded target layout, the decoder's launch form (a
+        captured step bakes it in: after a timed-out cooperative launch -- engine.coop_failed -- a new one is captured)[, accumulation role]"""
+        store, _ = self.model.engine()
+        key = (tuple(shape), store.trainable_signature(), self.criterion.training, tmax, store.coop_off)
+        return key if role is None else key + (role,)
+
+    def _wider(self, shape, tmax=0):
+        """the first captured key for this clip shape whose padded target layout holds ``tmax`` boxes per clip (any role), or None"""
+        want = self._key(shape, tmax)
+        return next((k for k in self.graphs if k[:3] == want[:3] and k[3] >= tmax and k[4] == want[4]), None)
 
     def input_buffers(self, clips_shape):
         """(clips, mask) buffers the captured step for this clip shape reads, or None before its first call: a producer that fills them in
         place and passes them back to ``__call__`` saves the step its 67 MB device-to-device copy."""
-        store, _ = self.model.engine()
-        for k, g in self.graphs.items():
-            if k[:3] == (tuple(clips_shape), store.trainable_signature(), self.criterion.training) and k[4] == store.coop_off:
-                return g.clips, g.mask
-        return None
+        k = self._wider(clips_shape)
+        return None if k is None else (self.graphs[k].clips, self.graphs[k].mask)
 
     # -- replay --------------------------------------------------------------------------------------------------------------
     def __call__(self, samples, targets, last=False):
@@ -364,20 +393,14 @@ class GraphedTrainStep:
         # AVA key frames) gets a graph with a wider layout instead of an error -- the reference has no such limit
         need = max([int(t["boxes"].shape[0]) for t in targets] + [1])
         tmax = max(self.tmax, (need + 15) // 16 * 16)
-        for k in self.graphs:                                     # a captured wider layout serves narrower batches too
-            if k[:3] == (tuple(clips.shape), store.trainable_signature(), self.criterion.training) and k[3] >= tmax and k[4] == store.coop_off:
-                tmax = k[3]
-                break
-        # (a captured step bakes the decoder's launch form in: after a timed-out cooperative launch -- engine.coop_failed -- a new one is captured)
-        key = (tuple(clips.shape), store.trainable_signature(), self.criterion.training, tmax, store.coop_off)
-        if role is not None:
-            key = key + (role,)
+        wider = self._wider(clips.shape, tmax)                    # a captured wider layout serves narrower batches too
+        key = self._key(clips.shape, tmax if wider is None else wider[3], role)
         g = self.graphs.get(key)
         if g is None:
             while len(self.graphs) >= self.max_graphs:            # LRU: a graph holds its own memory pool
                 self.graphs.popitem(last=False)
             try:
-                g = self._capture(clips.to(store.device, torch.float32), mask.to(store.device), targets, tmax, role)
+                g = self._capture(clips.to(store.device, torch.float32), mask.to(store.device), targets, key[3], role)
             except (RuntimeError, ValueError) as e:
                 raise CaptureFailed("%s: %s" % (type(e).__name__, e)) from e
             self.graphs[key] = g
@@ -395,56 +418,37 @@ class GraphedTrainStep:
             self.optimizer.mark_stepped()
         self.criterion.sync_weights(store.device)
         sizes = g.pt.sizes
-        red = g.red
-        if red is not None and not g.in_graph:
-            red.begin()
-            if role == "last":
-                red.pre_reduce = acc.fold                     # each cut's windows folded on this stream right before their all-reduce
-        marks = self.part_marks                               # bench.py: HIP-event stamps between the graph parts of the measured steps
+        red = None if g.in_graph else g.red                       # the replay drives the exchange (in-graph: graph A holds it)
+        marks = self.part_marks                                   # bench.py: HIP-event stamps between the graph parts of the measured steps
         if marks is not None:
             marks.append([])
-            self._mark()
-        g.A.replay()
-        if marks is not None:
-            self._mark()
-        if g.on_device:
-            self.criterion._indices, self.criterion._match_dev = None, (g.match, sizes)
-        else:
-            g.cost_host.copy_(g.cost, non_blocking=True)
-            torch.cuda.current_stream().synchronize()             # host assignment: the step's one host sync
-            match, indices = self.criterion.matcher.solve(g.cost_host.numpy(), sizes)
-            g.match_host.copy_(torch.from_numpy(match))
-            g.match.copy_(g.match_host, non_blocking=True)
-            L = len(indices)
-            self.criterion.last_indices = [indices[L - 1]] + indices[:L - 1]
-            g.B1.replay()
-        if g.parts:
-            # final at cut i: the stage that just ended, the stages above it, everything laid out behind the body [cuts[i], previous cut)
-            # and -- at the first cut -- everything laid out before the body (transformer, heads: [0, body_begin)); pending after the
-            # last cut: [body_begin, cuts[-1]) (stem, layer1, layer2)
-            hi = store.total
+        with red.step(fold=acc.fold if role == "last" else None) if red is not None else contextlib.nullcontext():
+            if marks is not None:
+                self._mark()
+            g.A.replay()
+            if marks is not None:
+                self._mark()
+            if g.on_device:
+                self.criterion._indices, self.criterion._match_dev = None, (g.match, sizes)
+            else:
+                g.cost_host.copy_(g.cost, non_blocking=True)
+                torch.cuda.current_stream().synchronize()         # host assignment: the step's one host sync
+                match, indices = self.criterion.matcher.solve(g.cost_host.numpy(), sizes)
+                g.match_host.copy_(torch.from_numpy(match))
+                g.match.copy_(g.match_host, non_blocking=True)
+                L = len(indices)
+                self.criterion.last_indices = [indices[L - 1]] + indices[:L - 1]
+                g.B1.replay()
+            # issue point i hands the windows final at cut i to the transport, then the backward of the stages below runs under it
             for i, part in enumerate(g.parts):
                 if red is not None:
-                    soft = i in g.flag_edges                  # ordered by the counter the graph part bumps, not by an event (csrc/stream_flag.hip)
-                    if soft:
-                        red.wait_for(i)
-                    red.reduce(g.cuts[i], hi, edge=not soft)
-                    if i == 0:
-                        red.reduce(0, g.body_begin, edge=False)
-                hi = g.cuts[i]
-                part.replay()                                 # the backward of the stages below, under the all-reduce
+                    red.issue(i, g.windows[i], counter=i in g.flag_edges)
+                part.replay()
                 if marks is not None:
                     self._mark()
             if red is not None:
-                soft = len(g.parts) in g.flag_edges
-                if soft:
-                    red.wait_for(len(g.parts))
-                red.reduce(g.body_begin, hi, edge=not soft)
-        elif red is not None and not g.in_graph:
-            red.reduce(0, store.total)
-        if red is not None and not g.in_graph:
-            red.finish(rest=False)                            # the optimizer graph waits for the side stream (events only)
-            red.pre_reduce = None
+                red.issue(len(g.parts), g.windows[-1], counter=len(g.parts) in g.flag_edges)
+                red.finish(rest=False)                            # the optimizer graph waits for the side stream (events only)
         if g.B2 is not None:
             g.B2.replay()
             if marks is not None:
@@ -571,22 +575,18 @@ def train_tuber_detection(cfg, model, criterion, data_loader, optimizer, epoch, 
         if accum.k != k:
             raise ValueError("ACCUM_STEPS = %d, but the step accumulates over %d micro-batches" % (k, accum.k))
         opt_step = accum.steps
-        acc_kw = dict(accum=accum, last=False)
     else:
-        n_steps, accum, acc_kw = n_iter, None, {}
+        n_steps, accum = n_iter, None
     for idx, data in enumerate(data_loader):
         samples, targets = data[0], data[1]
         samples = samples.to(dev)            # reference :121; for an input_pipeline.ClipBatch this IS the HIP pre-pass (uint8 frames -> fp32 batch)
         targets = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in t.items() if k != "image_id"} for t in targets]
+        last = idx + 1 == n_iter                                  # accumulation: the trailing partial group steps at the end of the epoch
         if accum is not None:
-            acc_kw["last"] = idx + 1 == n_iter                    # the trailing partial group steps at the end of the epoch
             steps_before = accum.steps
         if graphed is not None:
             try:
-                if accum is not None:
-                    loss, loss_dict = graphed(samples, targets, last=acc_kw["last"])
-                else:
-                    loss, loss_dict = graphed(samples, targets)   # NestedTensor: clips AND padding mask go to the captured buffers
+                loss, loss_dict = graphed(samples, targets, last=last)   # NestedTensor: clips AND padding mask go to the captured buffers
             except CaptureFailed as e:                            # a failed capture must not end the epoch
                 if getattr(model.engine()[0], "reducer", None) is not None:
                     raise                                         # N > 1: every rank must stay on the same collective sequence
@@ -594,9 +594,9 @@ def train_tuber_detection(cfg, model, criterion, data_loader, optimizer, epoch, 
                 print("[tuber] hipGraph step unavailable (%s: %s); continuing with the eager step" % (type(e).__name__, e), file=sys.stderr, flush=True)
                 graphed = None
                 model.__dict__.pop("_tuber_graphed", None)
-                loss, loss_dict = train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=epoch, cfg=cfg, **acc_kw)
+                loss, loss_dict = train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=epoch, cfg=cfg, accum=accum, last=last)
         else:
-            loss, loss_dict = train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=epoch, cfg=cfg, **acc_kw)
+            loss, loss_dict = train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=epoch, cfg=cfg, accum=accum, last=last)
         if accum is None:
             stepped, opt_idx = True, idx
         else:
