@@ -1,9 +1,12 @@
 """Eval forward latency of the three eval forms (round 6), BASELINE config 3 at its stated size (TubeR_CSN152_AVA21, 2 clips of 3x32x256x340),
 eager launches and a captured hipGraph replay:
     default                      eval precision mode: fp32 residual streams + fp32 decoder / box / actor heads (csrc/eval_f32.hip)
+    TUBER_EVAL_PRECISION=fp32_class   the same + the class branch once per clip in fp32 (round 7)
     TUBER_AB=eval_bf16_decoder   fp32 residual streams only
     TUBER_AB=eval_bf16_stream    the training path's rounding points (bf16-stored streams, bf16 MFMA decoder, cooperative decoder launch)
+EVAL_ROUNDS=n (default 1) repeats the modes n times, alternating them, with one captured graph per mode: same-box interleaved pairs.
 usage: python scripts/eval_latency.py [config.yaml H W]"""
+import contextlib
 import os
 import sys
 import time
@@ -37,16 +40,37 @@ def timed(fn, n=20):
     return 1e3 * (time.perf_counter() - t0) / n
 
 
-MODES = (("eval precision mode (default)", ()), ("fp32 streams only (eval_bf16_decoder)", ("eval_bf16_decoder",)), ("bf16 streams (eval_bf16_stream)", ("eval_bf16_stream",)))
+MODES = (("eval precision mode (default)", (), None), ("fp32 streams only (eval_bf16_decoder)", ("eval_bf16_decoder",), None),
+         ("bf16 streams (eval_bf16_stream)", ("eval_bf16_stream",), None), ("class branch in fp32 (fp32_class)", (), "fp32_class"))
 if os.environ.get("EVAL_MODES"):                                    # e.g. EVAL_MODES=0 under rocprofv3: the default mode only
     MODES = tuple(MODES[int(i)] for i in os.environ["EVAL_MODES"].split(","))
-for label, sw in MODES:
-    with ab.override(*sw), torch.no_grad():
-        eager = timed(lambda: model(clips))
-        g = torch.cuda.CUDAGraph()
-        model(clips)
-        torch.cuda.synchronize()
-        with torch.cuda.graph(g):
-            model(clips)
-        graph = timed(g.replay)
-    print("%-44s eager %7.3f ms   hipGraph replay %7.3f ms per 2-clip batch = %.3f ms per clip, %.1f clips/s" % (label, eager, graph, graph / 2, 2e3 / graph), flush=True)
+
+
+@contextlib.contextmanager
+def mode(sw, precision):
+    old = os.environ.pop("TUBER_EVAL_PRECISION", None)
+    if precision:
+        os.environ["TUBER_EVAL_PRECISION"] = precision
+    try:
+        with ab.override(*sw), torch.no_grad():
+            yield
+    finally:
+        os.environ.pop("TUBER_EVAL_PRECISION", None)
+        if old is not None:
+            os.environ["TUBER_EVAL_PRECISION"] = old
+
+
+graphs = {}
+for rnd in range(int(os.environ.get("EVAL_ROUNDS", "1"))):
+    for label, sw, precision in MODES:
+        with mode(sw, precision):
+            eager = timed(lambda: model(clips))
+            if label not in graphs:
+                g = torch.cuda.CUDAGraph()
+                model(clips)
+                torch.cuda.synchronize()
+                with torch.cuda.graph(g):
+                    model(clips)
+                graphs[label] = g
+            graph = timed(graphs[label].replay)
+        print("%-44s eager %7.3f ms   hipGraph replay %7.3f ms per 2-clip batch = %.3f ms per clip, %.1f clips/s" % (label, eager, graph, graph / 2, 2e3 / graph), flush=True)

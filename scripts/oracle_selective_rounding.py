@@ -2,7 +2,9 @@
 Runs oracle/tuber_oracle.py's forward with conv3d / linear rounding (operands and result, exact accumulation -- tests/parity_util.py's
 yardstick) switched on per module group, optionally with the block outputs and / or the LayerNorm outputs additionally rounded on store
 (what the training path of the HIP build does), and prints the max abs error of the three heads against the fp32 run.
-usage: python scripts/oracle_selective_rounding.py [config.yaml H W] [--spread] [--groups]"""
+--fp32-class adds the rows of TUBER_EVAL_PRECISION=fp32_class: what that mode leaves rounded (the body convs, input_proj, the encoder;
+the decoder and heads are fp32 in every eval precision mode, the class branch from class_proj through class_fc in this one).
+usage: python scripts/oracle_selective_rounding.py [config.yaml H W] [--spread] [--groups] [--fp32-class]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))
@@ -44,13 +46,13 @@ def lin(x, w, b=None):
     return ol(x, w, b)
 def conv(x, w, *a, **k):
     r = (G["body"] and w.shape[1] != 256 and not (w.shape[0] == 256 and w.dim() == 5 and w.shape[1] == 2048)) 
-    if w.shape[0] == 256 and w.shape[1] == 2048:      # input_proj / class_proj
-        r = "proj" in G["groups"]
+    if w.shape[0] == 256 and w.shape[1] == 2048:      # input_proj / class_proj (the oracle runs input_proj first)
+        r = "proj" in G["groups"] or ("input_proj" in G["groups"] and w is G["input_proj"])
     if r:
         return RoundBF.apply(oc(RoundBF.apply(x), RoundBF.apply(w), *a, **k))
     return oc(x, w, *a, **k)
 def linear(state_, p, x):
-    G["on"] = group(p) in G["groups"]
+    G["on"] = group(p) in G["groups"] or ("heads_but_class_fc" in G["groups"] and not p.startswith("class_fc") and group(p) == "heads")
     try: return olin(state_, p, x)
     finally: G["on"] = False
 def mha(state_, p, *a, **k):
@@ -69,7 +71,9 @@ def run(groups, body, stream=False, ln=False):
     O.F.conv3d, O.F.linear, O.linear, O.mha, O.bottleneck, O.layer_norm = conv, lin, linear, mha, bott, lnw
     try:
         with torch.no_grad():
-            return O.tuber_forward({k: v.clone() for k, v in state.items()}, cfg, clips, train=False)
+            st = {k: v.clone() for k, v in state.items()}
+            G["input_proj"] = st["input_proj.weight"]
+            return O.tuber_forward(st, cfg, clips, train=False)
     finally:
         O.F.conv3d, O.F.linear, O.linear, O.mha, O.bottleneck, O.layer_norm = oc, ol, olin, omha, obott, oln
 
@@ -79,6 +83,9 @@ rows = [("all convs / linears (the yardstick)", ALL, True, False, False), ("all 
 if "--groups" in sys.argv:
     rows += [("body convs only", (), True, False, False), ("transformer + heads only", ALL, False, False, False)] + [(g + " only", (g,), False, False, False) for g in ALL] + \
             [("all but heads", ("enc", "proj", "cls", "pool", "dec"), True, False, False), ("all but decoder + heads", ("enc", "proj", "cls", "pool"), True, False, False)]
+if "--fp32-class" in sys.argv:
+    rows += [("all but class_proj + cls + class_fc", ("enc", "dec", "heads_but_class_fc", "pool", "input_proj"), True, False, False),
+             ("body + input_proj + enc (fp32_class mode)", ("enc", "pool", "input_proj"), True, False, False)]
 for nm, gr, body, stream, ln in rows:
     out = run(gr, body, stream, ln)
     print("%-46s" % nm, "  ".join("%s %.3e" % (k, float((out[k] - ref[k]).abs().max())) for k in ("pred_logits", "pred_boxes", "pred_logits_b")), flush=True)

@@ -4,7 +4,11 @@ Every entry turns one fused / grouped form of the hot path back into the separat
 ("the fused conv4 backward is worth 0.2 ms") can be re-measured on the same build.  The alternative paths are part of the shipped
 library, so they are covered by the GPU suite the driver runs: ``tests/test_training_gpu.py::test_every_ab_switch_...`` is
 parametrised over ``KNOWN`` and holds every switch to the default path's gradients.  Unknown names are an error, not ignored.
-Measured-and-rejected paths are not kept behind switches; they are deleted ("Measured and rejected")."""
+Measured-and-rejected paths are not kept behind switches; they are deleted ("Measured and rejected").
+
+The eval precision is chosen by ``TUBER_EVAL_PRECISION`` (training ignores it): ``fp32_stream`` (default; fp32 residual streams, fp32 decoder and
+box / actor heads), ``bf16_stream`` (the training path's rounding points; also ``TUBER_AB=eval_bf16_stream``) or ``fp32_class`` (``fp32_stream``
+plus the class branch once per clip in fp32: the A/B of the actor logits' precision against the class branch's x6 bf16 form)."""
 import contextlib
 import os
 
@@ -65,6 +69,12 @@ def active():
 def eval_fp32_stream():
     """eval precision mode (default): under ``model.eval()`` the residual streams stay fp32 between the blocks / layers"""
     return not on("eval_bf16_stream") and os.environ.get("TUBER_EVAL_PRECISION", "fp32_stream") != "bf16_stream"
+
+
+def eval_class_f32():
+    """``TUBER_EVAL_PRECISION=fp32_class`` (opt-in): the eval precision mode plus the class branch run ONCE per clip in fp32, from class_proj
+    (on the body's fp32 output stream) through class_fc.  Off whenever the fp32 streams are off."""
+    return eval_fp32_stream() and os.environ.get("TUBER_EVAL_PRECISION") == "fp32_class"
 
 
 @contextlib.contextmanager

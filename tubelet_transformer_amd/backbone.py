@@ -396,6 +396,8 @@ class CSNRunner:
                 out_saved.append((x, c1, c3, c4, cd, y, (Ti, Hi, Wi, To, Hq, Wq), ymask))
             x = y
             Ti, Hi, Wi = To, Hq, Wq
+        # TUBER_EVAL_PRECISION=fp32_class: the fp32 stream of the last block is the class branch's class_proj operand (DETR._class_branch_f32 takes it)
+        self.last_y32 = y32 if precise and ab.eval_class_f32() else None
         return x, (Ti, Hi, Wi)
 
     # -- teacher-forced segments (tests: every bottleneck of the real-depth body in isolation, on the oracle's activations) ----------

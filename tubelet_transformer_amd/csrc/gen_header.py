@@ -76,6 +76,14 @@ DOC = {
                                 "the memory-side K / V projections of all decoder layers (models/transformer/transformer.py:232-237), which do not depend on the decoder state.",
     "tuber_attention_f32": "fp32 multi-head attention core (head dimension 32) of the eval precision mode: the decoder's self- and cross-attention "
                            "(nn.MultiheadAttention, transformer.py:218-240) with fp32 scores, softmax and values.",
+    "tuber_attention_f32_mapped": "tuber_attention_f32 with every operand read in place through a token map {ld,sL,s1,s2,B2} (tuber_attn_fwd's convention): "
+                                  "the class branch of TUBER_EVAL_PRECISION=fp32_class run once per clip in fp32 -- its t- and s-attention (nn.MultiheadAttention "
+                                  "self_attn_t / self_attn_s, transformer_layers.py:71-97) and the cross-attention of the decoder queries over the clip's "
+                                  "encoded features (tuber_ava.py:127-141) with K / V at stride 0 over the decoder layer. No key padding mask. "
+                                  "Lq, Lk <= 8: one thread per (sequence, query, head).",
+    "tuber_layernorm_f32_rows": "fp32 LayerNorm(x + res) (nn.LayerNorm, transformer_layers.py:58-69, post-norm) with fp32 operands and output, each with its own "
+                                "leading dimension, E = 256: the class branch's norm1_t / norm1_s (into the halves of the [t | s] concatenation) and norm2 "
+                                "under TUBER_EVAL_PRECISION=fp32_class.",
     "tuber_flag_signal": "software ordering edge between two HIP streams, producer side: *flag += 1 (release, agent scope) once everything enqueued on the stream "
                          "before it has completed; capturable as the last node of a graph part. With tuber_flag_wait it replaces the hipEventRecord / "
                          "hipStreamWaitEvent pair between the backward stream and the gradient exchange's stream (DistributedDataParallel's reducer, "

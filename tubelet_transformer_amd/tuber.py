@@ -11,6 +11,7 @@ Row orders used internally (all row-wise ops are order-agnostic; attention gets 
     backbone features   (b, t, hw)      encoder memory   (b, hw)        decoder / hs   (layer, b, query)
     class branch        (layer*B + b, t, hw)   -- the reference's permute/contiguous copies
     (tuber_ava.py:133-139, transformer_layers.py:77-91) are never materialised.
+                        (b, t, hw) under TUBER_EVAL_PRECISION=fp32_class in eval: the layer copies are identical, the branch runs once
 """
 import copy
 
@@ -293,6 +294,65 @@ class DETR(nn.Module):
             norm(tgt, None, "transformer.decoder.norm", y=hs.data_ptr() + 2 * i * R * E, y32=hs32.data_ptr() + 4 * i * R * E)
         return hs32
 
+    def _class_branch_f32(self, st, feat32, hs32, B, Tp, hw, Q, lay_n, E, H):
+        """TUBER_EVAL_PRECISION=fp32_class (eval only): the class branch (tuber_ava.py:127-141; transformer_layers.py:71-97) in fp32 on the master
+        parameters, ONCE per clip.  The reference replicates src_c along the batch once per decoder layer; without dropout the six copies are
+        bit-identical, so class_proj, the factorised t / s encoder layer, its FFN and the cross-attention's K / V projection run on the
+        R0 = B * T' * hw rows (b, t, hw) of the body's fp32 output stream feat32, and the cross-attention's lay_n * B * Q queries (the fp32
+        decoder output hs32, rows (layer, b, q)) attend over their clip's keys at stride 0 over the layer.  Returns the fp32 logits rows
+        (layer, b, q)."""
+        dev, F32 = st.device, torch.float32
+        fp = lambda name: st.flat.data_ptr() + 4 * st.offsets[name]
+        C = feat32.shape[1]
+        R0, Rq, L = B * Tp * hw, lay_n * B * Q, Tp * hw
+        cl = self.encoder.layers[0]
+        FF = cl.linear1.out_features
+        scale = float(E // H) ** -0.5
+        P = "encoder.layers.0"
+
+        def lin(x, ldx, w, b, y, ldy, M, N, K, act=0):
+            lib.call("tuber_linear_f32", x, ldx, None, 0, 0, w, K, b, y, ldy, M, N, K, act)
+
+        def attn(q, mq, k, mk, v, mv, o, mo, nb, Lq, Lk):
+            maps = [T._map(*m) for m in (mq, mk, mv, mo)]          # (held until the call returns: the library reads them at launch)
+            lib.call("tuber_attention_f32_mapped", q, maps[0].ctypes.data, k, maps[1].ctypes.data, v, maps[2].ctypes.data,
+                     o, maps[3].ctypes.data, nb, H, Lq, Lk, scale)
+
+        src = torch.empty(R0, E, dtype=F32, device=dev)
+        lin(feat32, C, fp("class_proj.weight"), fp("class_proj.bias"), src, E, R0, E, C)
+        cat = torch.empty(R0, 2 * E, dtype=F32, device=dev)                         # [t-attention | s-attention] features
+        qkv = torch.empty(R0, 3 * E, dtype=F32, device=dev)
+        a = torch.empty(R0, E, dtype=F32, device=dev)
+        ao = torch.empty(R0, E, dtype=F32, device=dev)
+        q0, k0, v0 = qkv.data_ptr(), qkv.data_ptr() + 4 * E, qkv.data_ptr() + 8 * E
+        # t: sequence over hw, batch (b, t);  s: sequence over t at stride hw, batch (b, hw)
+        for nm, m, nb, Ls, col in (("t", (1, hw, 0, 1), B * Tp, hw, 0), ("s", (hw, L, 1, hw), B * hw, Tp, E)):
+            S = P + ".self_attn_" + nm
+            lin(src, E, fp(S + ".in_proj_weight"), fp(S + ".in_proj_bias"), qkv, 3 * E, R0, 3 * E, E)
+            attn(q0, (3 * E,) + m, k0, (3 * E,) + m, v0, (3 * E,) + m, a, (E,) + m, nb, Ls, Ls)
+            lin(a, E, fp(S + ".out_proj.weight"), fp(S + ".out_proj.bias"), ao, E, R0, E, E)
+            lib.call("tuber_layernorm_f32_rows", ao, E, src, E, fp(P + ".norm1_" + nm + ".weight"), fp(P + ".norm1_" + nm + ".bias"),
+                     cat.data_ptr() + 4 * col, 2 * E, R0, E, 1e-5)
+        h = torch.empty(R0, FF, dtype=F32, device=dev)
+        lin(cat, 2 * E, fp(P + ".linear1.weight"), fp(P + ".linear1.bias"), h, FF, R0, FF, 2 * E, 1)
+        lin(h, FF, fp(P + ".linear2.weight"), fp(P + ".linear2.bias"), ao, E, R0, E, FF)
+        enc = torch.empty(R0, E, dtype=F32, device=dev)
+        lib.call("tuber_layernorm_f32_rows", ao, E, src, E, fp(P + ".norm2.weight"), fp(P + ".norm2.bias"), enc, E, R0, E, 1e-5)
+        kv = torch.empty(R0, 2 * E, dtype=F32, device=dev)
+        lin(enc, E, fp("cross_attn.in_proj_weight") + 4 * E * E, fp("cross_attn.in_proj_bias") + 4 * E, kv, 2 * E, R0, 2 * E, E)
+        q = torch.empty(Rq, E, dtype=F32, device=dev)
+        lin(hs32, E, fp("cross_attn.in_proj_weight"), fp("cross_attn.in_proj_bias"), q, E, Rq, E, E)
+        # queries: sequence over q, batch (layer, b); keys / values: clip b's L rows, the same for every layer (s1 = 0)
+        ac = torch.empty(Rq, E, dtype=F32, device=dev)
+        km = (1, 0, L, B)
+        attn(q, (E, 1, Q, 0, 1), kv, (2 * E,) + km, kv.data_ptr() + 4 * E, (2 * E,) + km, ac, (E, 1, Q, 0, 1), lay_n * B, Q, L)
+        qc = torch.empty(Rq, E, dtype=F32, device=dev)
+        lin(ac, E, fp("cross_attn.out_proj.weight"), fp("cross_attn.out_proj.bias"), qc, E, Rq, E, E)
+        NC = self.class_fc.out_features
+        logits = torch.empty(Rq, NC, dtype=F32, device=dev)
+        lin(qc, E, fp("class_fc.weight"), fp("class_fc.bias"), logits, NC, Rq, NC, E)
+        return logits
+
     def _decoder_coop_launch(self, st, log, kvs, qpos, hs, kpm, B, Q, Lm, lay_n, pdrop, pattn):
         """tuber_decoder_coop_fwd over what the dry run of the decoder's op sequence logged (12 ops per layer: in-proj, attention, out-proj,
         norm1, q-proj, attention, out-proj, norm2, linear1, linear2, norm3, decoder.norm)."""
@@ -469,31 +529,39 @@ class DETR(nn.Module):
             boxes = T.sigmoid(tp, T.linear(tp, x, "bbox_embed.layers.2.weight", "bbox_embed.layers.2.bias", out_f32=True))
 
         # ---- class branch (tuber_ava.py:127-141; transformer_layers.py:71-97) ----
-        src_c = T.linear(tp, feat, "class_proj.weight", "class_proj.bias")         # rows (b, t, hw)
-        R0 = B * Tp * hw
-        rep = T.gather_sum(tp, src_c, (lay_n, 1, R0, 1, 0, 0, 1, 0, 1.0), (1, 1, R0, lay_n, 0, 0, 1, R0, 1.0))  # rows (l,b,t,hw)
-        LB = lay_n * B
-        cl = self.encoder.layers[0]
-        pa_c, p1_c, pf_c = cl.self_attn_t.dropout * on, cl.dropout1.p * on, cl.dropout.p * on
-        P = "encoder.layers.0"
-        cat = torch.empty(lay_n * R0, 2 * E, dtype=BF, device=dev)                  # [t-attention | s-attention] features
-        qkv = T.linear(tp, rep, P + ".self_attn_t.in_proj_weight", P + ".self_attn_t.in_proj_bias")
-        mp = (1, hw, 0, 1)                       # sequence over hw, batch (lb, t)
-        a = T.attention(tp, ((0, 0), (0, E), (0, 2 * E)), (LB * Tp, H, hw, hw, mp, mp), None, pa_c, qkv)
-        a = T.linear(tp, a, P + ".self_attn_t.out_proj.weight", P + ".self_attn_t.out_proj.bias")
-        T.layer_norm(tp, a, rep, P + ".norm1_t", drop=p1_c, out=(cat, 0, 0))
-        qkv = T.linear(tp, rep, P + ".self_attn_s.in_proj_weight", P + ".self_attn_s.in_proj_bias")
-        mp = (hw, Tp * hw, 1, hw)                # sequence over t, batch (lb, hw)
-        a = T.attention(tp, ((0, 0), (0, E), (0, 2 * E)), (LB * hw, H, Tp, Tp, mp, mp), None, cl.self_attn_s.dropout * on, qkv)
-        a = T.linear(tp, a, P + ".self_attn_s.out_proj.weight", P + ".self_attn_s.out_proj.bias")
-        T.layer_norm(tp, a, rep, P + ".norm1_s", drop=p1_c, out=(cat, 0, E))
-        enc = T.layer_norm(tp, self._ffn(tp, cat, P, pf_c), rep, P + ".norm2", drop=pf_c)
-        q = T.linear(tp, hs, "cross_attn.in_proj_weight", "cross_attn.in_proj_bias", rows=(0, E))
-        kv = T.linear(tp, enc, "cross_attn.in_proj_weight", "cross_attn.in_proj_bias", rows=(E, 3 * E))
-        a = T.attention(tp, ((0, 0), (1, 0), (1, E)), (LB, H, Q, Tp * hw, (1, Q, 0, 1), (1, Tp * hw, 0, 1)), None,
-                        self.cross_attn.dropout * on, q, kv)
-        q_class = T.linear(tp, a, "cross_attn.out_proj.weight", "cross_attn.out_proj.bias", drop=self.dropout.p * on)
-        logits = T.linear(tp, q_class, "class_fc.weight", "class_fc.bias", out_f32=True)
+        feat32, runner.last_y32 = getattr(runner, "last_y32", None), None
+        if hs32 is not None and ab.eval_class_f32():
+            # TUBER_EVAL_PRECISION=fp32_class: once per clip, in fp32.  (Without the fp32 decoder output hs32 -- E / H != 32 or
+            # TUBER_AB=eval_bf16_decoder -- the mode keeps the bf16 branch below.)
+            if feat32 is None:
+                raise RuntimeError("TUBER_EVAL_PRECISION=fp32_class: the backbone did not produce its fp32 output stream")
+            logits = self._class_branch_f32(st, feat32, hs32, B, Tp, hw, Q, lay_n, E, H)
+        else:
+            src_c = T.linear(tp, feat, "class_proj.weight", "class_proj.bias")         # rows (b, t, hw)
+            R0 = B * Tp * hw
+            rep = T.gather_sum(tp, src_c, (lay_n, 1, R0, 1, 0, 0, 1, 0, 1.0), (1, 1, R0, lay_n, 0, 0, 1, R0, 1.0))  # rows (l,b,t,hw)
+            LB = lay_n * B
+            cl = self.encoder.layers[0]
+            pa_c, p1_c, pf_c = cl.self_attn_t.dropout * on, cl.dropout1.p * on, cl.dropout.p * on
+            P = "encoder.layers.0"
+            cat = torch.empty(lay_n * R0, 2 * E, dtype=BF, device=dev)                  # [t-attention | s-attention] features
+            qkv = T.linear(tp, rep, P + ".self_attn_t.in_proj_weight", P + ".self_attn_t.in_proj_bias")
+            mp = (1, hw, 0, 1)                       # sequence over hw, batch (lb, t)
+            a = T.attention(tp, ((0, 0), (0, E), (0, 2 * E)), (LB * Tp, H, hw, hw, mp, mp), None, pa_c, qkv)
+            a = T.linear(tp, a, P + ".self_attn_t.out_proj.weight", P + ".self_attn_t.out_proj.bias")
+            T.layer_norm(tp, a, rep, P + ".norm1_t", drop=p1_c, out=(cat, 0, 0))
+            qkv = T.linear(tp, rep, P + ".self_attn_s.in_proj_weight", P + ".self_attn_s.in_proj_bias")
+            mp = (hw, Tp * hw, 1, hw)                # sequence over t, batch (lb, hw)
+            a = T.attention(tp, ((0, 0), (0, E), (0, 2 * E)), (LB * hw, H, Tp, Tp, mp, mp), None, cl.self_attn_s.dropout * on, qkv)
+            a = T.linear(tp, a, P + ".self_attn_s.out_proj.weight", P + ".self_attn_s.out_proj.bias")
+            T.layer_norm(tp, a, rep, P + ".norm1_s", drop=p1_c, out=(cat, 0, E))
+            enc = T.layer_norm(tp, self._ffn(tp, cat, P, pf_c), rep, P + ".norm2", drop=pf_c)
+            q = T.linear(tp, hs, "cross_attn.in_proj_weight", "cross_attn.in_proj_bias", rows=(0, E))
+            kv = T.linear(tp, enc, "cross_attn.in_proj_weight", "cross_attn.in_proj_bias", rows=(E, 3 * E))
+            a = T.attention(tp, ((0, 0), (1, 0), (1, E)), (LB, H, Q, Tp * hw, (1, Q, 0, 1), (1, Tp * hw, 0, 1)), None,
+                            self.cross_attn.dropout * on, q, kv)
+            q_class = T.linear(tp, a, "cross_attn.out_proj.weight", "cross_attn.out_proj.bias", drop=self.dropout.p * on)
+            logits = T.linear(tp, q_class, "class_fc.weight", "class_fc.bias", out_f32=True)
         shapes = ((lay_n, B, Q, logits.shape[1]), lb_shape, (lay_n, B, Q, 4))
         return tp, (logits, logits_b, boxes), shapes
 
