@@ -13,6 +13,8 @@ Forward schedule per bottleneck (ir_CSN_152.py:70-90), all BN statistics fused i
     cd = gemm_nt(gather(x), Wd)    [+stats]   -> bn_finalize(down_sample.1)      (first block of a stage)
     y  = relu(bn4(c4) + (bn_d(cd) | x))
 """
+import operator
+
 import torch
 from torch import nn
 
@@ -23,6 +25,7 @@ BN_EPS = 1e-3       # ir_CSN_152.py:15
 BN_MOM = 0.1        # ir_CSN_152.py:16
 BF = torch.bfloat16
 CMAX = 2048
+_MOMENTUM = operator.attrgetter("momentum")
 
 
 class ResNeXtBottleneck(nn.Module):
@@ -102,8 +105,9 @@ def build_CSN(cfg):
 # fused schedule
 # ------------------------------------------------------------------------------------------------
 class _BN:
-    """Raw device pointers of one BatchNorm layer (params in the flat store + per-layer scratch)."""
-    __slots__ = ("C", "gamma", "beta", "rmean", "rvar", "nbt", "dgamma", "dbeta", "scale", "shift", "mean", "invstd",
+    """Raw device pointers of one BatchNorm layer (params in the flat store + per-layer scratch), its index and its module (whose
+    ``momentum`` every training-mode finalisation reads)."""
+    __slots__ = ("idx", "mod", "C", "gamma", "beta", "rmean", "rvar", "nbt", "dgamma", "dbeta", "scale", "shift", "mean", "invstd",
                  "cA", "cB", "cC")
 
 
@@ -126,6 +130,7 @@ class CSNRunner:
             b = _BN()
             i = len(self._bn_index)
             self._bn_index[mod_prefix] = i
+            b.idx, b.mod = i, mod
             f, g = store.flat.data_ptr(), store.gflat.data_ptr()
             ow, ob = store.offsets[mod_prefix + ".weight"], store.offsets[mod_prefix + ".bias"]
             b.C = mod.num_features
@@ -173,6 +178,10 @@ class CSNRunner:
         rows = sorted(self._bn_rows, key=lambda r: r[0])
         self._bn_table = torch.tensor([[b.gamma, b.beta, b.rmean, b.rvar, b.scale, b.shift, b.C, 0] for _, b in rows], dtype=torch.int64, device=dev)
         self._bn_cmax = max(b.C for _, b in rows)
+        self._bn_mods = [b.mod for _, b in rows]
+        self._nbt_ptrs = [b.nbt for _, b in rows]
+        self._cum = []                      # layers finalised in cumulative mode (momentum=None) by the running forward
+        self._adv_tables = {}               # their counter-address tables (tuber_bn_count_advance), by layer indices
         self._affine_ready = False
         self._ws = {}
         self._fa_max = lib.query("tuber_bn_bwd_fa_max_rows")
@@ -198,9 +207,45 @@ class CSNRunner:
         lib.call("tuber_stat_rows_reduce", st0, st1, R, C, o0, o1)
         return o0, o1, R2
 
+    # -- BatchNorm momentum (nn.BatchNorm3d.momentum, read on every training-mode forward) ------------
+    def _finalize_form(self, bn, name):
+        """(launcher, momentum argument) of a training-mode finalisation of ``bn``: the reference's 0.1 keeps the original launch; any
+        other value goes to the ``*_ex`` form; momentum=None (cumulative average, what torch.optim.swa_utils.update_bn sets) passes -1 and
+        leaves the layer's num_batches_tracked to ``_advance_counts`` at the end of the forward"""
+        m = bn.mod.momentum
+        if m is None:
+            self._cum.append(bn.idx)
+            return name + "_ex", -1.0
+        if m == BN_MOM:
+            return name, BN_MOM
+        if m < 0:
+            raise ValueError("BatchNorm momentum must be >= 0 or None, got %r" % (m,))
+        return name + "_ex", float(m)
+
+    def _advance_counts(self):
+        """num_batches_tracked += 1 of every layer the forward finalised in cumulative mode, in one launch (none when no module has
+        momentum=None): the finalisations themselves only read the counter, so that all their workgroups see the same count"""
+        cum, self._cum = self._cum, []
+        if not cum:
+            return
+        key = tuple(cum)
+        t = self._adv_tables.get(key)
+        if t is None:                       # built by the first (eager) forward of this set; a capture replays the warm-up's table
+            t = self._adv_tables[key] = torch.tensor([self._nbt_ptrs[i] for i in key], dtype=torch.int64).to(self.dev)
+        lib.call("tuber_bn_count_advance", t, len(key))
+
+    def momentum_signature(self):
+        """((layer, momentum), ...) of every BatchNorm whose momentum is not the reference's 0.1 -- () on the default path, which costs one
+        pass of C-level comparisons: a captured training step bakes the values into its launches (training.GraphedTrainStep._key)"""
+        moms = list(map(_MOMENTUM, self._bn_mods))
+        if moms.count(BN_MOM) == len(moms):
+            return ()
+        return tuple((i, m) for i, m in enumerate(moms) if m != BN_MOM)
+
     def _bn_train(self, bn, st0, st1, R, count):
         st0, st1, R = self._stat_rows(st0, st1, R, bn.C)
-        lib.call("tuber_bn_finalize", st0, st1, R, bn.C, float(count), bn.gamma, bn.beta, bn.rmean, bn.rvar, bn.nbt, BN_MOM, BN_EPS,
+        name, mom = self._finalize_form(bn, "tuber_bn_finalize")
+        lib.call(name, st0, st1, R, bn.C, float(count), bn.gamma, bn.beta, bn.rmean, bn.rvar, bn.nbt, mom, BN_EPS,
                  bn.scale, bn.shift, bn.mean, bn.invstd)
 
     def _bn_eval(self, bn):
@@ -236,6 +281,7 @@ class CSNRunner:
         if not train:
             lib.call("tuber_bn_eval_affine_multi", self._bn_table, self._bn_table.shape[0], self._bn_cmax, BN_EPS)
         self._affine_ready = not train
+        self._cum = []
         try:
             c0 = torch.empty(M0, 64, dtype=BF, device=dev)
             bn0 = self.stem_bn
@@ -253,6 +299,7 @@ class CSNRunner:
             lib.call("tuber_stem_pool_fwd", c0, self.stem_bn.scale, self.stem_bn.shift, x, arg, B * T, Ho, Wo, Hp, Wp)
             saved = {"stem": (clips if train else None, None, c0, arg, (B, T, Ho, Wo, Hp, Wp)), "blocks": [], "lo": 0}
             x, (Ti, Hi, Wi) = self._forward_blocks(x, B, (T, Hp, Wp), 0, len(self.blocks), train, saved["blocks"])
+            self._advance_counts()
         finally:
             self._affine_ready = False          # a block range run on its own afterwards (run_blocks) derives its own
         feat = x.view(B, Ti, Hi, Wi, 2048)
@@ -321,7 +368,8 @@ class CSNRunner:
                 st0 = st1 = None
             if pend is not None:
                 p0, p1, pR = self._stat_rows(pend[0], pend[1], pend[2], P)
-                lib.call("tuber_dwconv_tile_fwd_bn", c1, p0, p1, pR, float(pend[3]), b1.gamma, b1.beta, b1.rmean, b1.rvar, b1.nbt, BN_MOM, BN_EPS,
+                name, mom = self._finalize_form(b1, "tuber_dwconv_tile_fwd_bn")
+                lib.call(name, c1, p0, p1, pR, float(pend[3]), b1.gamma, b1.beta, b1.rmean, b1.rvar, b1.nbt, mom, BN_EPS,
                          b1.scale, b1.shift, b1.mean, b1.invstd, d["w3"], c3, st0, st1, B, Ti, Hi, Wi, P)
                 pend = None
             elif tile:
@@ -406,7 +454,9 @@ class CSNRunner:
         Returns (y rows of block hi-1, (To, Ho, Wo), saved) -- ``saved`` feeds ``backward_blocks``."""
         B, Ti, Hi, Wi = geom
         saved = {"blocks": [], "lo": lo, "B": B}
+        self._cum = []
         y, g = self._forward_blocks(x.contiguous(), B, (Ti, Hi, Wi), lo, hi, train, saved["blocks"])
+        self._advance_counts()
         return y, g, saved
 
     def backward_blocks(self, saved, dy, need_dx=True):

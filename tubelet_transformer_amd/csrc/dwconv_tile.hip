@@ -53,7 +53,8 @@ struct TileArgs {
     // every workgroup derives scale / shift of its 64 channels from the producer's bR partial rows (bst0 = sum x, bst1 = sum x^2,
     // bcount, bgamma as above); the workgroups with blockIdx.x == 0 publish scale / shift / mean / invstd for the backward and update
     // the running statistics
-    const float* fbeta; float* frmean; float* frvar; long long* fnbt; float fmom, feps;
+    // (fcum: cumulative average of momentum=None -- factor 1 / (*fnbt + 1), *fnbt left to tuber_bn_count_advance; as tuber_bn_finalize_ex)
+    const float* fbeta; float* frmean; float* frvar; long long* fnbt; float fmom, feps; int fcum;
     float* fscale; float* fshift; float* fmean; float* finvstd;
     TileGeom g;
 };
@@ -221,10 +222,11 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
                 a.finvstd[cc] = invstd;
                 if (a.frmean) {
                     const double unbiased = count > 1.f ? var * (double)count / ((double)count - 1.0) : var;
-                    a.frmean[cc] = (1.f - a.fmom) * f_rm + a.fmom * (float)mean;
-                    a.frvar[cc] = (1.f - a.fmom) * f_rv + a.fmom * (float)unbiased;
+                    const float m = a.fcum ? (float)(1.0 / (double)(*a.fnbt + 1)) : a.fmom;
+                    a.frmean[cc] = (1.f - m) * f_rm + m * (float)mean;
+                    a.frvar[cc] = (1.f - m) * f_rv + m * (float)unbiased;
                 }
-                if (a.fnbt && by == 0 && tid == 0) *a.fnbt += 1;
+                if (a.fnbt && !a.fcum && by == 0 && tid == 0) *a.fnbt += 1;
             }
         }
         __syncthreads();
@@ -837,16 +839,17 @@ int tuber_dwconv_tile_fwd(const void* x, const float* sc, const float* sh, const
 // tuber_dwconv_tile_fwd with the training-mode BatchNorm in front of it (bn1) finalised INSIDE the launch: pst0 / pst1 = the producing
 // conv's R partial rows [R][C] (sum x, sum x^2), count = rows behind them.  Writes scale / shift / mean / invstd [C] and updates
 // rmean / rvar / nbt (NULL: no running statistics) exactly as tuber_bn_finalize does -- that launch disappears from the forward chain.
-int tuber_dwconv_tile_fwd_bn(const void* x, const float* pst0, const float* pst1, int R, float count, const float* gamma, const float* beta,
-                             float* rmean, float* rvar, long long* nbt, float momentum, float eps, float* scale, float* shift,
-                             float* mean, float* invstd, const float* w, void* out, float* st0, float* st1,
-                             int N, int T, int H, int W, int C, hipStream_t stream) {
+static int dwconv_tile_fwd_fin(const void* x, const float* pst0, const float* pst1, int R, float count, const float* gamma, const float* beta,
+                               float* rmean, float* rvar, long long* nbt, float momentum, float eps, int cumulative, float* scale, float* shift,
+                               float* mean, float* invstd, const float* w, void* out, float* st0, float* st1,
+                               int N, int T, int H, int W, int C, hipStream_t stream) {
     if ((C & 63) || R <= 0 || !pst0 || !pst1 || !gamma || !beta || !scale || !shift || !mean || !invstd || (rmean == nullptr) != (rvar == nullptr))
         return TUBER_EINVAL;
+    if (cumulative && rmean && !nbt) return TUBER_EINVAL;
     TileArgs a{};
     a.in = (const bf16*)x; a.w = w; a.out = (bf16*)out; a.st0 = st0; a.st1 = st1;
     a.bst0 = pst0; a.bst1 = pst1; a.bR = R; a.bcount = count; a.bgamma = gamma;
-    a.fbeta = beta; a.frmean = rmean; a.frvar = rvar; a.fnbt = nbt; a.fmom = momentum; a.feps = eps;
+    a.fbeta = beta; a.frmean = rmean; a.frvar = rvar; a.fnbt = nbt; a.fmom = momentum; a.feps = eps; a.fcum = cumulative;
     a.fscale = scale; a.fshift = shift; a.fmean = mean; a.finvstd = invstd;
     a.g = make_geom(N, T, H, W, C);
     const TileGeom& g = a.g;
@@ -855,6 +858,24 @@ int tuber_dwconv_tile_fwd_bn(const void* x, const float* pst0, const float* pst1
     TUBER_LDS_OPT_IN(opt, dwconv_tile_fwd_fin_kernel, lds);
     hipLaunchKernelGGL(dwconv_tile_fwd_fin_kernel, dim3(g.N * g.tchunks * g.htiles * g.wtiles, g.C / 64), dim3(512), lds, stream, a);
     TUBER_RETURN_LAUNCH();
+}
+
+int tuber_dwconv_tile_fwd_bn(const void* x, const float* pst0, const float* pst1, int R, float count, const float* gamma, const float* beta,
+                             float* rmean, float* rvar, long long* nbt, float momentum, float eps, float* scale, float* shift,
+                             float* mean, float* invstd, const float* w, void* out, float* st0, float* st1,
+                             int N, int T, int H, int W, int C, hipStream_t stream) {
+    return dwconv_tile_fwd_fin(x, pst0, pst1, R, count, gamma, beta, rmean, rvar, nbt, momentum, eps, 0, scale, shift, mean, invstd,
+                               w, out, st0, st1, N, T, H, W, C, stream);
+}
+
+// tuber_dwconv_tile_fwd_bn with the momentum of tuber_bn_finalize_ex: as given, or (momentum < 0) the cumulative average of momentum=None,
+// which reads *nbt and leaves it for tuber_bn_count_advance
+int tuber_dwconv_tile_fwd_bn_ex(const void* x, const float* pst0, const float* pst1, int R, float count, const float* gamma, const float* beta,
+                                float* rmean, float* rvar, long long* nbt, float momentum, float eps, float* scale, float* shift,
+                                float* mean, float* invstd, const float* w, void* out, float* st0, float* st1,
+                                int N, int T, int H, int W, int C, hipStream_t stream) {
+    return dwconv_tile_fwd_fin(x, pst0, pst1, R, count, gamma, beta, rmean, rvar, nbt, momentum, eps, momentum < 0.f ? 1 : 0, scale, shift,
+                               mean, invstd, w, out, st0, st1, N, T, H, W, C, stream);
 }
 
 int tuber_dwconv_tile_bwd_data(const void* gout, const float* w, const void* x, const float* sc, const float* sh, void* dz,

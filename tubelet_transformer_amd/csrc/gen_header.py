@@ -214,6 +214,9 @@ DOC = {
                                 "finalised inside the conv -- every workgroup derives scale / shift of its 64 channels from the producing conv's R partial rows "
                                 "(pst0 = sum x, pst1 = sum x^2 over `count` rows; fp64 sums, the arithmetic of tuber_bn_finalize expression for expression), the first "
                                 "workgroup of each channel group writes scale / shift / mean / invstd [C] and updates rmean / rvar / nbt (NULL: none). Other arguments as tuber_dwconv_tile_fwd.",
+    "tuber_dwconv_tile_fwd_bn_ex": "tuber_dwconv_tile_fwd_bn with the momentum contract of tuber_bn_finalize_ex: the module's momentum as given, or (momentum < 0) "
+                                   "the cumulative average of nn.BatchNorm3d(momentum=None) with nbt read, not written (tuber_bn_count_advance). "
+                                   "reference: ir_CSN_152.py:46-51 under torch.optim.swa_utils.update_bn.",
     "tuber_dwconv_tile_fwd": "stride-1 conv3 (ir_CSN_152.py:48-51) with the input planes staged once per workgroup in an LDS ring (activated on the way in): "
                              "same contract as tuber_dwconv_fwd for st = ss = 1; partial-stat rows = tuber_dwconv_tile_blocks.",
     "tuber_dwconv_tile_bwd_data": "LDS-staged data gradient of the stride-1 conv3, fused with the backward of relu(bn1(.)) like tuber_dwconv_bwd_data.",
@@ -223,6 +226,13 @@ DOC = {
     "tuber_dw_wgrad_reduce": "dw[c][tap] (+)= sum_r partial[r][tap][c]: second stage of the depthwise weight gradient.",
     "tuber_bn_finalize": "training-mode nn.BatchNorm3d(eps=1e-3, momentum=0.1) statistics (ir_CSN_152.py:15-16,46,56,64,119,154): partial rows -> "
                          "mean/invstd, scale=gamma*invstd, shift=beta-mean*scale, running_mean/var (unbiased) and num_batches_tracked update.",
+    "tuber_bn_finalize_ex": "tuber_bn_finalize with the module's momentum as given (nn.BatchNorm3d.momentum, ir_CSN_152.py:15-16,46,56,64,119,154; "
+                            "running = (1 - m) * running + m * batch, num_batches_tracked += 1). momentum < 0 selects the cumulative average of "
+                            "momentum=None (torch.nn.modules.batchnorm._BatchNorm.forward): m = 1 / (n + 1) with n = *num_batches_tracked read on the device, "
+                            "which this launch leaves unchanged so that every workgroup sees the same n -- tuber_bn_count_advance increments it after the forward.",
+    "tuber_bn_count_advance": "num_batches_tracked += 1 (the `self.num_batches_tracked.add_(1)` of _BatchNorm.forward under momentum=None) for every BatchNorm "
+                              "of a DEVICE table of n int64 counter addresses, in ONE launch: the layers finalised in cumulative mode by tuber_bn_finalize_ex / "
+                              "tuber_dwconv_tile_fwd_bn_ex during the forward.",
     "tuber_stat_rows_reduce": "first stage for long partial-statistics lists (R > 512 rows: layer1): [R][C] x2 -> [tuber_stat_rows_reduced(R)][C] x2.",
     "tuber_stat_rows_reduced": "rows left by tuber_stat_rows_reduce (R itself when no first stage is needed).",
     "tuber_bn_eval_affine": "eval-mode BatchNorm3d folded to scale/shift from the running statistics.",

@@ -81,7 +81,7 @@ __global__ __launch_bounds__(NTH) void bn_finalize_kernel(
     const float* __restrict__ gamma, const float* __restrict__ beta,
     float* __restrict__ rmean, float* __restrict__ rvar, long long* __restrict__ nbt,
     float momentum, float eps,
-    float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ mean_out, float* __restrict__ invstd_out) {
+    float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ mean_out, float* __restrict__ invstd_out, int cumulative) {
     __shared__ double red[2][32][33];
     const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5;
     const int c = blockIdx.x * 32 + cl;
@@ -103,11 +103,20 @@ __global__ __launch_bounds__(NTH) void bn_finalize_kernel(
         invstd_out[c] = invstd;
         if (rmean) {
             const double unbiased = count > 1.f ? var * (double)count / ((double)count - 1.0) : var;
-            rmean[c] = (1.f - momentum) * rm0 + momentum * (float)mean;
-            rvar[c] = (1.f - momentum) * rv0 + momentum * (float)unbiased;
+            // cumulative average (momentum=None): factor 1 / (n + 1) from the count BEFORE this batch -- nobody writes *nbt in this launch
+            // (tuber_bn_count_advance does, after the forward), so every workgroup reads the same n
+            const float m = cumulative ? (float)(1.0 / (double)(*nbt + 1)) : momentum;
+            rmean[c] = (1.f - m) * rm0 + m * (float)mean;
+            rvar[c] = (1.f - m) * rv0 + m * (float)unbiased;
         }
     }
-    if (nbt && blockIdx.x == 0 && threadIdx.x == 0) *nbt += 1;
+    if (nbt && !cumulative && blockIdx.x == 0 && threadIdx.x == 0) *nbt += 1;
+}
+
+// num_batches_tracked += 1 for every BatchNorm of a device table of counter addresses (the layers finalised in cumulative mode)
+__global__ void bn_count_advance_kernel(const long* __restrict__ table, int n) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) *reinterpret_cast<long long*>(table[i]) += 1;
 }
 
 __global__ void bn_eval_affine_kernel(const float* __restrict__ gamma, const float* __restrict__ beta,
@@ -803,16 +812,41 @@ int tuber_stat_rows_reduce(const float* st0, const float* st1, int R, int C, flo
     TUBER_RETURN_LAUNCH();
 }
 
-int tuber_bn_finalize(const float* st0, const float* st1, int R, int C, float count, const float* gamma, const float* beta,
-                      float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps,
-                      float* scale, float* shift, float* mean, float* invstd, hipStream_t stream) {
+static int bn_finalize_launch(const float* st0, const float* st1, int R, int C, float count, const float* gamma, const float* beta,
+                              float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps,
+                              float* scale, float* shift, float* mean, float* invstd, int cumulative, hipStream_t stream) {
     if (R <= 0 || C <= 0) return TUBER_EINVAL;
     if (R <= 128)
         hipLaunchKernelGGL(bn_finalize_kernel<256>, dim3(ceil_div(C, 32)), dim3(256), 0, stream, st0, st1, R, C, count, gamma, beta,
-                           running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift, mean, invstd);
+                           running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift, mean, invstd, cumulative);
     else
         hipLaunchKernelGGL(bn_finalize_kernel<1024>, dim3(ceil_div(C, 32)), dim3(1024), 0, stream, st0, st1, R, C, count, gamma, beta,
-                           running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift, mean, invstd);
+                           running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift, mean, invstd, cumulative);
+    TUBER_RETURN_LAUNCH();
+}
+
+int tuber_bn_finalize(const float* st0, const float* st1, int R, int C, float count, const float* gamma, const float* beta,
+                      float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps,
+                      float* scale, float* shift, float* mean, float* invstd, hipStream_t stream) {
+    return bn_finalize_launch(st0, st1, R, C, count, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
+                              scale, shift, mean, invstd, 0, stream);
+}
+
+// tuber_bn_finalize with the module's momentum as given; momentum < 0 selects the cumulative average of momentum=None: factor 1 / (n + 1)
+// with n = *num_batches_tracked, which this launch then leaves unchanged (tuber_bn_count_advance advances it once the forward is done)
+int tuber_bn_finalize_ex(const float* st0, const float* st1, int R, int C, float count, const float* gamma, const float* beta,
+                         float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps,
+                         float* scale, float* shift, float* mean, float* invstd, hipStream_t stream) {
+    const int cumulative = momentum < 0.f;
+    if (cumulative && running_mean && !num_batches_tracked) return TUBER_EINVAL;
+    if ((running_mean == nullptr) != (running_var == nullptr)) return TUBER_EINVAL;
+    return bn_finalize_launch(st0, st1, R, C, count, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps,
+                              scale, shift, mean, invstd, cumulative, stream);
+}
+
+int tuber_bn_count_advance(const long* table, int n, hipStream_t stream) {
+    if (!table || n <= 0) return TUBER_EINVAL;
+    hipLaunchKernelGGL(bn_count_advance_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, stream, table, n);
     TUBER_RETURN_LAUNCH();
 }
 
