@@ -2,14 +2,19 @@
 """TubeR training-step throughput on MI355X (the headline metric of BASELINE.json).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
     python bench.py --gpus N ...            (no launcher: bench.py starts its own N ranks, one process per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A "step" = one full optimisation step of TubeR_CSN152_AVA21 (forward, Hungarian-matched criterion, backward, global-norm
 clip 0.1, AdamW) on 2 synthetic clips 3x32x256x340 per GPU, model in train() mode with dropout ON, inputs resident in HBM.
-Rank 0 prints ONE JSON line: whole-job clips/s, plus
+Rank 0 prints ONE JSON line: whole-job clips/s.  A plain run does only what that figure needs: set up, warm up, time the steps,
+write --dump-outputs, print the line.  With --full the line also carries
   * "roofline": the dominant kernel family of the step (picked by a HIP-event pre-pass over every launch), its
     ALGORITHMIC bytes per launch / average launch duration measured with HIP events INSIDE the timed steps, vs the 8 TB/s HBM peak;
+  * "ms_per_step_fed_device_copy" and (headline config) "input_pipeline": the same steps with the batch copied in / fed through
+    the GPU input pipeline;
+  * "comm" (N > 1 or a forced one-rank DDP run): the gradient exchange, measured over a few extra steps;
   * "cpu_baseline": the CPU oracle (stock PyTorch CPU ops, fp32, same graph) timed on this box's host cores on ONE clip
     of the same workload (N=1, rank 0 only).
 """
@@ -451,10 +456,14 @@ def main():
     ap.add_argument("--width", type=int, default=340)
     ap.add_argument("--pretrained-freeze", action="store_true", help="freeze stem + layer1 + layer2 like the pretrained recipe "
                     "(load_csn_mat, ir_CSN_152.py:251-254,301-303): the 704-GFLOP/clip workload of every real training run")
+    ap.add_argument("--full", action="store_true", help="also measure and check what the headline figure does not need: the roofline "
+                    "of the dominant kernel family, the steps with the batch copied in and behind the input pipeline, the gradient "
+                    "exchange (comm) and the CPU baseline; the --no-* switches below leave parts of it out")
     ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-roofline", action="store_true", help="no roofline pre-pass: the timed steps follow the warm-up directly "
+                    "(otherwise two untimed eager steps come between them, in a plain run too, so both start from the same state)")
     ap.add_argument("--eager", action="store_true", help="issue every launch from Python instead of replaying the captured hipGraphs")
-    ap.add_argument("--no-input-pipeline", action="store_true", help="skip the second measurement with the uint8 input feed inside the timed loop (default on the headline command)")
+    ap.add_argument("--no-input-pipeline", action="store_true", help="skip the second measurement with the uint8 input feed inside the timed loop (default on the headline command with --full)")
     ap.add_argument("--with-input-pipeline", action="store_true", help="after the headline measurement, time the same steps again with every "
                     "batch fed as uint8 frames through input_pipeline.ClipBatch.to(device) (H2D + resize + flip/crop/jitter/normalise/collate "
                     "on a side stream, double-buffered) and report both figures")
@@ -551,17 +560,21 @@ def main():
         step()
     dominant, prepass = None, None
     if not args.no_roofline:
+        # the pre-pass trains two more steps, so the timed steps start from the state these leave behind; a plain run takes the same
+        # two steps (only without the HIP events around the launches) so that its timed steps are those of a --full run
         eager_step()                                    # untimed: first eager step after the capture (allocator warm-up)
         torch.cuda.synchronize()
-        timer = LaunchTimer()
-        lib.set_launch_hook(timer)
+        timer = LaunchTimer() if args.full else None
+        if timer:
+            lib.set_launch_hook(timer)
         eager_step()
         torch.cuda.synchronize()
-        lib.set_launch_hook(None)
-        prepass = timer.summary()
-        if os.environ.get("TUBER_BENCH_SHAPES") and rank == 0:
-            print("\n".join(timer.by_shape(int(os.environ["TUBER_BENCH_SHAPES"]))), file=sys.stderr, flush=True)
-        dominant = dominant_from_trace(prepass, headline_run) or max((k for k in prepass if prepass[k]["bytes"] > 0), key=lambda k: prepass[k]["ms"])
+        if timer:
+            lib.set_launch_hook(None)
+            prepass = timer.summary()
+            if os.environ.get("TUBER_BENCH_SHAPES") and rank == 0:
+                print("\n".join(timer.by_shape(int(os.environ["TUBER_BENCH_SHAPES"]))), file=sys.stderr, flush=True)
+            dominant = dominant_from_trace(prepass, headline_run) or max((k for k in prepass if prepass[k]["bytes"] > 0), key=lambda k: prepass[k]["ms"])
     fence()
     t0 = time.perf_counter()
     loss = None
@@ -582,7 +595,9 @@ def main():
         timed_steps = min(args.steps, 3)
     red = getattr(model.engine()[0], "reducer", None)
     comm_info = None
-    if red is not None:
+    if red is not None and not args.full:
+        red.check()             # a lost stream-flag signal would have broken the order of the timed steps
+    elif red is not None:
         # the gradient exchange as it ran in the timed region + a few measured steps (HIP events around the optimizer stream's wait
         # for the transport = EXPOSED communication time), for the first multi-GPU run to be diagnosable from its one JSON line
         red.measure = True
@@ -604,7 +619,7 @@ def main():
         comm_info["graph_cuts"] = parts
     pipe_info = None
     fed_d2d_ms = None
-    if mode == "hipgraph" and rank == 0 and world == 1:
+    if args.full and mode == "hipgraph" and rank == 0 and world == 1:
         # the same K steps with a batch that is NOT already in the captured input buffers: + one 67 MB device-to-device copy per step (what
         # rounds 1-4 timed; the headline since round 5 is the resident form the contract prescribes)
         fence()
@@ -613,7 +628,7 @@ def main():
             step(clips)
         fence()
         fed_d2d_ms = 1e3 * (time.perf_counter() - t1) / args.steps
-    if args.with_input_pipeline or (headline_run and world == 1 and not args.no_input_pipeline and not args.no_roofline and mode == "hipgraph"):
+    if args.with_input_pipeline or (args.full and headline_run and world == 1 and not args.no_input_pipeline and not args.no_roofline and mode == "hipgraph"):
         pipe_info = timed_with_input_pipeline(step, args, hw, dev, fence)
     t = torch.tensor([dt], device=dev, dtype=torch.float64)
     if world > 1:
@@ -630,7 +645,7 @@ def main():
         "metric": "clips/sec (TubeR CSN-152 AVA2.1 training step fwd+bwd+clip+AdamW, 32x256x340 clips; whole job)" if headline else
                   "clips/sec (%s training step fwd+bwd+clip+AdamW, 32x%dx%d clips; whole job)" % (args.config.replace(".yaml", ""), hw[0], hw[1]),
         "value": round(total_clips / dt, 3), "unit": "clips/s", "per_gpu": round(total_clips / dt / world, 3),
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms, 3), "timed_region_s": round(dt, 4),
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "full": args.full, "ms_per_step": round(ms, 3), "timed_region_s": round(dt, 4),
         "ms_per_step_resident": round(ms, 3),
         "ms_per_step_fed_device_copy": round(fed_d2d_ms, 3) if fed_d2d_ms is not None else None,
         "higher_is_better": True,
@@ -712,7 +727,7 @@ def main():
         pipe_info["clips_per_s"] = round(args.batch * world * args.steps / pipe_info.pop("seconds"), 3)
         line["input_pipeline"] = pipe_info
         line["ms_per_step_fed_input_pipeline"] = pipe_info["ms_per_step"]
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         line["cpu_baseline"] = cpu_baseline(cfg, hw, dataset, batch=args.batch)
     # RCCL prints its banner through C stdio, which a pipe holds back until exit: tear the communicators down and drain every rank's
     # C buffers first, so that the JSON line is the last line this job writes to stdout.

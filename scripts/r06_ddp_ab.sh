@@ -4,7 +4,7 @@
 # two interleaved rounds.
 O=gpurun_out/${1:-r06_ddp}
 mkdir -p $O
-B="timeout 300 python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-roofline"
+B="timeout 300 python bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-roofline"
 for r in 1 2; do
   $B > $O/plain_$r.json 2>$O/plain_$r.err
   TUBER_FORCE_DDP=1 TUBER_DDP_CUTS=3 $B > $O/ddp_cut3_$r.json 2>/dev/null

@@ -2,7 +2,7 @@
 # round 6: the one-rank forced-DDP line: hybrid edges (counter at the first cut, events behind it; default) / all counters / all events / no edges / plain.  Same box, two rounds.
 O=gpurun_out/${1:-r06_ddp_hybrid}
 mkdir -p $O
-B="timeout 300 python bench.py --steps 30 --warmup 3 --no-cpu-baseline --no-roofline"
+B="timeout 300 python bench.py --full --steps 30 --warmup 3 --no-cpu-baseline --no-roofline"
 for r in 1 2; do
   $B > $O/plain_$r.json 2>/dev/null
   TUBER_FORCE_DDP=1 $B > $O/ddp_cut43_hybrid_$r.json 2>$O/err_hybrid.txt

@@ -620,7 +620,7 @@ def test_two_rank_bench_captures_the_graph_step(tmp_path):
     env.update(TUBER_SHARE_GPU="1", TUBER_DIST_BACKEND="gloo")
     # the driver's form: `python bench.py --gpus N`, no launcher -- bench.py starts its own ranks (VERDICT r03 missing #2)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--height", "64",
-           "--width", "96", "--no-cpu-baseline", "--no-roofline"]
+           "--width", "96", "--full", "--no-cpu-baseline", "--no-roofline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-2000:]
     assert "capture failed" not in r.stdout + r.stderr, (r.stdout + r.stderr)[-2000:]
@@ -633,6 +633,24 @@ def test_two_rank_bench_captures_the_graph_step(tmp_path):
     c = j["comm"]
     assert c["world"] == 2 and "process group (gloo)" in c["transport"] and c["ranks_seen_by_rccl"] is None
     assert c["windows_per_step"] >= 2 and c["bytes_per_step"] > 4 * 40e6 and "graph A" in c["launch"]
+
+
+def test_plain_bench_line_is_the_headline_only():
+    """A plain ``bench.py`` run measures the headline alone: the roofline, the fed-batch / input-pipeline steps and the CPU baseline
+    come with ``--full`` only."""
+    import json
+    import subprocess
+    import sys
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "TUBER_FORCE_DDP")}
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1", "--height", "64", "--width", "96"]
+    r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
+    assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
+    j = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert j["full"] is False and j["config"]["launch_mode"] == "hipgraph" and j["value"] > 0 and j["ms_per_step"] > 0
+    assert j["unit"] == "clips/s" and j["higher_is_better"] is True and j["dtype"] == "bf16" and math.isfinite(j["final_loss"])
+    assert j["ms_per_step_fed_device_copy"] is None
+    for k in ("roofline", "kernel_breakdown_ms_per_step", "input_pipeline", "comm", "cpu_baseline"):
+        assert k not in j, k
 
 
 def test_one_rank_of_a_multi_gpu_lease_minus_its_peers(tmp_path):
@@ -652,7 +670,7 @@ def test_one_rank_of_a_multi_gpu_lease_minus_its_peers(tmp_path):
     for k in ("TUBER_SHARE_GPU", "TUBER_DIST_BACKEND", "TUBER_NO_OWN_RCCL"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--height", "64", "--width", "96",
-           "--no-cpu-baseline", "--no-roofline"]
+           "--full", "--no-cpu-baseline", "--no-roofline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     assert r.returncode == 0, (r.stdout + r.stderr)[-3000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
