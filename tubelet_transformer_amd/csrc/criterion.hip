@@ -161,7 +161,9 @@ __global__ __launch_bounds__(256) void criterion_loss_kernel(CritArgs a) {
             const float w = j >= 0 ? a.pos_weight : 1.f;
             ce += w * (t * softplus_clamped(-x) + (1.f - t) * softplus_clamped(x));
             const float sg = 1.f / (1.f + __expf(-x));
-            a.g_logits[(base + bq) * a.C + c] = w * (sg - t) * inv;
+            // where a log is clamped (softplus >= 100, |x| >= 100) its term is constant: no gradient, as in the reference's BCE
+            const float gpos = -x >= 100.f ? 0.f : t * (sg - 1.f), gneg = x >= 100.f ? 0.f : (1.f - t) * sg;
+            a.g_logits[(base + bq) * a.C + c] = w * (gpos + gneg) * inv;
         }
         ce = block_sum(ce, red) * inv;
     } else {

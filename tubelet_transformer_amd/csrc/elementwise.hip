@@ -12,11 +12,6 @@ __global__ void cast_f32_bf16_kernel(const float* __restrict__ s, bf16* __restri
         for (long j = i; j < n; ++j) d[j] = f2bf(s[j]);
     }
 }
-__global__ void cast_bf16_f32_kernel(const bf16* __restrict__ s, float* __restrict__ d, long n) {
-    const long i = (long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i < n) d[i] = bf2f(s[i]);
-}
-
 // d = float(s) * scale, 8 elements (16 B in, 32 B out) per thread per trip; n and both pointers 16-byte aligned except the tail
 __global__ __launch_bounds__(256) void cast_bf16_f32_scale_kernel(const bf16* __restrict__ s, float* __restrict__ d, long n, float scale) {
     const long n8 = n >> 3;
@@ -279,10 +274,6 @@ extern "C" {
 
 int tuber_cast_f32_bf16(const float* src, void* dst, long n, hipStream_t stream) {
     hipLaunchKernelGGL(cast_f32_bf16_kernel, dim3(ceil_div(ceil_div(n, 8), 256)), dim3(256), 0, stream, src, (bf16*)dst, n);
-    TUBER_RETURN_LAUNCH();
-}
-int tuber_cast_bf16_f32(const void* src, float* dst, long n, hipStream_t stream) {
-    hipLaunchKernelGGL(cast_bf16_f32_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, stream, (const bf16*)src, dst, n);
     TUBER_RETURN_LAUNCH();
 }
 int tuber_cast_bf16_f32_scale(const void* src, float* dst, long n, float scale, hipStream_t stream) {

@@ -240,7 +240,6 @@ DOC = {
     "tuber_bn_bwd_apply": "dx = cA*dz + cB*x + cC (BatchNorm backward apply), bf16 [M,C].",
     "tuber_block_out_fwd": "bottleneck join y = relu(bn4(c4) + shortcut) (ir_CSN_152.py:81-90); shortcut = res or bn_ds(res) when rs/rh given.",
     "tuber_block_out_bwd": "backward of the join: dz = dy*[y>0] and the partial statistics of bn4 (and of the down_sample BN).",
-    "tuber_relu_bn_bwd_reduce": "dz = g*[x*sc+sh>0] + partial (sum dz, sum dz*x): backward of relu(bn(x)) when not fused elsewhere.",
     "tuber_rowblock_count": "partial-stat rows written by the row-blocked reduce kernels for M rows.",
     "tuber_layernorm_fwd": "y = LayerNorm(Dropout_p(x) (+ res)) over E in {256, 2048}, eps 1e-5 (nn.LayerNorm, transformer.py:163-167,229-247,116-123; "
                            "transformer_layers.py:84,91,96,437-445); saves xhat (bf16) and rstd for backward.",
@@ -289,7 +288,6 @@ DOC = {
     "tuber_criterion_loss": "all loss terms of all layers and their gradients w.r.t. logits / actor logits / boxes in one launch: AVA 3-way weighted CE + "
                             "weighted BCE (models/criterion.py:42-81), JHMDB (C+1)-way CE (:237-262), L1 + GIoU box losses (:97-117).",
     "tuber_cast_f32_bf16": "fp32 -> bf16 copy (bf16 shadow of the fp32 master weights).",
-    "tuber_cast_bf16_f32": "bf16 -> fp32 copy.",
     "tuber_cast_transpose": "W[R][C] fp32 -> W^T[C][ldt] bf16 (B operand of the data-gradient GEMM).",
     "tuber_rows_gather_sum": "out[(a,b,c)] = mul * sum_d in[a*sa+b*sb+c*sc+d*sd] over rows of E bf16: temporal AvgPool3d((4,1,1)) "
                              "(backbone_builder.py:44,73), its backward (broadcast), the x6 replication of src_c (tuber_ava.py:133) and its backward (sum).",

@@ -292,47 +292,6 @@ __global__ __launch_bounds__(256) void block_out_bwd_kernel(
     }
 }
 
-// generic "relu(bn(x))-masked gradient + stats":  dz = g * [x*sc+sh > 0]; partial sum dz, sum dz*x
-// (used for the stem BN; the bottleneck BNs get this fused into gemm / dwconv epilogues)
-__global__ __launch_bounds__(256) void relu_bn_bwd_reduce_kernel(
-    const bf16* __restrict__ g, const bf16* __restrict__ x, const float* __restrict__ sc, const float* __restrict__ sh,
-    bf16* __restrict__ dz, float* __restrict__ st0, float* __restrict__ st1, long M, int C, long rows_per_block) {
-    __shared__ float red[2][256][8 + 1];
-    const int tpr = C >> 3;
-    const int cg = threadIdx.x % tpr, rs = threadIdx.x / tpr;
-    const int rpp = 256 / tpr;
-    float a8[8], b8[8], s0[8], s1[8];
-    load8f(sc + cg * 8, a8); load8f(sh + cg * 8, b8);
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { s0[e] = 0.f; s1[e] = 0.f; }
-    const long r0 = (long)blockIdx.x * rows_per_block;
-    const long r1 = min(M, r0 + rows_per_block);
-    for (long row = r0 + rs; row < r1; row += rpp) {
-        const long off = row * C + cg * 8;
-        const bf16x8 gg = as_bf16x8(*(const uint4*)(g + off));
-        const bf16x8 xx = as_bf16x8(*(const uint4*)(x + off));
-        bf16x8 o;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            const float xv = bf2f(xx[e]);
-            const float v = fmaf(xv, a8[e], b8[e]) > 0.f ? bf2f(gg[e]) : 0.f;
-            o[e] = f2bf(v);
-            s0[e] += v; s1[e] += v * xv;
-        }
-        *(uint4*)(dz + off) = as_uint4(o);
-    }
-#pragma unroll
-    for (int e = 0; e < 8; ++e) { red[0][threadIdx.x][e] = s0[e]; red[1][threadIdx.x][e] = s1[e]; }
-    __syncthreads();
-    for (int ch = threadIdx.x; ch < C; ch += 256) {
-        const int g8 = ch >> 3, e = ch & 7;
-        float a = 0.f, b = 0.f;
-        for (int s = 0; s < rpp; ++s) { const int t = s * tpr + g8; a += red[0][t][e]; b += red[1][t][e]; }
-        st0[(long)blockIdx.x * C + ch] = a;
-        st1[(long)blockIdx.x * C + ch] = b;
-    }
-}
-
 // dx = A*dz + B*x + C   (BatchNorm backward apply)
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const bf16* __restrict__ dz, const bf16* __restrict__ x, const float* __restrict__ cA, const float* __restrict__ cB,
@@ -923,14 +882,6 @@ int tuber_block_out_bwd(const void* dy, const void* y, const void* c4, const voi
     if (!chan_ok(C)) return TUBER_EINVAL;
     hipLaunchKernelGGL(block_out_bwd_kernel, dim3(tuber_rowblock_count(M, C)), dim3(256), 0, stream, (const bf16*)dy, (const bf16*)y,
                        (const bf16*)c4, (const bf16*)cds, (bf16*)dz, st_dz, st_c4, st_ds, M, C, rows_per_block(M, C));
-    TUBER_RETURN_LAUNCH();
-}
-
-int tuber_relu_bn_bwd_reduce(const void* g, const void* x, const float* sc, const float* sh, void* dz, float* st0, float* st1,
-                             long M, int C, hipStream_t stream) {
-    if (!chan_ok(C)) return TUBER_EINVAL;
-    hipLaunchKernelGGL(relu_bn_bwd_reduce_kernel, dim3(tuber_rowblock_count(M, C)), dim3(256), 0, stream, (const bf16*)g,
-                       (const bf16*)x, sc, sh, (bf16*)dz, st0, st1, M, C, rows_per_block(M, C));
     TUBER_RETURN_LAUNCH();
 }
 
