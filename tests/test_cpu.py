@@ -668,3 +668,71 @@ def test_deferred_reduce_overwrites_only_windows_zero_grad_has_cleared():
     with ab.override("no_fresh_reduce"):
         d.add(P, A, 4096, 4096, 2, 0)
     assert d.entries[0][5] & 8 == 0
+
+
+def test_gemm_nt_keyword_helper_passes_the_positional_tuple_of_the_c_abi():
+    """lib.gemm_nt names the 30-argument tail of tuber_gemm_nt; the launch (and a launch hook: bench.py reads the positional arguments) must see
+    exactly the tuple the ten product call sites (backbone.py, tape.py) used to spell out positionally -- written out below as they stood -- and
+    the helper's parameters, with ``gather`` expanded, are the header's argument names, so helper and header cannot drift."""
+    import inspect
+    A, W, C, sc, sh, st0, st1, Cm, R, bias, seed = (object() for _ in range(11))      # stand-ins for tensors / device addresses
+    lda, ldb, ldc, ldx, M, N, K = 101, 102, 103, 104, 1040, 1050, 1060
+    To, Ho, Wo, Ti, Hi, Wi, st, ss = 2, 3, 4, 5, 6, 7, 8, 9
+    cases = [   # (the call as the site spells it now, the positional tuple the site passed before)
+        # backbone._gemm_stats, training: here the projection shortcut's strided gather
+        (lambda: lib.gemm_nt(A, lda, W, ldb, C, N, M, N, K, amode=0, a_scale=None, a_shift=None, gather=(To, Ho, Wo, Ti, Hi, Wi, st, ss), epi=1, stat0=st0, stat1=st1),
+         (A, lda, W, ldb, C, N, M, N, K, 0, None, None, 1, To, Ho, Wo, Ti, Hi, Wi, st, ss, 1, None, None, 0, 0, 0,
+          st0, st1, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)),
+        # backbone._gemm_stats, eval: here conv4 with the BatchNorm-apply prologue
+        (lambda: lib.gemm_nt(A, lda, W, ldb, C, N, M, N, K, amode=1, a_scale=sc, a_shift=sh, gather=None, epi=0, stat0=None, stat1=None),
+         (A, lda, W, ldb, C, N, M, N, K, 1, sc, sh, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, None, None, 0, 0, 0,
+          None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)),
+        # backbone: conv4 data gradient with the relu / bn3 backward epilogue
+        (lambda: lib.gemm_nt(A, lda, W, ldb, C, ldc, M, N, K, epi=2, stat0=st0, stat1=st1, Cm=Cm, ldcm=ldx, m_scale=sc, m_shift=sh),
+         (A, lda, W, ldb, C, ldc, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+          2, None, None, 0, 0, 0, st0, st1, Cm, ldx, sc, sh, 1.0, 0.0, None, 0, None, 0, None)),
+        # backbone: the projection shortcut's data gradient
+        (lambda: lib.gemm_nt(A, lda, W, ldb, C, ldc, M, N, K),
+         (A, lda, W, ldb, C, ldc, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0,
+          0, 0, None, None, 0, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)),
+        # backbone: conv1 data gradient with the residual
+        (lambda: lib.gemm_nt(A, lda, W, ldb, C, ldc, M, N, K, R=R, ldr=ldx),
+         (A, lda, W, ldb, C, ldc, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+          0, None, R, ldx, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)),
+        # tape.linear forward: bias, ReLU, fp32 output, Dropout
+        (lambda: lib.gemm_nt(A, K, W, K, C, N, M, N, K, bias=bias, relu=1, out_f32=1, drop_p=0.25, seed_ptr=seed, salt=12),
+         (A, K, W, K, C, N, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+          0, bias, None, 0, 1, 1, None, None, None, 0, None, None, 1.0, 0.25, seed, 12, None, 0, None)),
+        # tape.linear backward: data gradient pushed onto the stack
+        (lambda: lib.gemm_nt(A, lda, W, ldb, C, K, M, K, N),
+         (A, lda, W, ldb, C, K, M, K, N, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+          0, None, None, 0, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)),
+        # tape.linear backward: data gradient through the ReLU / Dropout mask of the saved activation (alpha = 1 / keep probability)
+        (lambda: lib.gemm_nt(A, lda, W, ldb, C, K, M, K, N, epi=2, Cm=Cm, ldcm=K, alpha=1.25),
+         (A, lda, W, ldb, C, K, M, K, N, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+          2, None, None, 0, 0, 0, None, None, Cm, K, None, None, 1.25, 0.0, None, 0, None, 0, None)),
+        # tape.linear backward: data gradient accumulated onto an existing gradient
+        (lambda: lib.gemm_nt(A, lda, W, ldb, C, K, M, K, N, R=R, ldr=K),
+         (A, lda, W, ldb, C, K, M, K, N, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+          0, None, R, K, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)),
+        # tape.in_proj backward: plain data gradient (here without a residual: ldr is passed all the same)
+        (lambda: lib.gemm_nt(A, N, W, ldb, C, K, M, K, 128, R=None, ldr=K),
+         (A, N, W, ldb, C, K, M, K, 128, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
+          0, None, None, K, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)),
+    ]
+    seen = []
+    lib.set_launch_hook(lambda name, args, launch: seen.append((name, args)))       # records and does not launch: no library, no GPU
+    try:
+        for spell, _ in cases:
+            spell()
+    finally:
+        lib.set_launch_hook(None)
+    assert len(seen) == len(cases) == 10
+    for i, ((name, args), (_, want)) in enumerate(zip(seen, cases)):
+        assert name == "tuber_gemm_nt" and len(args) == len(want) == 40, (i, name, len(args))
+        assert all(a is w or (type(a) is type(w) and a == w) for a, w in zip(args, want)), (i, args, want)
+    names = []
+    for n in inspect.signature(lib.gemm_nt).parameters:
+        names += ["gather", "To", "Ho", "Wo", "Ti", "Hi", "Wi", "st", "ss"] if n == "gather" else [n]
+    header = [a for _, a in next(args for _, name, args in lib.header_prototypes() if name == "tuber_gemm_nt")]
+    assert header[-1] == "stream" and names == header[:-1], (names, header)

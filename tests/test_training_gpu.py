@@ -166,7 +166,7 @@ def test_frozen_backbone_prefix_gradients_and_step(dev):
     bn_full = {k: v.clone() for k, v in model.state_dict().items() if k in bn0}
     _freeze_like_load_csn_mat(model)
     plans, stem, lowest = runner.trainable_plan()
-    assert not stem["any"] and runner.blocks[lowest]["stage"] == 3 and runner.blocks[lowest]["first"]
+    assert not stem["any"] and runner.blocks[lowest].stage == 3 and runner.blocks[lowest].first
     g_frozen = run()
     for k, v in model.state_dict().items():
         if k in bn0:

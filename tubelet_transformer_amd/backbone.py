@@ -14,6 +14,7 @@ Forward schedule per bottleneck (ir_CSN_152.py:70-90), all BN statistics fused i
     y  = relu(bn4(c4) + (bn_d(cd) | x))
 """
 import operator
+from typing import NamedTuple
 
 import torch
 from torch import nn
@@ -111,6 +112,34 @@ class _BN:
                  "cA", "cB", "cC")
 
 
+class _Block:
+    """One bottleneck of the schedule: its shape, its place in the body, its module, the raw device pointers of its weights (``w*`` bf16
+    shadow or fp32 master, ``g*`` flat gradient, ``w*t`` / ``ld*t`` transposed bf16 copy) and its BatchNorms; the ``*d`` ones are the
+    projection shortcut's (None on identity blocks)."""
+    __slots__ = ("cin", "p", "st", "ss", "ds", "off0", "stage", "first", "mod", "w1", "g1", "w1t", "ld1t", "w3", "g3", "w4", "g4", "w4t", "ld4t",
+                 "bn1", "bn3", "bn4", "wd", "gd", "wdt", "lddt", "bnd")
+
+    @property
+    def strided(self):
+        return self.st != 1 or self.ss != 1
+
+    @property
+    def c4(self):
+        return 4 * self.p
+
+
+# what a bottleneck's training forward keeps for its backward (geom = (Ti, Hi, Wi, To, Ho, Wo); ymask: the ReLU mask of y as a bit field, or None), and
+# what the stem's keeps (geom = (B, T, Ho, Wo, Hp, Wp) of the conv and pool outputs)
+_Saved = NamedTuple("_Saved", [(n, object) for n in ("x", "c1", "c3", "c4", "cd", "y", "geom", "ymask")])
+_SavedStem = NamedTuple("_SavedStem", [(n, object) for n in ("clips", "c0", "arg", "geom")])
+
+
+def _rows(B, geom):
+    """(input rows, output rows) of a bottleneck on a batch of B clips"""
+    Ti, Hi, Wi, To, Ho, Wo = geom
+    return B * Ti * Hi * Wi, B * To * Ho * Wo
+
+
 class CSNRunner:
     """Executes ResNeXt forward/backward for one ParamStore.  Pointers are cached as ints; every launch
     goes through the C ABI on torch's current stream."""
@@ -124,6 +153,9 @@ class CSNRunner:
         self._bn_index = {}
         self._bn_rows = []
         self.blocks = []
+        self.cut_stages = (3,)              # stages whose first block ends a gradient window (_bwd_cut); training.GraphedTrainStep sets them
+        self.split_hook = None              # called with the flat offset at such a cut (the graph-mode DDP step cuts its hipGraph there)
+        self.last_y32 = None                # fp32 output stream of the last eval forward under TUBER_EVAL_PRECISION=fp32_class
         sp = self.scratch.data_ptr()
 
         def mk_bn(mod_prefix, mod):
@@ -158,21 +190,23 @@ class CSNRunner:
             layer = getattr(body, "layer%d" % li)
             for bi, blk in enumerate(layer):
                 p = "%slayer%d.%d." % (prefix, li, bi)
-                d = {"cin": blk.conv1.in_channels, "p": blk.conv1.out_channels, "st": blk.temporal_stride, "ss": blk.stride,
-                     "ds": blk.down_sample is not None}
-                d["off0"] = store.offsets[p + "conv1.weight"]
-                d["stage"], d["first"] = li, bi == 0
-                d["mod"] = blk
-                d["w1"], _, d["g1"] = wptr(p + "conv1.weight")
-                d["w1t"], d["ld1t"] = tptr(p + "conv1.weight")
-                _, d["w3"], d["g3"] = wptr(p + "conv3.weight")
-                d["w4"], _, d["g4"] = wptr(p + "conv4.weight")
-                d["w4t"], d["ld4t"] = tptr(p + "conv4.weight")
-                d["bn1"], d["bn3"], d["bn4"] = mk_bn(p + "bn1", blk.bn1), mk_bn(p + "bn3", blk.bn3), mk_bn(p + "bn4", blk.bn4)
-                if d["ds"]:
-                    d["wd"], _, d["gd"] = wptr(p + "down_sample.0.weight")
-                    d["wdt"], d["lddt"] = tptr(p + "down_sample.0.weight")
-                    d["bnd"] = mk_bn(p + "down_sample.1", blk.down_sample[1])
+                d = _Block()
+                d.cin, d.p, d.st, d.ss = blk.conv1.in_channels, blk.conv1.out_channels, blk.temporal_stride, blk.stride
+                d.ds = blk.down_sample is not None
+                d.off0 = store.offsets[p + "conv1.weight"]
+                d.stage, d.first = li, bi == 0
+                d.mod = blk
+                d.w1, _, d.g1 = wptr(p + "conv1.weight")
+                d.w1t, d.ld1t = tptr(p + "conv1.weight")
+                _, d.w3, d.g3 = wptr(p + "conv3.weight")
+                d.w4, _, d.g4 = wptr(p + "conv4.weight")
+                d.w4t, d.ld4t = tptr(p + "conv4.weight")
+                d.bn1, d.bn3, d.bn4 = mk_bn(p + "bn1", blk.bn1), mk_bn(p + "bn3", blk.bn3), mk_bn(p + "bn4", blk.bn4)
+                d.wd = d.gd = d.wdt = d.lddt = d.bnd = None
+                if d.ds:
+                    d.wd, _, d.gd = wptr(p + "down_sample.0.weight")
+                    d.wdt, d.lddt = tptr(p + "down_sample.0.weight")
+                    d.bnd = mk_bn(p + "down_sample.1", blk.down_sample[1])
                 self.blocks.append(d)
         # eval mode: the affine form of EVERY BatchNorm in one launch at the start of the forward (tuber_bn_eval_affine_multi)
         rows = sorted(self._bn_rows, key=lambda r: r[0])
@@ -255,19 +289,17 @@ class CSNRunner:
     def _gemm_stats(self, A, lda, Wb, ldb, C, M, N, K, amode, sc, sh, gather, bn, train, defer=False):
         """conv as GEMM; in training mode also the following BatchNorm's statistics (``defer``: return the statistics rows (st0, st1, R)
         instead of finalising them -- the consumer does)."""
-        g = gather or (0, 0, 0, 0, 0, 0, 0, 0)
+        st0 = st1 = None
         if train:
             R = lib.query("tuber_gemm_nt_stat_rows", M, N)
             st0, st1 = self.ws("st0", R * N), self.ws("st1", R * N)
-            lib.call("tuber_gemm_nt", A, lda, Wb, ldb, C, N, M, N, K, amode, sc, sh, 1 if gather else 0, *g, 1, None, None, 0, 0, 0,
-                     st0, st1, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)
-            if defer:
-                return st0, st1, R
-            self._bn_train(bn, st0, st1, R, M)
-        else:
-            lib.call("tuber_gemm_nt", A, lda, Wb, ldb, C, N, M, N, K, amode, sc, sh, 1 if gather else 0, *g, 0, None, None, 0, 0, 0,
-                     None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)
+        lib.gemm_nt(A, lda, Wb, ldb, C, N, M, N, K, amode=amode, a_scale=sc, a_shift=sh, gather=gather, epi=1 if train else 0, stat0=st0, stat1=st1)
+        if not train:
             self._bn_eval(bn)
+        elif defer:
+            return st0, st1, R
+        else:
+            self._bn_train(bn, st0, st1, R, M)
 
     # -- forward ------------------------------------------------------------------------------------
     def forward(self, clips, train):
@@ -297,7 +329,7 @@ class CSNRunner:
             x = torch.empty(B * T * Hp * Wp, 64, dtype=BF, device=dev)
             arg = torch.empty(B * T * Hp * Wp, 64, dtype=torch.uint8, device=dev) if train else None
             lib.call("tuber_stem_pool_fwd", c0, self.stem_bn.scale, self.stem_bn.shift, x, arg, B * T, Ho, Wo, Hp, Wp)
-            saved = {"stem": (clips if train else None, None, c0, arg, (B, T, Ho, Wo, Hp, Wp)), "blocks": [], "lo": 0}
+            saved = {"stem": _SavedStem(clips if train else None, c0, arg, (B, T, Ho, Wo, Hp, Wp)), "blocks": [], "lo": 0}
             x, (Ti, Hi, Wi) = self._forward_blocks(x, B, (T, Hp, Wp), 0, len(self.blocks), train, saved["blocks"])
             self._advance_counts()
         finally:
@@ -320,46 +352,46 @@ class CSNRunner:
 
         def bn1_stats(blk, s0, s1, R, count):
             """bn1 of a stride-1 block is finalised INSIDE its depthwise forward kernel (tuber_dwconv_tile_fwd_bn): one launch less per block"""
-            if fold1 and blk["st"] == 1 and blk["ss"] == 1:
+            if fold1 and not blk.strided:
                 return (s0, s1, R, count)
-            self._bn_train(blk["bn1"], s0, s1, R, count)
+            self._bn_train(blk.bn1, s0, s1, R, count)
             return None
 
         for bi in range(lo, hi):
             d = self.blocks[bi]
-            cin, P, st, ss = d["cin"], d["p"], d["st"], d["ss"]
+            cin, P, st, ss, C4 = d.cin, d.p, d.st, d.ss, d.c4
             To, Hq, Wq = (Ti - 1) // st + 1, (Hi - 1) // ss + 1, (Wi - 1) // ss + 1
             Min, Mout = B * Ti * Hi * Wi, B * To * Hq * Wq
             cd = ymask = None
             if pre_c1 is not None:
                 c1, pre_c1 = pre_c1, None
-            elif (not ab.on("no_entry_conv") and d["ds"] and st == 1 and ss == 1 and lib.query("tuber_entry_conv_supported", cin, P, 4 * P) == 1):
+            elif (not ab.on("no_entry_conv") and d.ds and not d.strided and lib.query("tuber_entry_conv_supported", cin, P, C4) == 1):
                 # layer1's first block: conv1 and the projection-shortcut conv read the same [M, 64] input -- one persistent kernel
                 # produces both outputs (and both BatchNorms' statistics rows) from one pass over it (csrc/entry_conv.hip)
                 c1 = torch.empty(Min, P, dtype=BF, device=dev)
-                cd = torch.empty(Min, 4 * P, dtype=BF, device=dev)
+                cd = torch.empty(Min, C4, dtype=BF, device=dev)
                 if train:
                     Rt = (Min + 63) // 64
                     a0, a1 = self.ws("st0", Rt * P), self.ws("st1", Rt * P)
-                    e0, e1 = self.ws("std0", Rt * 4 * P), self.ws("std1", Rt * 4 * P)
+                    e0, e1 = self.ws("std0", Rt * C4), self.ws("std1", Rt * C4)
                 else:
                     a0 = a1 = e0 = e1 = None
-                lib.call("tuber_entry_conv_fwd", x, d["w1"], cin, d["wd"], cin, c1, cd, a0, a1, e0, e1, Min)
+                lib.call("tuber_entry_conv_fwd", x, d.w1, cin, d.wd, cin, c1, cd, a0, a1, e0, e1, Min)
                 if train:
                     pend = bn1_stats(d, a0, a1, Rt, Min)
-                    self._bn_train(d["bnd"], e0, e1, Rt, Min)
+                    self._bn_train(d.bnd, e0, e1, Rt, Min)
                 else:
-                    self._bn_eval(d["bn1"])
-                    self._bn_eval(d["bnd"])
+                    self._bn_eval(d.bn1)
+                    self._bn_eval(d.bnd)
             else:
                 c1 = torch.empty(Min, P, dtype=BF, device=dev)
-                if fold1 and st == 1 and ss == 1:
-                    pend = self._gemm_stats(x, cin, d["w1"], cin, c1, Min, P, cin, 0, None, None, None, d["bn1"], train, defer=True) + (Min,)
+                if fold1 and not d.strided:
+                    pend = self._gemm_stats(x, cin, d.w1, cin, c1, Min, P, cin, 0, None, None, None, d.bn1, train, defer=True) + (Min,)
                 else:
-                    self._gemm_stats(x, cin, d["w1"], cin, c1, Min, P, cin, 0, None, None, None, d["bn1"], train)
+                    self._gemm_stats(x, cin, d.w1, cin, c1, Min, P, cin, 0, None, None, None, d.bn1, train)
             c3 = torch.empty(Mout, P, dtype=BF, device=dev)
-            b1, b3, b4 = d["bn1"], d["bn3"], d["bn4"]
-            tile = st == 1 and ss == 1 and not ab.on("dw_register_tiled")        # LDS-staged kernels for the stride-1 blocks (47 of 50)
+            b1, b3, b4 = d.bn1, d.bn3, d.bn4
+            tile = not d.strided and not ab.on("dw_register_tiled")        # LDS-staged kernels for the stride-1 blocks (47 of 50)
             if train:
                 R = lib.query("tuber_dwconv_tile_blocks", B, Ti, Hi, Wi, P) if tile else lib.query("tuber_dwconv_fwd_stat_rows", B, To, Hq, Wq)
                 # (its own pair of buffers when the kernel also READS bn1's rows, which sit in st0 / st1)
@@ -370,35 +402,34 @@ class CSNRunner:
                 p0, p1, pR = self._stat_rows(pend[0], pend[1], pend[2], P)
                 name, mom = self._finalize_form(b1, "tuber_dwconv_tile_fwd_bn")
                 lib.call(name, c1, p0, p1, pR, float(pend[3]), b1.gamma, b1.beta, b1.rmean, b1.rvar, b1.nbt, mom, BN_EPS,
-                         b1.scale, b1.shift, b1.mean, b1.invstd, d["w3"], c3, st0, st1, B, Ti, Hi, Wi, P)
+                         b1.scale, b1.shift, b1.mean, b1.invstd, d.w3, c3, st0, st1, B, Ti, Hi, Wi, P)
                 pend = None
             elif tile:
-                lib.call("tuber_dwconv_tile_fwd", c1, b1.scale, b1.shift, d["w3"], c3, st0, st1, B, Ti, Hi, Wi, P)
+                lib.call("tuber_dwconv_tile_fwd", c1, b1.scale, b1.shift, d.w3, c3, st0, st1, B, Ti, Hi, Wi, P)
             else:
-                lib.call("tuber_dwconv_fwd", c1, b1.scale, b1.shift, d["w3"], c3, st0, st1, B, Ti, Hi, Wi, To, Hq, Wq, P, st, ss)
+                lib.call("tuber_dwconv_fwd", c1, b1.scale, b1.shift, d.w3, c3, st0, st1, B, Ti, Hi, Wi, To, Hq, Wq, P, st, ss)
             if train:
                 self._bn_train(b3, st0, st1, R, Mout)
             else:
                 self._bn_eval(b3)
-            y = torch.empty(Mout, 4 * P, dtype=BF, device=dev)
-            if precise and not d["ds"] and y32 is not None and not ab.on("no_eval_conv4_join"):
+            y = torch.empty(Mout, C4, dtype=BF, device=dev)
+            if precise and not d.ds and y32 is not None and not ab.on("no_eval_conv4_join"):
                 # eval precision mode, identity block: an eval-mode bn4 is a constant affine map, so conv4 + bn4 + the residual join + ReLU are ONE
                 # GEMM (tuber_gemm_nt_bn_out): c4 never reaches HBM, y leaves as the bf16 operand of the next block and as the fp32 stream
                 self._bn_eval(b4)
-                y32n = torch.empty(Mout, 4 * P, dtype=torch.float32, device=dev)
-                lib.call("tuber_gemm_nt_bn_out", c3, P, b3.scale, b3.shift, d["w4"], P, b4.scale, b4.shift, y32, 4 * P, y, 4 * P, y32n, 4 * P, Mout, 4 * P, P)
+                y32n = torch.empty(Mout, C4, dtype=torch.float32, device=dev)
+                lib.call("tuber_gemm_nt_bn_out", c3, P, b3.scale, b3.shift, d.w4, P, b4.scale, b4.shift, y32, C4, y, C4, y32n, C4, Mout, C4, P)
                 y32 = y32n
                 x = y
                 Ti, Hi, Wi = To, Hq, Wq
                 continue
-            c4 = torch.empty(Mout, 4 * P, dtype=BF, device=dev)
-            self._gemm_stats(c3, P, d["w4"], P, c4, Mout, 4 * P, P, 1, b3.scale, b3.shift, None, b4, train)
-            if d["ds"] and cd is None:
-                cd = torch.empty(Mout, 4 * P, dtype=BF, device=dev)
-                strided = st != 1 or ss != 1
-                gather = (To, Hq, Wq, Ti, Hi, Wi, st, ss) if strided else None
-                self._gemm_stats(x, cin, d["wd"], cin, cd, Mout, 4 * P, cin, 0, None, None, gather, d["bnd"], train)
-            res, rs, rh = (cd, d["bnd"].scale, d["bnd"].shift) if d["ds"] else (x, None, None)
+            c4 = torch.empty(Mout, C4, dtype=BF, device=dev)
+            self._gemm_stats(c3, P, d.w4, P, c4, Mout, C4, P, 1, b3.scale, b3.shift, None, b4, train)
+            if d.ds and cd is None:
+                cd = torch.empty(Mout, C4, dtype=BF, device=dev)
+                gather = (To, Hq, Wq, Ti, Hi, Wi, st, ss) if d.strided else None
+                self._gemm_stats(x, cin, d.wd, cin, cd, Mout, C4, cin, 0, None, None, gather, d.bnd, train)
+            res, rs, rh = (cd, d.bnd.scale, d.bnd.shift) if d.ds else (x, None, None)
             # layer1 (256-channel block output, the widest activations): the residual join AND the next bottleneck's conv1 (+ its
             # BatchNorm statistics) run as one persistent kernel that keeps the y tile in LDS (csrc/blockout_conv1.hip): y is written
             # once and not read back.  The next block may be layer2's first one (its conv1 is dense; the stride sits on the depthwise conv).
@@ -407,41 +438,41 @@ class CSNRunner:
                 # (all four stages.  Leaving layer1's three blocks -- 356 MB tensors, most of the mode's cost: 5.8 instead of 6.3 ms per 2-clip eval batch -- on
                 #  the bf16 stream and their fused kernels was built and measured: the oracle puts that at +6 % on the actor logits, the MI355X at 1.15e-2 ->
                 #  1.96e-2 on config 3, 0.04e-2 under the tolerance; the mode is there for the margin, so it keeps all of them)
-                y32n = torch.empty(Mout, 4 * P, dtype=torch.float32, device=dev)
-                if d["ds"]:
-                    lib.call("tuber_block_out_fwd_f32", c4, b4.scale, b4.shift, cd, rs, rh, None, y, y32n, Mout, 4 * P)
+                y32n = torch.empty(Mout, C4, dtype=torch.float32, device=dev)
+                if d.ds:
+                    lib.call("tuber_block_out_fwd_f32", c4, b4.scale, b4.shift, cd, rs, rh, None, y, y32n, Mout, C4)
                 else:                   # identity block: the fp32 stream of the block below (a segment that starts here has only the bf16 rows)
-                    lib.call("tuber_block_out_fwd_f32", c4, b4.scale, b4.shift, x, None, None, y32, y, y32n, Mout, 4 * P)
+                    lib.call("tuber_block_out_fwd_f32", c4, b4.scale, b4.shift, x, None, None, y32, y, y32n, Mout, C4)
                 y32 = y32n
-            elif (not ab.on("no_blockout_conv1") and nxt is not None and nxt["cin"] == 4 * P
-                    and lib.query("tuber_blockout_conv1_supported", 4 * P, nxt["p"]) == 1):
-                PN = nxt["p"]
+            elif (not ab.on("no_blockout_conv1") and nxt is not None and nxt.cin == C4
+                    and lib.query("tuber_blockout_conv1_supported", C4, nxt.p) == 1):
+                PN = nxt.p
                 pre_c1 = torch.empty(Mout, PN, dtype=BF, device=dev)
                 if train:
                     Rn = lib.query("tuber_gemm_nt_stat_rows", Mout, PN)
                     n0, n1 = self.ws("st0", Rn * PN), self.ws("st1", Rn * PN)
                 else:
                     n0 = n1 = None
-                if train and nxt["stage"] != d["stage"] and not ab.on("no_join_mask"):
+                if train and nxt.stage != d.stage and not ab.on("no_join_mask"):
                     # the last block of layer1: its join backward runs in layer2's first conv1 data-gradient GEMM (strided form) and reads the mask as a bit field
                     ymask = torch.empty(Mout, P // 2, dtype=torch.uint8, device=dev)
-                    lib.call("tuber_blockout_conv1_fwd_mask", c4, b4.scale, b4.shift, res, rs, rh, y, ymask, nxt["w1"], nxt["cin"], pre_c1, n0, n1, Mout, PN)
+                    lib.call("tuber_blockout_conv1_fwd_mask", c4, b4.scale, b4.shift, res, rs, rh, y, ymask, nxt.w1, nxt.cin, pre_c1, n0, n1, Mout, PN)
                 else:
-                    lib.call("tuber_blockout_conv1_fwd", c4, b4.scale, b4.shift, res, rs, rh, y, nxt["w1"], nxt["cin"], pre_c1, n0, n1, Mout, PN)
+                    lib.call("tuber_blockout_conv1_fwd", c4, b4.scale, b4.shift, res, rs, rh, y, nxt.w1, nxt.cin, pre_c1, n0, n1, Mout, PN)
                 if train:
                     pend = bn1_stats(nxt, n0, n1, Rn, Mout)
                 else:
-                    self._bn_eval(nxt["bn1"])
+                    self._bn_eval(nxt.bn1)
             elif train and not ab.on("no_join_mask"):
                 # training: the ReLU mask of y also leaves as a bit field -- what this block's join backward (inside the conv1
                 # data-gradient GEMM of the block above, tuber_gemm_nt_join_mask) reads instead of y: 1 / 16 of the bytes of a side operand of a
                 # launch that runs at the bandwidth of its side operands
                 ymask = torch.empty(Mout, P // 2, dtype=torch.uint8, device=dev)
-                lib.call("tuber_block_out_fwd_mask", c4, b4.scale, b4.shift, res, rs, rh, y, ymask, Mout, 4 * P)
+                lib.call("tuber_block_out_fwd_mask", c4, b4.scale, b4.shift, res, rs, rh, y, ymask, Mout, C4)
             else:
-                lib.call("tuber_block_out_fwd", c4, b4.scale, b4.shift, res, rs, rh, y, Mout, 4 * P)
+                lib.call("tuber_block_out_fwd", c4, b4.scale, b4.shift, res, rs, rh, y, Mout, C4)
             if train:
-                out_saved.append((x, c1, c3, c4, cd, y, (Ti, Hi, Wi, To, Hq, Wq), ymask))
+                out_saved.append(_Saved(x, c1, c3, c4, cd, y, (Ti, Hi, Wi, To, Hq, Wq), ymask))
             x = y
             Ti, Hi, Wi = To, Hq, Wq
         # TUBER_EVAL_PRECISION=fp32_class: the fp32 stream of the last block is the class branch's class_proj operand (DETR._class_branch_f32 takes it)
@@ -482,12 +513,12 @@ class CSNRunner:
         stem backward needed).  Read from ``requires_grad`` on every call: freezing may change between steps."""
         plans = []
         for d in self.blocks:
-            m = d["mod"]
+            m = d.mod
             f = {"w1": m.conv1.weight.requires_grad, "w3": m.conv3.weight.requires_grad, "w4": m.conv4.weight.requires_grad,
                  "bn1": m.bn1.weight.requires_grad or m.bn1.bias.requires_grad,
                  "bn3": m.bn3.weight.requires_grad or m.bn3.bias.requires_grad,
                  "bn4": m.bn4.weight.requires_grad or m.bn4.bias.requires_grad}
-            if d["ds"]:
+            if d.ds:
                 f["wd"] = m.down_sample[0].weight.requires_grad
                 f["bnd"] = m.down_sample[1].weight.requires_grad or m.down_sample[1].bias.requires_grad
             f["any"] = any(f.values())
@@ -554,275 +585,281 @@ class CSNRunner:
     def flush_wgrads(self):
         self.store.wq.flush()
 
+    def _slab_reduce(self, part, acc, g, n, S, C=0):
+        """second stage of a weight gradient whose kernel left ``S`` slabs of ``n`` fp32 partials in ``part`` (``store.partial``), summed into the flat
+        gradient at ``g``: deferred to the step's tuber_multi_reduce (mode 1 = the summation order of tuber_reduce_rows), or the same sum launched right
+        here (TUBER_AB=immediate_reduce).  ``C``: the depthwise layout ([27][C] blocks, tuber_dw_wgrad_reduce)."""
+        if acc == 2:
+            self.store.defer.add(part, g, n, n, S, 1, C)
+        elif C:
+            lib.call("tuber_dw_wgrad_reduce", part, g, S, C, 1)
+        else:
+            lib.call("tuber_reduce_rows", part, g, S, n, 1)
+
+    def _join_out(self, Min, cin, third):
+        """outputs of a join backward that runs inside the conv1 data gradient of the block above: (dz, sum-dz rows, sum-dz*c4 rows, sum-dz*cd rows of the
+        projection shortcut when ``third`` else None, R) -- the ``pre`` of the next iteration"""
+        Rj = lib.query("tuber_gemm_nt_stat_rows", Min, cin)
+        ja, jb = self.ws("stj0", Rj * cin), self.ws("stj1", Rj * cin)
+        jc = self.ws("stj2", Rj * cin) if third else None
+        return torch.empty(Min, cin, dtype=BF, device=self.dev), ja, jb, jc, Rj
+
     def _backward_blocks(self, sblocks, base, dy, B, lowest, top, plans, dx_below, red):
         """bottlenecks [lowest, top) in reverse; ``sblocks[i - base]`` holds block i's saved tensors; ``dx_below``: the gradient of
         block ``lowest``'s input is wanted (something trainable, or a caller, sits below it).  Returns that gradient (or None)."""
-        dev = self.dev
-        pre = None          # (dz, sum-dz rows, sum-dz*c4 rows, R) of this block's join backward, produced by the block above (tuber_gemm_nt_join)
-        wq = self.store.wq
+        pre = None          # (dz, sum-dz rows, sum-dz*c4 rows, sum-dz*cd rows, R) of this block's join backward, produced by the block above (_join_out)
         for bi in range(top - 1, lowest - 1, -1):
             d, sv, f = self.blocks[bi], sblocks[bi - base], plans[bi]
-            x, c1, c3, c4, cd, y, (Ti, Hi, Wi, To, Hq, Wq), _ymask = sv
-            cin, P, st, ss = d["cin"], d["p"], d["st"], d["ss"]
-            C4 = 4 * P
-            Min, Mout = B * Ti * Hi * Wi, B * To * Hq * Wq
-            b1, b3, b4 = d["bn1"], d["bn3"], d["bn4"]
+            lower = (self.blocks[bi - 1], sblocks[bi - 1 - base]) if bi > lowest else None
             need_dx = dx_below or bi > lowest
             # how deep the chain inside this block has to go: 7 = input gradient, 6 = conv1 weight, 5 = bn1, 4 = conv3 weight,
             # 3 = bn3, 2 = conv4 weight, 1 = bn4 / shortcut only
             depth = 7 if need_dx else (6 if f["w1"] else 5 if f["bn1"] else 4 if f["w3"] else 3 if f["bn3"] else 2 if f["w4"] else 1)
-            # join backward: dz + stats of bn4 (and the shortcut BN)
-            if pre is not None:
-                dz, sa, sb, sc_, R = pre        # (sc_: the projection shortcut's statistics rows when the join of a stage's first block was fused)
-                pre = None
-            else:
-                R = lib.query("tuber_rowblock_count", Mout, C4)
-                sa, sb, sc_ = self.ws("st0", R * C4), self.ws("st1", R * C4), self.ws("st2", R * C4)
-                dz = torch.empty(Mout, C4, dtype=BF, device=dev)
-                lib.call("tuber_block_out_bwd", dy, y, c4, cd, dz, sa, sb, sc_ if d["ds"] else None, Mout, C4)
-            dc4 = None
-            # layer1 (C4 = 256, P = 64: the widest activations): bn4's backward apply, the conv4 data gradient and the conv4 weight
-            # gradient run as ONE persistent kernel that reads dz and c4 once and never writes dc4 (csrc/conv4_bwd.hip)
-            fuse4 = (not ab.on("no_conv4_bwd_fused") and depth >= 3 and f["w4"]
-                     and lib.query("tuber_conv4_bwd_supported", C4, P) == 1)
-            if depth >= 2 or f["bn4"]:
-                dc4 = self._bn_bwd(b4, sa, sb, R, Mout, dz, c4, Mout, train=f["bn4"], apply=depth >= 2 and not fuse4)
-            dcd = None
-            # layer1's projection shortcut (64 -> 256 channels, stride 1): the same persistent kernel in its plain form does the shortcut
-            # BatchNorm's backward apply, the projection's data gradient and its weight gradient in one pass over dz and cd
-            fused = (not ab.on("no_proj_bwd_fused") and d["ds"] and st == 1 and ss == 1 and need_dx and f["wd"]
-                     and lib.query("tuber_conv4_bwd_supported", C4, cin) == 1)
-            if d["ds"] and (need_dx or f["wd"] or f["bnd"]):
-                dcd = self._bn_bwd(d["bnd"], sa, sc_, R, Mout, dz, cd, Mout, train=f["bnd"], apply=(need_dx or f["wd"]) and not fused)
-            # conv4: weight grad (A = relu(bn3(c3)) recomputed on load) and data grad fused with relu/bn3 backward
-            if f["w4"] and not fuse4:
-                self._wgrad(dc4, C4, c3, P, d["g4"], Mout, C4, P, 1, b3.scale, b3.shift)
-            dc3 = None
-            tile = st == 1 and ss == 1 and not ab.on("dw_register_tiled")
-            # bn3's backward apply (dc3 = cA*dz3 + cB*c3 + cC) is formed INSIDE the two depthwise backward kernels of the stride-1 blocks
-            # while they load their gradient operand: every workgroup derives the coefficients of its 64 channels from the partial rows
-            # of the conv4 data-gradient GEMM -- the bn_bwd_fa launch and the dc3 round trip through HBM disappear
-            R3 = lib.query("tuber_gemm_nt_stat_rows", Mout, P)
-            fuse3 = (not ab.on("no_bn3_in_dw") and tile and depth >= 5 and P % 64 == 0
-                     and (R3 <= self._fa_max or lib.query("tuber_stat_rows_reduced", R3) <= self._fa_max))
-            if depth >= 3:
-                s0, s1 = self.ws("st0u" if fuse3 else "st0", R3 * P), self.ws("st1u" if fuse3 else "st1", R3 * P)
-                dz3 = torch.empty(Mout, P, dtype=BF, device=dev)
-                if fuse4:
-                    S4 = lib.query("tuber_conv4_bwd_slabs", Mout)
-                    part4, acc4 = self.store.partial("c4f", S4 * C4 * P, self.ws)
-                    lib.call("tuber_conv4_bwd_fused", dz, c4, c3, d["w4t"], d["ld4t"], b4.cA, b4.cB, b4.cC, b3.scale, b3.shift,
-                             dz3, s0, s1, part4, Mout)
-                    g4 = d["g4"]
-                    if acc4 == 2:       # second stage deferred to the step's tuber_multi_reduce (mode 1 = the summation order of tuber_reduce_rows)
-                        self.store.defer.add(part4, g4 if isinstance(g4, int) else g4.data_ptr(), C4 * P, C4 * P, S4, 1)
-                    else:
-                        lib.call("tuber_reduce_rows", part4, g4, S4, C4 * P, 1)
-                else:
-                    lib.call("tuber_gemm_nt", dc4, C4, d["w4t"], d["ld4t"], dz3, P, Mout, P, C4, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                             2, None, None, 0, 0, 0, s0, s1, c3, P, b3.scale, b3.shift, 1.0, 0.0, None, 0, None, 0, None)
-                if fuse3:
-                    bs0, bs1, bR = (s0, s1, R3) if R3 <= self._fa_max else self._stat_rows(s0, s1, R3, P)
-                    bn3 = (dz3, c3, bs0, bs1, bR, float(Mout), b3.gamma, b3.mean, b3.invstd)
-                else:
-                    dc3 = self._bn_bwd(b3, s0, s1, R3, Mout, dz3, c3, Mout, train=f["bn3"], apply=depth >= 4)
-            # depthwise conv: weight grad, data grad fused with relu/bn1 backward
-            # (stride-1 blocks with the bn3 fold: ONE launch forms both gradients from one staged ring of dc3 -- 4 tensor passes instead of
-            #  the 7 of two kernels; csrc/dwconv_tile.hip: dwconv_tile_bwd_both_kernel)
-            both = not ab.on("no_dw_bwd_one_launch") and fuse3 and f["w3"] and depth >= 5
-            if both:
-                R1 = nb = lib.query("tuber_dwconv_tile_blocks", B, Ti, Hi, Wi, P)      # one [27][P] weight-gradient block per workgroup of the data-gradient grid
-                part, acc = self.store.partial("tn", nb * 27 * P, self.ws)
-                s0, s1 = self.ws("st0", R1 * P), self.ws("st1", R1 * P)
-                dz1 = torch.empty(Min, P, dtype=BF, device=dev)
-                lib.call("tuber_dwconv_tile_bwd_both_bn", *bn3, b3.dgamma if f["bn3"] else None, b3.dbeta if f["bn3"] else None,
-                         d["w3"], c1, b1.scale, b1.shift, dz1, s0, s1, part, B, Ti, Hi, Wi, P)
-                g3 = d["g3"]
-                if acc == 2:
-                    self.store.defer.add(part, g3 if isinstance(g3, int) else g3.data_ptr(), 27 * P, 27 * P, nb, 1, P)
-                else:           # immediate second stage (TUBER_AB=immediate_reduce): the same block sum, launched right here
-                    lib.call("tuber_dw_wgrad_reduce", part, g3, nb, P, 1)
-            elif f["w3"]:
-                nb = lib.query("tuber_dwconv_tile_wgrad_blocks", B, Ti, Hi, Wi, P) if tile else lib.query("tuber_dwconv_bwd_weight_blocks", B, To, Hq, Wq)
-                part, acc = self.store.partial("tn", nb * 27 * P, self.ws)
-
-                def dw_wgrad(dc3=dc3, c1=c1, b1=b1, part=part, acc=acc, d=d, nb=nb, tile=tile, geo=(B, Ti, Hi, Wi, To, Hq, Wq, P, st, ss),
-                             bn3=bn3 if fuse3 else None):
-                    B_, Ti_, Hi_, Wi_, To_, Hq_, Wq_, P_, st_, ss_ = geo
-                    if bn3 is not None:
-                        lib.call("tuber_dwconv_tile_bwd_weight_bn", *bn3, c1, b1.scale, b1.shift, part, d["g3"], acc, B_, Ti_, Hi_, Wi_, P_)
-                    elif tile:
-                        lib.call("tuber_dwconv_tile_bwd_weight", dc3, c1, b1.scale, b1.shift, part, d["g3"], acc, B_, Ti_, Hi_, Wi_, P_)
-                    else:
-                        lib.call("tuber_dwconv_bwd_weight", dc3, c1, b1.scale, b1.shift, part, d["g3"], acc, B_, Ti_, Hi_, Wi_,
-                                 To_, Hq_, Wq_, P_, st_, ss_)
-                    if acc == 2:
-                        g3 = d["g3"]
-                        self.store.defer.add(part, g3 if isinstance(g3, int) else g3.data_ptr(), 27 * P_, 27 * P_, nb, 1, P_)
-                dw_wgrad()
-            dc1 = None
-            if depth >= 5:
-                if not both:
-                    R1 = lib.query("tuber_dwconv_tile_blocks", B, Ti, Hi, Wi, P) if tile else lib.query("tuber_dwconv_bwd_data_stat_rows", B, Ti, Hi, Wi)
-                    s0, s1 = self.ws("st0", R1 * P), self.ws("st1", R1 * P)
-                    dz1 = torch.empty(Min, P, dtype=BF, device=dev)
-                if both:
-                    pass
-                elif fuse3:
-                    lib.call("tuber_dwconv_tile_bwd_data_bn", *bn3, b3.dgamma if f["bn3"] else None, b3.dbeta if f["bn3"] else None,
-                             d["w3"], c1, b1.scale, b1.shift, dz1, s0, s1, B, Ti, Hi, Wi, P)
-                elif tile:
-                    lib.call("tuber_dwconv_tile_bwd_data", dc3, d["w3"], c1, b1.scale, b1.shift, dz1, s0, s1, B, Ti, Hi, Wi, P)
-                else:
-                    lib.call("tuber_dwconv_bwd_data", dc3, d["w3"], c1, b1.scale, b1.shift, dz1, s0, s1, B, Ti, Hi, Wi, To, Hq, Wq, P, st, ss)
-                # layer1 (256-channel block input, P = 64): bn1's backward apply, the conv1 data gradient (with the lower block's join
-                # when that is an identity block) and the conv1 weight gradient run as ONE persistent kernel (csrc/conv1_bwd.hip)
-                strided_ds = d["ds"] and (st != 1 or ss != 1)
-                fuse1 = (not ab.on("no_conv1_bwd_fused") and need_dx and not strided_ds
-                         and lib.query("tuber_conv1_bwd_supported", cin, P) == 1)
-                dc1 = self._bn_bwd(b1, s0, s1, R1, Min, dz1, c1, Min, train=f["bn1"], apply=depth >= 6 and not fuse1)
-            else:
-                fuse1 = False
-            # conv1: weight grad and data grad (+ identity shortcut gradient as residual)
-            if f["w1"] and not fuse1:
-                self._wgrad(dc1, P, x, cin, d["g1"], Min, P, cin)
-            strided = st != 1 or ss != 1
-            gather = (To, Hq, Wq, Ti, Hi, Wi, st, ss) if (d["ds"] and strided) else None
-            if d["ds"] and f["wd"] and not fused:
-                self._wgrad(dcd, C4, x, cin, d["gd"], Mout, C4, cin, 0, None, None, gather)
+            join, pre = pre or self._bwd_join(d, sv, B, dy), None
+            dc4, dcd, fuse4, fuse_proj = self._bwd_bn4(d, sv, f, depth, need_dx, B, join)
+            dw = self._bwd_conv4_dw(d, sv, f, depth, B, join, dc4, fuse4)
+            g1, fuse1 = self._bwd_bn1(d, sv, f, depth, need_dx, B, dw)
+            res, dxd = self._bwd_shortcut(d, sv, f, need_dx, B, join, dcd, fuse_proj)
             if need_dx:
-                res = dz if not d["ds"] else None
-                if fused:
-                    bd = d["bnd"]
-                    dxd = torch.empty(Mout, cin, dtype=BF, device=dev)
-                    Sd = lib.query("tuber_conv4_bwd_slabs", Mout)
-                    partd, accd = self.store.partial("cdf", Sd * C4 * cin, self.ws)
-                    lib.call("tuber_conv4_bwd_fused", dz, cd, x, d["wdt"], d["lddt"], bd.cA, bd.cB, bd.cC, None, None, dxd, None, None, partd, Mout)
-                    gd = d["gd"]
-                    if accd == 2:
-                        self.store.defer.add(partd, gd if isinstance(gd, int) else gd.data_ptr(), C4 * cin, C4 * cin, Sd, 1)
-                    else:
-                        lib.call("tuber_reduce_rows", partd, gd, Sd, C4 * cin, 1)
-                    res = dxd
-                elif d["ds"]:
-                    dxd = torch.empty(Mout, cin, dtype=BF, device=dev)
-                    lib.call("tuber_gemm_nt", dcd, C4, d["wdt"], d["lddt"], dxd, cin, Mout, cin, C4, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0,
-                             0, 0, None, None, 0, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)
-                    if not strided:
-                        res = dxd           # stride-1 projection shortcut: its dense data gradient is the residual input
-                # The input gradient dx IS the gradient of the block below's output y (= this block's x).  When that block is an
-                # identity block and dx is complete after this GEMM, its join backward (dz = dx * [y > 0] + the bn4 statistics) runs
-                # as the GEMM's epilogue: dx never reaches HBM and the block_out_bwd launch of the next iteration is gone.
-                fuse = not ab.on("no_join_fusion") and bi - 1 >= lowest and not self.blocks[bi - 1]["ds"] and not (d["ds"] and strided)
-                # layer1: the persistent conv1-backward kernel also takes the join of the stage's FIRST block below it (one more LDS image: the
-                # projection shortcut's raw output, for its BatchNorm's statistics row) -- that join was a five-tensor block_out_bwd pass (170 us)
-                fuse_sr = (not ab.on("no_join_fusion") and not ab.on("no_strided_join_fusion") and bi - 1 >= lowest and not self.blocks[bi - 1]["ds"]
-                           and d["ds"] and strided and not fuse1 and Min % (Ti * Hi * Wi) == 0)
-                fuse_ds = (not ab.on("no_join_fusion") and not ab.on("no_ds_join_fusion") and bi - 1 >= lowest and self.blocks[bi - 1]["ds"]
-                           and not (d["ds"] and strided))
-                if fuse1:
-                    part1 = None
-                    if f["w1"]:
-                        S1 = lib.query("tuber_conv1_bwd_slabs", Min)
-                        part1, acc1 = self.store.partial("c1f", S1 * P * cin, self.ws)
-                    outx = torch.empty(Min, cin, dtype=BF, device=dev)
-                    cdl, jc = None, None
-                    if fuse or fuse_ds:
-                        c4l = sblocks[bi - 1 - base][3]
-                        Rj = lib.query("tuber_gemm_nt_stat_rows", Min, cin)
-                        ja, jb = self.ws("stj0", Rj * cin), self.ws("stj1", Rj * cin)
-                        if fuse_ds:
-                            cdl, jc = sblocks[bi - 1 - base][4], self.ws("stj2", Rj * cin)
-                    else:
-                        c4l, ja, jb = None, None, None
-                    lib.call("tuber_conv1_bwd_fused", dz1, c1, b1.cA, b1.cB, b1.cC, d["w1t"], d["ld1t"], res, x, c4l, cdl, outx, ja, jb, jc, part1, Min)
-                    if part1 is not None:
-                        g1 = d["g1"]
-                        if acc1 == 2:
-                            self.store.defer.add(part1, g1 if isinstance(g1, int) else g1.data_ptr(), P * cin, P * cin, S1, 1)
-                        else:
-                            lib.call("tuber_reduce_rows", part1, g1, S1, P * cin, 1)
-                    if fuse or fuse_ds:
-                        pre = (outx, ja, jb, jc, Rj)
-                        dy = None
-                    else:
-                        dy = outx
-                elif fuse:
-                    c4l = sblocks[bi - 1 - base][3]
-                    Rj = lib.query("tuber_gemm_nt_stat_rows", Min, cin)
-                    ja, jb = self.ws("stj0", Rj * cin), self.ws("stj1", Rj * cin)
-                    dzl = torch.empty(Min, cin, dtype=BF, device=dev)
-                    ym = sblocks[bi - 1 - base][7]                 # the lower block's ReLU mask as a bit field (tuber_block_out_fwd_mask), or None
-                    if ym is not None:
-                        lib.call("tuber_gemm_nt_join_mask", dc1, P, d["w1t"], d["ld1t"], dzl, cin, Min, cin, P, res, cin, ym, c4l, cin, ja, jb)
-                    else:
-                        lib.call("tuber_gemm_nt_join", dc1, P, d["w1t"], d["ld1t"], dzl, cin, Min, cin, P, res, cin, x, cin, c4l, cin, ja, jb)
-                    pre = (dzl, ja, jb, None, Rj)
-                    dy = None
-                elif fuse_ds:
-                    # the block below is its stage's first block (layer2 / layer3 / layer4): the join epilogue also takes the statistics row of its
-                    # projection shortcut's BatchNorm (sum dz*cd) -- no stand-alone five-tensor block_out_bwd
-                    sv_l = sblocks[bi - 1 - base]
-                    Rj = lib.query("tuber_gemm_nt_stat_rows", Min, cin)
-                    ja, jb, jc = self.ws("stj0", Rj * cin), self.ws("stj1", Rj * cin), self.ws("stj2", Rj * cin)
-                    dzl = torch.empty(Min, cin, dtype=BF, device=dev)
-                    if sv_l[7] is not None:
-                        lib.call("tuber_gemm_nt_join_ds_mask", dc1, P, d["w1t"], d["ld1t"], dzl, cin, Min, cin, P, res, cin, sv_l[7], sv_l[3], cin, sv_l[4], cin, ja, jb, jc)
-                    else:
-                        lib.call("tuber_gemm_nt_join_ds", dc1, P, d["w1t"], d["ld1t"], dzl, cin, Min, cin, P, res, cin, x, cin, sv_l[3], cin, sv_l[4], cin, ja, jb, jc)
-                    pre = (dzl, ja, jb, jc, Rj)
-                    dy = None
-                elif fuse_sr:
-                    # a stage's first block above an identity block (layer1 | layer2, layer2 | layer3, layer3 | layer4): the strided projection
-                    # shortcut's gradient dxd is added at its sampled rows INSIDE the join epilogue -- no dx tensor, no scatter-add launch, no
-                    # stand-alone block_out_bwd pass over the previous stage's widest tensors (128 us at the layer1 | layer2 boundary)
-                    c4l = sblocks[bi - 1 - base][3]
-                    Rj = lib.query("tuber_gemm_nt_stat_rows", Min, cin)
-                    ja, jb = self.ws("stj0", Rj * cin), self.ws("stj1", Rj * cin)
-                    dzl = torch.empty(Min, cin, dtype=BF, device=dev)
-                    ym = sblocks[bi - 1 - base][7]
-                    if ym is not None:
-                        lib.call("tuber_gemm_nt_join_strided_mask", dc1, P, d["w1t"], d["ld1t"], dzl, cin, Min, cin, P, dxd, cin, To, Hq, Wq, Ti, Hi, Wi, st, ss,
-                                 ym, c4l, cin, ja, jb)
-                    else:
-                        lib.call("tuber_gemm_nt_join_strided", dc1, P, d["w1t"], d["ld1t"], dzl, cin, Min, cin, P, dxd, cin, To, Hq, Wq, Ti, Hi, Wi, st, ss,
-                                 x, cin, c4l, cin, ja, jb)
-                    pre = (dzl, ja, jb, None, Rj)
-                    dy = None
-                else:
-                    dx = torch.empty(Min, cin, dtype=BF, device=dev)
-                    lib.call("tuber_gemm_nt", dc1, P, d["w1t"], d["ld1t"], dx, cin, Min, cin, P, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                             0, None, res, cin, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)
-                    if d["ds"] and strided:
-                        lib.call("tuber_rows_scatter_add", dx, dxd, Mout, To, Hq, Wq, Ti, Hi, Wi, st, ss, cin)
-                    dy = dx
-            # layer1 / layer2 weight gradients are long GEMMs: launched per bottleneck (their operands are 45-180 MB each);
-            # layer3 / layer4 ones are short: up to 8 (four bottlenecks) share a launch
-            # stage boundaries at which the gradient windows above them are made FINAL (queued weight-gradient groups launched, deferred
-            # second-stage sums landed): always where layer3 ends; the graph-mode DDP step (training.GraphedTrainStep) adds the end of
-            # layer4 -- set BEFORE its eager warm-up, so warm-up and capture build the same launch groups and reduce tables
-            at_cut = d["first"] and d["stage"] in getattr(self, "cut_stages", (3,))
-            if d["stage"] <= 2 or red is not None or at_cut:
-                self.flush_wgrads()
-            if red is not None:
-                self.store.defer.flush()         # the slice handed to RCCL must include the deferred second-stage reductions
-                red.notify(d["off0"])
-            hook = getattr(self, "split_hook", None)
-            if at_cut:
-                self.store.defer.flush()
-            if hook is not None and at_cut and need_dx:
-                # every parameter at flat offsets >= off0 (this stage, the stages above it, everything behind the body) and everything
-                # laid out in front of the body (transformer, heads) is final here: the graph-mode DDP step cuts its hipGraph at this
-                # point and all-reduces those windows under the backward of the stages below
-                hook(d["off0"])
+                dy, pre = self._bwd_conv1(d, sv, f, B, lower, g1, fuse1, res, dxd)
+            self._bwd_cut(d, need_dx, red)
         return dy
+
+    def _bwd_join(self, d, sv, B, dy):
+        """join backward: dz + stats of bn4 (and the shortcut BN) -> (dz, sum-dz rows, sum-dz*c4 rows, sum-dz*cd rows, R)"""
+        C4, (_, Mout) = d.c4, _rows(B, sv.geom)
+        R = lib.query("tuber_rowblock_count", Mout, C4)
+        sa, sb, sc_ = self.ws("st0", R * C4), self.ws("st1", R * C4), self.ws("st2", R * C4)
+        dz = torch.empty(Mout, C4, dtype=BF, device=self.dev)
+        lib.call("tuber_block_out_bwd", dy, sv.y, sv.c4, sv.cd, dz, sa, sb, sc_ if d.ds else None, Mout, C4)
+        return dz, sa, sb, sc_, R
+
+    def _bwd_bn4(self, d, sv, f, depth, need_dx, B, join):
+        """bn4's and the projection shortcut BatchNorm's backward and the conv4 weight gradient -> (dc4, dcd, fuse4, fuse_proj)"""
+        dz, sa, sb, sc_, R = join       # (sc_: the projection shortcut's statistics rows when the join of a stage's first block was fused)
+        P, C4, (_, Mout) = d.p, d.c4, _rows(B, sv.geom)
+        dc4 = None
+        # layer1 (C4 = 256, P = 64: the widest activations): bn4's backward apply, the conv4 data gradient and the conv4 weight
+        # gradient run as ONE persistent kernel that reads dz and c4 once and never writes dc4 (csrc/conv4_bwd.hip)
+        fuse4 = (not ab.on("no_conv4_bwd_fused") and depth >= 3 and f["w4"]
+                 and lib.query("tuber_conv4_bwd_supported", C4, P) == 1)
+        if depth >= 2 or f["bn4"]:
+            dc4 = self._bn_bwd(d.bn4, sa, sb, R, Mout, dz, sv.c4, Mout, train=f["bn4"], apply=depth >= 2 and not fuse4)
+        dcd = None
+        # layer1's projection shortcut (64 -> 256 channels, stride 1): the same persistent kernel in its plain form does the shortcut
+        # BatchNorm's backward apply, the projection's data gradient and its weight gradient in one pass over dz and cd
+        fuse_proj = (not ab.on("no_proj_bwd_fused") and d.ds and not d.strided and need_dx and f["wd"]
+                     and lib.query("tuber_conv4_bwd_supported", C4, d.cin) == 1)
+        if d.ds and (need_dx or f["wd"] or f["bnd"]):
+            dcd = self._bn_bwd(d.bnd, sa, sc_, R, Mout, dz, sv.cd, Mout, train=f["bnd"], apply=(need_dx or f["wd"]) and not fuse_proj)
+        # conv4: weight grad (A = relu(bn3(c3)) recomputed on load) and data grad fused with relu/bn3 backward
+        if f["w4"] and not fuse4:
+            self._wgrad(dc4, C4, sv.c3, P, d.g4, Mout, C4, P, 1, d.bn3.scale, d.bn3.shift)
+        return dc4, dcd, fuse4, fuse_proj
+
+    def _bwd_conv4_dw(self, d, sv, f, depth, B, join, dc4, fuse4):
+        """conv4 data gradient (relu / bn3 backward fused), bn3's backward and the depthwise conv's two gradients (relu / bn1 backward fused).
+        Returns (dz1, sum rows, sum*c1 rows, R1) for bn1's backward, or None when the chain ends above it (depth < 5)."""
+        dev = self.dev
+        dz = join[0]
+        c1, c3 = sv.c1, sv.c3
+        P, C4, st, ss = d.p, d.c4, d.st, d.ss
+        Ti, Hi, Wi, To, Hq, Wq = sv.geom
+        Min, Mout = _rows(B, sv.geom)
+        b1, b3, b4 = d.bn1, d.bn3, d.bn4
+        dc3 = None
+        tile = not d.strided and not ab.on("dw_register_tiled")
+        # bn3's backward apply (dc3 = cA*dz3 + cB*c3 + cC) is formed INSIDE the two depthwise backward kernels of the stride-1 blocks
+        # while they load their gradient operand: every workgroup derives the coefficients of its 64 channels from the partial rows
+        # of the conv4 data-gradient GEMM -- the bn_bwd_fa launch and the dc3 round trip through HBM disappear
+        R3 = lib.query("tuber_gemm_nt_stat_rows", Mout, P)
+        fuse3 = (not ab.on("no_bn3_in_dw") and tile and depth >= 5 and P % 64 == 0
+                 and (R3 <= self._fa_max or lib.query("tuber_stat_rows_reduced", R3) <= self._fa_max))
+        if depth >= 3:
+            s0, s1 = self.ws("st0u" if fuse3 else "st0", R3 * P), self.ws("st1u" if fuse3 else "st1", R3 * P)
+            dz3 = torch.empty(Mout, P, dtype=BF, device=dev)
+            if fuse4:
+                S4 = lib.query("tuber_conv4_bwd_slabs", Mout)
+                part4, acc4 = self.store.partial("c4f", S4 * C4 * P, self.ws)
+                lib.call("tuber_conv4_bwd_fused", dz, sv.c4, c3, d.w4t, d.ld4t, b4.cA, b4.cB, b4.cC, b3.scale, b3.shift,
+                         dz3, s0, s1, part4, Mout)
+                self._slab_reduce(part4, acc4, d.g4, C4 * P, S4)
+            else:
+                lib.gemm_nt(dc4, C4, d.w4t, d.ld4t, dz3, P, Mout, P, C4, epi=2, stat0=s0, stat1=s1, Cm=c3, ldcm=P, m_scale=b3.scale, m_shift=b3.shift)
+            if fuse3:
+                bs0, bs1, bR = (s0, s1, R3) if R3 <= self._fa_max else self._stat_rows(s0, s1, R3, P)
+                bn3 = (dz3, c3, bs0, bs1, bR, float(Mout), b3.gamma, b3.mean, b3.invstd)
+            else:
+                dc3 = self._bn_bwd(b3, s0, s1, R3, Mout, dz3, c3, Mout, train=f["bn3"], apply=depth >= 4)
+        # depthwise conv: weight grad, data grad fused with relu/bn1 backward
+        # (stride-1 blocks with the bn3 fold: ONE launch forms both gradients from one staged ring of dc3 -- 4 tensor passes instead of
+        #  the 7 of two kernels; csrc/dwconv_tile.hip: dwconv_tile_bwd_both_kernel)
+        both = not ab.on("no_dw_bwd_one_launch") and fuse3 and f["w3"] and depth >= 5
+        if both:
+            R1 = nb = lib.query("tuber_dwconv_tile_blocks", B, Ti, Hi, Wi, P)      # one [27][P] weight-gradient block per workgroup of the data-gradient grid
+            part, acc = self.store.partial("tn", nb * 27 * P, self.ws)
+            s0, s1 = self.ws("st0", R1 * P), self.ws("st1", R1 * P)
+            dz1 = torch.empty(Min, P, dtype=BF, device=dev)
+            lib.call("tuber_dwconv_tile_bwd_both_bn", *bn3, b3.dgamma if f["bn3"] else None, b3.dbeta if f["bn3"] else None,
+                     d.w3, c1, b1.scale, b1.shift, dz1, s0, s1, part, B, Ti, Hi, Wi, P)
+            self._slab_reduce(part, acc, d.g3, 27 * P, nb, P)       # (immediate form: the same block sum, launched right here)
+            return dz1, s0, s1, R1
+        if f["w3"]:
+            nb = lib.query("tuber_dwconv_tile_wgrad_blocks", B, Ti, Hi, Wi, P) if tile else lib.query("tuber_dwconv_bwd_weight_blocks", B, To, Hq, Wq)
+            part, acc = self.store.partial("tn", nb * 27 * P, self.ws)
+            if fuse3:
+                lib.call("tuber_dwconv_tile_bwd_weight_bn", *bn3, c1, b1.scale, b1.shift, part, d.g3, acc, B, Ti, Hi, Wi, P)
+            elif tile:
+                lib.call("tuber_dwconv_tile_bwd_weight", dc3, c1, b1.scale, b1.shift, part, d.g3, acc, B, Ti, Hi, Wi, P)
+            else:
+                lib.call("tuber_dwconv_bwd_weight", dc3, c1, b1.scale, b1.shift, part, d.g3, acc, B, Ti, Hi, Wi, To, Hq, Wq, P, st, ss)
+            if acc == 2:            # (acc 1: these launchers sum their partials into g3 themselves)
+                self._slab_reduce(part, acc, d.g3, 27 * P, nb, P)
+        if depth < 5:
+            return None
+        R1 = lib.query("tuber_dwconv_tile_blocks", B, Ti, Hi, Wi, P) if tile else lib.query("tuber_dwconv_bwd_data_stat_rows", B, Ti, Hi, Wi)
+        s0, s1 = self.ws("st0", R1 * P), self.ws("st1", R1 * P)
+        dz1 = torch.empty(Min, P, dtype=BF, device=dev)
+        if fuse3:
+            lib.call("tuber_dwconv_tile_bwd_data_bn", *bn3, b3.dgamma if f["bn3"] else None, b3.dbeta if f["bn3"] else None,
+                     d.w3, c1, b1.scale, b1.shift, dz1, s0, s1, B, Ti, Hi, Wi, P)
+        elif tile:
+            lib.call("tuber_dwconv_tile_bwd_data", dc3, d.w3, c1, b1.scale, b1.shift, dz1, s0, s1, B, Ti, Hi, Wi, P)
+        else:
+            lib.call("tuber_dwconv_bwd_data", dc3, d.w3, c1, b1.scale, b1.shift, dz1, s0, s1, B, Ti, Hi, Wi, To, Hq, Wq, P, st, ss)
+        return dz1, s0, s1, R1
+
+    def _bwd_bn1(self, d, sv, f, depth, need_dx, B, dw):
+        """bn1's backward and the conv1 weight gradient -> (conv1's gradient operand, fuse1): dc1, or the raw dz1 when the fused kernel applies bn1 itself"""
+        Min, _ = _rows(B, sv.geom)
+        g1, fuse1 = None, False
+        if dw is not None:
+            dz1, s0, s1, R1 = dw
+            # layer1 (256-channel block input, P = 64): bn1's backward apply, the conv1 data gradient (with the lower block's join
+            # when that is an identity block) and the conv1 weight gradient run as ONE persistent kernel (csrc/conv1_bwd.hip)
+            fuse1 = (not ab.on("no_conv1_bwd_fused") and need_dx and not (d.ds and d.strided)
+                     and lib.query("tuber_conv1_bwd_supported", d.cin, d.p) == 1)
+            dc1 = self._bn_bwd(d.bn1, s0, s1, R1, Min, dz1, sv.c1, Min, train=f["bn1"], apply=depth >= 6 and not fuse1)
+            g1 = dz1 if fuse1 else dc1
+        # conv1: weight grad and data grad (+ identity shortcut gradient as residual)
+        if f["w1"] and not fuse1:
+            self._wgrad(g1, d.p, sv.x, d.cin, d.g1, Min, d.p, d.cin)
+        return g1, fuse1
+
+    def _bwd_shortcut(self, d, sv, f, need_dx, B, join, dcd, fuse_proj):
+        """the shortcut's share of the input gradient -> (res, dxd): ``res`` is what the conv1 data gradient takes as its residual (dz of an identity
+        block, the dense data gradient of a stride-1 projection, None), ``dxd`` the projection's data gradient (a strided one is added at its sampled rows)"""
+        dz = join[0]
+        cin, C4, x = d.cin, d.c4, sv.x
+        Ti, Hi, Wi, To, Hq, Wq = sv.geom
+        _, Mout = _rows(B, sv.geom)
+        if d.ds and f["wd"] and not fuse_proj:
+            gather = (To, Hq, Wq, Ti, Hi, Wi, d.st, d.ss) if d.strided else None
+            self._wgrad(dcd, C4, x, cin, d.gd, Mout, C4, cin, 0, None, None, gather)
+        if not need_dx or not d.ds:
+            return (dz if need_dx else None), None
+        dxd = torch.empty(Mout, cin, dtype=BF, device=self.dev)
+        if fuse_proj:
+            bd = d.bnd
+            Sd = lib.query("tuber_conv4_bwd_slabs", Mout)
+            partd, accd = self.store.partial("cdf", Sd * C4 * cin, self.ws)
+            lib.call("tuber_conv4_bwd_fused", dz, sv.cd, x, d.wdt, d.lddt, bd.cA, bd.cB, bd.cC, None, None, dxd, None, None, partd, Mout)
+            self._slab_reduce(partd, accd, d.gd, C4 * cin, Sd)
+        else:
+            lib.gemm_nt(dcd, C4, d.wdt, d.lddt, dxd, cin, Mout, cin, C4)
+        return (None if d.strided else dxd), dxd        # stride-1 projection shortcut: its dense data gradient is the residual input
+
+    def _bwd_conv1(self, d, sv, f, B, lower, g1, fuse1, res, dxd):
+        """conv1 data gradient, with the join backward of the block below (``lower`` = its (block, saved) records, None at the end of the chain) in one
+        of the fused forms -> (dy, pre): the gradient of this block's input, or the join outputs the next iteration takes instead"""
+        cin, P, st, ss, b1, x = d.cin, d.p, d.st, d.ss, d.bn1, sv.x
+        Ti, Hi, Wi, To, Hq, Wq = sv.geom
+        Min, Mout = _rows(B, sv.geom)
+        lb, ls = lower or (None, None)
+        strided_ds = d.ds and d.strided
+        # The input gradient dx IS the gradient of the block below's output y (= this block's x).  When that block is an
+        # identity block and dx is complete after this GEMM, its join backward (dz = dx * [y > 0] + the bn4 statistics) runs
+        # as the GEMM's epilogue: dx never reaches HBM and the block_out_bwd launch of the next iteration is gone.
+        fuse = not ab.on("no_join_fusion") and lb is not None and not lb.ds and not strided_ds
+        # layer1: the persistent conv1-backward kernel also takes the join of the stage's FIRST block below it (one more LDS image: the
+        # projection shortcut's raw output, for its BatchNorm's statistics row) -- that join was a five-tensor block_out_bwd pass (170 us)
+        fuse_sr = (not ab.on("no_join_fusion") and not ab.on("no_strided_join_fusion") and lb is not None and not lb.ds
+                   and strided_ds and not fuse1 and Min % (Ti * Hi * Wi) == 0)
+        fuse_ds = (not ab.on("no_join_fusion") and not ab.on("no_ds_join_fusion") and lb is not None and lb.ds
+                   and not strided_ds)
+        if fuse1:
+            part1 = None
+            if f["w1"]:
+                S1 = lib.query("tuber_conv1_bwd_slabs", Min)
+                part1, acc1 = self.store.partial("c1f", S1 * P * cin, self.ws)
+            if fuse or fuse_ds:
+                pre = outx, ja, jb, jc, _ = self._join_out(Min, cin, fuse_ds)
+                c4l, cdl = ls.c4, (ls.cd if fuse_ds else None)
+            else:
+                pre, outx = None, torch.empty(Min, cin, dtype=BF, device=self.dev)
+                c4l = cdl = ja = jb = jc = None
+            lib.call("tuber_conv1_bwd_fused", g1, sv.c1, b1.cA, b1.cB, b1.cC, d.w1t, d.ld1t, res, x, c4l, cdl, outx, ja, jb, jc, part1, Min)
+            if part1 is not None:
+                self._slab_reduce(part1, acc1, d.g1, P * cin, S1)
+            return (None, pre) if pre is not None else (outx, None)
+        if fuse or fuse_ds or fuse_sr:
+            pre = dzl, ja, jb, jc, _ = self._join_out(Min, cin, fuse_ds)
+            head = (g1, P, d.w1t, d.ld1t, dzl, cin, Min, cin, P)
+            ym = ls.ymask                   # the lower block's ReLU mask as a bit field (tuber_block_out_fwd_mask), or None
+            if fuse:
+                if ym is not None:
+                    lib.call("tuber_gemm_nt_join_mask", *head, res, cin, ym, ls.c4, cin, ja, jb)
+                else:
+                    lib.call("tuber_gemm_nt_join", *head, res, cin, x, cin, ls.c4, cin, ja, jb)
+            elif fuse_ds:
+                # the block below is its stage's first block (layer2 / layer3 / layer4): the join epilogue also takes the statistics row of its
+                # projection shortcut's BatchNorm (sum dz*cd) -- no stand-alone five-tensor block_out_bwd
+                if ym is not None:
+                    lib.call("tuber_gemm_nt_join_ds_mask", *head, res, cin, ym, ls.c4, cin, ls.cd, cin, ja, jb, jc)
+                else:
+                    lib.call("tuber_gemm_nt_join_ds", *head, res, cin, x, cin, ls.c4, cin, ls.cd, cin, ja, jb, jc)
+            else:
+                # a stage's first block above an identity block (layer1 | layer2, layer2 | layer3, layer3 | layer4): the strided projection
+                # shortcut's gradient dxd is added at its sampled rows INSIDE the join epilogue -- no dx tensor, no scatter-add launch, no
+                # stand-alone block_out_bwd pass over the previous stage's widest tensors (128 us at the layer1 | layer2 boundary)
+                if ym is not None:
+                    lib.call("tuber_gemm_nt_join_strided_mask", *head, dxd, cin, To, Hq, Wq, Ti, Hi, Wi, st, ss, ym, ls.c4, cin, ja, jb)
+                else:
+                    lib.call("tuber_gemm_nt_join_strided", *head, dxd, cin, To, Hq, Wq, Ti, Hi, Wi, st, ss, x, cin, ls.c4, cin, ja, jb)
+            return None, pre
+        dx = torch.empty(Min, cin, dtype=BF, device=self.dev)
+        lib.gemm_nt(g1, P, d.w1t, d.ld1t, dx, cin, Min, cin, P, R=res, ldr=cin)
+        if strided_ds:
+            lib.call("tuber_rows_scatter_add", dx, dxd, Mout, To, Hq, Wq, Ti, Hi, Wi, st, ss, cin)
+        return dx, None
+
+    def _bwd_cut(self, d, need_dx, red):
+        """the end of a block's backward: launch what is queued and land what is deferred where a gradient window has to be final"""
+        # layer1 / layer2 weight gradients are long GEMMs: launched per bottleneck (their operands are 45-180 MB each);
+        # layer3 / layer4 ones are short: up to 8 (four bottlenecks) share a launch
+        # stage boundaries at which the gradient windows above them are made FINAL (queued weight-gradient groups launched, deferred
+        # second-stage sums landed): always where layer3 ends; the graph-mode DDP step (training.GraphedTrainStep) adds the end of
+        # layer4 -- set BEFORE its eager warm-up, so warm-up and capture build the same launch groups and reduce tables
+        at_cut = d.first and d.stage in self.cut_stages
+        if d.stage <= 2 or red is not None or at_cut:
+            self.flush_wgrads()
+        if red is not None:
+            self.store.defer.flush()         # the slice handed to RCCL must include the deferred second-stage reductions
+            red.notify(d.off0)
+        if at_cut:
+            self.store.defer.flush()
+        if self.split_hook is not None and at_cut and need_dx:
+            # every parameter at flat offsets >= off0 (this stage, the stages above it, everything behind the body) and everything
+            # laid out in front of the body (transformer, heads) is final here: the graph-mode DDP step cuts its hipGraph at this
+            # point and all-reduces those windows under the backward of the stages below
+            self.split_hook(d.off0)
 
     def backward(self, saved, dfeat):
         """dfeat bf16 [B*T'*h*w, 2048] (gradient of the returned features).  Parameter gradients of the TRAINABLE tensors are
         accumulated into the ParamStore's flat gradient buffer; the chain stops at the lowest block with a trainable tensor."""
         dev = self.dev
         dy = dfeat
-        B = saved["stem"][4][0]
+        clips, c0, arg, (B, T, Ho, Wo, Hp, Wp) = saved["stem"]
         red = getattr(self.store, "reducer", None)
         plans, stem_plan, lowest = self.trainable_plan()
         if red is not None:           # everything behind the body (pool decoder of the 'decode' configs) is final ...
@@ -834,7 +871,6 @@ class CSNRunner:
         if not stem_plan["any"]:
             return
         # stem: pool + relu + bn backward, then the 3->64 conv weight gradient (implicit GEMM over the clip)
-        clips, _, c0, arg, (B, T, Ho, Wo, Hp, Wp) = saved["stem"]
         M0 = B * T * Ho * Wo
         R = lib.query("tuber_stem_pool_bwd_stat_rows", M0)
         s0, s1 = self.ws("st0", R * 64), self.ws("st1", R * 64)

@@ -98,6 +98,16 @@ def call(name, *args):
     return _call(name, *args)
 
 
+def gemm_nt(A, lda, B, ldb, C, ldc, M, N, K, *, amode=0, a_scale=None, a_shift=None, gather=None, epi=0, bias=None,
+            R=None, ldr=0, relu=0, out_f32=0, stat0=None, stat1=None, Cm=None, ldcm=0, m_scale=None, m_shift=None, alpha=1.0,
+            drop_p=0.0, seed_ptr=None, salt=0, A2=None, lda2=0, a_coef2=None):
+    """``tuber_gemm_nt`` by keyword: the one entry point with a 30-argument tail of defaults.  ``gather``: None, or the strided row map
+    (To, Ho, Wo, Ti, Hi, Wi, st, ss) of the down_sample conv.  Goes through ``call``, so a launch hook sees the C ABI's positional tuple."""
+    return call("tuber_gemm_nt", A, lda, B, ldb, C, ldc, M, N, K, amode, a_scale, a_shift, 1 if gather else 0,
+                *(gather or (0, 0, 0, 0, 0, 0, 0, 0)), epi, bias, R, ldr, relu, out_f32, stat0, stat1, Cm, ldcm, m_scale, m_shift,
+                alpha, drop_p, seed_ptr, salt, A2, lda2, a_coef2)
+
+
 def _call(name, *args):
     lib = load()
     sig = _sigs[name]

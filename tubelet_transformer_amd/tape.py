@@ -226,8 +226,7 @@ def linear(tp, x, wname, bname=None, rows=None, relu=False, out_f32=False, drop=
     if tp.dry:
         tp.dry_log.append(("linear", dict(x=x, y=y, w=wb, b=bias, relu=relu, p=p, salt=salt, out_f32=out_f32)))
     else:
-        lib.call("tuber_gemm_nt", x, K, wb, K, y, N, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                 0, bias, None, 0, 1 if relu else 0, 1 if out_f32 else 0, None, None, None, 0, None, None, 1.0, p, st.seed, salt, None, 0, None)
+        lib.gemm_nt(x, K, wb, K, y, N, M, N, K, bias=bias, relu=1 if relu else 0, out_f32=1 if out_f32 else 0, drop_p=p, seed_ptr=st.seed, salt=salt)
     if not tp.train:
         return y
     wreq = st.trainable(wname)
@@ -347,8 +346,7 @@ def linear(tp, x, wname, bname=None, rows=None, relu=False, out_f32=False, drop=
         tx = tp.target(x)
         dx = torch.empty(M, K, dtype=BF, device=dev)
         if id(tx) in tp.stack:
-            lib.call("tuber_gemm_nt", gb, ldg, wt, ldt, dx, K, M, K, Kred, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                     0, None, None, 0, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)
+            lib.gemm_nt(gb, ldg, wt, ldt, dx, K, M, K, Kred)
             tp.put(tx, dx)
             return
         r = tp.force(tp.g.pop(id(tx), None))
@@ -356,15 +354,13 @@ def linear(tp, x, wname, bname=None, rows=None, relu=False, out_f32=False, drop=
             tp.g[id(tx)] = r
             r = None
         if id(tx) in tp.mask and r is None and tx is x:
-            lib.call("tuber_gemm_nt", gb, ldg, wt, ldt, dx, K, M, K, Kred, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                     2, None, None, 0, 0, 0, None, None, x, K, None, None, tp.mask[id(tx)], 0.0, None, 0, None, 0, None)
+            lib.gemm_nt(gb, ldg, wt, ldt, dx, K, M, K, Kred, epi=2, Cm=x, ldcm=K, alpha=tp.mask[id(tx)])
             tp.premasked.add(id(tx))
         elif M <= 64 and Kred >= 1024 and K % 16 == 0 and ldg % 8 == 0 and not ab.on("no_in_proj_dx2"):
             # few rows, long reduction (the decoder's linear1): 16 workgroups x 4 waves over the reduction instead of 4 wave-split tiles
             lib.call("tuber_rows_dx2", gb, ldg, M, Kred, Kred, wt, ldt, K, dx, r, None)
         else:
-            lib.call("tuber_gemm_nt", gb, ldg, wt, ldt, dx, K, M, K, Kred, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                     0, None, r, K, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)
+            lib.gemm_nt(gb, ldg, wt, ldt, dx, K, M, K, Kred, R=r, ldr=K)
         tp.put(tx, dx)
     tp.rec(bwd)
     return y
@@ -445,8 +441,7 @@ def in_proj(tp, x, addend, wname, bname, rows, add_cols):
         # data gradients
         toff, _, _, ldt = st.tinfo[wname]
         wt = st.tshadow.data_ptr() + 2 * (toff + r0)           # W^T[:, r0:r1]: column offset, ld = ldt
-        plain = lambda ncols, res, out: lib.call("tuber_gemm_nt", g, N, wt, ldt, out, K, M, K, ncols, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
-                                                 0, None, res, K, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)
+        plain = lambda ncols, res, out: lib.gemm_nt(g, N, wt, ldt, out, K, M, K, ncols, R=res, ldr=K)
         shared = False
         if xreq and areq and M <= 64 and K % 64 == 0 and not ab.on("no_in_proj_dx2"):
             # few rows (the decoder's queries): both data gradients from ONE pass over g and W -- the addend's is a prefix of x's reduction

@@ -529,7 +529,7 @@ class DETR(nn.Module):
             boxes = T.sigmoid(tp, T.linear(tp, x, "bbox_embed.layers.2.weight", "bbox_embed.layers.2.bias", out_f32=True))
 
         # ---- class branch (tuber_ava.py:127-141; transformer_layers.py:71-97) ----
-        feat32, runner.last_y32 = getattr(runner, "last_y32", None), None
+        feat32, runner.last_y32 = runner.last_y32, None
         if hs32 is not None and ab.eval_class_f32():
             # TUBER_EVAL_PRECISION=fp32_class: once per clip, in fp32.  (Without the fp32 decoder output hs32 -- E / H != 32 or
             # TUBER_AB=eval_bf16_decoder -- the mode keeps the bf16 branch below.)
