@@ -1,8 +1,10 @@
 """Record the launch sequence of the schedule: ``python scripts/launch_sequence.py OUTDIR`` writes OUTDIR/<case>.txt, one line per launch =
-the entry-point name and every argument (pointers as 0 / p -- addresses depend on the allocator -- everything else by value).  Two trees that
+the entry-point name and every argument (pointers as 0 / p -- addresses depend on the allocator -- everything else by value); a tuber_gemm_tn_group
+line goes on with every TnArgs field of its host entries, a tuber_multi_reduce line with "n stride S mode C next" of every entry of its device table.  Two trees that
 launch the same kernels with the same scalar operands produce byte-identical files (``cmp``); which buffer went where is what
 ``bench.py --dump-outputs`` covers.  Smoke shape: CSN-152 / AVA 2.1, synthetic weights, 2 clips of 32 x 64 x 96, eager steps, fixed seeds.
 tests/test_launch_sequence_gpu.py holds the default training step and eval forward to tests/golden/launch_sequence_*.txt (written by this script)."""
+import ctypes
 import os
 import sys
 
@@ -12,6 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 from tubelet_transformer_amd import ab, lib, synth  # noqa: E402
 from tubelet_transformer_amd.config import load_cfg  # noqa: E402
+from tubelet_transformer_amd.engine import DeferredReduce, TnArgs  # noqa: E402
 from tubelet_transformer_amd.training import build_optimizer, train_step  # noqa: E402
 from tubelet_transformer_amd.tuber import build_model  # noqa: E402
 
@@ -28,7 +31,14 @@ def record(fn):
 
     def hook(name, args, launch):
         word = lambda v, t: ("0" if v is None or (isinstance(v, int) and v == 0) else "p") if "*" in t or t == "hipStream_t" else repr(v)
-        lines.append(" ".join([name] + [word(v, t) for v, (t, _) in zip(args, lib._sigs[name])]))
+        words = [name] + [word(v, t) for v, (t, _) in zip(args, lib._sigs[name])]
+        if name == "tuber_gemm_tn_group":        # the host argument block: every TnArgs field of every entry, under the same rule
+            for e in args[0][:args[1]]:
+                words += [word(getattr(e, k), "*" if c is ctypes.c_void_p else "") for k, c in TnArgs._fields_]
+        elif name == "tuber_multi_reduce":       # the device table (eager steps: the copy is allowed); the P / out addresses stay unprinted
+            for e in args[0].cpu().numpy().view(DeferredReduce._ENTRY):
+                words += [str(int(e[k])) for k in ("n", "stride", "S", "mode", "C", "next")]
+        lines.append(" ".join(words))
         return launch(name, *args)
     lib.set_launch_hook(hook)
     try:

@@ -61,8 +61,8 @@ def side_seq():
         sc, sh = torch.rand(K, device=dev) + 0.5, torch.randn(K, device=dev)
         S = lib.query("tuber_gemm_tn_slabs", M, N, K)
         part, out = torch.empty(max(S, 1) * N * K, device=dev), torch.zeros(N, K, device=dev)
-        ents.append(TnArgs(G.data_ptr(), N, A.data_ptr(), K, part.data_ptr(), out.data_ptr(), 2 if S > 1 else 1, M, N, K, amode, 0,
-                           0, 0, 0, 0, 0, 0, 0, 0, sc.data_ptr() if amode else None, sh.data_ptr() if amode else None, None))
+        ents.append(TnArgs(G=G.data_ptr(), ldg=N, A=A.data_ptr(), lda=K, partial=part.data_ptr(), out=out.data_ptr(), accumulate=2 if S > 1 else 1,
+                           M=M, N=N, K=K, amode=amode, a_scale=sc.data_ptr() if amode else None, a_shift=sh.data_ptr() if amode else None))
         keep.append((G, A, sc, sh, part, out))
     arr = (TnArgs * len(ents))(*ents)
     keep.append(arr)

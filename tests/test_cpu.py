@@ -736,3 +736,150 @@ def test_gemm_nt_keyword_helper_passes_the_positional_tuple_of_the_c_abi():
         names += ["gather", "To", "Ho", "Wo", "Ti", "Hi", "Wi", "st", "ss"] if n == "gather" else [n]
     header = [a for _, a in next(args for _, name, args in lib.header_prototypes() if name == "tuber_gemm_nt")]
     assert header[-1] == "stream" and names == header[:-1], (names, header)
+
+
+def test_wgrad_protocol_queues_launches_and_defers_what_the_three_call_sites_did():
+    """ParamStore.wgrad is the one host-side launch protocol of tuber_gemm_tn.  It is driven here with the calls of its three sites (tape.linear,
+    tape.in_proj, CSNRunner._wgrad); what it queues (every TnArgs field, the kept tensors, the deferred tuples), what it launches at once and what it
+    registers must be what those sites spelled out themselves before the fold -- written out below as they stood, for the default path, for
+    TUBER_AB=no_wgrad_groups and for TUBER_AB=immediate_reduce.  No launch, no GPU: a recording launch hook, a recording queue, and a counting stand-in
+    for the arena (DeferredReduce.alloc asks the HIP runtime whether a capture is running); the slab / bias queries are host functions of the library."""
+    from tubelet_transformer_amd import ab
+    from tubelet_transformer_amd.engine import DeferredReduce, ParamStore, TnArgs, WgradQueue
+
+    class Arena(DeferredReduce):
+        def alloc(self, n):
+            allocs.append(n)
+            return 0x100000 * len(allocs)
+
+        def add(self, *entry):
+            deferred.append(entry)
+
+    class Queue(WgradQueue):
+        def add(self, args, keep, defers):
+            queued.append((tuple(getattr(args, k) for k, _ in TnArgs._fields_), keep, defers))
+
+    st = ParamStore.__new__(ParamStore)
+    st.device, st._scratch, st.defer = torch.device("cpu"), {}, Arena("cpu")
+    st.wq = Queue(st)
+    allocs, deferred, queued, launched = [], [], [], []
+    gb, x, g, addend, G, A = (torch.zeros(8) for _ in range(6))                      # stand-ins for the operand tensors
+    gw, gbias, sc, sh, out = 0x7000000, 0x7100000, 0x7200000, 0x7300000, 0x7400000  # device addresses (flat gradient windows, BatchNorm vectors)
+    A1, A2, A3, A4 = (0x100000 * i for i in (1, 2, 3, 4))                            # the arena's answers, in order
+    Z8 = (0,) * 8
+    Z10 = (0,) * 10
+    tn = lambda: st.scratch("tn", 1)                                                 # the store's cached scratch (immediate_reduce)
+    cs = lambda: st.scratch("cs", 1)
+    gather = (2, 4, 5, 4, 8, 10, 2, 2)
+    slabs = lambda M, N, K: lib.query("tuber_gemm_tn_slabs", M, N, K)
+    fuses = lambda M, N, K, ldg, lda: lib.query("tuber_gemm_tn_fuses_bias", M, N, K, ldg, lda)
+    # the shapes below are chosen for these answers of the library
+    assert (slabs(30, 256, 256), fuses(30, 256, 256, 256, 256)) == (1, 1) and (slabs(16896, 256, 256), fuses(16896, 256, 256, 256, 256)) == (16, 2)
+    assert fuses(30, 80, 260, 128, 260) == 0 and fuses(30, 3, 256, 64, 256) == 0 and (slabs(30, 8, 256), fuses(30, 8, 256, 64, 256)) == (1, 1)
+    assert [(slabs(M, n, 256), fuses(M, n, 256, 768, 256)) for M in (30, 1408) for n in (512, 256)] == [(1, 1), (1, 1), (4, 2), (6, 2)]
+    assert (slabs(5632, 1024, 256), fuses(5632, 1024, 256, 1024, 256)) == (2, 2) and (slabs(80, 512, 256), fuses(80, 512, 256, 512, 256)) == (1, 1)
+
+    def in_proj(M):         # tape.in_proj: N = 768 packed rows, the first 512 against x + addend, both row blocks through the group entry
+        return [st.wgrad(g.data_ptr() + 2 * c0, 768, x, 256, gw + 4 * c0 * 256, M, n, 256, (g, x, a2), bias_grad=gbias + 4 * c0, A2=a2,
+                         lda2=256 if a2 is not None else 0, via_group=True) for c0, n, a2 in ((0, 512, addend), (512, 256, None))]
+    gp, xp, ap = g.data_ptr(), x.data_ptr(), addend.data_ptr()
+    # per case: the call, then per mode (queued, launched, deferred, arena allocations, return value) as the site produced them
+    cases = {
+        "linear, one slab, bias fused": (
+            lambda: st.wgrad(gb, 256, x, 256, gw, 30, 256, 256, (gb, x), bias_grad=gbias, pad_cols=True), {
+                "default": lambda: ([((gb.data_ptr(), 256, xp, 256, None, gw, 1, 30, 256, 256, *Z10, None, None, gbias, None, 0), (gb, x), [])], [], [], [], True),
+                "no_wgrad_groups": lambda: ([], [("tuber_gemm_tn", (gb, 256, x, 256, None, gw, 1, 30, 256, 256, 0, None, None, 0, *Z8, None, 0, None, None, None, gbias))],
+                                            [], [], True),
+                "immediate_reduce": "default"}),
+        "linear, sixteen slabs, bias partial rows": (
+            lambda: st.wgrad(gb, 256, x, 256, gw, 16896, 256, 256, (gb, x), bias_grad=gbias, pad_cols=True), {
+                "default": lambda: ([((gb.data_ptr(), 256, xp, 256, A1, gw, 2, 16896, 256, 256, *Z10, None, None, A2, None, 0), (gb, x),
+                                      [(A1, gw, 65536, 65536, 16, 0), (A2, gbias, 256, 256, 16, 1)])], [], [], [16 * 65536, 16 * 256], True),
+                "no_wgrad_groups": lambda: ([], [("tuber_gemm_tn", (gb, 256, x, 256, A1, gw, 2, 16896, 256, 256, 0, None, None, 0, *Z8, None, 0, None, None, None, A2))],
+                                            [(A1, gw, 65536, 65536, 16, 0), (A2, gbias, 256, 256, 16, 1)], [16 * 65536, 16 * 256], True),
+                "immediate_reduce": lambda: ([], [("tuber_gemm_tn", (gb, 256, x, 256, tn(), gw, 1, 16896, 256, 256, 0, None, None, 0, *Z8, None, 0, None, None, None, cs())),
+                                                  ("tuber_reduce_rows", (cs(), gbias, 16, 256, 1))], [], [], True)}),
+        "linear, shape the transpose-read kernel does not take (K = 260): the 28-argument tuber_gemm_tn, bias left to tuber_colsum": (
+            lambda: st.wgrad(gb, 128, x, 260, gw, 30, 80, 260, (gb, x), bias_grad=gbias, pad_cols=True), {
+                "default": lambda: ([], [("tuber_gemm_tn", (gb, 128, x, 260, None, gw, 1, 30, 80, 260, 0, None, None, 0, *Z8, None, 0, None, None, None, None))], [], [], False),
+                "no_wgrad_groups": "default", "immediate_reduce": "default"}),
+        "linear, frozen bias: no bias query": (
+            lambda: st.wgrad(gb, 256, x, 256, gw, 30, 256, 256, (gb, x), bias_grad=None, pad_cols=True), {
+                "default": lambda: ([((gb.data_ptr(), 256, xp, 256, None, gw, 1, 30, 256, 256, *Z10, None, None, None, None, 0), (gb, x), [])], [], [], [], False),
+                "no_wgrad_groups": lambda: ([], [("tuber_gemm_tn", (gb, 256, x, 256, None, gw, 1, 30, 256, 256, 0, None, None, 0, *Z8, None, 0, None, None, None, None))],
+                                            [], [], False),
+                "immediate_reduce": "default"}),
+        "the padded 3-output head": (
+            lambda: st.wgrad(gb, 64, x, 256, gw, 30, 3, 256, (gb, x), bias_grad=gbias, pad_cols=True), {
+                "default": lambda: ([((gb.data_ptr(), 64, xp, 256, None, A1, 0, 30, 8, 256, *Z10, None, None, None, None, 0), (gb, x), [(A1, gw, 768, 2048, 1, 0)])],
+                                    [], [], [2048], False),
+                "no_wgrad_groups": lambda: ([], [("tuber_gemm_tn", (gb, 64, x, 256, None, gw, 1, 30, 3, 256, 0, None, None, 0, *Z8, None, 0, None, None, None, None))],
+                                            [], [], False),
+                "immediate_reduce": "no_wgrad_groups"}),
+        "in-projection, one slab: row block with A2, row block without": (
+            lambda: in_proj(30), {
+                "default": lambda: ([((gp, 768, xp, 256, None, gw, 1, 30, 512, 256, *Z10, None, None, gbias, ap, 256), (g, x, addend), []),
+                                     ((gp + 1024, 768, xp, 256, None, gw + 4 * 512 * 256, 1, 30, 256, 256, *Z10, None, None, gbias + 2048, None, 0), (g, x, None), [])],
+                                    [], [], [], [True, True]),
+                "no_wgrad_groups": lambda: ([], [("tuber_gemm_tn_group", [(gp, 768, xp, 256, None, gw, 1, 30, 512, 256, *Z10, None, None, gbias, ap, 256)]),
+                                                 ("tuber_gemm_tn_group", [(gp + 1024, 768, xp, 256, None, gw + 4 * 512 * 256, 1, 30, 256, 256, *Z10, None, None, gbias + 2048, None, 0)])],
+                                            [], [], [True, True]),
+                "immediate_reduce": "default"}),
+        "in-projection, several slabs": (
+            lambda: in_proj(1408), {
+                "default": lambda: ([((gp, 768, xp, 256, A1, gw, 2, 1408, 512, 256, *Z10, None, None, A2, ap, 256), (g, x, addend),
+                                      [(A1, gw, 131072, 131072, 4, 0), (A2, gbias, 512, 512, 4, 1)]),
+                                     ((gp + 1024, 768, xp, 256, A3, gw + 4 * 512 * 256, 2, 1408, 256, 256, *Z10, None, None, A4, None, 0), (g, x, None),
+                                      [(A3, gw + 4 * 512 * 256, 65536, 65536, 6, 0), (A4, gbias + 2048, 256, 256, 6, 1)])],
+                                    [], [], [4 * 131072, 4 * 512, 6 * 65536, 6 * 256], [True, True]),
+                "no_wgrad_groups": lambda: ([], [("tuber_gemm_tn_group", [(gp, 768, xp, 256, A1, gw, 2, 1408, 512, 256, *Z10, None, None, A2, ap, 256)]),
+                                                 ("tuber_gemm_tn_group", [(gp + 1024, 768, xp, 256, A3, gw + 4 * 512 * 256, 2, 1408, 256, 256, *Z10, None, None, A4, None, 0)])],
+                                            [(A1, gw, 131072, 131072, 4, 0), (A2, gbias, 512, 512, 4, 1),
+                                             (A3, gw + 4 * 512 * 256, 65536, 65536, 6, 0), (A4, gbias + 2048, 256, 256, 6, 1)],
+                                            [4 * 131072, 4 * 512, 6 * 65536, 6 * 256], [True, True]),
+                # (the group entry refuses several slabs under accumulate = 1 on the device; the host protocol of the site is pinned all the same)
+                "immediate_reduce": lambda: ([], [("tuber_gemm_tn_group", [(gp, 768, xp, 256, tn(), gw, 1, 1408, 512, 256, *Z10, None, None, cs(), ap, 256)]),
+                                                  ("tuber_reduce_rows", (cs(), gbias, 4, 512, 1)),
+                                                  ("tuber_gemm_tn_group", [(gp + 1024, 768, xp, 256, tn(), gw + 4 * 512 * 256, 1, 1408, 256, 256, *Z10, None, None, cs(), None, 0)]),
+                                                  ("tuber_reduce_rows", (cs(), gbias + 2048, 6, 256, 1))], [], [], [True, True])}),
+        "backbone conv4 with the BatchNorm-apply prologue (amode 1, scale, shift), two slabs": (
+            lambda: st.wgrad(G, 1024, A, 256, out, 5632, 1024, 256, (G, A), amode=1, a_scale=sc, a_shift=sh, gather=None), {
+                "default": lambda: ([((G.data_ptr(), 1024, A.data_ptr(), 256, A1, out, 2, 5632, 1024, 256, 1, 0, *Z8, sc, sh, None, None, 0), (G, A),
+                                      [(A1, out, 262144, 262144, 2, 0)])], [], [], [2 * 262144], False),
+                "no_wgrad_groups": lambda: ([], [("tuber_gemm_tn", (G, 1024, A, 256, A1, out, 2, 5632, 1024, 256, 1, sc, sh, 0, *Z8, None, 0, None, None, None, None))],
+                                            [(A1, out, 262144, 262144, 2, 0)], [2 * 262144], False),
+                "immediate_reduce": lambda: ([], [("tuber_gemm_tn", (G, 1024, A, 256, tn(), out, 1, 5632, 1024, 256, 1, sc, sh, 0, *Z8, None, 0, None, None, None, None))],
+                                             [], [], False)}),
+        "backbone projection shortcut with the strided gather": (
+            lambda: st.wgrad(G, 512, A, 256, out, 80, 512, 256, (G, A), amode=0, a_scale=None, a_shift=None, gather=gather), {
+                "default": lambda: ([((G.data_ptr(), 512, A.data_ptr(), 256, None, out, 1, 80, 512, 256, 0, 1, *gather, None, None, None, None, 0), (G, A), [])],
+                                    [], [], [], False),
+                "no_wgrad_groups": lambda: ([], [("tuber_gemm_tn", (G, 512, A, 256, None, out, 1, 80, 512, 256, 0, None, None, 1, *gather, None, 0, None, None, None, None))],
+                                            [], [], False),
+                "immediate_reduce": "default"}),
+    }
+
+    def hook(name, args, launch):       # records and does not launch; a host argument block is read out while it is alive
+        if name == "tuber_gemm_tn_group":
+            args = [tuple(getattr(e, k) for k, _ in TnArgs._fields_) for e in args[0][:args[1]]]
+        launched.append((name, args))
+    same = lambda a, w: a is w or (type(a) is type(w) and a == w)
+    lib.set_launch_hook(hook)
+    try:
+        for mode in ("default", "no_wgrad_groups", "immediate_reduce"):
+            with ab.override(*(() if mode == "default" else (mode,))):
+                for title, (spell, wants) in cases.items():
+                    del allocs[:], deferred[:], queued[:], launched[:]
+                    ret = spell()
+                    want = wants[mode]
+                    wq, wl, wd, wa, wr = (wants[want] if isinstance(want, str) else want)()
+                    assert ret == wr and allocs == wa and deferred == wd, (mode, title, ret, allocs, deferred)
+                    assert len(queued) == len(wq) and len(launched) == len(wl), (mode, title, queued, launched)
+                    for (ga, gk, gd), (a, k, d) in zip(queued, wq):
+                        assert ga == a and len(gk) == len(k) and all(p is q for p, q in zip(gk, k)) and gd == d, (mode, title, ga, a, gd, d)
+                    for (gn, ga), (n, a) in zip(launched, wl):
+                        assert gn == n and len(ga) == len(a) and all(same(p, q) for p, q in zip(ga, a)), (mode, title, gn, ga, a)
+                    if wl and wl[0][0] == "tuber_gemm_tn":
+                        assert len(wl[0][1]) == 28
+    finally:
+        lib.set_launch_hook(None)

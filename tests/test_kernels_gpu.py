@@ -974,9 +974,10 @@ def test_gemm_tn_group_is_bit_identical_to_single_launches(dev):
             acc = 2 if S > 1 else 1
             bg = torch.full((max(S, 1) * N,), 0.5, device=dev) if bias else None
             if grouped:
-                entries.append(TnArgs(G.data_ptr(), N, A.data_ptr(), K, part.data_ptr() if part is not None else None, out.data_ptr(), acc, M, N, K,
-                                      amode, 1 if gather else 0, *g, sc.data_ptr() if amode else None, sh.data_ptr() if amode else None,
-                                      bg.data_ptr() if bias else None))
+                entries.append(TnArgs(G=G.data_ptr(), ldg=N, A=A.data_ptr(), lda=K, partial=part.data_ptr() if part is not None else None, out=out.data_ptr(),
+                                      accumulate=acc, M=M, N=N, K=K, amode=amode, gather=1 if gather else 0,
+                                      **dict(zip(("To", "Ho", "Wo", "Ti", "Hi", "Wi", "st", "ss"), g)), a_scale=sc.data_ptr() if amode else None,
+                                      a_shift=sh.data_ptr() if amode else None, bias_grad=bg.data_ptr() if bias else None))
             else:
                 lib.call("tuber_gemm_tn", G, N, A, K, part, out, acc, M, N, K, amode, sc if amode else None, sh if amode else None,
                          1 if gather else 0, *g, None, 0, None, None, None, bg)
@@ -1197,8 +1198,8 @@ def test_gemm_nt_addproj_and_its_weight_gradient(dev, M, N, K, add_cols):
     dW = torch.zeros(add_cols, K, device=dev)
     db = torch.zeros(max(S, 1) * add_cols, device=dev)
     part = torch.zeros(max(S, 1) * add_cols * K, device=dev)
-    arr = (TnArgs * 1)(TnArgs(g.data_ptr(), N, x.data_ptr(), K, part.data_ptr() if S > 1 else None, dW.data_ptr(), 2 if S > 1 else 1, M, add_cols, K,
-                              0, 0, 0, 0, 0, 0, 0, 0, 0, 0, None, None, db.data_ptr(), pos.data_ptr(), K))
+    arr = (TnArgs * 1)(TnArgs(G=g.data_ptr(), ldg=N, A=x.data_ptr(), lda=K, partial=part.data_ptr() if S > 1 else None, out=dW.data_ptr(),
+                              accumulate=2 if S > 1 else 1, M=M, N=add_cols, K=K, bias_grad=db.data_ptr(), A2=pos.data_ptr(), lda2=K))
     lib.call("tuber_gemm_tn_group", arr, 1)
     got = part.view(S, add_cols, K).sum(0) if S > 1 else dW
     gb = db.view(max(S, 1), add_cols).sum(0)

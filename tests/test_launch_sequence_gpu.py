@@ -11,7 +11,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 @pytest.mark.gpu
 def test_default_training_step_and_eval_forward_launch_the_recorded_sequence(dev, golden_dir, monkeypatch):
     """CSN-152 / AVA 2.1 at the smoke shape, first eager training step and first eval forward of a fresh model: entry point, every scalar
-    argument and the NULL-ness of every pointer argument of every launch equal tests/golden/launch_sequence_{train,eval}.txt line by line."""
+    argument and the NULL-ness of every pointer argument of every launch -- for a grouped weight-gradient launch every field of its host
+    entries too, for the deferred reduction every entry of its device table -- equal tests/golden/launch_sequence_{train,eval}.txt line by line."""
     from tubelet_transformer_amd import ab
     assert ab.active() == [], "the recording is the default path's"
     monkeypatch.delenv("TUBER_EVAL_PRECISION", raising=False)

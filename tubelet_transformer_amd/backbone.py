@@ -20,7 +20,6 @@ import torch
 from torch import nn
 
 from . import ab, lib
-from .engine import TnArgs, WgradQueue
 
 BN_EPS = 1e-3       # ir_CSN_152.py:15
 BN_MOM = 0.1        # ir_CSN_152.py:16
@@ -567,20 +566,8 @@ class CSNRunner:
 
     def _wgrad(self, G, ldg, A, lda, out, M, N, K, amode=0, sc=None, sh=None, gather=None):
         """weight gradient dW[N,K] += G^T f(A).  Nothing consumes it before the optimizer, so it is only QUEUED (engine.WgradQueue:
-        operand tensors kept alive) and launched together with its neighbours in one tuber_gemm_tn_group launch."""
-        S = lib.query("tuber_gemm_tn_slabs", M, N, K)
-        part, acc = self.store.partial("tn", S * N * K, self.ws) if S > 1 else (None, 1)
-        g = gather or (0, 0, 0, 0, 0, 0, 0, 0)
-        outp = out if isinstance(out, int) else out.data_ptr()
-        wq = self.store.wq
-        if wq.enabled and (S == 1 or acc == 2) and WgradQueue.eligible(M, N, K, ldg, lda):
-            ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
-            wq.add(TnArgs(ptr(G), ldg, ptr(A), lda, ptr(part), outp, acc, M, N, K, amode, 1 if gather else 0, *g, ptr(sc), ptr(sh), None),
-                   (G, A), [(part, outp, N * K, N * K, S, 0 if S <= 16 else 1)] if acc == 2 else [])
-            return
-        lib.call("tuber_gemm_tn", G, ldg, A, lda, part, out, acc, M, N, K, amode, sc, sh, 1 if gather else 0, *g, None, 0, None, None, None, None)
-        if acc == 2:
-            self.store.defer.add(part, outp, N * K, N * K, S, 0 if S <= 16 else 1)
+        operand tensors kept alive) and launched together with its neighbours in one tuber_gemm_tn_group launch (ParamStore.wgrad)."""
+        self.store.wgrad(G, ldg, A, lda, out, M, N, K, (G, A), amode=amode, a_scale=sc, a_shift=sh, gather=gather)
 
     def flush_wgrads(self):
         self.store.wq.flush()
@@ -680,7 +667,7 @@ class CSNRunner:
             dz3 = torch.empty(Mout, P, dtype=BF, device=dev)
             if fuse4:
                 S4 = lib.query("tuber_conv4_bwd_slabs", Mout)
-                part4, acc4 = self.store.partial("c4f", S4 * C4 * P, self.ws)
+                part4, acc4 = self.store.partial("c4f", S4 * C4 * P)
                 lib.call("tuber_conv4_bwd_fused", dz, sv.c4, c3, d.w4t, d.ld4t, b4.cA, b4.cB, b4.cC, b3.scale, b3.shift,
                          dz3, s0, s1, part4, Mout)
                 self._slab_reduce(part4, acc4, d.g4, C4 * P, S4)
@@ -697,7 +684,7 @@ class CSNRunner:
         both = not ab.on("no_dw_bwd_one_launch") and fuse3 and f["w3"] and depth >= 5
         if both:
             R1 = nb = lib.query("tuber_dwconv_tile_blocks", B, Ti, Hi, Wi, P)      # one [27][P] weight-gradient block per workgroup of the data-gradient grid
-            part, acc = self.store.partial("tn", nb * 27 * P, self.ws)
+            part, acc = self.store.partial("tn", nb * 27 * P)
             s0, s1 = self.ws("st0", R1 * P), self.ws("st1", R1 * P)
             dz1 = torch.empty(Min, P, dtype=BF, device=dev)
             lib.call("tuber_dwconv_tile_bwd_both_bn", *bn3, b3.dgamma if f["bn3"] else None, b3.dbeta if f["bn3"] else None,
@@ -706,7 +693,7 @@ class CSNRunner:
             return dz1, s0, s1, R1
         if f["w3"]:
             nb = lib.query("tuber_dwconv_tile_wgrad_blocks", B, Ti, Hi, Wi, P) if tile else lib.query("tuber_dwconv_bwd_weight_blocks", B, To, Hq, Wq)
-            part, acc = self.store.partial("tn", nb * 27 * P, self.ws)
+            part, acc = self.store.partial("tn", nb * 27 * P)
             if fuse3:
                 lib.call("tuber_dwconv_tile_bwd_weight_bn", *bn3, c1, b1.scale, b1.shift, part, d.g3, acc, B, Ti, Hi, Wi, P)
             elif tile:
@@ -762,7 +749,7 @@ class CSNRunner:
         if fuse_proj:
             bd = d.bnd
             Sd = lib.query("tuber_conv4_bwd_slabs", Mout)
-            partd, accd = self.store.partial("cdf", Sd * C4 * cin, self.ws)
+            partd, accd = self.store.partial("cdf", Sd * C4 * cin)
             lib.call("tuber_conv4_bwd_fused", dz, sv.cd, x, d.wdt, d.lddt, bd.cA, bd.cB, bd.cC, None, None, dxd, None, None, partd, Mout)
             self._slab_reduce(partd, accd, d.gd, C4 * cin, Sd)
         else:
@@ -791,7 +778,7 @@ class CSNRunner:
             part1 = None
             if f["w1"]:
                 S1 = lib.query("tuber_conv1_bwd_slabs", Min)
-                part1, acc1 = self.store.partial("c1f", S1 * P * cin, self.ws)
+                part1, acc1 = self.store.partial("c1f", S1 * P * cin)
             if fuse or fuse_ds:
                 pre = outx, ja, jb, jc, _ = self._join_out(Min, cin, fuse_ds)
                 c4l, cdl = ls.c4, (ls.cd if fuse_ds else None)

@@ -52,11 +52,6 @@ class WgradQueue:
     def enabled(self):
         return not ab.on("no_wgrad_groups")      # A/B switch: one tuber_gemm_tn launch per weight gradient
 
-    @staticmethod
-    def eligible(M, N, K, ldg, lda):
-        """shapes the transpose-read kernel takes (64 x 64 output tiles, 8-element aligned)"""
-        return not ((N | K | ldg | lda) & 7) and lib.query("tuber_gemm_tn_fuses_bias", M, N, K, ldg, lda) != 0
-
     def add(self, args, keep, defers):
         """args: TnArgs; keep: tensors that must outlive the launch; defers: DeferredReduce.add argument tuples registered at flush"""
         self.q.append((args, keep, defers))
@@ -243,6 +238,7 @@ class ParamStore:
         self.coop_sync = torch.zeros(4, dtype=torch.int32, device=self.device)
         self.coop_off = False            # set by coop_failed(): a timed-out cooperative launch switches this engine to the launch chain
         self.defer = DeferredReduce(self.device)
+        self._scratch = {}               # key -> fp32 scratch tensor (scratch)
 
         def _window(ptr, n, g=self.gflat):
             o = (ptr - g.data_ptr()) // 4
@@ -290,12 +286,73 @@ class ParamStore:
         from .ddp import trainable_ranges
         return trainable_ranges(self)
 
-    def partial(self, key, numel, fallback):
-        """scratch for a weight-gradient kernel's partials -> (pointer or tensor, accumulate flag): arena + 2 when the second stage is
-        deferred to ``defer.flush()``, else ``fallback(key, numel)`` (the shared workspace) + 1."""
+    def scratch(self, key, numel):
+        """device address of ``numel`` fp32 of scratch, one buffer per key (launches are serialised on the stream); grows, lives as long as the store.
+        Live under TUBER_AB=immediate_reduce only: the default path takes its partials from the arena."""
+        t = self._scratch.get(key)
+        if t is None or t.numel() < numel:
+            t = self._scratch[key] = torch.empty(int(numel * 1.25) + 64, dtype=torch.float32, device=self.device)
+        return t.data_ptr()
+
+    def partial(self, key, numel):
+        """scratch for a weight-gradient kernel's partials -> (device address, accumulate flag): arena + 2 when the second stage is
+        deferred to ``defer.flush()``, else ``scratch(key, numel)`` + 1."""
         if self.defer.enabled:
             return self.defer.alloc(numel), 2
-        return fallback(key, numel), 1
+        return self.scratch(key, numel), 1
+
+    def wgrad(self, G, ldg, A, lda, out, M, N, K, keep, *, amode=0, a_scale=None, a_shift=None, gather=None, bias_grad=None, A2=None, lda2=0,
+              pad_cols=False, via_group=False):
+        """weight gradient out[N,K] += G[M,N]^T f(A [+ A2])[M,K], the ONE host-side launch protocol of tuber_gemm_tn (tape.linear, tape.in_proj,
+        CSNRunner._wgrad).  Nothing reads a weight gradient before the optimizer, so it is queued where it can be (WgradQueue: ``keep`` = the operand
+        tensors, alive until the launch; slab reductions registered at flush) and launched at once otherwise (reductions registered / run right here).
+        ``bias_grad``: the bias gradient's address, when the caller wants it -> True when this launch produces it (else: tuber_colsum, tape._bias_colsum).
+        ``pad_cols`` (tape.linear): N that is no multiple of 8 may run over the zero-padded columns of G.
+        ``via_group`` (tape.in_proj): the shape IS a transpose-read shape -- asserted, where the other two sites gate the queue on ``eligible`` -- and an
+        un-queued launch is a tuber_gemm_tn_group of one, the only entry that carries A2 (both row blocks take it, with and without A2; it refuses
+        several slabs under accumulate = 1, so immediate_reduce on an in-projection that splits into slabs is an error today).  The other sites launch
+        tuber_gemm_tn."""
+        wq, defer = self.wq, self.defer
+        ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
+        gth = dict(zip(("To", "Ho", "Wo", "Ti", "Hi", "Wi", "st", "ss"), gather)) if gather else {}
+        entry = lambda **kw: TnArgs(G=ptr(G), ldg=ldg, A=ptr(A), lda=lda, M=M, K=K, amode=amode, gather=1 if gather else 0, a_scale=ptr(a_scale),
+                                    a_shift=ptr(a_shift), A2=ptr(A2), lda2=lda2, **gth, **kw)
+        slabs = lambda n: lib.query("tuber_gemm_tn_slabs", M, n, K)
+        fuses = lambda n: lib.query("tuber_gemm_tn_fuses_bias", M, n, K, ldg, lda)
+        eligible = lambda n: not ((n | K | ldg | lda) & 7) and fuses(n) != 0       # shapes the transpose-read kernel takes (64 x 64 tiles, 8-element aligned)
+        out, N8 = ptr(out), _ceil(N, 8)
+        if pad_cols and N8 != N and wq.enabled and defer.enabled and ldg >= N8 and eligible(N8) and slabs(N8) == 1:
+            # a head with 3 or 4 outputs (class_embed_b, the last box layer): the transpose-read kernel wants multiples of 8, so the product runs
+            # over the zero-padded columns of G into arena scratch [N8][K] and the deferred reduction adds its first N rows to the gradient --
+            # queued with its neighbours instead of a tuber_gemm_tn launch of its own (8 - 12 us each on the critical path)
+            tmp = defer.alloc(N8 * K)
+            wq.add(entry(out=tmp, accumulate=0, N=N8), keep, [(tmp, out, N * K, N8 * K, 1, 0)])
+            return False
+        S = slabs(N)
+        # bias gradient inside the GEMM: 1 = accumulated directly (single slab), 2 = one partial row per slab
+        fuse_b = fuses(N) if bias_grad is not None else 0
+        assert fuse_b or not via_group, "in-projection shapes are transpose-read shapes"
+        part, acc = self.partial("tn", S * N * K) if S > 1 else (None, 1)
+        bpart = self.partial("cs", S * N)[0] if fuse_b == 2 else None
+        bptr = bias_grad if fuse_b == 1 else bpart
+        defers = []
+        if acc == 2:
+            defers.append((part, out, N * K, N * K, S, 0 if S <= 16 else 1))
+            if fuse_b == 2:
+                defers.append((bpart, bias_grad, N, N, S, 1))
+        if wq.enabled and (S == 1 or acc == 2) and (via_group or eligible(N)):
+            wq.add(entry(partial=part, out=out, accumulate=acc, N=N, bias_grad=bptr), keep, defers)
+            return bool(fuse_b)
+        if via_group:
+            lib.call("tuber_gemm_tn_group", (TnArgs * 1)(entry(partial=part, out=out, accumulate=acc, N=N, bias_grad=bptr)), 1)
+        else:
+            lib.call("tuber_gemm_tn", G, ldg, A, lda, part, out, acc, M, N, K, amode, a_scale, a_shift, 1 if gather else 0,
+                     *(gather or (0, 0, 0, 0, 0, 0, 0, 0)), None, 0, None, None, None, bptr)
+        for d in defers:
+            defer.add(*d)
+        if fuse_b == 2 and acc != 2:
+            lib.call("tuber_reduce_rows", bpart, bias_grad, S, N, 1)
+        return bool(fuse_b)
 
     def zero_grad(self):
         self.gflat.zero_()

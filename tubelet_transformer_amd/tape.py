@@ -22,18 +22,8 @@ import numpy as np
 import torch
 
 from . import ab, lib
-from .engine import TnArgs
 
 BF = torch.bfloat16
-_WS = {}
-
-
-def workspace(dev, key, numel):
-    t = _WS.get((dev, key))
-    if t is None or t.numel() < numel:
-        t = torch.empty(int(numel * 1.25) + 64, dtype=torch.float32, device=dev)
-        _WS[(dev, key)] = t
-    return t
 
 
 def _ceil(x, m):
@@ -126,6 +116,22 @@ class Tape:
             lib.call("tuber_axpby", cur, self.force(g), out, cur.numel(), 1.0, 1.0)
             self.g[id(t)] = out
 
+    def residual(self, tx, M, K, rec=None):
+        """the existing gradient of ``tx`` (a target), removed, for the residual input of the GEMM that produces the next contribution -- when it is a
+        contiguous bf16 [M, K] tensor; anything else stays where it is (-> None; Tape.put adds then), and gradients on a stack are never taken.
+        ``rec`` (the fused LayerNorm path, linear.fused_dgrad): looks before it forces, and also leaves an unsummed _Pair (Tape.put on a pair_ok
+        tensor: left to the stand-alone GEMM, which forces it) and a gradient still pending on ``rec`` itself."""
+        if id(tx) in self.stack:
+            return None
+        r = self.g.pop(id(tx), None)
+        if rec is None:
+            r = self.force(r)
+        if r is not None and (isinstance(r, _Pair) or r.dtype != BF or tuple(r.shape) != (M, K) or not r.is_contiguous()
+                              or (rec is not None and self.pending.get(id(r)) is rec)):
+            self.g[id(tx)] = r
+            return None
+        return self.force(r)
+
     def backward(self, seeds):
         for t, g in seeds:
             if g is not None:
@@ -159,7 +165,7 @@ class _PendingLN:
     normalised (attention out_proj, the FFN's linear2) -- runs next and launches LayerNorm backward + its own data-gradient GEMM as ONE
     kernel (tuber_ln_bwd_dx).  Anyone else who touches the two gradient tensors first (Tape.force) gets the stand-alone launch."""
 
-    def __init__(self, tp, g, gptr, ldg, xhat, rstd, gamma, dx, dxd, p, salt, M, E, register, g2=None):
+    def __init__(self, tp, *, g, gptr, ldg, g2, xhat, rstd, gamma, dx, dxd, p, salt, M, E, register):
         self.tp, self.g, self.gptr, self.ldg, self.xhat, self.rstd, self.gamma = tp, g, gptr, ldg, xhat, rstd, gamma
         self.g2 = g2                                     # a second, unsummed contribution to the LayerNorm output's gradient (or None)
         self.dx, self.dxd, self.p, self.salt, self.M, self.E, self.register = dx, dxd, p, salt, M, E, register
@@ -209,6 +215,16 @@ class _PendingLN:
 # --------------------------------------------------------------------------------------------------
 # ops
 # --------------------------------------------------------------------------------------------------
+def _bias_colsum(st, g, ldg, out, M, N):
+    """out[N] += the column sums of g[M, N] (leading dimension ldg): a bias gradient no weight-gradient GEMM produced, the row sum of param_rows.
+    Several row blocks leave partials: reduced at the step's flush (deferred), or by the kernel itself."""
+    R = lib.query("tuber_colsum_blocks", M)
+    part, acc = st.partial("cs", R * N) if R > 1 else (None, 1)
+    lib.call("tuber_colsum", g, part, out, acc, M, N, ldg)
+    if acc == 2:
+        st.defer.add(part, out, N, N, R, 1)
+
+
 def linear(tp, x, wname, bname=None, rows=None, relu=False, out_f32=False, drop=0.0):
     """y = [Dropout]([relu](x @ W[r0:r1]^T + b[r0:r1])) -- nn.Linear / packed in-projection slices / 1x1x1 Conv3d."""
     st = tp.store
@@ -242,40 +258,12 @@ def linear(tp, x, wname, bname=None, rows=None, relu=False, out_f32=False, drop=
     toff, _, _, ldt = st.tinfo[wname]
     if not relu and not out_f32 and p == 0.0 and N == 256 and r0 == 0 and xreq and ldt >= N and lib.query("tuber_ln_bwd_dx_pays", M, N, K) == 1:
         tp.lin_out.add(id(y))                            # a LayerNorm over y may leave its backward to this linear's (layer_norm.bwd)
+    Np = _ceil(N, 64)
+    wt = st.tshadow.data_ptr() + 2 * (toff + r0)         # W^T[:, r0:r1]: column offset, ld = ldt
 
-    def fused_dgrad(rec, g):
-        """the data gradient of x together with the pending LayerNorm backward that produces g (one launch); mirrors the epilogue choice of
-        the stand-alone GEMM below.  -> True when launched."""
-        tx = tp.target(x)
-        if id(tx) in tp.stack:
-            return False
-        wt = st.tshadow.data_ptr() + 2 * (toff + r0)
-        r = tp.g.pop(id(tx), None)
-        if isinstance(r, _Pair) or (r is not None and (r.dtype != BF or tuple(r.shape) != (M, K) or not r.is_contiguous() or tp.pending.get(id(r)) is rec)):
-            tp.g[id(tx)] = r                             # (an unsummed pair, Tape.put on a pair_ok tensor: left to the stand-alone GEMM, which forces it; ADVICE r05)
-            return False
-        tp.force(r)
-        dx = torch.empty(M, K, dtype=BF, device=dev)
-        if id(tx) in tp.mask and r is None and tx is x:
-            rec.fuse(wt, ldt, K, dx, None, x, tp.mask[id(tx)])
-            tp.premasked.add(id(tx))
-        else:
-            rec.fuse(wt, ldt, K, dx, r, None, 1.0)
-        tp.put(tx, dx)
-        return True
-
-    def bwd():
-        g = tp.take(y, force=False)
-        if g is None:
-            return
-        rec = tp.pending.get(id(g))
-        dgrad_done = False
-        if rec is not None:
-            if id(y) in tp.lin_out and g is (rec.dxd if rec.p > 0.0 else rec.dx) and g.dtype == BF and tuple(g.shape) == (M, N):
-                dgrad_done = fused_dgrad(rec, g)         # (before the weight gradient below: a full queue launches at once and reads g)
-            if not dgrad_done:
-                rec.force()
-        Np = _ceil(N, 64)
+    def grad_operand(g):
+        """the bf16 operand of both gradient GEMMs -> (gb, ldg): g cast / zero-padded to a multiple of 64 columns, through the ReLU mask or the Dropout
+        of the forward epilogue"""
         if g.dtype != BF:
             gb = torch.empty(M, Np, dtype=BF, device=dev)
             lib.call("tuber_cast_pad_rows", g if g.dtype == torch.float32 else g.float(), gb, M, N, Np)
@@ -295,65 +283,44 @@ def linear(tp, x, wname, bname=None, rows=None, relu=False, out_f32=False, drop=
             gm = torch.empty_like(gb)
             lib.call("tuber_dropout", gb, gm, M * N, p, st.seed, salt)    # same (seed, salt, m*N+n) stream as the epilogue
             gb = gm
+        return gb, ldg
+
+    def param_grads(gb, ldg):
+        """weight and bias gradient; heads with 3 or 4 outputs may run over the padded columns of gb (ParamStore.wgrad)"""
         gw = st.gflat.data_ptr() + 4 * (st.offsets[wname] + r0 * K)
-        ws = lambda k, n: workspace(dev, k, n)
         gbias = st.gflat.data_ptr() + 4 * (st.offsets[bname] + r0) if breq else None
-        fuse_b = 0
-        N8 = _ceil(N, 8)
-        if (wreq and N8 != N and st.wq.enabled and st.defer.enabled and ldg >= N8 and st.wq.eligible(M, N8, K, ldg, K)
-                and lib.query("tuber_gemm_tn_slabs", M, N8, K) == 1):
-            # a head with 3 or 4 outputs (class_embed_b, the last box layer): the transpose-read kernel wants multiples of 8, so the product runs
-            # over the zero-padded columns of gb into arena scratch [N8][K] and the deferred reduction adds its first N rows to the gradient --
-            # queued with its neighbours instead of a tuber_gemm_tn launch of its own (8 - 12 us each on the critical path)
-            scratch = st.defer.alloc(N8 * K)
-            st.wq.add(TnArgs(gb.data_ptr(), ldg, x.data_ptr(), K, None, scratch, 0, M, N8, K, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, None, None, None),
-                      (gb, x), [(scratch, gw, N * K, N8 * K, 1, 0)])
-        elif wreq:
-            S = lib.query("tuber_gemm_tn_slabs", M, N, K)
-            # bias gradient inside the GEMM: 1 = accumulated directly (single slab), 2 = one partial row per slab
-            fuse_b = lib.query("tuber_gemm_tn_fuses_bias", M, N, K, ldg, K) if breq else 0
-            part, acc = st.partial("tn", S * N * K, ws) if S > 1 else (None, 1)
-            bpart = st.partial("cs", S * N, ws)[0] if fuse_b == 2 else None
-            bptr = gbias if fuse_b == 1 else bpart
-            defers = []
-            if acc == 2:
-                defers.append((part, gw, N * K, N * K, S, 0 if S <= 16 else 1))
-                if fuse_b == 2:
-                    defers.append((bpart, gbias, N, N, S, 1))
-            if st.wq.enabled and (S == 1 or acc == 2) and st.wq.eligible(M, N, K, ldg, K):
-                # nothing reads a weight gradient before the optimizer: queued, launched with its neighbours (engine.WgradQueue)
-                ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
-                st.wq.add(TnArgs(gb.data_ptr(), ldg, x.data_ptr(), K, ptr(part), gw, acc, M, N, K, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, None, None, ptr(bptr)),
-                          (gb, x), defers)
-            else:
-                lib.call("tuber_gemm_tn", gb, ldg, x, K, part, gw, acc, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0, None, 0, None, None, None, bptr)
-                for d in defers:
-                    st.defer.add(*d)
-                if fuse_b == 2 and acc != 2:
-                    lib.call("tuber_reduce_rows", bpart, gbias, S, N, 1)
-        if breq and not fuse_b:
-            nbc = lib.query("tuber_colsum_blocks", M)
-            part, acc = st.partial("cs", nbc * N, ws) if nbc > 1 else (None, 1)
-            lib.call("tuber_colsum", gb, part, gbias, acc, M, N, ldg)
-            if acc == 2:
-                st.defer.add(part, gbias, N, N, nbc, 1)
-        if not xreq or dgrad_done:
-            return
-        # data gradient; accumulation with an existing gradient of x and the ReLU/Dropout mask of x are GEMM epilogues
-        wt = st.tshadow.data_ptr() + 2 * (toff + r0)           # W^T[:, r0:r1]: column offset, ld = ldt
+        fused = wreq and st.wgrad(gb, ldg, x, K, gw, M, N, K, (gb, x), bias_grad=gbias, pad_cols=True)
+        if breq and not fused:
+            _bias_colsum(st, gb, ldg, gbias, M, N)
+
+    def fused_dgrad(rec):
+        """the data gradient of x together with the pending LayerNorm backward that produces g (one launch); mirrors the epilogue choice of
+        the stand-alone GEMM below.  -> True when launched."""
+        tx = tp.target(x)
+        if id(tx) in tp.stack:
+            return False
+        r = tp.residual(tx, M, K, rec)
+        if r is None and id(tx) in tp.g:                 # (a gradient that cannot be the residual input: the stand-alone GEMM; ADVICE r05)
+            return False
+        dx = torch.empty(M, K, dtype=BF, device=dev)
+        if id(tx) in tp.mask and r is None and tx is x:
+            rec.fuse(wt, ldt, K, dx, None, x, tp.mask[id(tx)])
+            tp.premasked.add(id(tx))
+        else:
+            rec.fuse(wt, ldt, K, dx, r, None, 1.0)
+        tp.put(tx, dx)
+        return True
+
+    def data_grad(gb, ldg):
+        """the stand-alone data-gradient GEMM; accumulation with an existing gradient of x and the ReLU/Dropout mask of x are its epilogues"""
         Kred = Np if (r0 == 0 and Np <= ldt) else N             # padded columns of both operands are zero
         assert Kred % 64 == 0, "row slices must be multiples of 64"
         tx = tp.target(x)
         dx = torch.empty(M, K, dtype=BF, device=dev)
+        r = tp.residual(tx, M, K)
         if id(tx) in tp.stack:
             lib.gemm_nt(gb, ldg, wt, ldt, dx, K, M, K, Kred)
-            tp.put(tx, dx)
-            return
-        r = tp.force(tp.g.pop(id(tx), None))
-        if r is not None and (r.dtype != BF or tuple(r.shape) != (M, K) or not r.is_contiguous()):
-            tp.g[id(tx)] = r
-            r = None
-        if id(tx) in tp.mask and r is None and tx is x:
+        elif id(tx) in tp.mask and r is None and tx is x:
             lib.gemm_nt(gb, ldg, wt, ldt, dx, K, M, K, Kred, epi=2, Cm=x, ldcm=K, alpha=tp.mask[id(tx)])
             tp.premasked.add(id(tx))
         elif M <= 64 and Kred >= 1024 and K % 16 == 0 and ldg % 8 == 0 and not ab.on("no_in_proj_dx2"):
@@ -362,6 +329,22 @@ def linear(tp, x, wname, bname=None, rows=None, relu=False, out_f32=False, drop=
         else:
             lib.gemm_nt(gb, ldg, wt, ldt, dx, K, M, K, Kred, R=r, ldr=K)
         tp.put(tx, dx)
+
+    def bwd():
+        g = tp.take(y, force=False)
+        if g is None:
+            return
+        rec = tp.pending.get(id(g))
+        dgrad_done = False
+        if rec is not None:
+            if id(y) in tp.lin_out and g is (rec.dxd if rec.p > 0.0 else rec.dx) and g.dtype == BF and tuple(g.shape) == (M, N):
+                dgrad_done = fused_dgrad(rec)            # (before the weight gradient below: a full queue launches at once and reads g)
+            if not dgrad_done:
+                rec.force()
+        gb, ldg = grad_operand(g)
+        param_grads(gb, ldg)
+        if xreq and not dgrad_done:
+            data_grad(gb, ldg)
     tp.rec(bwd)
     return y
 
@@ -399,45 +382,17 @@ def in_proj(tp, x, addend, wname, bname, rows, add_cols):
         if g is None:
             return
         assert g.dtype == BF and g.is_contiguous()
-        ws = lambda k, n: workspace(dev, k, n)
         gw = st.gflat.data_ptr() + 4 * (st.offsets[wname] + r0 * K)
         gbias = st.gflat.data_ptr() + 4 * (st.offsets[bname] + r0)
         # weight / bias gradients: row block [0, add_cols) against x + addend, row block [add_cols, N) against x
         blocks = [(0, add_cols, addend)] + ([(add_cols, N, None)] if add_cols < N else [])
         for c0, c1, a2 in blocks:
-            n = c1 - c0
             gptr = g.data_ptr() + 2 * c0
             if wreq:
-                S = lib.query("tuber_gemm_tn_slabs", M, n, K)
-                fuse_b = lib.query("tuber_gemm_tn_fuses_bias", M, n, K, N, K) if breq else 0
-                assert fuse_b, "in-projection shapes are transpose-read shapes"
-                part, acc = st.partial("tn", S * n * K, ws) if S > 1 else (None, 1)
-                bpart = st.partial("cs", S * n, ws)[0] if fuse_b == 2 else None
-                bptr = (gbias + 4 * c0) if fuse_b == 1 else bpart
-                out = gw + 4 * c0 * K
-                defers = []
-                if acc == 2:
-                    defers.append((part, out, n * K, n * K, S, 0 if S <= 16 else 1))
-                    if fuse_b == 2:
-                        defers.append((bpart, gbias + 4 * c0, n, n, S, 1))
-                ptr = lambda t: None if t is None else (t if isinstance(t, int) else t.data_ptr())
-                args = TnArgs(gptr, N, x.data_ptr(), K, ptr(part), out, acc, M, n, K, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, None, None, ptr(bptr),
-                              ptr(a2), K if a2 is not None else 0)
-                if st.wq.enabled and (S == 1 or acc == 2):
-                    st.wq.add(args, (g, x, a2), defers)
-                else:
-                    arr = (TnArgs * 1)(args)
-                    lib.call("tuber_gemm_tn_group", arr, 1)
-                    for d in defers:
-                        st.defer.add(*d)
-                    if fuse_b == 2 and acc != 2:
-                        lib.call("tuber_reduce_rows", bpart, gbias + 4 * c0, S, n, 1)
+                st.wgrad(gptr, N, x, K, gw + 4 * c0 * K, M, c1 - c0, K, (g, x, a2), bias_grad=gbias + 4 * c0 if breq else None,
+                         A2=a2, lda2=K if a2 is not None else 0, via_group=True)
             elif breq:
-                nbc = lib.query("tuber_colsum_blocks", M)
-                part, acc = st.partial("cs", nbc * n, ws) if nbc > 1 else (None, 1)
-                lib.call("tuber_colsum", gptr, part, gbias + 4 * c0, acc, M, n, N)
-                if acc == 2:
-                    st.defer.add(part, gbias + 4 * c0, n, n, nbc, 1)
+                _bias_colsum(st, gptr, N, gbias + 4 * c0, M, c1 - c0)
         # data gradients
         toff, _, _, ldt = st.tinfo[wname]
         wt = st.tshadow.data_ptr() + 2 * (toff + r0)           # W^T[:, r0:r1]: column offset, ld = ldt
@@ -446,12 +401,7 @@ def in_proj(tp, x, addend, wname, bname, rows, add_cols):
         if xreq and areq and M <= 64 and K % 64 == 0 and not ab.on("no_in_proj_dx2"):
             # few rows (the decoder's queries): both data gradients from ONE pass over g and W -- the addend's is a prefix of x's reduction
             tx = tp.target(x)
-            r = None
-            if id(tx) not in tp.stack:
-                r = tp.force(tp.g.pop(id(tx), None))
-                if r is not None and (r.dtype != BF or tuple(r.shape) != (M, K) or not r.is_contiguous()):
-                    tp.g[id(tx)] = r
-                    r = None
+            r = tp.residual(tx, M, K)
             if r is not None or add_cols < N:            # (else the two gradients are the same tensor: the one plain GEMM below)
                 dx = torch.empty(M, K, dtype=BF, device=dev)
                 da = torch.empty(M, K, dtype=BF, device=dev)
@@ -462,12 +412,7 @@ def in_proj(tp, x, addend, wname, bname, rows, add_cols):
         if xreq:
             tx = tp.target(x)
             dx = torch.empty(M, K, dtype=BF, device=dev)
-            r = None
-            if id(tx) not in tp.stack:
-                r = tp.force(tp.g.pop(id(tx), None))
-                if r is not None and (r.dtype != BF or tuple(r.shape) != (M, K) or not r.is_contiguous()):
-                    tp.g[id(tx)] = r
-                    r = None
+            r = tp.residual(tx, M, K)
             plain(N, r, dx)                                  # an existing gradient of x is accumulated by the GEMM's residual input
             tp.put(tx, dx)
             shared = r is None and add_cols == N             # dx is the bare product g.W over the addend's columns
@@ -548,9 +493,9 @@ def layer_norm(tp, x, res, prefix, drop=0.0, out=None):
             """partial rows [nb][2E] for the kernel about to be launched + where their sums go -> (partial, dgamma, dbeta, accumulate flag)"""
             dgamma = st.gflat.data_ptr() + 4 * st.offsets[prefix + ".weight"]
             dbeta = st.gflat.data_ptr() + 4 * st.offsets[prefix + ".bias"]
-            part, acc = st.partial("ln", 2 * nb * E, lambda k, n: workspace(dev, k, n))
+            part, acc = st.partial("ln", 2 * nb * E)
             if not preq and acc != 2:          # frozen LayerNorm, immediate reductions: gamma/beta gradients go to scratch
-                dgamma = workspace(dev, "ln_frozen", 2 * E).data_ptr()
+                dgamma = st.scratch("ln_frozen", 2 * E)
                 dbeta = dgamma + 4 * E
             if acc == 2 and preq:
                 if dbeta == dgamma + 4 * E:
@@ -560,7 +505,8 @@ def layer_norm(tp, x, res, prefix, drop=0.0, out=None):
                     st.defer.add(part + 4 * E, dbeta, E, 2 * E, nb, 1)
             return part, dgamma, dbeta, acc
 
-        rec = _PendingLN(tp, g, gptr, ldg, xhat, rstd, gamma, dx, dxd, p, salt, M, E, register, g2)
+        rec = _PendingLN(tp, g=g, gptr=gptr, ldg=ldg, g2=g2, xhat=xhat, rstd=rstd, gamma=gamma, dx=dx, dxd=dxd, p=p, salt=salt, M=M, E=E,
+                         register=register)
         # the backward of the linear that produced x runs next and can take the LayerNorm backward into its data-gradient launch
         # (tuber_ln_bwd_dx); everything else gets the stand-alone kernel right here
         fusable = xreq and out is None and st.defer.enabled and not ab.on("no_ln_bwd_fusion") and id(tp.target(x)) in tp.lin_out
@@ -728,11 +674,7 @@ def param_rows(tp, name, B):
                 allg = torch.cat(gs, dim=0)                      # [n*B*Q, E] -> rows (use, b) of [Q*E]
             else:
                 allg = gs[0]
-            R = lib.query("tuber_colsum_blocks", n * B)
-            part, acc = st.partial("cs", R * Q * E, lambda k, m: workspace(st.device, k, m)) if R > 1 else (None, 1)
-            lib.call("tuber_colsum", allg, part, gp, acc, n * B, Q * E, Q * E)
-            if acc == 2:
-                st.defer.add(part, gp, Q * E, Q * E, R, 1)
+            _bias_colsum(st, allg, Q * E, gp, n * B, Q * E)
         tp.rec(bwd)
     return out
 
