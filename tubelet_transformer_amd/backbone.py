@@ -26,6 +26,7 @@ BN_MOM = 0.1        # ir_CSN_152.py:16
 BF = torch.bfloat16
 CMAX = 2048
 _MOMENTUM = operator.attrgetter("momentum")
+_TRAINING = operator.attrgetter("training")
 
 
 class ResNeXtBottleneck(nn.Module):
@@ -216,6 +217,10 @@ class CSNRunner:
         self._cum = []                      # layers finalised in cumulative mode (momentum=None) by the running forward
         self._adv_tables = {}               # their counter-address tables (tuber_bn_count_advance), by layer indices
         self._affine_ready = False
+        self._frozen = frozenset()          # indices of the layers the running training-mode forward treats as frozen (module.training == False)
+        self._frozen_tables = {}            # their device tables (tuber_bn_frozen_affine_multi), by layer indices
+        self._frozen_rows = [[b.gamma, b.beta, b.rmean, b.rvar, b.scale, b.shift, b.mean, b.invstd, b.cA, b.cB, b.cC, b.C] for _, b in rows]
+        self._save_from = 0                 # blocks below it whose BatchNorms are all frozen keep nothing for a backward (forward())
         self._ws = {}
         self._fa_max = lib.query("tuber_bn_bwd_fa_max_rows")
         # flat offset where the parameters after the CSN body begin (gradient all-reduce slicing, ddp.py)
@@ -275,6 +280,31 @@ class CSNRunner:
             return ()
         return tuple((i, m) for i, m in enumerate(moms) if m != BN_MOM)
 
+    # -- frozen BatchNorm (nn.BatchNorm3d.training == False inside a training-mode forward; read on every such forward) ------------
+    def frozen_signature(self):
+        """indices of the BatchNorm layers whose module is in eval mode -- () while every module trains, which costs one pass of C-level
+        attribute reads: a captured training step bakes the set into its launches (training.GraphedTrainStep._key)"""
+        if all(map(_TRAINING, self._bn_mods)):
+            return ()
+        return tuple(i for i, m in enumerate(self._bn_mods) if not m.training)
+
+    def _begin_frozen(self, train):
+        """the frozen set of the forward that starts here, and everything both passes read of those layers (scale / shift, mean, invstd,
+        cA / cB / cC) in ONE launch -- none while the set is empty.  A frozen layer is the constant affine map of the eval path: no statistics
+        epilogue, no finalisation, no write to its running buffers; its backward is dx = gamma * invstd * dz."""
+        sig = self.frozen_signature() if train else ()
+        self._frozen = frozenset(sig)
+        if not sig:
+            return
+        t = self._frozen_tables.get(sig)
+        if t is None:                       # built by the first (eager) forward of this set; a capture replays the warm-up's table
+            t = self._frozen_tables[sig] = torch.tensor([self._frozen_rows[i] for i in sig], dtype=torch.int64).to(self.dev)
+        lib.call("tuber_bn_frozen_affine_multi", t, len(sig), max(self._frozen_rows[i][-1] for i in sig), BN_EPS)
+
+    def _all_frozen(self, d):
+        fz = self._frozen
+        return d.bn1.idx in fz and d.bn3.idx in fz and d.bn4.idx in fz and (not d.ds or d.bnd.idx in fz)
+
     def _bn_train(self, bn, st0, st1, R, count):
         st0, st1, R = self._stat_rows(st0, st1, R, bn.C)
         name, mom = self._finalize_form(bn, "tuber_bn_finalize")
@@ -282,13 +312,14 @@ class CSNRunner:
                  bn.scale, bn.shift, bn.mean, bn.invstd)
 
     def _bn_eval(self, bn):
-        if not self._affine_ready:          # a block range run on its own (tests); forward() has every layer's affine form from one launch
+        if not self._affine_ready and bn.idx not in self._frozen:          # a block range run on its own (tests); forward() has every layer's affine form from one launch
             lib.call("tuber_bn_eval_affine", bn.gamma, bn.beta, bn.rmean, bn.rvar, BN_EPS, bn.scale, bn.shift, bn.C)
 
     def _gemm_stats(self, A, lda, Wb, ldb, C, M, N, K, amode, sc, sh, gather, bn, train, defer=False):
         """conv as GEMM; in training mode also the following BatchNorm's statistics (``defer``: return the statistics rows (st0, st1, R)
         instead of finalising them -- the consumer does)."""
         st0 = st1 = None
+        train = train and bn.idx not in self._frozen       # a frozen layer: the plain conv launch, as in eval mode
         if train:
             R = lib.query("tuber_gemm_nt_stat_rows", M, N)
             st0, st1 = self.ws("st0", R * N), self.ws("st1", R * N)
@@ -313,10 +344,15 @@ class CSNRunner:
             lib.call("tuber_bn_eval_affine_multi", self._bn_table, self._bn_table.shape[0], self._bn_cmax, BN_EPS)
         self._affine_ready = not train
         self._cum = []
+        self._begin_frozen(train)
+        fz = self._frozen
+        # eval-form trunk: no backward ever runs below the lowest trainable block, so blocks there whose BatchNorms are all frozen save nothing
+        plan = self.trainable_plan() if fz else None
+        self._save_from = plan[2] if fz else 0
         try:
             c0 = torch.empty(M0, 64, dtype=BF, device=dev)
             bn0 = self.stem_bn
-            if train:
+            if train and bn0.idx not in fz:
                 R = lib.query("tuber_stem_conv_blocks", B, T, H, W)
                 st0, st1 = self.ws("st0", R * 64), self.ws("st1", R * 64)
                 lib.call("tuber_stem_conv_fwd", clips, self.stem_wpad, c0, st0, st1, B, T, H, W)
@@ -326,13 +362,15 @@ class CSNRunner:
                 self._bn_eval(bn0)
             Hp, Wp = (Ho + 2 - 3) // 2 + 1, (Wo + 2 - 3) // 2 + 1
             x = torch.empty(B * T * Hp * Wp, 64, dtype=BF, device=dev)
-            arg = torch.empty(B * T * Hp * Wp, 64, dtype=torch.uint8, device=dev) if train else None
+            keep0 = train and not (bn0.idx in fz and not plan[1]["any"])
+            arg = torch.empty(B * T * Hp * Wp, 64, dtype=torch.uint8, device=dev) if keep0 else None
             lib.call("tuber_stem_pool_fwd", c0, self.stem_bn.scale, self.stem_bn.shift, x, arg, B * T, Ho, Wo, Hp, Wp)
-            saved = {"stem": _SavedStem(clips if train else None, c0, arg, (B, T, Ho, Wo, Hp, Wp)), "blocks": [], "lo": 0}
+            saved = {"stem": _SavedStem(clips if keep0 else None, c0 if keep0 else None, arg, (B, T, Ho, Wo, Hp, Wp)), "blocks": [], "lo": 0}
             x, (Ti, Hi, Wi) = self._forward_blocks(x, B, (T, Hp, Wp), 0, len(self.blocks), train, saved["blocks"])
             self._advance_counts()
         finally:
             self._affine_ready = False          # a block range run on its own afterwards (run_blocks) derives its own
+            self._save_from = 0
         feat = x.view(B, Ti, Hi, Wi, 2048)
         return feat, saved
 
@@ -348,9 +386,12 @@ class CSNRunner:
         # bf16-STORED stream of the training path exceeds by 1.7x on the actor logits and 2x on the boxes (measured on the oracle)
         precise = not train and ab.eval_fp32_stream()
         y32 = None
+        fz = self._frozen
 
         def bn1_stats(blk, s0, s1, R, count):
             """bn1 of a stride-1 block is finalised INSIDE its depthwise forward kernel (tuber_dwconv_tile_fwd_bn): one launch less per block"""
+            if blk.bn1.idx in fz:
+                return None
             if fold1 and not blk.strided:
                 return (s0, s1, R, count)
             self._bn_train(blk.bn1, s0, s1, R, count)
@@ -362,6 +403,8 @@ class CSNRunner:
             To, Hq, Wq = (Ti - 1) // st + 1, (Hi - 1) // ss + 1, (Wi - 1) // ss + 1
             Min, Mout = B * Ti * Hi * Wi, B * To * Hq * Wq
             cd = ymask = None
+            b1, b3, b4 = d.bn1, d.bn3, d.bn4
+            keep = train and not (bi < self._save_from and self._all_frozen(d))       # (eval-form trunk: nothing saved, no ReLU mask)
             if pre_c1 is not None:
                 c1, pre_c1 = pre_c1, None
             elif (not ab.on("no_entry_conv") and d.ds and not d.strided and lib.query("tuber_entry_conv_supported", cin, P, C4) == 1):
@@ -369,7 +412,8 @@ class CSNRunner:
                 # produces both outputs (and both BatchNorms' statistics rows) from one pass over it (csrc/entry_conv.hip)
                 c1 = torch.empty(Min, P, dtype=BF, device=dev)
                 cd = torch.empty(Min, C4, dtype=BF, device=dev)
-                if train:
+                stats = train and not (b1.idx in fz and d.bnd.idx in fz)       # (the kernel writes both pairs of rows or none)
+                if stats:
                     Rt = (Min + 63) // 64
                     a0, a1 = self.ws("st0", Rt * P), self.ws("st1", Rt * P)
                     e0, e1 = self.ws("std0", Rt * C4), self.ws("std1", Rt * C4)
@@ -377,21 +421,22 @@ class CSNRunner:
                     a0 = a1 = e0 = e1 = None
                 lib.call("tuber_entry_conv_fwd", x, d.w1, cin, d.wd, cin, c1, cd, a0, a1, e0, e1, Min)
                 if train:
-                    pend = bn1_stats(d, a0, a1, Rt, Min)
-                    self._bn_train(d.bnd, e0, e1, Rt, Min)
+                    pend = bn1_stats(d, a0, a1, Rt, Min) if stats else None
+                    if d.bnd.idx not in fz:
+                        self._bn_train(d.bnd, e0, e1, Rt, Min)
                 else:
                     self._bn_eval(d.bn1)
                     self._bn_eval(d.bnd)
             else:
                 c1 = torch.empty(Min, P, dtype=BF, device=dev)
-                if fold1 and not d.strided:
+                if fold1 and not d.strided and b1.idx not in fz:
                     pend = self._gemm_stats(x, cin, d.w1, cin, c1, Min, P, cin, 0, None, None, None, d.bn1, train, defer=True) + (Min,)
                 else:
                     self._gemm_stats(x, cin, d.w1, cin, c1, Min, P, cin, 0, None, None, None, d.bn1, train)
             c3 = torch.empty(Mout, P, dtype=BF, device=dev)
-            b1, b3, b4 = d.bn1, d.bn3, d.bn4
             tile = not d.strided and not ab.on("dw_register_tiled")        # LDS-staged kernels for the stride-1 blocks (47 of 50)
-            if train:
+            train3 = train and b3.idx not in fz
+            if train3:
                 R = lib.query("tuber_dwconv_tile_blocks", B, Ti, Hi, Wi, P) if tile else lib.query("tuber_dwconv_fwd_stat_rows", B, To, Hq, Wq)
                 # (its own pair of buffers when the kernel also READS bn1's rows, which sit in st0 / st1)
                 st0, st1 = (self.ws("st0b", R * P), self.ws("st1b", R * P)) if pend is not None else (self.ws("st0", R * P), self.ws("st1", R * P))
@@ -407,7 +452,7 @@ class CSNRunner:
                 lib.call("tuber_dwconv_tile_fwd", c1, b1.scale, b1.shift, d.w3, c3, st0, st1, B, Ti, Hi, Wi, P)
             else:
                 lib.call("tuber_dwconv_fwd", c1, b1.scale, b1.shift, d.w3, c3, st0, st1, B, Ti, Hi, Wi, To, Hq, Wq, P, st, ss)
-            if train:
+            if train3:
                 self._bn_train(b3, st0, st1, R, Mout)
             else:
                 self._bn_eval(b3)
@@ -447,22 +492,22 @@ class CSNRunner:
                     and lib.query("tuber_blockout_conv1_supported", C4, nxt.p) == 1):
                 PN = nxt.p
                 pre_c1 = torch.empty(Mout, PN, dtype=BF, device=dev)
-                if train:
+                if train and nxt.bn1.idx not in fz:
                     Rn = lib.query("tuber_gemm_nt_stat_rows", Mout, PN)
                     n0, n1 = self.ws("st0", Rn * PN), self.ws("st1", Rn * PN)
                 else:
                     n0 = n1 = None
-                if train and nxt.stage != d.stage and not ab.on("no_join_mask"):
+                if keep and nxt.stage != d.stage and not ab.on("no_join_mask"):
                     # the last block of layer1: its join backward runs in layer2's first conv1 data-gradient GEMM (strided form) and reads the mask as a bit field
                     ymask = torch.empty(Mout, P // 2, dtype=torch.uint8, device=dev)
                     lib.call("tuber_blockout_conv1_fwd_mask", c4, b4.scale, b4.shift, res, rs, rh, y, ymask, nxt.w1, nxt.cin, pre_c1, n0, n1, Mout, PN)
                 else:
                     lib.call("tuber_blockout_conv1_fwd", c4, b4.scale, b4.shift, res, rs, rh, y, nxt.w1, nxt.cin, pre_c1, n0, n1, Mout, PN)
-                if train:
+                if n0 is not None:
                     pend = bn1_stats(nxt, n0, n1, Rn, Mout)
                 else:
                     self._bn_eval(nxt.bn1)
-            elif train and not ab.on("no_join_mask"):
+            elif keep and not ab.on("no_join_mask"):
                 # training: the ReLU mask of y also leaves as a bit field -- what this block's join backward (inside the conv1
                 # data-gradient GEMM of the block above, tuber_gemm_nt_join_mask) reads instead of y: 1 / 16 of the bytes of a side operand of a
                 # launch that runs at the bandwidth of its side operands
@@ -471,7 +516,7 @@ class CSNRunner:
             else:
                 lib.call("tuber_block_out_fwd", c4, b4.scale, b4.shift, res, rs, rh, y, Mout, C4)
             if train:
-                out_saved.append(_Saved(x, c1, c3, c4, cd, y, (Ti, Hi, Wi, To, Hq, Wq), ymask))
+                out_saved.append(_Saved(x, c1, c3, c4, cd, y, (Ti, Hi, Wi, To, Hq, Wq), ymask) if keep else None)
             x = y
             Ti, Hi, Wi = To, Hq, Wq
         # TUBER_EVAL_PRECISION=fp32_class: the fp32 stream of the last block is the class branch's class_proj operand (DETR._class_branch_f32 takes it)
@@ -485,6 +530,7 @@ class CSNRunner:
         B, Ti, Hi, Wi = geom
         saved = {"blocks": [], "lo": lo, "B": B}
         self._cum = []
+        self._begin_frozen(train)
         y, g = self._forward_blocks(x.contiguous(), B, (Ti, Hi, Wi), lo, hi, train, saved["blocks"])
         self._advance_counts()
         return y, g, saved
@@ -505,8 +551,9 @@ class CSNRunner:
     # LR_BACKBONE <= 0: the whole body, backbone_builder.py:38-40) and autograd then neither computes those gradients nor walks the
     # graph below the first trainable tensor.  Same here: weight-gradient kernels and dgamma/dbeta of frozen tensors are not
     # launched / written (their slices of the flat gradient buffer stay zero, ``p.grad`` is None) and the data-gradient chain stops
-    # at the lowest block that still has a trainable tensor.  BatchNorm keeps using batch statistics and updating its running
-    # buffers in train mode, as the reference's frozen-but-train-mode BatchNorm3d does.
+    # at the lowest block that still has a trainable tensor.  A BatchNorm whose MODULE is in train mode keeps using batch statistics and
+    # updating its running buffers, as the reference's frozen-but-train-mode BatchNorm3d does; one whose module is in eval mode
+    # (``bn.eval()`` after ``model.train()``, CONFIG.MODEL.FREEZE_BN, bn_stats.freeze_batchnorm) is frozen: see ``_begin_frozen``.
     def trainable_plan(self):
         """([per-block flag dicts], stem flags, index of the lowest block whose backward must run (len(blocks) = none),
         stem backward needed).  Read from ``requires_grad`` on every call: freezing may change between steps."""
@@ -546,6 +593,8 @@ class CSNRunner:
         (Forming dx inside the consuming GEMMs instead -- tuber_gemm_nt amode 2 / tuber_gemm_tn G2 -- removes this kernel and
         7.6 GB/step of HBM traffic but was measured 0.85 ms/step SLOWER on MI355X: the GEMMs are instruction/latency bound,
         not bandwidth bound, and the two-operand prologue costs them more than the apply kernel)"""
+        if bn.idx in self._frozen:
+            return self._bn_bwd_frozen(bn, st0, st1, R, dz, x, M, train, apply)
         fa = apply and not ab.on("no_bn_bwd_fa") and bn.C % 128 == 0
         if fa and R > self._fa_max and not ab.on("no_bn_bwd_fa_after_reduce"):
             st0, st1, R = self._stat_rows(st0, st1, R, bn.C)       # layer1 / layer2: 64 rows after the first stage -> finalize + apply as one launch
@@ -560,6 +609,29 @@ class CSNRunner:
                  bn.dgamma if train else None, bn.dbeta if train else None, 1)
         if not apply:
             return None
+        dx = torch.empty(M, bn.C, dtype=BF, device=self.dev)
+        lib.call("tuber_bn_bwd_apply", dz, x, bn.cA, bn.cB, bn.cC, dx, M, bn.C)
+        return dx
+
+    def _bn_bwd_frozen(self, bn, st0, st1, R, dz, x, M, train, apply):
+        """``_bn_bwd`` of a frozen layer: dx = cA * dz with cA = gamma * invstd (cB = cC = 0, all three written by the forward's
+        tuber_bn_frozen_affine_multi for the kernels that take them); the partial rows are read only for dgamma / dbeta (``train``)"""
+        fa = apply and not ab.on("no_bn_bwd_fa") and bn.C % 128 == 0
+        if fa and train and R > self._fa_max and not ab.on("no_bn_bwd_fa_after_reduce"):
+            st0, st1, R = self._stat_rows(st0, st1, R, bn.C)
+        if fa and (not train or R <= self._fa_max):
+            dx = torch.empty(M, bn.C, dtype=BF, device=self.dev)
+            lib.call("tuber_bn_bwd_fa_frozen", st0 if train else None, st1 if train else None, R if train else 0, bn.C, bn.gamma, bn.mean, bn.invstd,
+                     bn.dgamma if train else None, bn.dbeta if train else None, dz, dx, M)
+            return dx
+        if train:
+            st0, st1, R = self._stat_rows(st0, st1, R, bn.C)
+            lib.call("tuber_bn_frozen_param_grads", st0, st1, R, bn.C, bn.mean, bn.invstd, bn.dgamma, bn.dbeta)
+        if not apply:
+            return None
+        # the 64-channel layers (stem, layer1's bn1 / bn3 off their fused paths), long lists and TUBER_AB=no_bn_bwd_fa: the train-mode apply kernel
+        # on cB = cC = 0.  It still READS x (one tensor pass more than the frozen layer needs) and forms 0 * x, so a non-finite activation
+        # poisons dx here as it does in train mode; the one-launch and depthwise forms above do not have x as an operand
         dx = torch.empty(M, bn.C, dtype=BF, device=self.dev)
         lib.call("tuber_bn_bwd_apply", dz, x, bn.cA, bn.cB, bn.cC, dx, M, bn.C)
         return dx
@@ -673,9 +745,16 @@ class CSNRunner:
                 self._slab_reduce(part4, acc4, d.g4, C4 * P, S4)
             else:
                 lib.gemm_nt(dc4, C4, d.w4t, d.ld4t, dz3, P, Mout, P, C4, epi=2, stat0=s0, stat1=s1, Cm=c3, ldcm=P, m_scale=b3.scale, m_shift=b3.shift)
-            if fuse3:
+            frz3 = b3.idx in self._frozen
+            sfx = "_frozen" if frz3 else ""
+            if fuse3 and frz3:
+                # frozen bn3: the same fused kernels in their frozen form (dc3 = gamma * invstd * dz3 on load); the rows only for dgamma / dbeta
+                bs0, bs1, bR = (None, None, 0) if not f["bn3"] else (s0, s1, R3) if R3 <= self._fa_max else self._stat_rows(s0, s1, R3, P)
+                bn3 = (dz3, bs0, bs1, bR, b3.gamma, b3.mean, b3.invstd)
+                bn3w = (dz3, b3.gamma, b3.mean, b3.invstd)
+            elif fuse3:
                 bs0, bs1, bR = (s0, s1, R3) if R3 <= self._fa_max else self._stat_rows(s0, s1, R3, P)
-                bn3 = (dz3, c3, bs0, bs1, bR, float(Mout), b3.gamma, b3.mean, b3.invstd)
+                bn3 = bn3w = (dz3, c3, bs0, bs1, bR, float(Mout), b3.gamma, b3.mean, b3.invstd)
             else:
                 dc3 = self._bn_bwd(b3, s0, s1, R3, Mout, dz3, c3, Mout, train=f["bn3"], apply=depth >= 4)
         # depthwise conv: weight grad, data grad fused with relu/bn1 backward
@@ -687,7 +766,7 @@ class CSNRunner:
             part, acc = self.store.partial("tn", nb * 27 * P)
             s0, s1 = self.ws("st0", R1 * P), self.ws("st1", R1 * P)
             dz1 = torch.empty(Min, P, dtype=BF, device=dev)
-            lib.call("tuber_dwconv_tile_bwd_both_bn", *bn3, b3.dgamma if f["bn3"] else None, b3.dbeta if f["bn3"] else None,
+            lib.call("tuber_dwconv_tile_bwd_both_bn" + sfx, *bn3, b3.dgamma if f["bn3"] else None, b3.dbeta if f["bn3"] else None,
                      d.w3, c1, b1.scale, b1.shift, dz1, s0, s1, part, B, Ti, Hi, Wi, P)
             self._slab_reduce(part, acc, d.g3, 27 * P, nb, P)       # (immediate form: the same block sum, launched right here)
             return dz1, s0, s1, R1
@@ -695,7 +774,7 @@ class CSNRunner:
             nb = lib.query("tuber_dwconv_tile_wgrad_blocks", B, Ti, Hi, Wi, P) if tile else lib.query("tuber_dwconv_bwd_weight_blocks", B, To, Hq, Wq)
             part, acc = self.store.partial("tn", nb * 27 * P)
             if fuse3:
-                lib.call("tuber_dwconv_tile_bwd_weight_bn", *bn3, c1, b1.scale, b1.shift, part, d.g3, acc, B, Ti, Hi, Wi, P)
+                lib.call("tuber_dwconv_tile_bwd_weight_bn" + sfx, *bn3w, c1, b1.scale, b1.shift, part, d.g3, acc, B, Ti, Hi, Wi, P)
             elif tile:
                 lib.call("tuber_dwconv_tile_bwd_weight", dc3, c1, b1.scale, b1.shift, part, d.g3, acc, B, Ti, Hi, Wi, P)
             else:
@@ -706,9 +785,11 @@ class CSNRunner:
             return None
         R1 = lib.query("tuber_dwconv_tile_blocks", B, Ti, Hi, Wi, P) if tile else lib.query("tuber_dwconv_bwd_data_stat_rows", B, Ti, Hi, Wi)
         s0, s1 = self.ws("st0", R1 * P), self.ws("st1", R1 * P)
+        if tile and b1.idx in self._frozen and not f["bn1"]:
+            s0 = s1 = None      # a frozen bn1 with frozen affine parameters reads no rows, and the LDS-staged data-gradient kernels take NULL (the others do not)
         dz1 = torch.empty(Min, P, dtype=BF, device=dev)
         if fuse3:
-            lib.call("tuber_dwconv_tile_bwd_data_bn", *bn3, b3.dgamma if f["bn3"] else None, b3.dbeta if f["bn3"] else None,
+            lib.call("tuber_dwconv_tile_bwd_data_bn" + sfx, *bn3, b3.dgamma if f["bn3"] else None, b3.dbeta if f["bn3"] else None,
                      d.w3, c1, b1.scale, b1.shift, dz1, s0, s1, B, Ti, Hi, Wi, P)
         elif tile:
             lib.call("tuber_dwconv_tile_bwd_data", dc3, d.w3, c1, b1.scale, b1.shift, dz1, s0, s1, B, Ti, Hi, Wi, P)

@@ -149,7 +149,8 @@ def get_cfg_defaults():
         NAME="", SINGLE_FRAME=True, BACKBONE_NAME="CSN-152", TEMPORAL_DS_STRATEGY="avg", LAST_STRIDE=False,
         GENERATE_LFB=False, ENC_LAYERS=6, DEC_LAYERS=6, D_MODEL=256, NHEAD=8, DIM_FEEDFORWARD=2048,
         QUERY_NUM=15, NORMALIZE_BEFORE=False, DROPOUT=0.1, DS_RATE=8, TEMP_LEN=32, PRETRAINED=False,
-        PRETRAIN_BACKBONE_DIR="", PRETRAIN_TRANSFORMER_DIR="", PRETRAINED_PATH="", LOAD=False, LOAD_FC=True),
+        PRETRAIN_BACKBONE_DIR="", PRETRAIN_TRANSFORMER_DIR="", PRETRAINED_PATH="", LOAD=False, LOAD_FC=True,
+        FREEZE_BN="none"),      # backbone BatchNorm layers kept in eval mode while training: none | frozen | all (bn_stats.py; not a reference key)
         new_allowed=True)
     cfg.MATCHER = CfgNode(dict(COST_CLASS=12, COST_BBOX=5, COST_GIOU=2, BNY_LOSS=True, BEFORE=False),
                           new_allowed=True)

@@ -60,9 +60,12 @@ struct TileArgs {
 };
 
 // (bx, by) = the workgroup's position in ITS problem's grid: the kernels below pass blockIdx, the merged backward launch an offset one
-template <int MODE, bool BNG = false, bool ACT = true, bool FIN = false>
+// FRZ (with BNG): the BatchNorm above is FROZEN (module in eval mode): cA = gamma * invstd, cB = cC = 0 from the per-channel vectors alone;
+// the partial rows are read only by the workgroups that accumulate dgamma / dbeta (bx == 0, pointers not NULL), bcount is not used
+template <int MODE, bool BNG = false, bool ACT = true, bool FIN = false, bool FRZ = false>
 __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx, const int by) {
     static_assert(!FIN || (MODE == M_FWD && ACT && !BNG), "FIN: the forward conv behind a training-mode BatchNorm + ReLU");
+    static_assert(!FRZ || BNG, "FRZ: the frozen form of a BNG variant");
     extern __shared__ __attribute__((aligned(16))) float smem[];        // ring[3][PLANE] | red
     const TileGeom g = a.g;
     const int tid = threadIdx.x;
@@ -97,7 +100,8 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
     const long plane_elems = (long)g.H * g.W * g.C;
     const bf16* in_n = a.in + (long)n * g.T * plane_elems;
     constexpr bool STG2 = BNG && MODE == M_BWD_DATA;        // the staged tensor is formed from two tensors
-    const bf16* in2_n = STG2 ? a.xu + (long)n * g.T * plane_elems : nullptr;
+    constexpr bool XU = BNG && !FRZ;                        // the BatchNorm's input is an operand (frozen: cB = 0, it is not read)
+    const bf16* in2_n = STG2 && XU ? a.xu + (long)n * g.T * plane_elems : nullptr;
     uint2 regs[NLD], regs_a[NLD], regs_b[NLD];     // regs: the steady-state prefetch set; _a / _b: the two extra planes of the prologue
     uint2 regx[STG2 ? NLD : 1], regx_a[STG2 ? NLD : 1], regx_b[STG2 ? NLD : 1];
     // input plane t -> registers.  The loads are UNCONDITIONAL: slots outside the volume read element 0 of a valid plane (s_off = 0,
@@ -109,7 +113,7 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
         const bf16* p = in_n + (long)(tok ? t : 0) * plane_elems;
 #pragma unroll
         for (int i = 0; i < NLD; ++i) regs[i] = *(const uint2*)(p + s_off[i]);
-        if constexpr (STG2) {
+        if constexpr (STG2 && XU) {
             const bf16* p2 = in2_n + (long)(tok ? t : 0) * plane_elems;
 #pragma unroll
             for (int i = 0; i < NLD; ++i) rx[i] = *(const uint2*)(p2 + s_off[i]);
@@ -124,7 +128,11 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
             if (s_lds[i] < 0) continue;
             const bf16x4 v = as_bf16x4(regs[i]);
             float4 o;
-            if constexpr (STG2) {
+            if constexpr (STG2 && !XU) {
+                const bool ok = tok && s_ok[i];
+                o.x = ok ? kA[0] * bf2f(v[0]) : 0.f; o.y = ok ? kA[1] * bf2f(v[1]) : 0.f;
+                o.z = ok ? kA[2] * bf2f(v[2]) : 0.f; o.w = ok ? kA[3] * bf2f(v[3]) : 0.f;
+            } else if constexpr (STG2) {
                 const bool ok = tok && s_ok[i];          // the gradient is zero outside the volume (cC must not leak into the padding)
                 const bf16x4 u = as_bf16x4(rx[i]);
                 o.x = ok ? fmaf(kA[0], bf2f(v[0]), fmaf(kB[0], bf2f(u[0]), kC[0])) : 0.f;
@@ -239,7 +247,8 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
     if constexpr (BNG) {
         double* red = (double*)smem;                     // [2][32][64] in the (still empty) ring
         float* coef = smem + 3 * PLANE + 27 * 64;        // [3][64] behind the filter taps
-        {
+        const bool derive = !FRZ || (bx == 0 && a.bdgamma != nullptr);      // (workgroup-uniform; constant in the train-mode form)
+        if (derive) {
             const int q = tid & 15, rg = tid >> 4;       // 16 channel quads x 32 row groups
             double sa[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
             const float* p0 = a.bst0 + c0 + q * 4;
@@ -263,28 +272,36 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
 #pragma unroll
             for (int e = 0; e < 4; ++e) { red[(0 * 32 + rg) * 64 + q * 4 + e] = sa[e]; red[(1 * 32 + rg) * 64 + q * 4 + e] = sb[e]; }
         }
-        __syncthreads();
+        if (derive) __syncthreads();
         // two levels (all 512 threads sum 8 row groups each, then 64 threads sum 4): the 32-entry serial fp64 chain of one wave was ~2 us of
         // every workgroup's prologue.  (fp64 sums of fp32 partial rows are exact, so the association does not change the result.)
         double* red2 = red + 2 * 32 * 64;                // [2][4][64]
-        {
+        if (derive) {
             const int which = tid >> 8, part = (tid >> 6) & 3, ch = tid & 63;
             double s = 0.0;
 #pragma unroll
             for (int k = 0; k < 8; ++k) s += red[(which * 32 + part * 8 + k) * 64 + ch];
             red2[(which * 4 + part) * 64 + ch] = s;
         }
-        __syncthreads();
+        if (derive) __syncthreads();
         if (tid < 64) {
-            const double sa = (red2[(0 * 4 + 0) * 64 + tid] + red2[(0 * 4 + 1) * 64 + tid]) + (red2[(0 * 4 + 2) * 64 + tid] + red2[(0 * 4 + 3) * 64 + tid]);
-            const double sb = (red2[(1 * 4 + 0) * 64 + tid] + red2[(1 * 4 + 1) * 64 + tid]) + (red2[(1 * 4 + 2) * 64 + tid] + red2[(1 * 4 + 3) * 64 + tid]);
+            double sa = 0.0, sb = 0.0;
+            if (derive) {
+                sa = (red2[(0 * 4 + 0) * 64 + tid] + red2[(0 * 4 + 1) * 64 + tid]) + (red2[(0 * 4 + 2) * 64 + tid] + red2[(0 * 4 + 3) * 64 + tid]);
+                sb = (red2[(1 * 4 + 0) * 64 + tid] + red2[(1 * 4 + 1) * 64 + tid]) + (red2[(1 * 4 + 2) * 64 + tid] + red2[(1 * 4 + 3) * 64 + tid]);
+            }
             const int cc = c0 + tid;
             const double mu = a.bmean[cc], rr = a.binvstd[cc], gm = a.bgamma[cc];
             const double sum_dz = sa, sum_dz_xhat = (sb - mu * sa) * rr;
-            const double m1 = sum_dz / a.bcount, m2 = sum_dz_xhat / a.bcount;
             coef[0 * 64 + tid] = (float)(gm * rr);
-            coef[1 * 64 + tid] = (float)(-gm * rr * rr * m2);
-            coef[2 * 64 + tid] = (float)(gm * rr * rr * m2 * mu - gm * rr * m1);
+            if constexpr (FRZ) {
+                coef[1 * 64 + tid] = 0.f;
+                coef[2 * 64 + tid] = 0.f;
+            } else {
+                const double m1 = sum_dz / a.bcount, m2 = sum_dz_xhat / a.bcount;
+                coef[1 * 64 + tid] = (float)(-gm * rr * rr * m2);
+                coef[2 * 64 + tid] = (float)(gm * rr * rr * m2 * mu - gm * rr * m1);
+            }
             if (bx == 0 && a.bdgamma) {
                 a.bdgamma[cc] += (float)sum_dz_xhat;
                 a.bdbeta[cc] += (float)sum_dz;
@@ -330,7 +347,7 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
         for (int j = 0; j < 4; ++j) {
             const long oc = (long)min(wo0 + j, g.W - 1) * g.C;
             sd[j] = *(const uint2*)(a.aux + ob + oc);
-            if constexpr (SD2) sx[j] = *(const uint2*)(a.xu + ob + oc);
+            if constexpr (SD2 && XU) sx[j] = *(const uint2*)(a.xu + ob + oc);
         }
     };
     uint2 side_nx[4] = {make_uint2(0, 0), make_uint2(0, 0), make_uint2(0, 0), make_uint2(0, 0)};
@@ -346,7 +363,7 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
         const long obase = (((long)n * g.T + t) * g.H + ho) * (long)g.W * g.C + c;
         if constexpr (MODE == M_BWD_WEIGHT) {
 #pragma unroll
-            for (int j = 0; j < 4; ++j) { side[j] = side_nx[j]; if constexpr (SD2) sidx[j] = sidx_nx[j]; }
+            for (int j = 0; j < 4; ++j) { side[j] = side_nx[j]; if constexpr (SD2 && XU) sidx[j] = sidx_nx[j]; }
             if (t + 1 < t1) side_fetch(t + 1, side_nx, sidx_nx);
         } else if (MODE != M_FWD) {
             side_fetch(t, side, sidx);
@@ -360,7 +377,14 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const bf16x4 v = as_bf16x4(side[j]);
-                if constexpr (SD2) {
+                if constexpr (SD2 && !XU) {
+                    const bool ok = row_ok && wo0 + j < g.W;
+                    float q[4];
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) q[e] = ok ? kA[e] * bf2f(v[e]) : 0.f;
+                    gv[j][0] = f32x2{q[0], q[1]};
+                    gv[j][1] = f32x2{q[2], q[3]};
+                } else if constexpr (SD2) {
                     const bool ok = row_ok && wo0 + j < g.W;      // zero gradient outside the volume
                     const bf16x4 u = as_bf16x4(sidx[j]);
                     float q[4];
@@ -478,12 +502,12 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
     }
 }
 
-template <int MODE, bool BNG = false, bool ACT = true>
+template <int MODE, bool BNG = false, bool ACT = true, bool FRZ = false>
 // Workgroup -> tile: the hardware deals consecutive workgroups round-robin over the 8 XCDs, so with bx = blockIdx.x the spatial neighbours
 // of a tile (which share its halo columns / rows) sit on 8 different L2s and every XCD fetches its own copy of every halo from memory.
 // xcd_remap gives each XCD a CONTIGUOUS range of tile ids -- whole planes of spatially adjacent tiles -- so halos are L2 hits.  The tile id
 // also indexes the statistics rows / partial blocks, so results do not depend on the mapping.
-__global__ __launch_bounds__(512) void dwconv_tile_kernel(TileArgs a) { dwconv_tile_body<MODE, BNG, ACT>(a, xcd_remap(blockIdx.x, gridDim.x), blockIdx.y); }
+__global__ __launch_bounds__(512) void dwconv_tile_kernel(TileArgs a) { dwconv_tile_body<MODE, BNG, ACT, false, FRZ>(a, xcd_remap(blockIdx.x, gridDim.x), blockIdx.y); }
 // the forward conv that also finalises the BatchNorm in front of it (TileArgs: FIN)
 __global__ __launch_bounds__(512) void dwconv_tile_fwd_fin_kernel(TileArgs a) { dwconv_tile_body<M_FWD, false, true, true>(a, xcd_remap(blockIdx.x, gridDim.x), blockIdx.y); }
 
@@ -502,6 +526,8 @@ __global__ __launch_bounds__(512) void dwconv_tile_fwd_fin_kernel(TileArgs a) { 
 // gradient's state does not fit 256 VGPRs (415 spilled).  Here a thread owns 2 channels x 8 consecutive columns of one tile row:
 // 54 accumulators, ds_read_b64 operand reads (32 lanes x 8 B = all 64 banks once), packed FMAs on the channel pair.
 // ---------------------------------------------------------------------------------------------------------------------------------
+// FRZ: the frozen form of the BatchNorm above, as in dwconv_tile_body.
+template <bool FRZ = false>
 __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
     extern __shared__ __attribute__((aligned(16))) float smem[];        // ring[3][PLANE] | taps [27][64] | coef [3][64]
     const TileGeom g = a.g;
@@ -530,16 +556,18 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
     }
     const long plane_elems = (long)g.H * g.W * g.C;
     const bf16* in_n = a.in + (long)n * g.T * plane_elems;
-    const bf16* in2_n = a.xu + (long)n * g.T * plane_elems;
+    const bf16* in2_n = FRZ ? nullptr : a.xu + (long)n * g.T * plane_elems;       // (frozen: cB = 0, xu is not read)
     uint2 regs[NLD], regs_a[NLD], regs_b[NLD], regx[NLD], regx_a[NLD], regx_b[NLD];
     auto fetch = [&](int t, uint2 (&rg)[NLD], uint2 (&rx)[NLD]) {          // unconditional loads (see dwconv_tile_body)
         const bool tok = t >= 0 && t < g.T;
         const bf16* p = in_n + (long)(tok ? t : 0) * plane_elems;
-        const bf16* p2 = in2_n + (long)(tok ? t : 0) * plane_elems;
 #pragma unroll
         for (int i = 0; i < NLD; ++i) rg[i] = *(const uint2*)(p + s_off[i]);
+        if constexpr (!FRZ) {
+            const bf16* p2 = in2_n + (long)(tok ? t : 0) * plane_elems;
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) rx[i] = *(const uint2*)(p2 + s_off[i]);
+            for (int i = 0; i < NLD; ++i) rx[i] = *(const uint2*)(p2 + s_off[i]);
+        }
     };
     auto park = [&](int t, const uint2 (&rg)[NLD], const uint2 (&rx)[NLD]) {      // g = cA*dzu + cB*xu + cC, fp32, zero outside the volume
         const bool tok = t >= 0 && t < g.T;
@@ -550,9 +578,16 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
 #pragma unroll
         for (int i = 0; i < NLD; ++i) {
             if (i == NLD - 1 && tid + 512 * i >= NPOS * 16) continue;
-            const bf16x4 v = as_bf16x4(rg[i]), u = as_bf16x4(rx[i]);
+            const bf16x4 v = as_bf16x4(rg[i]);
             const bool ok = tok && s_ok[i];
             float4 o;
+            if constexpr (FRZ) {
+                o.x = ok ? kA[0] * bf2f(v[0]) : 0.f; o.y = ok ? kA[1] * bf2f(v[1]) : 0.f;
+                o.z = ok ? kA[2] * bf2f(v[2]) : 0.f; o.w = ok ? kA[3] * bf2f(v[3]) : 0.f;
+                *(float4*)(dst + 4 * (tid + 512 * i)) = o;
+                continue;
+            }
+            const bf16x4 u = as_bf16x4(rx[i]);
             o.x = ok ? fmaf(kA[0], bf2f(v[0]), fmaf(kB[0], bf2f(u[0]), kC[0])) : 0.f;
             o.y = ok ? fmaf(kA[1], bf2f(v[1]), fmaf(kB[1], bf2f(u[1]), kC[1])) : 0.f;
             o.z = ok ? fmaf(kA[2], bf2f(v[2]), fmaf(kB[2], bf2f(u[2]), kC[2])) : 0.f;
@@ -568,11 +603,18 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
     const int dq = tid & 15, drg = tid >> 4;
     const float* const dp0 = a.bst0 + c0 + dq * 4;
     const float* const dp1 = a.bst1 + c0 + dq * 4;
+    const bool derive = !FRZ || (bx == 0 && a.bdgamma != nullptr);      // (workgroup-uniform; constant in the train-mode form)
     float4 du[4], dv[4];
+    if constexpr (FRZ) {
 #pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const long rr = min(drg + 32 * k, a.bR - 1);
-        du[k] = *(const float4*)(dp0 + rr * g.C); dv[k] = *(const float4*)(dp1 + rr * g.C);
+        for (int k = 0; k < 4; ++k) du[k] = dv[k] = make_float4(0.f, 0.f, 0.f, 0.f);
+    }
+    if (derive) {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const long rr = min(drg + 32 * k, a.bR - 1);
+            du[k] = *(const float4*)(dp0 + rr * g.C); dv[k] = *(const float4*)(dp1 + rr * g.C);
+        }
     }
     float wreg[4];
 #pragma unroll
@@ -601,7 +643,7 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
     {
         double* red = (double*)smem;                     // [2][32][64] in the (still empty) ring
         float* coef = smem + 3 * PLANE + 27 * 64;        // [3][64] behind the filter taps
-        {
+        if (derive) {
             const int q = dq, rg = drg;
             double sa[4] = {0, 0, 0, 0}, sb[4] = {0, 0, 0, 0};
 #pragma unroll
@@ -618,26 +660,34 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
 #pragma unroll
             for (int e = 0; e < 4; ++e) { red[(0 * 32 + rg) * 64 + q * 4 + e] = sa[e]; red[(1 * 32 + rg) * 64 + q * 4 + e] = sb[e]; }
         }
-        __syncthreads();
+        if (derive) __syncthreads();
         double* red2 = red + 2 * 32 * 64;                // [2][4][64]
-        {
+        if (derive) {
             const int which = tid >> 8, part = (tid >> 6) & 3, ch = tid & 63;
             double s = 0.0;
 #pragma unroll
             for (int k = 0; k < 8; ++k) s += red[(which * 32 + part * 8 + k) * 64 + ch];
             red2[(which * 4 + part) * 64 + ch] = s;
         }
-        __syncthreads();
+        if (derive) __syncthreads();
         if (tid < 64) {
-            const double sa = (red2[(0 * 4 + 0) * 64 + tid] + red2[(0 * 4 + 1) * 64 + tid]) + (red2[(0 * 4 + 2) * 64 + tid] + red2[(0 * 4 + 3) * 64 + tid]);
-            const double sb = (red2[(1 * 4 + 0) * 64 + tid] + red2[(1 * 4 + 1) * 64 + tid]) + (red2[(1 * 4 + 2) * 64 + tid] + red2[(1 * 4 + 3) * 64 + tid]);
+            double sa = 0.0, sb = 0.0;
+            if (derive) {
+                sa = (red2[(0 * 4 + 0) * 64 + tid] + red2[(0 * 4 + 1) * 64 + tid]) + (red2[(0 * 4 + 2) * 64 + tid] + red2[(0 * 4 + 3) * 64 + tid]);
+                sb = (red2[(1 * 4 + 0) * 64 + tid] + red2[(1 * 4 + 1) * 64 + tid]) + (red2[(1 * 4 + 2) * 64 + tid] + red2[(1 * 4 + 3) * 64 + tid]);
+            }
             const int cc = c0 + tid;
             const double mu = d_mu, rr = d_rr, gm = d_gm;
             const double sum_dz = sa, sum_dz_xhat = (sb - mu * sa) * rr;
-            const double m1 = sum_dz / a.bcount, m2 = sum_dz_xhat / a.bcount;
             coef[0 * 64 + tid] = (float)(gm * rr);
-            coef[1 * 64 + tid] = (float)(-gm * rr * rr * m2);
-            coef[2 * 64 + tid] = (float)(gm * rr * rr * m2 * mu - gm * rr * m1);
+            if constexpr (FRZ) {
+                coef[1 * 64 + tid] = 0.f;
+                coef[2 * 64 + tid] = 0.f;
+            } else {
+                const double m1 = sum_dz / a.bcount, m2 = sum_dz_xhat / a.bcount;
+                coef[1 * 64 + tid] = (float)(-gm * rr * rr * m2);
+                coef[2 * 64 + tid] = (float)(gm * rr * rr * m2 * mu - gm * rr * m1);
+            }
             if (bx == 0 && a.bdgamma) {
                 a.bdgamma[cc] += (float)sum_dz_xhat;
                 a.bdbeta[cc] += (float)sum_dz;
@@ -792,14 +842,33 @@ TileGeom make_geom(int N, int T, int H, int W, int C, bool wgrad = false) {
     return g;
 }
 
-template <int MODE, bool BNG = false>
+template <int MODE, bool BNG = false, bool FRZ = false>
 int launch_tile(TileArgs& a, hipStream_t stream) {
     const TileGeom& g = a.g;
     dim3 grid(g.N * g.tchunks * g.htiles * g.wtiles, g.C / 64), block(512);
     const size_t lds = (3 * PLANE + 27 * 64 + 3 * 64) * sizeof(float);       // ring + filter taps + BNG coefficients (wgrad reuses the ring for its reduction)
     static LdsOptIn opt;                                   // (one per instantiation) > 64 KB of dynamic LDS needs the opt-in once per kernel and device
-    TUBER_LDS_OPT_IN(opt, (dwconv_tile_kernel<MODE, BNG>), lds);
-    hipLaunchKernelGGL((dwconv_tile_kernel<MODE, BNG>), grid, block, lds, stream, a);
+    TUBER_LDS_OPT_IN(opt, (dwconv_tile_kernel<MODE, BNG, true, FRZ>), lds);
+    hipLaunchKernelGGL((dwconv_tile_kernel<MODE, BNG, true, FRZ>), grid, block, lds, stream, a);
+    TUBER_RETURN_LAUNCH();
+}
+
+// launch of dwconv_tile_bwd_both_kernel (arguments checked by the callers)
+template <bool FRZ>
+static int dwconv_tile_bwd_both(const void* dzu, const void* xu, const float* bst0, const float* bst1, int R, float count,
+                                const float* gamma, const float* mean, const float* invstd, float* dgamma, float* dbeta,
+                                const float* w, const void* x, const float* sc, const float* sh, void* dz, float* st0, float* st1,
+                                float* partial, int N, int T, int H, int W, int C, hipStream_t stream) {
+    TileArgs a{};
+    a.in = (const bf16*)dzu; a.xu = (const bf16*)xu; a.sc = sc; a.sh = sh; a.w = w; a.out = (bf16*)dz; a.aux = (const bf16*)x;
+    a.st0 = st0; a.st1 = st1; a.P = partial;
+    a.bst0 = bst0; a.bst1 = bst1; a.bR = R; a.bcount = count; a.bgamma = gamma; a.bmean = mean; a.binvstd = invstd;
+    a.bdgamma = dgamma; a.bdbeta = dbeta;
+    a.g = make_geom(N, T, H, W, C);
+    const size_t lds = (3 * PLANE + 27 * 64 + 3 * 64) * sizeof(float);
+    static LdsOptIn opt;
+    TUBER_LDS_OPT_IN(opt, dwconv_tile_bwd_both_kernel<FRZ>, lds);
+    hipLaunchKernelGGL(dwconv_tile_bwd_both_kernel<FRZ>, dim3(a.g.N * a.g.tchunks * a.g.htiles * a.g.wtiles, C / 64), dim3(512), lds, stream, a);
     TUBER_RETURN_LAUNCH();
 }
 
@@ -942,17 +1011,53 @@ int tuber_dwconv_tile_bwd_both_bn(const void* dzu, const void* xu, const float* 
                                   const float* w, const void* x, const float* sc, const float* sh, void* dz, float* st0, float* st1,
                                   float* partial, int N, int T, int H, int W, int C, hipStream_t stream) {
     if ((C & 63) || !sc || !sh || R <= 0 || R > 128 || !bst0 || !bst1 || !partial || !dz || !st0 || !st1) return TUBER_EINVAL;
+    return dwconv_tile_bwd_both<false>(dzu, xu, bst0, bst1, R, count, gamma, mean, invstd, dgamma, dbeta, w, x, sc, sh, dz, st0, st1, partial,
+                                       N, T, H, W, C, stream);
+}
+
+// The three *_bn forms for a FROZEN bn3 (module in eval mode inside a training step): dc3 = gamma * invstd * dzu formed on load, so a frozen
+// layer stays on the fused path (no tuber_bn_bwd_fa launch, no dc3 tensor).  No count, and bn3's input c3 is not an operand (cB = 0).  The partial rows (bst0, bst1, R <= 128) are read only
+// for dgamma / dbeta (accumulated, +=); with those NULL (frozen affine parameters) the rows may be NULL and R is ignored.
+static inline bool frozen_rows_ok(const float* bst0, const float* bst1, int R, const float* dgamma, const float* dbeta) {
+    if ((dgamma == nullptr) != (dbeta == nullptr)) return false;
+    return !dgamma || (R > 0 && R <= 128 && bst0 && bst1);
+}
+
+int tuber_dwconv_tile_bwd_data_bn_frozen(const void* dzu, const float* bst0, const float* bst1, int R,
+                                         const float* gamma, const float* mean, const float* invstd, float* dgamma, float* dbeta,
+                                         const float* w, const void* x, const float* sc, const float* sh, void* dz,
+                                         float* st0, float* st1, int N, int T, int H, int W, int C, hipStream_t stream) {
+    if ((C & 63) || !sc || !sh || !gamma || !mean || !invstd || !frozen_rows_ok(bst0, bst1, R, dgamma, dbeta)) return TUBER_EINVAL;
     TileArgs a{};
-    a.in = (const bf16*)dzu; a.xu = (const bf16*)xu; a.sc = sc; a.sh = sh; a.w = w; a.out = (bf16*)dz; a.aux = (const bf16*)x;
-    a.st0 = st0; a.st1 = st1; a.P = partial;
-    a.bst0 = bst0; a.bst1 = bst1; a.bR = R; a.bcount = count; a.bgamma = gamma; a.bmean = mean; a.binvstd = invstd;
+    a.in = (const bf16*)dzu; a.sc = sc; a.sh = sh; a.w = w; a.out = (bf16*)dz; a.aux = (const bf16*)x;
+    a.st0 = st0; a.st1 = st1;
+    a.bst0 = bst0; a.bst1 = bst1; a.bR = R; a.bgamma = gamma; a.bmean = mean; a.binvstd = invstd;
     a.bdgamma = dgamma; a.bdbeta = dbeta;
     a.g = make_geom(N, T, H, W, C);
-    const size_t lds = (3 * PLANE + 27 * 64 + 3 * 64) * sizeof(float);
-    static LdsOptIn opt;
-    TUBER_LDS_OPT_IN(opt, dwconv_tile_bwd_both_kernel, lds);
-    hipLaunchKernelGGL(dwconv_tile_bwd_both_kernel, dim3(a.g.N * a.g.tchunks * a.g.htiles * a.g.wtiles, C / 64), dim3(512), lds, stream, a);
-    TUBER_RETURN_LAUNCH();
+    return launch_tile<M_BWD_DATA, true, true>(a, stream);
+}
+
+int tuber_dwconv_tile_bwd_weight_bn_frozen(const void* dzu, const float* gamma, const float* mean, const float* invstd,
+                                           const void* x, const float* sc, const float* sh, float* partial, float* dw, int accumulate,
+                                           int N, int T, int H, int W, int C, hipStream_t stream) {
+    if ((C & 63) || !sc || !sh || !gamma || !mean || !invstd) return TUBER_EINVAL;
+    TileArgs a{};
+    a.in = (const bf16*)x; a.sc = sc; a.sh = sh; a.aux = (const bf16*)dzu; a.P = partial;
+    a.bgamma = gamma; a.bmean = mean; a.binvstd = invstd;
+    a.g = make_geom(N, T, H, W, C, true);
+    const int rc = launch_tile<M_BWD_WEIGHT, true, true>(a, stream);
+    if (rc || accumulate == 2) return rc;
+    return tuber_dw_wgrad_reduce(partial, dw, a.g.N * a.g.tchunks * a.g.htiles * a.g.wtiles, C, accumulate, stream);
+}
+
+int tuber_dwconv_tile_bwd_both_bn_frozen(const void* dzu, const float* bst0, const float* bst1, int R,
+                                         const float* gamma, const float* mean, const float* invstd, float* dgamma, float* dbeta,
+                                         const float* w, const void* x, const float* sc, const float* sh, void* dz, float* st0, float* st1,
+                                         float* partial, int N, int T, int H, int W, int C, hipStream_t stream) {
+    if ((C & 63) || !sc || !sh || !gamma || !mean || !invstd || !partial || !dz || !st0 || !st1
+        || !frozen_rows_ok(bst0, bst1, R, dgamma, dbeta)) return TUBER_EINVAL;
+    return dwconv_tile_bwd_both<true>(dzu, nullptr, bst0, bst1, R, 0.f, gamma, mean, invstd, dgamma, dbeta, w, x, sc, sh, dz, st0, st1, partial,
+                                      N, T, H, W, C, stream);
 }
 
 }  // extern "C"

@@ -19,6 +19,21 @@ DOC = {
                        "derives the coefficients of its 128-channel strip from the R partial rows (fp64) and applies dx = cA*dz + cB*x + cC to its rows; "
                        "dgamma / dbeta accumulated by the first row chunk (NULL: frozen BatchNorm). autograd of nn.BatchNorm3d (ir_CSN_152.py:46,56,64,154).",
     "tuber_bn_bwd_fa_max_rows": "largest R tuber_bn_bwd_fa accepts.",
+    "tuber_bn_frozen_affine_multi": "the FROZEN BatchNorm layers of a training-mode forward (nn.BatchNorm3d with module.training == False inside model.train(): "
+                                    "F.batch_norm(training=False), models/backbones/ir_CSN_152.py:46,56,64,119,154) in ONE launch over a device table of "
+                                    "{gamma, beta, running_mean, running_var, scale, shift, mean, invstd, cA, cB, cC, C} rows: scale / shift bit-identical to "
+                                    "tuber_bn_eval_affine, mean = running_mean, invstd = 1 / sqrt(running_var + eps), and the backward coefficients cA = gamma * invstd, "
+                                    "cB = cC = 0, so every backward kernel that takes (cA, cB, cC) runs unchanged. The running buffers are not written.",
+    "tuber_bn_frozen_param_grads": "dgamma += sum dz * (x - running_mean) * invstd, dbeta += sum dz of a frozen BatchNorm whose affine parameters train (autograd of "
+                                   "F.batch_norm(training=False), ir_CSN_152.py:46,56,64,119,154) from the partial rows (sum dz, sum dz*x) of the train-mode path: "
+                                   "no count, no coefficient output.",
+    "tuber_bn_bwd_fa_frozen": "tuber_bn_bwd_fa for a frozen BatchNorm: dx = gamma * invstd * dz in one launch (autograd of F.batch_norm(training=False), "
+                              "ir_CSN_152.py:46,56,64,154); x is not an operand, the partial rows are read only for dgamma / dbeta (NULL: not at all).",
+    "tuber_dwconv_tile_bwd_data_bn_frozen": "tuber_dwconv_tile_bwd_data_bn with a FROZEN bn3 above the depthwise conv (ir_CSN_152.py:53-56 with bn3.training == False): "
+                                            "dc3 = gamma * invstd * dzu formed on load; the partial rows are read only for dgamma / dbeta (NULL: not at all).",
+    "tuber_dwconv_tile_bwd_weight_bn_frozen": "tuber_dwconv_tile_bwd_weight_bn with a FROZEN bn3 (ir_CSN_152.py:53-56): takes no partial rows.",
+    "tuber_dwconv_tile_bwd_both_bn_frozen": "tuber_dwconv_tile_bwd_both_bn with a FROZEN bn3 (ir_CSN_152.py:53-56): data and weight gradient of the depthwise conv in one "
+                                            "launch with dc3 = gamma * invstd * dzu formed on load; dz and dgamma / dbeta bit-identical to tuber_dwconv_tile_bwd_data_bn_frozen.",
     "tuber_ln_bwd_dx": "tuber_layernorm_bwd (partial rows only) + the data-gradient tuber_gemm_nt of the linear layer in front of the LayerNorm in ONE launch: "
                        "autograd of tgt = norm(tgt + dropout(sublayer)) where the sublayer ends in out_proj / linear2 (models/transformer/transformer.py:160-167,229-247). "
                        "Every workgroup runs the LayerNorm backward of its 32 rows itself and multiplies the bf16 result from LDS with W on MFMA; the column-0 workgroups "

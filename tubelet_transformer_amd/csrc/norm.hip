@@ -141,6 +141,51 @@ __global__ void bn_eval_affine_multi_kernel(const BnAffineRow* __restrict__ tabl
     r.shift[c] = r.beta[c] - r.rmean[c] * sc;
 }
 
+// FROZEN BatchNorm layers (module in eval mode inside a training step): the layer is the constant affine map of the eval path, and its
+// backward is dx = gamma * invstd * dz.  One launch per forward over a device table of the frozen layers only writes everything both
+// passes read: scale / shift (the expressions of bn_eval_affine_kernel, so bit-identical to it), mean = running_mean, invstd, and the
+// backward coefficients cA = gamma * invstd, cB = cC = 0 -- so every backward kernel that TAKES (cA, cB, cC) runs unchanged.
+struct BnFrozenRow { const float* gamma; const float* beta; const float* rmean; const float* rvar; float* scale; float* shift;
+                     float* mean; float* invstd; float* cA; float* cB; float* cC; long C; };
+__global__ void bn_frozen_affine_multi_kernel(const BnFrozenRow* __restrict__ table, float eps) {
+    const BnFrozenRow r = table[blockIdx.y];
+    const int c = blockIdx.x * blockDim.x + threadIdx.x;
+    if (c >= r.C) return;
+    const float g = r.gamma[c], mu = r.rmean[c], v = r.rvar[c];
+    const float sc = g / sqrtf(v + eps);
+    r.scale[c] = sc;
+    r.shift[c] = r.beta[c] - mu * sc;
+    // invstd as the train-mode finalisation forms it (fp64, rounded once); scale above is the fp32 expression of the eval kernel, which bit identity
+    // with the eval path needs -- so the backward slope cA = g * inv and the forward slope sc may differ in the last fp32 bit (far below bf16)
+    const float inv = (float)(1.0 / sqrt((double)v + (double)eps));
+    r.mean[c] = mu;
+    r.invstd[c] = inv;
+    r.cA[c] = g * inv;
+    r.cB[c] = 0.f;
+    r.cC[c] = 0.f;
+}
+
+// dgamma += sum dz * (x - running_mean) * invstd, dbeta += sum dz of a frozen layer with trainable affine parameters, from the partial
+// rows (sum dz, sum dz*x) the train-mode path produces anyway: no count, no coefficients, no 1 / count terms
+template <int NTH>
+__global__ __launch_bounds__(NTH) void bn_frozen_param_grads_kernel(
+    const float* __restrict__ st0, const float* __restrict__ st1, int R, int C,
+    const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ dgamma, float* __restrict__ dbeta) {
+    __shared__ double red[2][32][33];
+    const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5;
+    const int c = blockIdx.x * 32 + cl;
+    const bool fin = threadIdx.x < 32 && c < C;
+    const float mu_f = fin ? mean[c] : 0.f, r_f = fin ? invstd[c] : 0.f;
+    const float dg0 = fin ? dgamma[c] : 0.f, db0 = fin ? dbeta[c] : 0.f;
+    double a, b;
+    bn_partial_sums<NTH>(st0, st1, R, C, blockIdx.x * 32, red, a, b);
+    if (rg == 0 && c < C) {
+        const double mu = mu_f, r = r_f;
+        dgamma[c] = dg0 + (float)((b - mu * a) * r);
+        dbeta[c] = db0 + (float)a;
+    }
+}
+
 // dL/dx = A*dz + B*x + C per channel;  dgamma = sum dz*xhat, dbeta = sum dz
 template <int NTH>
 __global__ __launch_bounds__(NTH) void bn_bwd_finalize_kernel(
@@ -325,7 +370,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
 // layer3's bn4 (M = 5632, C = 1024) is 44 x 8 = 352 workgroups at 128 rows -- the launch runs at the pace of the CUs that carry two --
 // and 32 x 8 = 256 at 176 rows.
 #define FA_CS 128          // channels per strip
-template <int KR>
+// FRZ: the frozen form (module in eval mode): dx = gamma * invstd * dz -- x is not read, and the partial rows only by the row chunk that
+// writes dgamma / dbeta (not at all when those are NULL)
+template <int KR, bool FRZ = false>
 __global__ __launch_bounds__(256) void bn_bwd_fa_kernel(
     const float* __restrict__ st0, const float* __restrict__ st1, int R, int C, float count,
     const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ invstd,
@@ -347,10 +394,11 @@ __global__ __launch_bounds__(256) void bn_bwd_fa_kernel(
         const long row = r0 + rs + 16 * k;
         const long off = min(row, M - 1) * C + c0 + cg * 8;
         pd[k] = *(const uint4*)(dz + off);
-        px[k] = *(const uint4*)(x + off);
+        if constexpr (!FRZ) px[k] = *(const uint4*)(x + off);
     }
+    const bool derive = !FRZ || (blockIdx.x == 0 && dgamma != nullptr);      // (workgroup-uniform)
     // ---- derive: thread = (row group rg of 8, channel quad q of 32) ----
-    {
+    if (derive) {
         const int q = tid & 31, rg = tid >> 5;
         double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
         const float* p0 = st0 + c0 + q * 4;
@@ -377,15 +425,19 @@ __global__ __launch_bounds__(256) void bn_bwd_fa_kernel(
     __syncthreads();
     if (tid < FA_CS) {
         double a = 0.0, b = 0.0;
+        if (derive) {
 #pragma unroll
-        for (int k = 0; k < 8; ++k) { a += red[0][k][tid]; b += red[1][k][tid]; }
+            for (int k = 0; k < 8; ++k) { a += red[0][k][tid]; b += red[1][k][tid]; }
+        }
         const int c = c0 + tid;
         const double mu = mean[c], rr = invstd[c], g = gamma[c];
         const double sum_dz = a, sum_dz_xhat = (b - mu * a) * rr;
-        const double m1 = sum_dz / count, m2 = sum_dz_xhat / count;
         coef[0][tid] = (float)(g * rr);
-        coef[1][tid] = (float)(-g * rr * rr * m2);
-        coef[2][tid] = (float)(g * rr * rr * m2 * mu - g * rr * m1);
+        if constexpr (!FRZ) {
+            const double m1 = sum_dz / count, m2 = sum_dz_xhat / count;
+            coef[1][tid] = (float)(-g * rr * rr * m2);
+            coef[2][tid] = (float)(g * rr * rr * m2 * mu - g * rr * m1);
+        }
         if (blockIdx.x == 0 && dgamma) {
             dgamma[c] += (float)sum_dz_xhat;
             dbeta[c] += (float)sum_dz;
@@ -395,15 +447,24 @@ __global__ __launch_bounds__(256) void bn_bwd_fa_kernel(
     // ---- apply ----
     float ca[8], cb[8], cc[8];
 #pragma unroll
-    for (int e = 0; e < 8; ++e) { ca[e] = coef[0][cg * 8 + e]; cb[e] = coef[1][cg * 8 + e]; cc[e] = coef[2][cg * 8 + e]; }
+    for (int e = 0; e < 8; ++e) {
+        ca[e] = coef[0][cg * 8 + e];
+        if constexpr (!FRZ) { cb[e] = coef[1][cg * 8 + e]; cc[e] = coef[2][cg * 8 + e]; }
+    }
 #pragma unroll
     for (int k = 0; k < FA_ROWS / 16; ++k) {
         const long row = r0 + rs + 16 * k;
         if (row >= r1) break;
-        const bf16x8 d = as_bf16x8(pd[k]), xx = as_bf16x8(px[k]);
+        const bf16x8 d = as_bf16x8(pd[k]);
         bf16x8 o;
+        if constexpr (FRZ) {
 #pragma unroll
-        for (int e = 0; e < 8; ++e) o[e] = f2bf(fmaf(ca[e], bf2f(d[e]), fmaf(cb[e], bf2f(xx[e]), cc[e])));
+            for (int e = 0; e < 8; ++e) o[e] = f2bf(ca[e] * bf2f(d[e]));
+        } else {
+            const bf16x8 xx = as_bf16x8(px[k]);
+#pragma unroll
+            for (int e = 0; e < 8; ++e) o[e] = f2bf(fmaf(ca[e], bf2f(d[e]), fmaf(cb[e], bf2f(xx[e]), cc[e])));
+        }
         *(uint4*)(dx + row * C + c0 + cg * 8) = as_uint4(o);
     }
 }
@@ -824,6 +885,28 @@ int tuber_bn_eval_affine_multi(const void* table, int n, int cmax, float eps, hi
     TUBER_RETURN_LAUNCH();
 }
 
+// The frozen layers of a training-mode forward (nn.BatchNorm3d with module.training == False) in ONE launch.  table: n rows of 12 64-bit
+// words in DEVICE memory -- the pointers gamma, beta, running_mean, running_var, then the outputs scale, shift, mean, invstd, cA, cB, cC, then
+// the channel count.  scale / shift as tuber_bn_eval_affine (bit for bit); mean = running_mean; cA = gamma * invstd, cB = cC = 0.
+int tuber_bn_frozen_affine_multi(const void* table, int n, int cmax, float eps, hipStream_t stream) {
+    if (!table || n <= 0 || n > 65535 || cmax <= 0) return TUBER_EINVAL;
+    hipLaunchKernelGGL(bn_frozen_affine_multi_kernel, dim3(ceil_div(cmax, 256), n), dim3(256), 0, stream, (const BnFrozenRow*)table, eps);
+    TUBER_RETURN_LAUNCH();
+}
+
+// dgamma / dbeta (ACCUMULATED, +=) of a frozen BatchNorm whose affine parameters train, from the R partial rows (sum dz, sum dz*x)
+int tuber_bn_frozen_param_grads(const float* st0, const float* st1, int R, int C, const float* mean, const float* invstd,
+                                float* dgamma, float* dbeta, hipStream_t stream) {
+    if (R <= 0 || C <= 0 || (C & 3) || !st0 || !st1 || !mean || !invstd || !dgamma || !dbeta) return TUBER_EINVAL;
+    if (R <= 128)
+        hipLaunchKernelGGL(bn_frozen_param_grads_kernel<256>, dim3(ceil_div(C, 32)), dim3(256), 0, stream, st0, st1, R, C, mean, invstd,
+                           dgamma, dbeta);
+    else
+        hipLaunchKernelGGL(bn_frozen_param_grads_kernel<1024>, dim3(ceil_div(C, 32)), dim3(1024), 0, stream, st0, st1, R, C, mean, invstd,
+                           dgamma, dbeta);
+    TUBER_RETURN_LAUNCH();
+}
+
 int tuber_bn_bwd_finalize(const float* st0, const float* st1, int R, int C, float count, const float* gamma, const float* mean,
                           const float* invstd, float* cA, float* cB, float* cC, float* dgamma, float* dbeta, int accumulate,
                           hipStream_t stream) {
@@ -913,6 +996,22 @@ int tuber_bn_bwd_fa(const float* st0, const float* st1, int R, int C, float coun
     const int kr = g_fa_rows_forced ? g_fa_rows_forced : fa_rows_per_thread(M, C);
 #define FA_LAUNCH(KR) hipLaunchKernelGGL(bn_bwd_fa_kernel<KR>, dim3(ceil_div(M, 16L * KR), C / FA_CS), dim3(256), 0, stream, st0, st1, R, C, \
                                          count, gamma, mean, invstd, dgamma, dbeta, (const bf16*)dz, (const bf16*)x, (bf16*)dx, M)
+    if (kr == 4) FA_LAUNCH(4);
+    else if (kr == 11) FA_LAUNCH(11);
+    else FA_LAUNCH(8);
+#undef FA_LAUNCH
+    TUBER_RETURN_LAUNCH();
+}
+
+// tuber_bn_bwd_fa for a FROZEN layer: dx = gamma * invstd * dz in one launch (no x operand, no count).  The partial rows are read only by
+// the row chunk that accumulates dgamma / dbeta; with those NULL (frozen affine parameters) st0 / st1 may be NULL and R is ignored.
+int tuber_bn_bwd_fa_frozen(const float* st0, const float* st1, int R, int C, const float* gamma, const float* mean, const float* invstd,
+                           float* dgamma, float* dbeta, const void* dz, void* dx, long M, hipStream_t stream) {
+    if (C <= 0 || (C % FA_CS) || M <= 0 || !gamma || !mean || !invstd || (dgamma == nullptr) != (dbeta == nullptr)) return TUBER_EINVAL;
+    if (dgamma && (R <= 0 || R > 128 || !st0 || !st1)) return TUBER_EINVAL;
+    const int kr = g_fa_rows_forced ? g_fa_rows_forced : fa_rows_per_thread(M, C);
+#define FA_LAUNCH(KR) hipLaunchKernelGGL((bn_bwd_fa_kernel<KR, true>), dim3(ceil_div(M, 16L * KR), C / FA_CS), dim3(256), 0, stream, st0, st1, R, C, \
+                                         0.f, gamma, mean, invstd, dgamma, dbeta, (const bf16*)dz, (const bf16*)nullptr, (bf16*)dx, M)
     if (kr == 4) FA_LAUNCH(4);
     else if (kr == 11) FA_LAUNCH(11);
     else FA_LAUNCH(8);

@@ -162,9 +162,17 @@ class CaptureFailed(RuntimeError):
     """the hipGraph capture of a training step did not complete (the eager step remains available)"""
 
 
+_FROZEN_TAG = "frozen_bn"
+
+
 def _momenta(key):
     """the BatchNorm momentum part of a GraphedTrainStep key (a tuple behind the fixed five entries; the role is a string), or ()"""
-    return key[5] if len(key) > 5 and isinstance(key[5], tuple) else ()
+    return next((e for e in key[5:] if isinstance(e, tuple) and e[:1] != (_FROZEN_TAG,)), ())
+
+
+def _frozen(key):
+    """the frozen-BatchNorm part of a GraphedTrainStep key: (tag, layer indices) behind the fixed five entries, or ()"""
+    return next((e for e in key[5:] if isinstance(e, tuple) and e[:1] == (_FROZEN_TAG,)), ())
 
 
 class GraphedTrainStep:
@@ -367,18 +375,23 @@ class GraphedTrainStep:
         """graph key: clip shape, set of trainable tensors, train / eval criterion, padded target layout, the decoder's launch form (a
         captured step bakes it in: after a timed-out cooperative launch -- engine.coop_failed -- a new one is captured)[, the BatchNorm
         momenta that differ from the reference's 0.1 (baked into the finalisation launches: a changed momentum captures a new step; absent
-        while every module has 0.1)][, accumulation role]"""
+        while every module has 0.1)][, the frozen BatchNorm layers (modules in eval mode: their launches differ; absent while every module
+        trains, so freezing or unfreezing a layer captures a new step)][, accumulation role]"""
         store, runner = self.model.engine()
         key = (tuple(shape), store.trainable_signature(), self.criterion.training, tmax, store.coop_off)
         mom = runner.momentum_signature()
         if mom:
             key += (mom,)
+        frz = runner.frozen_signature()
+        if frz:
+            key += ((_FROZEN_TAG, frz),)
         return key if role is None else key + (role,)
 
     def _wider(self, shape, tmax=0):
         """the first captured key for this clip shape whose padded target layout holds ``tmax`` boxes per clip (any role), or None"""
         want = self._key(shape, tmax)
-        return next((k for k in self.graphs if k[:3] == want[:3] and k[3] >= tmax and k[4] == want[4] and _momenta(k) == _momenta(want)), None)
+        return next((k for k in self.graphs if k[:3] == want[:3] and k[3] >= tmax and k[4] == want[4] and _momenta(k) == _momenta(want)
+                     and _frozen(k) == _frozen(want)), None)
 
     def input_buffers(self, clips_shape):
         """(clips, mask) buffers the captured step for this clip shape reads, or None before its first call: a producer that fills them in

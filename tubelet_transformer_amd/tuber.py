@@ -189,6 +189,16 @@ class DETR(nn.Module):
         self._store = None
         self._runner = None
         self._anchor = None
+        self.freeze_bn = "none"                # CONFIG.MODEL.FREEZE_BN / bn_stats.freeze_batchnorm: BatchNorm layers train() keeps in eval mode
+
+    def train(self, mode=True):
+        """nn.Module.train, then the frozen-BatchNorm policy again (evaluated now: ``requires_grad`` may have changed): the training loop
+        calls model.train() every epoch, which would otherwise put every frozen layer back into train mode"""
+        super().train(mode)
+        if mode and getattr(self, "freeze_bn", "none") != "none":       # (getattr: an object pickled before the attribute existed)
+            from .bn_stats import apply_freeze_policy
+            apply_freeze_policy(self)
+        return self
 
     # -- engine ----------------------------------------------------------------------------------
     def engine(self):
@@ -622,6 +632,8 @@ def build_model(cfg):
                  hidden_dim=C.MODEL.D_MODEL, temporal_length=C.MODEL.TEMP_LEN, generate_lfb=C.MODEL.GENERATE_LFB,
                  backbone_name=C.MODEL.BACKBONE_NAME, ds_rate=C.MODEL.DS_RATE, last_stride=C.MODEL.LAST_STRIDE,
                  dataset_mode=C.DATA.DATASET_NAME)
+    from .bn_stats import freeze_batchnorm
+    freeze_batchnorm(model, C.MODEL.get("FREEZE_BN", "none"))      # (a config node built without the defaults has no such key)
     matcher = build_matcher(cfg)
     weight_dict = {"loss_ce": C.LOSS_COFS.DICE_COF, "loss_bbox": C.LOSS_COFS.BBOX_COF, "loss_giou": C.LOSS_COFS.GIOU_COF,
                    "loss_ce_b": 1}
