@@ -59,10 +59,30 @@ def load_model(model, cfg, load_fc=True):
         if not load_fc:
             tensors = {k: v for k, v in tensors.items() if not _strip(k).startswith("fc.")}
         _copy_into(model, tensors, what="checkpoint")
+        load_weight_average(model, ckpt, cfg)
         print("=> loaded checkpoint '{}' (epoch {})".format(path, ckpt.get("epoch")))
     else:
         print("=> no checkpoint found at '{}'".format(path))
     return model, None
+
+
+def load_weight_average(model, ckpt, cfg=None):
+    """restore the weight averager (weight_avg.py) a checkpoint holds (``ema_state``: the flat average, the update count, the settings, kept
+    BatchNorm statistics) into the model's averager -- the one cached on the model, or, with CONFIG.TRAIN.EMA.ENABLE, a new one that the
+    training loop will find there.  Returns it, or None when the file has none or nothing asks for one."""
+    state = ckpt.get("ema_state") if isinstance(ckpt, dict) else None
+    if state is None:
+        return None
+    from .weight_avg import KEY, WeightAverage, averager_of
+    bare = model.module if hasattr(model, "module") else model
+    avg = averager_of(bare)
+    if avg is None:
+        E = getattr(cfg.CONFIG.TRAIN, "EMA", None) if cfg is not None else None
+        if E is None or not E.ENABLE:
+            return None
+        avg = bare.__dict__[KEY] = WeightAverage(bare, **state["settings"])
+    avg.load_state(state)
+    return avg
 
 
 def load_detr_weights(model, pretrain_dir, cfg):
@@ -99,7 +119,8 @@ def load_detr_weights(model, pretrain_dir, cfg):
 
 def save_checkpoint(cfg, epoch, model, max_accuracy, optimizer, lr_scheduler, ddp_prefix=True):
     """utils/model_utils.py:118-134: {model, optimizer, lr_scheduler, max_accuracy, epoch, config} ->
-    {BASE_PATH}/{EXP_NAME}/{SAVE_DIR}/ckpt_epoch_{e}.pth."""
+    {BASE_PATH}/{EXP_NAME}/{SAVE_DIR}/ckpt_epoch_{e}.pth.  A model with a weight averager also gets "model_ema" (the averaged
+    state_dict, same key form as "model") and "ema_state" (resume)."""
     sd = model.state_dict()
     if ddp_prefix:
         sd = {"module." + k: v for k, v in sd.items()}
@@ -108,6 +129,11 @@ def save_checkpoint(cfg, epoch, model, max_accuracy, optimizer, lr_scheduler, dd
                   "lr_scheduler": lr_scheduler.state_dict() if lr_scheduler is not None else None,
                   "max_accuracy": max_accuracy, "epoch": epoch,
                   "config": cfg.to_dict() if hasattr(cfg, "to_dict") else cfg}
+    from .weight_avg import averager_of
+    avg = averager_of(model)
+    if avg is not None:                  # the averaged model under the same names as "model", and what a resume needs (weight_avg.py)
+        save_state["model_ema"] = {("module." + k if ddp_prefix else k): v.detach().cpu() for k, v in avg.state_dict().items()}
+        save_state["ema_state"] = avg.state()
     d = os.path.join(cfg.CONFIG.LOG.BASE_PATH, cfg.CONFIG.LOG.EXP_NAME, cfg.CONFIG.LOG.SAVE_DIR)
     os.makedirs(d, exist_ok=True)
     path = os.path.join(d, "ckpt_epoch_%d.pth" % epoch)

@@ -141,7 +141,10 @@ def get_cfg_defaults():
     cfg.TRAIN = CfgNode(dict(
         START_EPOCH=0, EPOCH_NUM=20, BATCH_SIZE=2, LR=1e-4, MIN_LR=1e-5, LR_BACKBONE=1e-5,
         W_DECAY=1e-4, LR_POLICY="step", AUX_LOSS=True,
-        ACCUM_STEPS=1), new_allowed=True)      # micro-batches per optimizer step (accum.py; not a reference key)
+        ACCUM_STEPS=1,                         # micro-batches per optimizer step (accum.py; not a reference key)
+        # weight averaging inside the training step (weight_avg.py; not reference keys): MODE ema | swa, updates at the optimizer steps
+        # t >= START with (t - START) % PERIOD == 0, EVAL: validate with the averaged weights
+        EMA=dict(ENABLE=False, MODE="ema", DECAY=0.9999, WARMUP=False, START=0, PERIOD=1, EVAL=True)), new_allowed=True)
     cfg.VAL = CfgNode(dict(FREQ=2, BATCH_SIZE=1), new_allowed=True)
     cfg.DATA = CfgNode(dict(
         DATASET_NAME="ava", NUM_CLASSES=80, IMG_SIZE=256, TEMP_LEN=32, FRAME_RATE=2), new_allowed=True)

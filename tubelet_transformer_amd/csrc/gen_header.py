@@ -290,6 +290,13 @@ DOC = {
                                  "non-finite loss (video_action_recognition.py:195-198).",
     "tuber_adamw_segment": "AdamW update (torch.optim.AdamW semantics: decoupled decay, bias correction) of one contiguous flat segment with the "
                            "clip coefficient applied to the gradient on the fly (video_action_recognition.py:154; groups train_tuber_ava.py:41-58).",
+    "tuber_weight_average": "weight averaging of the flat fp32 parameter buffer in one streaming pass: avg[i] += w * (p[i] - avg[i]) (an element with p == avg keeps its "
+                            "bits; w == 1 stores p exactly). mode 0 (ema) restates timm's ModelEmaV2, w = 1 - decay, with warmup w = 1 - min(decay, (1 + n) / (10 + n)); "
+                            "mode 1 (swa) the default avg_fn of torch.optim.swa_utils.AveragedModel, w = 1 / n; n = *n_avg + 1, w formed in fp64 and rounded once. "
+                            "table = DEVICE {float decay; int mode, warmup, start, period}. With clip (norm_out of tuber_grad_norm_clip_coef) a step AdamW skipped "
+                            "(clip[1] < 0) is not averaged; with step_ptr (the AdamW step count t) the update happens iff t >= start and (t - start) % period == 0; "
+                            "a NULL pointer drops its test. *n_avg advances by one iff the update was applied (a one-thread launch behind the pass). The reference "
+                            "trains without weight averaging (the epoch loop of train_tuber_ava.py:73-84); the grid is capped at 2048 workgroups of 256 threads x 4 elements.",
     "tuber_grad_accum": "gradient accumulation over m micro-batches (DistributedDataParallel's mean over ranks reproduced on fewer GPUs: the mean of "
                         "independent per-rank backward passes, utils/model_utils.py:47-49) over a DEVICE table of nwin [begin, end) int64 windows of the flat "
                         "fp32 gradient buffer, in ONE launch: mode 0 acc = g, mode 1 acc += g, mode 2 g = (acc + g) * scale (scale_dev[0] when given). "

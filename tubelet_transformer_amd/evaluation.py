@@ -192,6 +192,20 @@ def _forward_checked(model, samples):
     return outputs
 
 
+def _with_averaged_weights(fn):
+    """CONFIG.TRAIN.EMA.ENABLE and .EVAL with a weight averager on the model (weight_avg.py): the loop runs on the averaged weights
+    (``WeightAverage.applied``: the live weights and buffers are back afterwards); otherwise exactly the plain loop"""
+    import functools
+
+    @functools.wraps(fn)
+    def run(cfg, model, *args, **kwargs):
+        from .weight_avg import eval_context
+        with eval_context(cfg, model):
+            return fn(cfg, model, *args, **kwargs)
+    return run
+
+
+@_with_averaged_weights
 @torch.no_grad()
 def validate_tuber_detection(cfg, model, criterion, postprocessors, data_loader, epoch, writer=None, excluded_timestamps=None,
                              verbose=True):
@@ -323,6 +337,7 @@ class FrameMAPUCF(FrameMAP):
                 self.det.setdefault(key, []).append((x + 1, np.asarray(v[0:4], dtype=float), float(scores[x])))
 
 
+@_with_averaged_weights
 @torch.no_grad()
 def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loader, epoch, writer=None, verbose=True):
     """utils/video_action_recognition.py:456-689 (called by train_tuber_jhmdb.py:83 / eval_tuber_jhmdb.py:77): eval-mode forward on

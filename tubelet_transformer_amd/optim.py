@@ -32,6 +32,7 @@ class FusedClipAdamW(torch.optim.Optimizer):
         self.hyper = torch.zeros(len(self.param_groups), 2, dtype=torch.float32, device=dev)
         self._hyper_host = None
         self._hyper_pin = None          # pinned staging of the table: per-iteration schedulers change lr every step, no blocking copy
+        self.averager = None            # weight_avg.WeightAverage attached to this optimizer: one more launch behind the segments of step()
         # flat segments with uniform hyper-parameters: walk the store in layout order
         by_ptr = {}
         for gi, group in enumerate(self.param_groups):
@@ -137,6 +138,9 @@ class FusedClipAdamW(torch.optim.Optimizer):
             lib.call("tuber_adamw_segment", f, st.gflat.data_ptr() + 4 * o, self.exp_avg.data_ptr() + 4 * o,
                      self.exp_avg_sq.data_ptr() + 4 * o, end - o, clip, float(g["lr"]), float(b1), float(b2), float(g["eps"]),
                      float(g["weight_decay"]), self.t_dev, 0, self.hyper.data_ptr() + 8 * gi)
+        if self.averager is not None:
+            # EMA / SWA of the parameters just written, in the same graph as the step: cadence from t_dev, nothing after a skipped step
+            self.averager.step_update(self.t_dev, clip)
         return None
 
 

@@ -17,6 +17,7 @@ import torch
 from . import ab
 from .ddp import attach_reducer, broadcast_parameters, cut_windows
 from .optim import FusedClipAdamW, adopt, build_param_groups
+from .weight_avg import KEY as _AVG_KEY, averager_for
 
 
 def deploy_model(model, cfg, is_tuber=True, device=None):
@@ -98,6 +99,9 @@ def train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=0,
         if max_norm and max_norm > 0:
             torch.nn.utils.clip_grad_norm_(model.parameters(), max_norm)
         optimizer.step()
+        avg = model.__dict__.get(_AVG_KEY)
+        if avg is not None and avg.drives(optimizer):
+            avg.update()                   # an optimizer the averaging launch cannot ride in: averaged eagerly behind its step
     if accum is not None:
         accum.end_micro()
     return losses.detach(), loss_dict
@@ -112,6 +116,9 @@ class _Snapshot:
                       (opt.exp_avg_sq, opt.exp_avg_sq.clone()), (opt.t_dev, opt.t_dev.clone())]
         self.items += [(b, b.clone()) for b in model.buffers()]
         self.items += [(t, t.clone()) for t in extra if t is not None]       # gradient accumulation: acc, BatchNorm snapshot, fold scale
+        avg = getattr(opt, "averager", None)
+        if avg is not None:                                                  # weight averaging: the warm-up passes are no updates either
+            self.items += [(t, t.clone()) for t in (avg.avg, avg.n_avg)]
 
     def restore(self):
         with torch.no_grad():
@@ -163,16 +170,22 @@ class CaptureFailed(RuntimeError):
 
 
 _FROZEN_TAG = "frozen_bn"
+_AVG_TAG = "weight_avg"
 
 
 def _momenta(key):
     """the BatchNorm momentum part of a GraphedTrainStep key (a tuple behind the fixed five entries; the role is a string), or ()"""
-    return next((e for e in key[5:] if isinstance(e, tuple) and e[:1] != (_FROZEN_TAG,)), ())
+    return next((e for e in key[5:] if isinstance(e, tuple) and e[:1] not in ((_FROZEN_TAG,), (_AVG_TAG,))), ())
 
 
 def _frozen(key):
     """the frozen-BatchNorm part of a GraphedTrainStep key: (tag, layer indices) behind the fixed five entries, or ()"""
     return next((e for e in key[5:] if isinstance(e, tuple) and e[:1] == (_FROZEN_TAG,)), ())
+
+
+def _averaged(key):
+    """the weight-averaging part of a GraphedTrainStep key: (tag, averager serial) behind the fixed five entries, or ()"""
+    return next((e for e in key[5:] if isinstance(e, tuple) and e[:1] == (_AVG_TAG,)), ())
 
 
 class GraphedTrainStep:
@@ -376,7 +389,8 @@ class GraphedTrainStep:
         captured step bakes it in: after a timed-out cooperative launch -- engine.coop_failed -- a new one is captured)[, the BatchNorm
         momenta that differ from the reference's 0.1 (baked into the finalisation launches: a changed momentum captures a new step; absent
         while every module has 0.1)][, the frozen BatchNorm layers (modules in eval mode: their launches differ; absent while every module
-        trains, so freezing or unfreezing a layer captures a new step)][, accumulation role]"""
+        trains, so freezing or unfreezing a layer captures a new step)][, the weight averager attached to the optimizer (its launch and
+        addresses are part of the optimizer step; absent while none is attached)][, accumulation role]"""
         store, runner = self.model.engine()
         key = (tuple(shape), store.trainable_signature(), self.criterion.training, tmax, store.coop_off)
         mom = runner.momentum_signature()
@@ -385,13 +399,16 @@ class GraphedTrainStep:
         frz = runner.frozen_signature()
         if frz:
             key += ((_FROZEN_TAG, frz),)
+        avg = getattr(getattr(self, "optimizer", None), "averager", None)
+        if avg is not None:
+            key += ((_AVG_TAG, avg.serial),)
         return key if role is None else key + (role,)
 
     def _wider(self, shape, tmax=0):
         """the first captured key for this clip shape whose padded target layout holds ``tmax`` boxes per clip (any role), or None"""
         want = self._key(shape, tmax)
         return next((k for k in self.graphs if k[:3] == want[:3] and k[3] >= tmax and k[4] == want[4] and _momenta(k) == _momenta(want)
-                     and _frozen(k) == _frozen(want)), None)
+                     and _frozen(k) == _frozen(want) and _averaged(k) == _averaged(want)), None)
 
     def input_buffers(self, clips_shape):
         """(clips, mask) buffers the captured step for this clip shape reads, or None before its first call: a producer that fills them in
@@ -568,9 +585,13 @@ def train_tuber_detection(cfg, model, criterion, data_loader, optimizer, epoch, 
     ``CONFIG.TRAIN.ACCUM_STEPS = k > 1`` (accum.py): the optimizer steps every k batches on the mean gradient of the group -- an
     8-rank x 2-clip step on one GPU with k = 8 -- and once more on the trailing partial group (1/m) at the end of the epoch; the
     cosine ``lr_scheduler.step_update`` is called per optimizer step with the optimizer-step index.  Meters and the non-finite check
-    stay per batch."""
+    stay per batch.
+
+    ``CONFIG.TRAIN.EMA.ENABLE`` (weight_avg.py): an EMA / SWA of the weights is kept by one more launch behind every optimizer step -- in
+    the captured step with AdamW, eagerly after any other optimizer; the averager is created on first use and cached on the model."""
     import time
     k = accum_steps(cfg)
+    averager_for(cfg, model, optimizer)
     model.train()
     criterion.train()
     dev = next(model.parameters()).device
