@@ -144,7 +144,10 @@ def get_cfg_defaults():
         ACCUM_STEPS=1,                         # micro-batches per optimizer step (accum.py; not a reference key)
         # weight averaging inside the training step (weight_avg.py; not reference keys): MODE ema | swa, updates at the optimizer steps
         # t >= START with (t - START) % PERIOD == 0, EVAL: validate with the averaged weights
-        EMA=dict(ENABLE=False, MODE="ema", DECAY=0.9999, WARMUP=False, START=0, PERIOD=1, EVAL=True)), new_allowed=True)
+        EMA=dict(ENABLE=False, MODE="ema", DECAY=0.9999, WARMUP=False, START=0, PERIOD=1, EVAL=True),
+        # per-tensor gradient / parameter / update statistics inside the training step (monitor.py; not reference keys): a row every EVERY
+        # optimizer steps, the last HISTORY rows kept on the device
+        MONITOR=dict(ENABLE=False, EVERY=50, HISTORY=8)), new_allowed=True)
     cfg.VAL = CfgNode(dict(FREQ=2, BATCH_SIZE=1), new_allowed=True)
     cfg.DATA = CfgNode(dict(
         DATASET_NAME="ava", NUM_CLASSES=80, IMG_SIZE=256, TEMP_LEN=32, FRAME_RATE=2), new_allowed=True)

@@ -297,6 +297,21 @@ DOC = {
                             "(clip[1] < 0) is not averaged; with step_ptr (the AdamW step count t) the update happens iff t >= start and (t - start) % period == 0; "
                             "a NULL pointer drops its test. *n_avg advances by one iff the update was applied (a one-thread launch behind the pass). The reference "
                             "trains without weight averaging (the epoch loop of train_tuber_ava.py:73-84); the grid is capped at 2048 workgroups of 256 threads x 4 elements.",
+    "tuber_tensor_stats": "the step monitor: one 8-float row per parameter tensor over the flat fp32 buffers -- {sum g^2, max |g|, non-finite g, g == 0, sum p^2, max |p|, "
+                          "non-finite p, sum u^2} with sums and maxima over the finite elements, counts as floats (saturated at 2^24) and u = (m / bc1) / (sqrt(v) / sqrt(bc2) + eps), "
+                          "the AdamW direction of tuber_adamw_segment before lr and without the decay term (bc = 1 - beta^t formed in fp64 from the fp32 beta, rounded once; "
+                          "m or v NULL: 0). What p.grad.norm() / p.norm() per parameter would cost ~700 launches and a host sync for; the reference logs the loss terms only "
+                          "(utils/video_action_recognition.py:182-220). Deterministic, no atomics, three launches: 256 threads per chunk of <= tuber_tensor_stats_chunk() elements "
+                          "of one tensor -> partial[n_chunks][8]; a wave per tensor adds its chunks in a fixed order; one thread does the bookkeeping. "
+                          "tensors = DEVICE TensorStatsTensor[] {int chunk0, nchunks; float beta1, beta2, eps;}, chunks = DEVICE TensorStatsChunk[] {long off; int n, tensor;} "
+                          "(off = first element, 64-element aligned window start + a multiple of the chunk). state = DEVICE int[4] {every, history, bad_count, bad_step}. "
+                          "With step_ptr (the AdamW step count t) and clip (norm_out of tuber_grad_norm_clip_coef): a good step records iff t % every == 0, into "
+                          "ring[(t / every) % history][n_tensors][8] with row_step[slot] = t, row_norm[slot] = {clip[0], clip[1]}, otherwise every workgroup returns at once; a step "
+                          "AdamW skipped (clip[1] < 0) writes bad[n_tensors][8] and bad_step = t only while bad_count == 0 (keep-first) and always advances bad_count. "
+                          "NULL clip: a good step; NULL step_ptr: no cadence, ring slot 0, no bias correction. g, p, m, v 16-byte aligned.",
+    "tuber_tensor_stats_chunk": "largest number of elements in one chunk of tuber_tensor_stats (a multiple of 64).",
+    "tuber_tensor_stats_tensor_bytes": "sizeof(TensorStatsTensor) as compiled (host-side layout check).",
+    "tuber_tensor_stats_chunk_bytes": "sizeof(TensorStatsChunk) as compiled (host-side layout check).",
     "tuber_grad_accum": "gradient accumulation over m micro-batches (DistributedDataParallel's mean over ranks reproduced on fewer GPUs: the mean of "
                         "independent per-rank backward passes, utils/model_utils.py:47-49) over a DEVICE table of nwin [begin, end) int64 windows of the flat "
                         "fp32 gradient buffer, in ONE launch: mode 0 acc = g, mode 1 acc += g, mode 2 g = (acc + g) * scale (scale_dev[0] when given). "

@@ -33,6 +33,7 @@ class FusedClipAdamW(torch.optim.Optimizer):
         self._hyper_host = None
         self._hyper_pin = None          # pinned staging of the table: per-iteration schedulers change lr every step, no blocking copy
         self.averager = None            # weight_avg.WeightAverage attached to this optimizer: one more launch behind the segments of step()
+        self.monitor = None             # monitor.StepMonitor attached to this optimizer: its launches close step(), behind the averager's
         # flat segments with uniform hyper-parameters: walk the store in layout order
         by_ptr = {}
         for gi, group in enumerate(self.param_groups):
@@ -141,6 +142,9 @@ class FusedClipAdamW(torch.optim.Optimizer):
         if self.averager is not None:
             # EMA / SWA of the parameters just written, in the same graph as the step: cadence from t_dev, nothing after a skipped step
             self.averager.step_update(self.t_dev, clip)
+        if self.monitor is not None:
+            # per-tensor statistics of the gradient just applied and the parameters / moments just written (the bad slot after a skipped step)
+            self.monitor.step_update(self, clip)
         return None
 
 

@@ -17,6 +17,7 @@ import torch
 from . import ab
 from .ddp import attach_reducer, broadcast_parameters, cut_windows
 from .optim import FusedClipAdamW, adopt, build_param_groups
+from .monitor import KEY as _MON_KEY, monitor_for
 from .weight_avg import KEY as _AVG_KEY, averager_for
 
 
@@ -102,6 +103,9 @@ def train_step(model, criterion, optimizer, samples, targets, max_norm, epoch=0,
         avg = model.__dict__.get(_AVG_KEY)
         if avg is not None and avg.drives(optimizer):
             avg.update()                   # an optimizer the averaging launch cannot ride in: averaged eagerly behind its step
+        mon = model.__dict__.get(_MON_KEY)
+        if mon is not None and mon.drives(optimizer):
+            mon.probe()                    # likewise the step monitor: the unconditional form, without moments
     if accum is not None:
         accum.end_micro()
     return losses.detach(), loss_dict
@@ -119,6 +123,9 @@ class _Snapshot:
         avg = getattr(opt, "averager", None)
         if avg is not None:                                                  # weight averaging: the warm-up passes are no updates either
             self.items += [(t, t.clone()) for t in (avg.avg, avg.n_avg)]
+        mon = getattr(opt, "monitor", None)
+        if mon is not None:                                                  # step monitor: the warm-up passes record nothing
+            self.items.append((mon.mem, mon.mem.clone()))
 
     def restore(self):
         with torch.no_grad():
@@ -171,11 +178,12 @@ class CaptureFailed(RuntimeError):
 
 _FROZEN_TAG = "frozen_bn"
 _AVG_TAG = "weight_avg"
+_MON_TAG = "step_monitor"
 
 
 def _momenta(key):
     """the BatchNorm momentum part of a GraphedTrainStep key (a tuple behind the fixed five entries; the role is a string), or ()"""
-    return next((e for e in key[5:] if isinstance(e, tuple) and e[:1] not in ((_FROZEN_TAG,), (_AVG_TAG,))), ())
+    return next((e for e in key[5:] if isinstance(e, tuple) and e[:1] not in ((_FROZEN_TAG,), (_AVG_TAG,), (_MON_TAG,))), ())
 
 
 def _frozen(key):
@@ -186,6 +194,11 @@ def _frozen(key):
 def _averaged(key):
     """the weight-averaging part of a GraphedTrainStep key: (tag, averager serial) behind the fixed five entries, or ()"""
     return next((e for e in key[5:] if isinstance(e, tuple) and e[:1] == (_AVG_TAG,)), ())
+
+
+def _monitored(key):
+    """the step-monitor part of a GraphedTrainStep key: (tag, monitor serial) behind the fixed five entries, or ()"""
+    return next((e for e in key[5:] if isinstance(e, tuple) and e[:1] == (_MON_TAG,)), ())
 
 
 class GraphedTrainStep:
@@ -390,7 +403,8 @@ class GraphedTrainStep:
         momenta that differ from the reference's 0.1 (baked into the finalisation launches: a changed momentum captures a new step; absent
         while every module has 0.1)][, the frozen BatchNorm layers (modules in eval mode: their launches differ; absent while every module
         trains, so freezing or unfreezing a layer captures a new step)][, the weight averager attached to the optimizer (its launch and
-        addresses are part of the optimizer step; absent while none is attached)][, accumulation role]"""
+        addresses are part of the optimizer step; absent while none is attached)][, the step monitor attached to the optimizer (likewise)]
+        [, accumulation role]"""
         store, runner = self.model.engine()
         key = (tuple(shape), store.trainable_signature(), self.criterion.training, tmax, store.coop_off)
         mom = runner.momentum_signature()
@@ -402,13 +416,17 @@ class GraphedTrainStep:
         avg = getattr(getattr(self, "optimizer", None), "averager", None)
         if avg is not None:
             key += ((_AVG_TAG, avg.serial),)
+        mon = getattr(getattr(self, "optimizer", None), "monitor", None)
+        if mon is not None:
+            key += ((_MON_TAG, mon.serial),)
         return key if role is None else key + (role,)
 
     def _wider(self, shape, tmax=0):
         """the first captured key for this clip shape whose padded target layout holds ``tmax`` boxes per clip (any role), or None"""
         want = self._key(shape, tmax)
         return next((k for k in self.graphs if k[:3] == want[:3] and k[3] >= tmax and k[4] == want[4] and _momenta(k) == _momenta(want)
-                     and _frozen(k) == _frozen(want) and _averaged(k) == _averaged(want)), None)
+                     and _frozen(k) == _frozen(want) and _averaged(k) == _averaged(want)
+                     and _monitored(k) == _monitored(want)), None)
 
     def input_buffers(self, clips_shape):
         """(clips, mask) buffers the captured step for this clip shape reads, or None before its first call: a producer that fills them in
@@ -588,10 +606,18 @@ def train_tuber_detection(cfg, model, criterion, data_loader, optimizer, epoch, 
     stay per batch.
 
     ``CONFIG.TRAIN.EMA.ENABLE`` (weight_avg.py): an EMA / SWA of the weights is kept by one more launch behind every optimizer step -- in
-    the captured step with AdamW, eagerly after any other optimizer; the averager is created on first use and cached on the model."""
+    the captured step with AdamW, eagerly after any other optimizer; the averager is created on first use and cached on the model.
+
+    ``CONFIG.TRAIN.MONITOR.ENABLE`` (monitor.py): per-tensor gradient / parameter / update statistics are recorded on the device every
+    ``EVERY`` optimizer steps by launches behind the optimizer step; at the iterations where the loop syncs anyway (``print_freq``) rank 0
+    writes the newest row's per-group ``monitor/{grad_norm,param_norm,update_ratio}/<group>`` and ``monitor/zero_grad_fraction`` to
+    ``writer``, a row with non-finite parameters stops training on every rank, and the FloatingPointError of a non-finite loss names the
+    tensors that were non-finite in the first skipped step."""
     import time
     k = accum_steps(cfg)
     averager_for(cfg, model, optimizer)
+    monitor = monitor_for(cfg, model, optimizer)
+    monitor_t = -1                                                # step count of the newest row already written to ``writer``
     model.train()
     criterion.train()
     dev = next(model.parameters()).device
@@ -662,7 +688,11 @@ def train_tuber_detection(cfg, model, criterion, data_loader, optimizer, epoch, 
         # the launch chain at this same iteration and training continues.
         tracker.update(loss, store.coop_sync)
         if idx % print_freq == 0:
-            _check_tracker(tracker, store, loss_dict, epoch, idx, rank, world, _dist)      # (a captured step is keyed on store.coop_off: re-captured by itself)
+            if monitor is None:
+                _check_tracker(tracker, store, loss_dict, epoch, idx, rank, world, _dist)  # (a captured step is keyed on store.coop_off: re-captured by itself)
+            else:
+                _check_tracker_monitored(monitor, tracker, store, loss_dict, epoch, idx, rank, world, _dist)
+                monitor_t = _read_monitor(monitor, writer if rank == 0 else None, idx + epoch * n_iter, monitor_t, epoch, idx)
         if rank == 0 and (idx % print_freq == 0 or idx + 1 == n_iter):
             avg = meters.averages()
             lr = optimizer.param_groups[-1]["lr"]
@@ -681,8 +711,58 @@ def train_tuber_detection(cfg, model, criterion, data_loader, optimizer, epoch, 
                 writer.add_scalar("train/loss_ce_b", avg["loss_ce_b"], it)
         end = time.time()
     if loss is not None:
-        _check_tracker(tracker, store, loss_dict, epoch, n_iter - 1, rank, world, _dist)
+        if monitor is None:
+            _check_tracker(tracker, store, loss_dict, epoch, n_iter - 1, rank, world, _dist)
+        else:
+            _check_tracker_monitored(monitor, tracker, store, loss_dict, epoch, n_iter - 1, rank, world, _dist)
+            _read_monitor(monitor, None, 0, monitor_t, epoch, n_iter - 1)
     return loss
+
+
+def _read_monitor(monitor, writer, it, seen, epoch, idx):
+    """The step monitor at an iteration that has just synchronised (one device-to-host read).  Non-finite PARAMETERS -- in the newest recorded
+    row, or in the table of the first skipped step -- stop training: a NaN weight that the loss does not see (a box head whose NaN boxes
+    merely stay unmatched) would otherwise skip or poison every step from here on.  Every rank holds the same parameters and records the
+    same tables, so all ranks stop at this iteration.  With a ``writer`` a row newer than step ``seen`` goes out as ``monitor/*`` scalars.
+    Returns the step count of the newest row seen so far."""
+    rows, bad = monitor.read()
+    new = bool(rows) and rows[0][0] > seen
+    for where, table in ((("the first skipped step, after optimizer step %d (%d skipped since)" % bad[:2], bad[2]),) if bad else ()) + \
+                        ((("optimizer step %d" % rows[0][0], rows[0][3]),) if new else ()):
+        params = monitor.nonfinite_names(table, "param")
+        if params:
+            raise FloatingPointError("step monitor: %d tensor(s) with a non-finite parameter in %s (seen at epoch %d, iteration %d), first %s; "
+                                     "tensors with a non-finite gradient there: %d, first %s"
+                                     % (len(params), where, epoch, idx, params[:20], len(monitor.nonfinite_names(table, "grad")),
+                                        monitor.nonfinite_names(table, "grad")[:20]))
+    if not new:
+        return seen
+    if writer is not None:
+        for name, s in monitor.summary(rows[0]).items():
+            if name == "all":
+                writer.add_scalar("monitor/zero_grad_fraction", s["zero_grad_fraction"], it)
+            else:
+                for k in ("grad_norm", "param_norm", "update_ratio"):
+                    writer.add_scalar("monitor/%s/%s" % (k, name), s[k], it)
+    return rows[0][0]
+
+
+def _check_tracker_monitored(monitor, *args):
+    """``_check_tracker`` whose FloatingPointError also says WHERE the first skipped step was non-finite (monitor.StepMonitor.bad)"""
+    try:
+        switched = _check_tracker(*args)
+        if switched:
+            monitor.clear_bad()              # the steps a timed-out cooperative launch poisoned are explained: re-arm the bad slot
+        return switched
+    except FloatingPointError as e:
+        bad = monitor.bad()
+        if bad is None:
+            raise
+        step, count, table = bad
+        grads, params = monitor.nonfinite_names(table, "grad"), monitor.nonfinite_names(table, "param")
+        raise FloatingPointError("%s; step monitor: the first skipped step followed optimizer step %d (bad_step), %d step(s) skipped since "
+                                 "(bad_count); %d tensor(s) with a non-finite gradient, first %s; %d tensor(s) with a non-finite parameter, "
+                                 "first %s" % (e, step, count, len(grads), grads[:20], len(params), params[:20])) from e
 
 
 class _StepTracker:
