@@ -12,6 +12,9 @@ OUT = os.path.join(HERE, "lib")
 LIB = os.path.join(OUT, "libtuber_hip.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result"]
+# per-source flags, appended (the last -ffp-contract wins).  frame_map.hip decides "IoU >= threshold" exactly as the host evaluator does: under
+# -ffp-contract=fast the backend fuses across statements whatever `#pragma clang fp contract(off)` says; under "on" the pragma holds.
+SOURCE_FLAGS = {"frame_map.hip": ["-ffp-contract=on"]}
 if os.environ.get("TUBER_AB_VARIANTS"):      # also build the measured-and-rejected GEMM tile variants (tuning runs only; not the product library)
     FLAGS.append("-DTUBER_AB_VARIANTS")
 
@@ -23,7 +26,7 @@ def sources():
 def _stamp():
     """compile flags + compiler path: part of every object's staleness key (an object built with other flags is stale
     even when its source is older)"""
-    return " ".join([HIPCC] + FLAGS)
+    return " ".join([HIPCC] + FLAGS + ["%s:%s" % (k, " ".join(v)) for k, v in sorted(SOURCE_FLAGS.items())])
 
 
 def _stale(target, deps):
@@ -45,7 +48,7 @@ def build(force=False, verbose=True):
         objs.append(obj)
         if force or _stale(obj, [src] + hdrs):
             lang = ["-x", "hip"] if src.endswith(".hip") else []
-            jobs.append([HIPCC] + FLAGS + lang + ["-c", src, "-o", obj])
+            jobs.append([HIPCC] + FLAGS + SOURCE_FLAGS.get(os.path.basename(src), []) + lang + ["-c", src, "-o", obj])
 
     def run(cmd):
         if verbose:

@@ -148,7 +148,12 @@ def get_cfg_defaults():
         # per-tensor gradient / parameter / update statistics inside the training step (monitor.py; not reference keys): a row every EVERY
         # optimizer steps, the last HISTORY rows kept on the device
         MONITOR=dict(ENABLE=False, EVERY=50, HISTORY=8)), new_allowed=True)
-    cfg.VAL = CfgNode(dict(FREQ=2, BATCH_SIZE=1), new_allowed=True)
+    cfg.VAL = CfgNode(dict(
+        FREQ=2, BATCH_SIZE=1,
+        # frame-mAP of validate_tuber_detection computed on the device (device_map.py; not reference keys): ENABLE keeps detections and
+        # ground truth in device buffers and runs the two frame_map.hip kernels instead of the host FrameMAP over the result files;
+        # FILES: the per-rank result files are written as well (reference format), False: no file, no host copy of the detections
+        DEVICE_MAP=dict(ENABLE=False, FILES=True)), new_allowed=True)
     cfg.DATA = CfgNode(dict(
         DATASET_NAME="ava", NUM_CLASSES=80, IMG_SIZE=256, TEMP_LEN=32, FRAME_RATE=2), new_allowed=True)
     cfg.MODEL = CfgNode(dict(

@@ -399,11 +399,18 @@ class PostProcess(nn.Module):
 
 class PostProcessAVA(nn.Module):
     @torch.no_grad()
-    def forward(self, outputs, target_sizes):
+    def decode(self, outputs, target_sizes):
+        """(class scores, xyxy boxes in pixels, actor probability) as tensors on the outputs' device: what ``forward`` copies to the
+        host, for consumers that stay on the device (device_map.py)"""
         lb, lg, bx = outputs["pred_logits_b"].float(), outputs["pred_logits"].float(), outputs["pred_boxes"].float()
         assert len(lg) == len(target_sizes) and target_sizes.shape[1] == 2
         pb = lb.softmax(-1)[:, :, 1:2]
         prob = lg.sigmoid() * ((pb > 0.8).float() * pb)
         h, w = target_sizes.to(bx.device).unbind(1)
         boxes = box_ops.box_cxcywh_to_xyxy(bx) * torch.stack([w, h, w, h], dim=1)[:, None, :]
+        return prob, boxes, pb
+
+    @torch.no_grad()
+    def forward(self, outputs, target_sizes):
+        prob, boxes, pb = self.decode(outputs, target_sizes)
         return prob.cpu().numpy(), boxes.cpu().numpy(), pb.cpu().numpy()

@@ -309,6 +309,19 @@ DOC = {
                           "ring[(t / every) % history][n_tensors][8] with row_step[slot] = t, row_norm[slot] = {clip[0], clip[1]}, otherwise every workgroup returns at once; a step "
                           "AdamW skipped (clip[1] < 0) writes bad[n_tensors][8] and bad_step = t only while bad_count == 0 (keep-first) and always advances bad_count. "
                           "NULL clip: a good step; NULL step_ptr: no cadence, ring slot 0, no bias correction. g, p, m, v 16-byte aligned.",
+    "tuber_frame_match": "validation frame-mAP on the device, matching step: for every frame f (rows [det_off[f], det_off[f + 1]) of det_box [N][4] fp32 xyxy / det_score "
+                         "[N][C] fp32; rows [gt_off[f], gt_off[f + 1]) of gt_box [G][4] fp64 / gt_lab [G][C] bytes; det_off, gt_off DEVICE int[F + 1]) and every class c the "
+                         "greedy matching of the PASCAL evaluator the reference drives (evaluates/evaluate_ava.py:150, evaluates/utils/per_image_evaluation.py:354-366,445-449): "
+                         "valid detections by descending score[:, c] (equal scores by ascending row: a defined rule, the reference inherits numpy's unstable sort), j = first arg-max of "
+                         "the fp64 IoU over the frame's ground-truth boxes labelled c, true positive iff iou[j] >= iou_thr and j not taken. flags [N][C] bytes: 1 true positive, 0 false "
+                         "positive, 2 not counted (x1 >= x2 or y1 >= y2; class_mask[c] == 0, NULL mask: all classes), 3 a frame beyond the bounds (nothing decided). Sizes no frame list can "
+                         "meet (N > F * max_dets, G > F * max_gt), bad sizes or pointers: negative, nothing launched. One workgroup per frame, lanes over classes, the n x g IoU table in LDS.",
+    "tuber_frame_match_max_dets": "detections per frame tuber_frame_match takes (64).",
+    "tuber_frame_match_max_gt": "ground-truth boxes per frame tuber_frame_match takes (32).",
+    "tuber_ranked_ap": "validation frame-mAP on the device, ranking step: VOC average precision per class (area under the monotone precision envelope, summed where recall changes; "
+                       "evaluates/utils/metrics.py compute_precision_recall + compute_average_precision) from flags_ranked [C][N] bytes in rank order (1 true positive, 0 false positive, "
+                       "anything else counts nowhere) and n_gt [C]: ap [C] fp64, NaN where n_gt <= 0, 0.0 where nothing is counted; n_tp [C] true positives (NULL: not wanted). One workgroup "
+                       "per class, fp64, two sweeps over 4096-entry chunks with carries in a fixed order: no atomics, the same bits every run. N == 0 is legal.",
     "tuber_tensor_stats_chunk": "largest number of elements in one chunk of tuber_tensor_stats (a multiple of 64).",
     "tuber_tensor_stats_tensor_bytes": "sizeof(TensorStatsTensor) as compiled (host-side layout check).",
     "tuber_tensor_stats_chunk_bytes": "sizeof(TensorStatsChunk) as compiled (host-side layout check).",

@@ -1,0 +1,285 @@
+"""Validation frame-mAP on the device (csrc/frame_map.hip): an opt-in replacement for the result files + ``evaluation.FrameMAP`` at the end
+of ``validate_tuber_detection`` (``CONFIG.VAL.DEVICE_MAP``).
+
+``DeviceFrameMAP`` keeps the decoded detections of the loop in growing device buffers (the host knows every count, so nothing is read back
+while the loop runs), the few ground-truth boxes on the host, and computes at the end what ``FrameMAP`` computes from the files: per
+(frame, class) the greedy score-ordered matching (``tuber_frame_match``), per class the ranking (``torch.sort``, plumbing) and the VOC average
+precision (``tuber_ranked_ap``), then the mean by the host code both evaluators share (``evaluation.mean_ap``).
+
+Equal scores: the reference orders by numpy's default sort, whose permutation of equal keys is an artefact of introsort.  Here the rule is
+DEFINED: equal scores keep store order -- frame id ascending (ids in order of first appearance among the detections), then row order --
+inside a frame and in the per-class ranking.  That is ``FrameMAP(stable=True)``, always; it is the unmodified ``FrameMAP()`` whenever no
+class has two equal scores.  ``evaluate()`` leaves the number of rows per class that share their score with another row in ``ties``.
+
+A store on the CPU, and a store with a frame beyond the kernel's bounds (``tuber_frame_match_max_dets`` detections,
+``tuber_frame_match_max_gt`` ground-truth boxes), is evaluated by ``to_host_evaluator().evaluate()``: no frame is ever dropped or cut.
+"""
+import logging
+
+import numpy as np
+import torch
+
+from . import lib
+from .evaluation import FrameMAP, mean_ap
+
+log = logging.getLogger(__name__)
+
+
+class DeviceFrameMAP:
+    """Arguments as ``evaluation.FrameMAP``; ``device``: where the detection buffers live (a CPU store runs the host evaluator)."""
+
+    def __init__(self, class_num, class_whitelist=None, exclude_keys=(), iou_threshold=0.5, gt_min_score=1e-2, device="cuda"):
+        self.class_num, self.iou = int(class_num), float(iou_threshold)
+        self.whitelist = set(class_whitelist) if class_whitelist is not None else None
+        self.exclude = set(exclude_keys)
+        self.gt_min_score = gt_min_score
+        self.device = torch.device(device)
+        self.frame_ids, self.frame_keys = {}, []          # frames with detections: key -> id, in order of first appearance
+        self.det_count = []                               # rows per frame id
+        self.row_fid = []                                 # frame id per stored row (host)
+        self.n = 0                                        # rows stored (the cursor: a host integer)
+        self._box = torch.empty((0, 4), dtype=torch.float32, device=self.device)
+        self._score = torch.empty((0, self.class_num), dtype=torch.float32, device=self.device)
+        self.gt_keys, self._gt_box, self._gt_lab = [], [], []
+        self.ties = None                                  # after evaluate(): {class_id: rows that share their score with another row}
+        self.path = None                                  # after evaluate(): "device" or "host"
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # the store
+    # ------------------------------------------------------------------------------------------------------------------
+    def _wanted(self, cls):
+        return self.whitelist is None or cls in self.whitelist
+
+    def _settings(self):
+        return dict(class_num=self.class_num, class_whitelist=self.whitelist, exclude_keys=self.exclude, iou_threshold=self.iou,
+                    gt_min_score=self.gt_min_score)
+
+    def _reserve(self, extra):
+        need = self.n + extra
+        if need <= self._box.shape[0]:
+            return
+        cap = max(need, 2 * self._box.shape[0], 1024)
+        box = torch.empty((cap, 4), dtype=torch.float32, device=self.device)
+        score = torch.empty((cap, self.class_num), dtype=torch.float32, device=self.device)
+        box[:self.n] = self._box[:self.n]
+        score[:self.n] = self._score[:self.n]
+        self._box, self._score = box, score
+
+    @property
+    def boxes(self):
+        return self._box[:self.n]
+
+    @property
+    def scores(self):
+        return self._score[:self.n]
+
+    def add_detections(self, keys, boxes, scores):
+        """``keys``: one frame key per row; ``boxes`` [n, 4] fp32 xyxy, ``scores`` [n, C] fp32 on the store's device.  Rows of an excluded
+        key are dropped (``FrameMAP.load_detections`` skips their lines).  No device read."""
+        keys = list(keys)
+        assert boxes.shape == (len(keys), 4) and scores.shape == (len(keys), self.class_num), (boxes.shape, scores.shape, len(keys))
+        assert boxes.dtype == torch.float32 and scores.dtype == torch.float32
+        keep = [i for i, k in enumerate(keys) if k not in self.exclude]
+        if len(keep) != len(keys):
+            if not keep:
+                return
+            sel = torch.tensor(keep, dtype=torch.long).to(self.device)
+            boxes, scores, keys = boxes.index_select(0, sel), scores.index_select(0, sel), [keys[i] for i in keep]
+        for k in keys:
+            fid = self.frame_ids.get(k)
+            if fid is None:
+                fid = self.frame_ids[k] = len(self.frame_keys)
+                self.frame_keys.append(k)
+                self.det_count.append(0)
+            self.det_count[fid] += 1
+            self.row_fid.append(fid)
+        self._reserve(len(keys))
+        self._box[self.n:self.n + len(keys)] = boxes
+        self._score[self.n:self.n + len(keys)] = scores
+        self.n += len(keys)
+
+    def add_ground_truth(self, keys, boxes, labels):
+        """``keys``: one frame key per box; ``boxes`` [m, 4] xyxy (kept fp64), ``labels`` [m, C] (a class is set where its value exceeds
+        ``gt_min_score``).  Host data: take them from the loader's CPU tensors."""
+        keys = list(keys)
+        boxes = np.asarray(boxes.detach().cpu().numpy() if torch.is_tensor(boxes) else boxes, dtype=np.float64).reshape(-1, 4)
+        labels = np.asarray(labels.detach().cpu().numpy() if torch.is_tensor(labels) else labels, dtype=np.float64).reshape(-1, self.class_num)
+        assert len(boxes) == len(keys) == len(labels), (len(boxes), len(keys), len(labels))
+        for i, k in enumerate(keys):
+            if k in self.exclude:
+                continue
+            self.gt_keys.append(k)
+            self._gt_box.append(boxes[i])
+            self._gt_lab.append(labels[i])
+
+    def gt_arrays(self):
+        """(boxes [m, 4] fp64, labels [m, C] fp64) in store order"""
+        if not self.gt_keys:
+            return np.zeros((0, 4)), np.zeros((0, self.class_num))
+        return np.stack(self._gt_box), np.stack(self._gt_lab)
+
+    @classmethod
+    def merge(cls, stores):
+        """One store holding the rows of ``stores`` in the order given (rank order: the order in which rank 0 loads the result files);
+        a key seen in several of them maps to one frame id."""
+        first = stores[0]
+        out = cls(device=first.device, **first._settings())
+        for s in stores:
+            out.add_detections([s.frame_keys[f] for f in s.row_fid], s.boxes.to(out.device), s.scores.to(out.device))
+            gb, gl = s.gt_arrays()
+            out.add_ground_truth(s.gt_keys, gb, gl)
+        return out
+
+    def all_gather_merge(self):
+        """Under torch.distributed: every rank's store merged in rank order (a collective; every rank gets the merged store).  The tensors
+        are padded to the largest row count and gathered, the keys and the ground truth travel as objects."""
+        import torch.distributed as dist
+        world = dist.get_world_size()
+        gb, gl = self.gt_arrays()
+        meta = [None] * world
+        dist.all_gather_object(meta, dict(n=self.n, frame_keys=self.frame_keys, row_fid=self.row_fid, gt_keys=self.gt_keys, gt_box=gb, gt_lab=gl))
+        nmax = max(m["n"] for m in meta)
+        box = torch.zeros((nmax, 4), dtype=torch.float32, device=self.device)
+        score = torch.zeros((nmax, self.class_num), dtype=torch.float32, device=self.device)
+        box[:self.n], score[:self.n] = self.boxes, self.scores
+        boxes, scores = [torch.empty_like(box) for _ in range(world)], [torch.empty_like(score) for _ in range(world)]
+        dist.all_gather(boxes, box)
+        dist.all_gather(scores, score)
+        parts = []
+        for m, b, s in zip(meta, boxes, scores):
+            part = DeviceFrameMAP(device=self.device, **self._settings())
+            part.add_detections([m["frame_keys"][f] for f in m["row_fid"]], b[:m["n"]], s[:m["n"]])
+            part.add_ground_truth(m["gt_keys"], m["gt_box"], m["gt_lab"])
+            parts.append(part)
+        return DeviceFrameMAP.merge(parts)
+
+    # ------------------------------------------------------------------------------------------------------------------
+    # evaluation
+    # ------------------------------------------------------------------------------------------------------------------
+    def to_host_evaluator(self, stable=True):
+        """A ``FrameMAP`` whose gt / det dictionaries hold the store, in store order: what ``load_gt`` / ``load_detections`` build from
+        result files with the same lines."""
+        ev = FrameMAP(self.class_num, class_whitelist=self.whitelist, exclude_keys=self.exclude, iou_threshold=self.iou,
+                      gt_min_score=self.gt_min_score, stable=stable)
+        gb, gl = self.gt_arrays()
+        for k, box, lab in zip(self.gt_keys, gb, gl):
+            for x in np.nonzero(lab > self.gt_min_score)[0]:
+                if self._wanted(int(x) + 1):
+                    ev.gt.setdefault(k, []).append((int(x) + 1, np.asarray(box, dtype=float)))
+        boxes = self.boxes.cpu().numpy().astype(np.float64)
+        scores = self.scores.cpu().numpy().astype(np.float64)
+        wanted = [x for x in range(self.class_num) if self._wanted(x + 1)]
+        for r, fid in enumerate(self.row_fid):
+            items = ev.det.setdefault(self.frame_keys[fid], [])
+            box, row = boxes[r], scores[r].tolist()
+            items.extend((x + 1, box, row[x]) for x in wanted)
+        return ev
+
+    @staticmethod
+    def _nan_last(s):
+        """torch.sort ranks NaN first, np.argsort(-score) last: a NaN score (a broken model) ranks below every number"""
+        return s.masked_fill_(s != s, float("-inf"))
+
+    @staticmethod
+    def _tie_counts(ranked):
+        """rows per class that share their score with a neighbour of the descending ranking [C, N]"""
+        if ranked.shape[1] < 2:
+            return torch.zeros(ranked.shape[0], dtype=torch.int64, device=ranked.device)
+        eq = ranked[:, 1:] == ranked[:, :-1]
+        member = torch.zeros(ranked.shape, dtype=torch.bool, device=ranked.device)
+        member[:, 1:] |= eq
+        member[:, :-1] |= eq
+        return member.sum(dim=1)
+
+    def _finish(self, ap, ties):
+        per_class = {c + 1: float(ap[c]) for c in range(self.class_num) if self._wanted(c + 1) and not np.isnan(ap[c])}
+        self.ties = {c + 1: int(ties[c]) for c in range(self.class_num) if self._wanted(c + 1)}
+        ncat = max(self.whitelist) if self.whitelist else self.class_num
+        return mean_ap(per_class, ncat), per_class
+
+    def _evaluate_host(self):
+        self.path = "host"
+        ev = self.to_host_evaluator(stable=True)
+        mAP, per_class = ev.evaluate()
+        s = self.scores.cpu().t().contiguous()
+        ranked = torch.sort(self._nan_last(s), dim=1, descending=True, stable=True).values if s.numel() else s
+        ties = self._tie_counts(ranked).numpy()
+        self.ties = {c + 1: int(ties[c]) for c in range(self.class_num) if self._wanted(c + 1)}
+        return mAP, per_class
+
+    def device_arrays(self):
+        """The operands of ``tuber_frame_match`` on the store's device: rows stable-sorted by frame id, the two CSR offset arrays over all
+        frames (frames that only have ground truth come after those with detections), label bytes, class mask, boxes per class."""
+        C, dev = self.class_num, self.device
+        ids = dict(self.frame_ids)
+        gfid = np.asarray([ids.setdefault(k, len(ids)) for k in self.gt_keys], dtype=np.int64)
+        F = len(ids)
+        fid = torch.tensor(self.row_fid, dtype=torch.int32).to(dev)
+        order = torch.sort(fid, stable=True).indices if self.n else torch.zeros(0, dtype=torch.long, device=dev)
+        box, score = self.boxes.index_select(0, order).contiguous(), self.scores.index_select(0, order).contiguous()
+        det_n = np.zeros(F, dtype=np.int64)
+        det_n[:len(self.det_count)] = self.det_count
+        gt_n = np.bincount(gfid, minlength=F) if F else np.zeros(0, dtype=np.int64)
+        det_off = np.concatenate([[0], np.cumsum(det_n)]).astype(np.int32)
+        gt_off = np.concatenate([[0], np.cumsum(gt_n)]).astype(np.int32)
+        gb, gl = self.gt_arrays()
+        gorder = np.argsort(gfid, kind="stable")
+        mask = np.asarray([1 if self._wanted(c + 1) else 0 for c in range(C)], dtype=np.uint8)
+        lab = ((gl[gorder] > self.gt_min_score) & (mask[None, :] != 0)).astype(np.uint8)
+        n_gt = lab.sum(axis=0).astype(np.int32)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        return dict(F=F, N=self.n, G=len(gfid), C=C, order=order, det_box=box, det_score=score, det_off=up(det_off), gt_box=up(gb[gorder]),
+                    gt_lab=up(lab), gt_off=up(gt_off), class_mask=up(mask), n_gt=up(n_gt), max_dets=int(det_n.max()) if F else 0,
+                    max_gt=int(gt_n.max()) if F else 0)
+
+    def match_flags(self, a=None):
+        """``tuber_frame_match`` over the store: flags [N, C] uint8 for the rows in frame order (``device_arrays()['order']``)"""
+        a = a or self.device_arrays()
+        flags = torch.empty((a["N"], a["C"]), dtype=torch.uint8, device=self.device)
+        lib.call("tuber_frame_match", a["det_box"], a["det_score"], a["det_off"], a["gt_box"], a["gt_lab"], a["gt_off"], a["class_mask"],
+                 a["F"], a["N"], a["G"], a["C"], self.iou, flags)
+        return flags
+
+    def evaluate(self, timings=None):
+        """-> (mAP, {class_id: AP}); ``ties`` and ``path`` are set.  Bitwise reproducible run to run.  ``timings``: a dict that receives
+        the device time of every stage in ms (HIP events) and the host time of the read-back (scripts/device_map_bench.py)."""
+        if self.device.type != "cuda":
+            return self._evaluate_host()
+        marks = []
+
+        def mark(name):
+            if timings is not None:
+                e = torch.cuda.Event(enable_timing=True)
+                e.record()
+                marks.append((name, e))
+        mark("start")
+        a = self.device_arrays()
+        if a["max_dets"] > lib.query("tuber_frame_match_max_dets") or a["max_gt"] > lib.query("tuber_frame_match_max_gt"):
+            log.warning("DeviceFrameMAP: a frame has %d detections / %d ground-truth boxes, beyond the kernel's %d / %d: evaluating on the host",
+                        a["max_dets"], a["max_gt"], lib.query("tuber_frame_match_max_dets"), lib.query("tuber_frame_match_max_gt"))
+            return self._evaluate_host()
+        self.path = "device"
+        C, N = a["C"], a["N"]
+        mark("frame_sort_and_uploads")
+        flags = self.match_flags(a)
+        mark("tuber_frame_match")
+        # every class's ranking: scores descending over all rows, equal scores in store order (NaN last, as np.argsort(-score) has it)
+        ranked, idx = torch.sort(self._nan_last(a["det_score"].t().contiguous()), dim=1, descending=True, stable=True)
+        flags_ranked = flags.t().contiguous().gather(1, idx) if N else torch.empty((C, 0), dtype=torch.uint8, device=self.device)
+        mark("rank_sort_and_gather")
+        ap = torch.empty(C, dtype=torch.float64, device=self.device)
+        n_tp = torch.empty(C, dtype=torch.int32, device=self.device)
+        lib.call("tuber_ranked_ap", flags_ranked, a["n_gt"], C, N, ap, n_tp)
+        mark("tuber_ranked_ap")
+        ties = self._tie_counts(ranked)
+        mark("tie_count")
+        if timings is not None:
+            import time
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        ap, ties = ap.cpu().numpy(), ties.cpu().numpy()
+        if timings is not None:
+            timings["read_back_ms"] = (time.perf_counter() - t0) * 1e3
+            for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
+                timings[name + "_ms"] = e0.elapsed_time(e1)
+        return self._finish(ap, ties)

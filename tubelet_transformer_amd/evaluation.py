@@ -7,7 +7,8 @@ so the reference's own evaluator can be pointed at them unchanged, and a compact
 (``evaluates/evaluate_ava.py:17-171`` driving the vendored PASCAL evaluator ``evaluates/utils/object_detection_evaluation.py:309``:
 per-class VOC average precision at IoU >= 0.5, greedy score-ordered matching, one detection per ground-truth box, classes without
 ground truth excluded from the mean).  ``tests/golden/frame_map_case.json`` pins it against the reference evaluator run in the
-build container (``oracle/gen_eval_golden.py``).  Host-side code: runs once per epoch on rank 0 (not throughput relevant).
+build container (``oracle/gen_eval_golden.py``).  Host-side code: runs once per epoch on rank 0 -- nothing on the golden case, minutes at
+AVA's size, which is what ``CONFIG.VAL.DEVICE_MAP`` (device_map.py: the same metric on the device, no files needed) is for.
 """
 import glob
 import math
@@ -68,11 +69,25 @@ def _average_precision(precision, recall):
     return float(np.sum((r[idx] - r[idx - 1]) * p[idx]))
 
 
-class FrameMAP:
-    """Frame-level mean average precision from the result files (STDetectionEvaluater semantics, evaluate_ava.py:17-171)."""
+def mean_ap(per_class, ncat):
+    """the reference's mean: np.nanmean over an array indexed by class id up to the largest category id, NaN where a class has no
+    ground truth (object_detection_evaluation.py: average_precision_per_class) -- same summation order, same bits.  Shared by
+    FrameMAP and device_map.DeviceFrameMAP."""
+    arr = np.full(max(ncat, max(per_class) if per_class else 0), np.nan)
+    for cls, ap in per_class.items():
+        arr[cls - 1] = ap
+    return float(np.nanmean(arr)) if per_class else float("nan")
 
-    def __init__(self, class_num, class_whitelist=None, exclude_keys=(), iou_threshold=0.5, gt_min_score=1e-2):
+
+class FrameMAP:
+    """Frame-level mean average precision from the result files (STDetectionEvaluater semantics, evaluate_ava.py:17-171).
+    ``stable=False`` orders equal scores as the reference does (numpy's default sort: an artefact of introsort); ``stable=True`` keeps
+    them in file order, inside a frame and in the per-class ranking -- the rule device_map.DeviceFrameMAP computes by.  Without equal
+    scores the two are the same evaluator."""
+
+    def __init__(self, class_num, class_whitelist=None, exclude_keys=(), iou_threshold=0.5, gt_min_score=1e-2, stable=False):
         self.class_num, self.iou = class_num, iou_threshold
+        self.stable = stable
         self.whitelist = set(class_whitelist) if class_whitelist is not None else None
         self.exclude = set(exclude_keys)
         self.gt_min_score = gt_min_score
@@ -104,14 +119,17 @@ class FrameMAP:
                     if self._wanted(x + 1):
                         self.det.setdefault(key, []).append((x + 1, box, float(s)))
 
-    def evaluate(self):
-        """-> (mAP, {class_id: AP}).  Detections of images without ground truth count as false positives (the PASCAL evaluator
-        scores them against an empty ground-truth list, object_detection_evaluation.py:601-620)."""
+    def num_categories_(self):
+        return getattr(self, "num_categories", None) or (max(self.whitelist) if self.whitelist else self.class_num)
+
+    def match(self):
+        """-> (n_gt, scores, tps): ground-truth boxes per class, and per class the lists (one entry per image, in image order) of the
+        valid detections' scores in matching order and of their true-positive flags.  Detections of images without ground truth count as
+        false positives (the PASCAL evaluator scores them against an empty ground-truth list, object_detection_evaluation.py:601-620)."""
         # The data flow (and therefore the resolution of score ties) follows the reference exactly: per image all (box, class)
         # entries in file order are ordered by np.argsort(-score) (evaluate_ava.py:150), matched greedily per class in that
         # order (per_image_evaluation.py:354-366), concatenated per class in image order, and ranked by np.argsort(score)[::-1]
         # (metrics.py:56-57).  numpy's default sort is deterministic, so equal inputs give the reference's permutation.
-        per_class = {}
         n_gt = {}
         for key, items in self.gt.items():
             for cls, _ in items:
@@ -122,7 +140,7 @@ class FrameMAP:
             cls_a = np.asarray([d[0] for d in dets], dtype=int)
             box_a = np.vstack([d[1] for d in dets])
             sc_a = np.asarray([d[2] for d in dets], dtype=float)
-            index = np.argsort(-sc_a)
+            index = np.argsort(-sc_a, kind="stable") if self.stable else np.argsort(-sc_a)
             cls_a, box_a, sc_a = cls_a[index], box_a[index], sc_a[index]
             valid = (box_a[:, 0] < box_a[:, 2]) & (box_a[:, 1] < box_a[:, 3])      # per_image_evaluation.py:445-449
             cls_a, box_a, sc_a = cls_a[valid], box_a[valid], sc_a[valid]
@@ -142,6 +160,12 @@ class FrameMAP:
                             tp[i] = True
                 scores.setdefault(cls, []).append(sc_a[sel])
                 tps.setdefault(cls, []).append(tp)
+        return n_gt, scores, tps
+
+    def evaluate(self):
+        """-> (mAP, {class_id: AP})"""
+        n_gt, scores, tps = self.match()
+        per_class = {}
         for cls in range(1, self.class_num + 1):
             if not self._wanted(cls) or n_gt.get(cls, 0) == 0:
                 continue
@@ -149,18 +173,11 @@ class FrameMAP:
                 per_class[cls] = 0.0
                 continue
             s = np.concatenate(scores[cls]); t = np.concatenate(tps[cls])
-            order = np.argsort(s)[::-1]
+            order = np.argsort(-s, kind="stable") if self.stable else np.argsort(s)[::-1]
             t = t[order]
             ctp = np.cumsum(t).astype(float); cfp = np.cumsum(~t).astype(float)
             per_class[cls] = _average_precision(ctp / np.maximum(ctp + cfp, np.finfo(np.float64).eps), ctp / n_gt[cls])
-        # the reference's mean: np.nanmean over an array indexed by class id up to the largest category id, NaN where a class has
-        # no ground truth (object_detection_evaluation.py: average_precision_per_class) -- same summation order, same bits
-        ncat = getattr(self, "num_categories", None) or (max(self.whitelist) if self.whitelist else self.class_num)
-        arr = np.full(max(ncat, max(per_class) if per_class else 0), np.nan)
-        for cls, ap in per_class.items():
-            arr[cls - 1] = ap
-        mAP = float(np.nanmean(arr)) if per_class else float("nan")
-        return mAP, per_class
+        return mean_ap(per_class, self.num_categories_()), per_class
 
 
 def read_labelmap(path):
@@ -205,6 +222,17 @@ def _with_averaged_weights(fn):
     return run
 
 
+def _whitelist_and_excluded(C, excluded_timestamps):
+    """(class whitelist from DATA.LABEL_PATH for the 80-class label space or None, excluded frame keys from the csv) of the AVA metric"""
+    white = None
+    if getattr(C.DATA, "LABEL_PATH", None) and os.path.isfile(C.DATA.LABEL_PATH):
+        _, white = read_labelmap(C.DATA.LABEL_PATH)
+    excl = []
+    if excluded_timestamps and os.path.isfile(excluded_timestamps):
+        excl = [l.strip().replace(",", "_") for l in open(excluded_timestamps) if l.strip()]
+    return (white if C.DATA.NUM_CLASSES == 80 else None), excl
+
+
 @_with_averaged_weights
 @torch.no_grad()
 def validate_tuber_detection(cfg, model, criterion, postprocessors, data_loader, epoch, writer=None, excluded_timestamps=None,
@@ -225,19 +253,43 @@ def validate_tuber_detection(cfg, model, criterion, postprocessors, data_loader,
         for p in glob.glob(os.path.join(res, "*.txt")):
             os.remove(p)
     det_scores, det_boxes, det_binary, det_ids, gt_labels, gt_boxes, gt_ids = [], [], [], [], [], [], []
+    # CONFIG.VAL.DEVICE_MAP (device_map.py): the detections stay on the device and the metric is computed there; the files are optional then
+    dm = getattr(C.VAL, "DEVICE_MAP", None)
+    store, files = None, True
+    if dm is not None and dm.ENABLE:
+        from .device_map import DeviceFrameMAP
+        white, excl = _whitelist_and_excluded(C, excluded_timestamps)
+        store = DeviceFrameMAP(C.DATA.NUM_CLASSES, class_whitelist=white, exclude_keys=excl, device=dev)
+        files = bool(dm.FILES)
     meters = {k: [0.0, 0] for k in ("loss", "loss_bbox", "loss_giou", "loss_ce", "loss_ce_b", "class_error")}
     end = time.time()
     for idx, data in enumerate(data_loader):
         samples, targets = data[0], data[1]
         samples = samples.to(dev)            # reference :280 / :513; runs the HIP clip pre-pass when the loader yields ClipBatch
         batch_id = [t["image_id"] for t in targets]
+        host_targets = targets               # the loader's own tensors: the device evaluator takes its ground truth from them, without a sync
         targets = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in t.items() if k != "image_id"} for t in targets]
         outputs = _forward_checked(model, samples)
         loss_dict = criterion(outputs, targets)
         sizes = torch.stack([t["size"] for t in targets], dim=0)
-        scores, boxes, output_b = postprocessors["bbox"](outputs, sizes)
         Q = C.MODEL.QUERY_NUM
-        for b in range(scores.shape[0]):
+        if store is None:
+            scores, boxes, output_b = postprocessors["bbox"](outputs, sizes)
+        else:
+            d_scores, d_boxes, d_binary = postprocessors["bbox"].decode(outputs, sizes)
+            if files:                        # what PostProcessAVA.forward returns, bit for bit
+                scores, boxes, output_b = d_scores.cpu().numpy(), d_boxes.cpu().numpy(), d_binary.cpu().numpy()
+            for b in range(len(targets)):
+                frame_id, key_pos = batch_id[b][0], batch_id[b][1]
+                sl = slice(None) if C.MODEL.SINGLE_FRAME else slice(key_pos // C.MODEL.DS_RATE * Q, (key_pos // C.MODEL.DS_RATE + 1) * Q)
+                store.add_detections([frame_id] * Q, d_boxes[b, sl], d_scores[b, sl])
+                raw = host_targets[b]["raw_boxes"]
+                sel = (raw[:, 1] == key_pos).nonzero().reshape(-1)
+                rb = raw[sel].reshape(len(sel), -1)
+                first = float(host_targets[0]["raw_boxes"][0, 0])
+                store.add_ground_truth([batch_id[int(float(rb[x, 0]) - first)][0] for x in range(len(rb))], rb[:, 2:6].double(),
+                                       host_targets[b]["labels"][sel].reshape(len(sel), -1))
+        for b in range(len(targets) if files else 0):
             frame_id, key_pos = batch_id[b][0], batch_id[b][1]
             if not C.MODEL.SINGLE_FRAME:
                 k = key_pos // C.MODEL.DS_RATE
@@ -268,25 +320,26 @@ def validate_tuber_detection(cfg, model, criterion, postprocessors, data_loader,
         end = time.time()
     cat = lambda xs, w: np.concatenate(xs, axis=0) if xs else np.zeros((0, w))
     nc = C.DATA.NUM_CLASSES
-    write_result_files(C.LOG.BASE_PATH, C.LOG.RES_DIR, rank, det_ids, cat(det_boxes, 4), cat(det_scores, nc), cat(det_binary, 1),
-                       gt_ids, cat(gt_boxes, 6), cat(gt_labels, nc))
+    if files:
+        write_result_files(C.LOG.BASE_PATH, C.LOG.RES_DIR, rank, det_ids, cat(det_boxes, 4), cat(det_scores, nc), cat(det_binary, 1),
+                           gt_ids, cat(gt_boxes, 6), cat(gt_labels, nc))
     if writer is not None and rank == 0:
         for k, (s, c) in meters.items():
             writer.add_scalar("val/" + k, s / max(c, 1), epoch)
     if dist.is_available() and dist.is_initialized():
         dist.barrier()
+    if store is not None and ddp:
+        store = store.all_gather_merge()     # every rank's rows in rank order: the order in which rank 0 loads the files
     mAP = 0.0
     if rank == 0:
-        white = None
-        if getattr(C.DATA, "LABEL_PATH", None) and os.path.isfile(C.DATA.LABEL_PATH):
-            _, white = read_labelmap(C.DATA.LABEL_PATH)
-        excl = []
-        if excluded_timestamps and os.path.isfile(excluded_timestamps):
-            excl = [l.strip().replace(",", "_") for l in open(excluded_timestamps) if l.strip()]
-        ev = FrameMAP(nc, class_whitelist=white if nc == 80 else None, exclude_keys=excl)
-        ev.load_gt([os.path.join(res, "GT_%d.txt" % r) for r in range(world)])
-        ev.load_detections([os.path.join(res, "%d.txt" % r) for r in range(world)])
-        mAP, per_class = ev.evaluate()
+        if store is not None:
+            mAP, per_class = store.evaluate()
+        else:
+            white, excl = _whitelist_and_excluded(C, excluded_timestamps)
+            ev = FrameMAP(nc, class_whitelist=white, exclude_keys=excl)
+            ev.load_gt([os.path.join(res, "GT_%d.txt" % r) for r in range(world)])
+            ev.load_detections([os.path.join(res, "%d.txt" % r) for r in range(world)])
+            mAP, per_class = ev.evaluate()
         if verbose:
             print("mAP: %.5f" % mAP)
         if writer is not None:

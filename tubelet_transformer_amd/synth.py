@@ -175,3 +175,41 @@ def zero_dropout(model):
         if isinstance(getattr(m, "dropout", None), float):
             m.dropout = 0.0
     return model
+
+
+def synthetic_frame_map_case(frames, dets=15, classes=80, seed=7, max_gt=5, gated=0.0, hw=(64, 96)):
+    """A synthetic validation result for the frame-mAP evaluators (evaluation.FrameMAP, device_map.DeviceFrameMAP): ``frames`` frames with
+    ``dets`` detection rows each and 0..``max_gt`` ground-truth boxes with 1..3 labels each.  The scores are the distinct values
+    ``perm(n * C) / (n * C)`` (n * C < 2^24, so they stay distinct in fp32): no class has two equal scores.  ``gated``: fraction of rows
+    whose scores are all 0, like the actor gate of PostProcessAVA -- the only ties then.  About half of the detections sit near a
+    ground-truth box (IoU on both sides of 0.5), the rest anywhere.  numpy arrays: ``det_keys`` [n], ``det_boxes`` [n, 4] fp32 xyxy,
+    ``det_scores`` [n, C] fp32, ``gt_keys`` [m], ``gt_boxes`` [m, 4] fp64, ``gt_labels`` [m, C] fp64 (0 / 1)."""
+    import numpy as np
+    n = frames * dets
+    assert n * classes < 2 ** 24
+    rng = np.random.default_rng(seed)
+    H, W = hw
+    scores = (rng.permutation(n * classes).astype(np.float64) / (n * classes)).astype(np.float32).reshape(n, classes)
+    if gated > 0:
+        scores[rng.random(n) < gated] = 0.0
+    keys = ["vid%03d_%04d" % (f // 100, 900 + f % 100) for f in range(frames)]
+    det_keys, det_boxes, gt_keys, gt_boxes, gt_labels = [], [], [], [], []
+    for f in range(frames):
+        g = int(rng.integers(0, max_gt + 1))
+        xy = rng.uniform(0, 0.6, (g, 2)) * [W, H]
+        wh = rng.uniform(0.15, 0.4, (g, 2)) * [W, H]
+        gb = np.concatenate([xy, xy + wh], axis=1).astype(np.float32).astype(np.float64)
+        for j in range(g):
+            lab = np.zeros(classes)
+            lab[rng.choice(classes, size=int(rng.integers(1, min(3, classes) + 1)), replace=False)] = 1.0
+            gt_keys.append(keys[f]); gt_boxes.append(gb[j]); gt_labels.append(lab)
+        for i in range(dets):
+            if g and rng.random() < 0.5:
+                j = int(rng.integers(0, g))
+                box = gb[j] + rng.normal(0, 0.12, 4) * np.tile(gb[j, 2:] - gb[j, :2], 2)
+            else:
+                p = rng.uniform(0, 0.7, 2) * [W, H]
+                box = np.concatenate([p, p + rng.uniform(0.1, 0.3, 2) * [W, H]])
+            det_keys.append(keys[f]); det_boxes.append(box)
+    return dict(det_keys=det_keys, det_boxes=np.asarray(det_boxes, dtype=np.float32).reshape(n, 4), det_scores=scores, gt_keys=gt_keys,
+                gt_boxes=np.asarray(gt_boxes, dtype=np.float64).reshape(-1, 4), gt_labels=np.asarray(gt_labels, dtype=np.float64).reshape(-1, classes))
