@@ -7,7 +7,12 @@ the rows gated to score 0 like the real decode, tie-free otherwise (synth.synthe
   ``--repeats`` calls, and its parts from HIP events: frame sort + uploads, tuber_frame_match, ranking sort + gather, tuber_ranked_ap, tie
   count, read-back.
 
+``--ucf`` measures the same quantities for the JHMDB / UCF101-24 loop (validate_tuber_ucf_detection: FrameMAPUCF against
+DeviceFrameMAPUCF) on a store of 8192 frames x 10 detections x 24 classes (synth.synthetic_frame_map_ucf_case) and writes
+profiles/device_map_ucf_bench.json.
+
     python scripts/device_map_bench.py [--frames 4096] [--repeats 5] [--host-limit 900] [--out profiles/device_map_bench.json]
+    python scripts/device_map_bench.py --ucf [--frames 8192] [--repeats 5] [--out profiles/device_map_ucf_bench.json]
     python scripts/device_map_bench.py --host-only DIR      (the child: prints one JSON line)
 """
 import argparse
@@ -25,10 +30,14 @@ sys.path.insert(0, ROOT)
 import numpy as np  # noqa: E402
 
 from tubelet_transformer_amd import synth  # noqa: E402
-from tubelet_transformer_amd.evaluation import FrameMAP, write_result_files  # noqa: E402
+from tubelet_transformer_amd.evaluation import FrameMAP, FrameMAPUCF, write_result_files  # noqa: E402
 
 
 def case_of(args):
+    if args.ucf:
+        case = synth.synthetic_frame_map_ucf_case(args.frames, dets=args.dets, classes=args.classes, seed=args.seed)
+        case["det_scores"] = case["det_probs"]
+        return case
     return synth.synthetic_frame_map_case(args.frames, dets=args.dets, classes=args.classes, seed=args.seed, gated=0.2)
 
 
@@ -36,13 +45,13 @@ def host_path(args, d):
     case = case_of(args)
     n, m = len(case["det_keys"]), len(case["gt_keys"])
     t0 = time.perf_counter()
-    dp, gp = write_result_files(d, "res", 0, case["det_keys"], case["det_boxes"], case["det_scores"], np.zeros((n, 1), np.float32),
+    dp, gp = write_result_files(d, "res", 0, case["det_keys"], case["det_boxes"], case["det_scores"], np.zeros((n, 0 if args.ucf else 1), np.float32),
                                 case["gt_keys"], np.concatenate([np.zeros((m, 2)), case["gt_boxes"]], axis=1), case["gt_labels"])
     t1 = time.perf_counter()
     out = {}
     for stable in (False, True):
         ta = time.perf_counter()
-        ev = FrameMAP(args.classes, stable=stable)
+        ev = FrameMAPUCF(args.classes, stable=stable) if args.ucf else FrameMAP(args.classes, stable=stable)
         ev.load_gt([gp])
         ev.load_detections([dp])
         tb = time.perf_counter()
@@ -56,25 +65,30 @@ def host_path(args, d):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--frames", type=int, default=4096)
-    ap.add_argument("--dets", type=int, default=15)
-    ap.add_argument("--classes", type=int, default=80)
+    ap.add_argument("--ucf", action="store_true", help="the JHMDB / UCF101-24 evaluator on 8192 frames x 10 detections x 24 classes")
+    ap.add_argument("--frames", type=int, default=None)
+    ap.add_argument("--dets", type=int, default=None)
+    ap.add_argument("--classes", type=int, default=None)
     ap.add_argument("--seed", type=int, default=7)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--host-limit", type=float, default=900.0, help="seconds the host path may take before it is given up")
     ap.add_argument("--host-only", metavar="DIR", default=None)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "device_map_bench.json"))
+    ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    for k, v in zip(("frames", "dets", "classes"), (8192, 10, 24) if args.ucf else (4096, 15, 80)):
+        if getattr(args, k) is None:
+            setattr(args, k, v)
+    args.out = args.out or os.path.join(ROOT, "profiles", "device_map_ucf_bench.json" if args.ucf else "device_map_bench.json")
     if args.host_only:
         print(json.dumps(host_path(args, args.host_only)))
         return
     import torch
-    from tubelet_transformer_amd.device_map import DeviceFrameMAP
+    from tubelet_transformer_amd.device_map import DeviceFrameMAP, DeviceFrameMAPUCF
     if not torch.cuda.is_available():
         raise SystemExit("device_map_bench.py measures on the GPU: none found")
     dev = torch.device("cuda:0")
     case = case_of(args)
-    st = DeviceFrameMAP(args.classes, device=dev)
+    st = DeviceFrameMAPUCF(args.classes, device=dev) if args.ucf else DeviceFrameMAP(args.classes, device=dev)
     n = len(case["det_keys"])
     step = 2 * args.dets                                       # the loop's batches: two clips
     t0 = time.perf_counter()
@@ -101,14 +115,15 @@ def main():
     host = None
     with tempfile.TemporaryDirectory() as d:
         cmd = [sys.executable, os.path.abspath(__file__), "--host-only", d, "--frames", str(args.frames), "--dets", str(args.dets),
-               "--classes", str(args.classes), "--seed", str(args.seed)]
+               "--classes", str(args.classes), "--seed", str(args.seed)] + (["--ucf"] if args.ucf else [])
         try:
             r = subprocess.run(cmd, capture_output=True, text=True, timeout=args.host_limit, env=dict(os.environ, HIP_VISIBLE_DEVICES=""))
             host = json.loads(r.stdout.strip().splitlines()[-1]) if r.returncode == 0 else dict(error=r.stderr[-2000:])
         except subprocess.TimeoutExpired:
             host = dict(error="not measured: the host path did not finish in %.0f s" % args.host_limit)
-    result = dict(workload="synthetic store: %d frames x %d detections x %d classes, 0..5 ground-truth boxes per frame, 1/5 of the rows gated to 0"
-                           % (args.frames, args.dets, args.classes), repeats=args.repeats, device=device, host=host)
+    what = ("synthetic UCF-style store: %d frames x %d detections x (%d classes + no-object), 0..3 ground-truth boxes per frame, 1/4 of the rows no-object"
+            if args.ucf else "synthetic store: %d frames x %d detections x %d classes, 0..5 ground-truth boxes per frame, 1/5 of the rows gated to 0")
+    result = dict(workload=what % (args.frames, args.dets, args.classes), repeats=args.repeats, device=device, host=host)
     os.makedirs(os.path.dirname(args.out), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(result, f, indent=1)

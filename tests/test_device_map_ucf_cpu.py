@@ -1,0 +1,181 @@
+"""The JHMDB / UCF101-24 device frame-mAP evaluator (device_map.DeviceFrameMAPUCF) without a GPU: the ``stable`` keyword of FrameMAPUCF, a
+CPU-resident store (everything except the kernels: store, key order, the global exclude list, merge, the host evaluator it falls back to),
+the tie-free generator the GPU tests rely on, and ``PostProcess.decode``."""
+import json
+import os
+
+import numpy as np
+import pytest
+import torch
+
+from tubelet_transformer_amd import synth
+from tubelet_transformer_amd.device_map import DeviceFrameMAP, DeviceFrameMAPUCF
+from tubelet_transformer_amd.evaluation import FrameMAPUCF, _parse, write_result_files
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+TINY_KEY = "clip02_00010"
+
+
+def _bits(x):
+    return np.float64(x).view(np.int64)
+
+
+@pytest.fixture(scope="module")
+def golden():
+    return json.load(open(os.path.join(HERE, "golden", "frame_map_ucf_case.json")))
+
+
+def _golden_files(g, d):
+    gt, det = os.path.join(str(d), "GT_0.txt"), os.path.join(str(d), "0.txt")
+    open(gt, "w").write("\n".join(g["gt_lines"]) + "\n")
+    open(det, "w").write("\n".join(g["det_lines"]) + "\n")
+    return gt, det
+
+
+def _from_files(gt, det, class_num, **kw):
+    ev = FrameMAPUCF(class_num=class_num, **kw)
+    ev.load_gt([gt] if isinstance(gt, str) else gt)
+    ev.load_detections([det] if isinstance(det, str) else det)
+    return ev
+
+
+def _feed(st, dets, gts):
+    """parsed result-file lines into a store"""
+    K, dev = st.class_num, st.device
+    if dets:
+        st.add_detections([k for k, _ in dets], torch.tensor([v[0:4] for _, v in dets], dtype=torch.float32).to(dev),
+                          torch.tensor([v[4:5 + K] for _, v in dets], dtype=torch.float32).to(dev))
+    if gts:
+        st.add_ground_truth([k for k, _ in gts], np.asarray([v[2:6] for _, v in gts]), np.asarray([v[6:] for _, v in gts]))
+
+
+def _golden_store(g, device="cpu"):
+    """the golden case's lines fed to a store, a few lines at a time"""
+    st = DeviceFrameMAPUCF(class_num=g["class_num"], device=device)
+    dets, gts = [_parse(l) for l in g["det_lines"]], [_parse(l) for l in g["gt_lines"]]
+    for i in range(0, len(dets), 7):
+        _feed(st, dets[i:i + 7], None)
+    for i in range(0, len(gts), 5):
+        _feed(st, None, gts[i:i + 5])
+    return st
+
+
+def _golden_values(g):
+    """(mAP, {class_id: AP}) as recorded from the reference evaluator"""
+    return g["mAP"], {c + 1: v for c, v in enumerate(g["per_class_ap"].values()) if v is not None}
+
+
+def _same_bits(got, want):
+    (gm, gp), (wm, wp) = got, want
+    assert _bits(gm) == _bits(wm) and gp.keys() == wp.keys() and len(wp) > 0
+    assert all(_bits(gp[c]) == _bits(wp[c]) for c in wp)
+
+
+def _ucf_files(case, d, name):
+    """result files in the format of validate_tuber_ucf_detection from a synthetic case -> (GT path, detection path)"""
+    n, m = len(case["det_keys"]), len(case["gt_keys"])
+    dp, gp = write_result_files(str(d), name, 0, case["det_keys"], case["det_boxes"], case["det_probs"], np.zeros((n, 0)),
+                                case["gt_keys"], np.concatenate([np.zeros((m, 2)), case["gt_boxes"]], axis=1), case["gt_labels"])
+    return gp, dp
+
+
+def _ucf_store(case, device="cpu", step=30):
+    st = DeviceFrameMAPUCF(class_num=case["det_probs"].shape[1] - 1, device=device)
+    for i in range(0, len(case["det_keys"]), step):
+        st.add_detections(case["det_keys"][i:i + step], torch.from_numpy(case["det_boxes"][i:i + step]).to(device),
+                          torch.from_numpy(case["det_probs"][i:i + step]).to(device))
+    st.add_ground_truth(case["gt_keys"], case["gt_boxes"], case["gt_labels"])
+    return st
+
+
+def test_stable_keyword_keeps_the_recorded_bits(golden, tmp_path):
+    gt, det = _golden_files(golden, tmp_path)
+    want = _golden_values(golden)
+    assert FrameMAPUCF().stable is False
+    _same_bits(_from_files(gt, det, golden["class_num"]).evaluate(), want)
+    _same_bits(_from_files(gt, det, golden["class_num"], stable=True).evaluate(), want)
+    # the case has no equal scores inside a class, and the store's fp32 changes no arg-max and no bit of the result
+    ev = _from_files(gt, det, golden["class_num"])
+    _, scores, _ = ev.match()
+    assert all(len(np.unique(np.concatenate(s))) == sum(len(x) for x in s) for s in scores.values())
+
+
+def test_cpu_store_reproduces_the_evaluator_on_the_golden_files(golden, tmp_path):
+    gt, det = _golden_files(golden, tmp_path)
+    ref = _from_files(gt, det, golden["class_num"], stable=True)
+    st = _golden_store(golden)
+    assert isinstance(st, DeviceFrameMAP)                              # one store, not a copy
+    ev = st.to_host_evaluator()
+    assert isinstance(ev, FrameMAPUCF) and ev.stable is True and st.to_host_evaluator(stable=False).stable is False
+    assert list(ev.det) == list(ref.det) and list(ev.gt) == list(ref.gt) and ev.exclude == ref.exclude == {TINY_KEY}
+    assert TINY_KEY not in ev.det and TINY_KEY in {_parse(l)[0] for l in golden["det_lines"]}
+    assert all([(c, s) for c, _, s in ev.det[k]] == [(c, float(np.float32(s))) for c, _, s in ref.det[k]] for k in ref.det)
+    got = st.evaluate()
+    assert st.path == "host" and sum(st.ties.values()) == 0 and set(st.ties) == set(range(1, golden["class_num"] + 1))
+    _same_bits(got, _golden_values(golden))
+    _same_bits(got, ref.evaluate())
+
+
+def test_the_exclude_list_is_global_across_a_merge(golden):
+    dets, gts = [_parse(l) for l in golden["det_lines"]], [_parse(l) for l in golden["gt_lines"]]
+    tiny = [i for i, (k, v) in enumerate(gts) if (v[4] - v[2]) * (v[5] - v[3]) < 10]
+    assert [gts[i][0] for i in tiny] == [TINY_KEY]
+    mine = [d for d in dets if d[0] == TINY_KEY]
+    rest = [d for d in dets if d[0] != TINY_KEY]
+    assert mine and any(int(np.argmax(v[4:])) != golden["class_num"] for _, v in mine)    # rows that would count were the frame not excluded
+    cut = tiny[0]
+    a, b, one = (DeviceFrameMAPUCF(class_num=golden["class_num"], device="cpu") for _ in range(3))
+    _feed(a, mine + rest[:100], gts[:cut])                             # the frame's detections here ...
+    _feed(b, rest[100:], gts[cut:])                                    # ... the tiny box there
+    _feed(one, mine + rest[:100], gts[:cut])
+    _feed(one, rest[100:], gts[cut:])
+    assert TINY_KEY in a.to_host_evaluator().det and TINY_KEY not in a.to_host_evaluator().exclude
+    m = DeviceFrameMAPUCF.merge([a, b])
+    assert isinstance(m, DeviceFrameMAPUCF) and m.frame_keys == one.frame_keys and m.row_fid == one.row_fid and m.gt_keys == one.gt_keys
+    assert torch.equal(m.boxes, one.boxes) and torch.equal(m.scores, one.scores)
+    assert all(np.array_equal(x, y) for x, y in zip(m.gt_arrays(), one.gt_arrays()))
+    assert TINY_KEY not in m.to_host_evaluator().det
+    _same_bits(m.evaluate(), one.evaluate())
+    _same_bits(m.evaluate(), _golden_values(golden))                   # the order of the lines moves no bit of this tie-free case
+
+
+def test_the_synthetic_ucf_generator_meets_its_conditions(tmp_path):
+    case = synth.synthetic_frame_map_ucf_case(48, seed=11)
+    p = case["det_probs"]
+    n, C = 48 * 10, 21
+    assert p.dtype == np.float32 and p.shape == (n, C + 1) and case["det_boxes"].dtype == np.float32 and case["gt_labels"].shape[1] == 21
+    assert np.allclose(p.sum(axis=1, dtype=np.float64), 1.0, atol=1e-6)
+    top = p.max(axis=1)
+    assert (top > 0.5).all() and len(np.unique(top)) == n and ((p == top[:, None]).sum(axis=1) == 1).all()
+    assert (case["gt_labels"].sum(axis=1) == 1).all()
+    gp, dp = _ucf_files(case, tmp_path, "synth")
+    ev, evs = _from_files(gp, dp, C), _from_files(gp, dp, C, stable=True)
+    _same_bits(ev.evaluate(), evs.evaluate())
+    _, scores, tps = ev.match()
+    n_tp = sum(int(t.sum()) for ts in tps.values() for t in ts)
+    no_object = float((p.argmax(axis=1) == C).mean())
+    only_dets = set(case["det_keys"]) - set(case["gt_keys"])
+    print("true positives %d, excluded frames %d, detection-only frames %d, no-object rows %.3f, classes with 0 < AP < 1: %d"
+          % (n_tp, len(ev.exclude), len(only_dets), no_object, sum(0 < v < 1 for v in ev.evaluate()[1].values())))
+    assert n_tp >= 20 and len(ev.exclude) >= 1 and len(only_dets) >= 1 and 1 / 8 <= no_object <= 1 / 2
+    st = _ucf_store(case)
+    _same_bits(st.evaluate(), ev.evaluate())
+    assert st.path == "host" and sum(st.ties.values()) == 0
+
+
+def test_postprocess_forward_is_decode_copied_to_numpy():
+    from tubelet_transformer_amd.criterion import PostProcess
+    g = torch.Generator().manual_seed(5)
+    out = {"pred_logits": torch.randn(2, 320, 22, generator=g), "pred_boxes": torch.rand(2, 320, 4, generator=g),
+           "pred_logits_b": 3 * torch.randn(2, 320, 3, generator=g)}
+    sizes = torch.tensor([[64, 96], [48, 80]])
+    post = PostProcess()
+    dec = post.decode(out, sizes)
+    fwd = post(out, sizes)
+    assert all(torch.is_tensor(d) for d in dec) and all(isinstance(f, np.ndarray) for f in fwd)
+    assert [tuple(d.shape) for d in dec] == [(2, 320, 22), (2, 320, 4), (2, 320, 2)] == [f.shape for f in fwd]
+    for d, f in zip(dec, fwd):
+        assert d.dtype == torch.float32 and f.dtype == np.float32
+        assert np.array_equal(np.ascontiguousarray(d.numpy()).view(np.int32), np.ascontiguousarray(f).view(np.int32))
+    want = torch.softmax(out["pred_logits"], -1).numpy()
+    assert np.array_equal(fwd[0].view(np.int32), want.view(np.int32))

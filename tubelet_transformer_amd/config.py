@@ -150,9 +150,10 @@ def get_cfg_defaults():
         MONITOR=dict(ENABLE=False, EVERY=50, HISTORY=8)), new_allowed=True)
     cfg.VAL = CfgNode(dict(
         FREQ=2, BATCH_SIZE=1,
-        # frame-mAP of validate_tuber_detection computed on the device (device_map.py; not reference keys): ENABLE keeps detections and
-        # ground truth in device buffers and runs the two frame_map.hip kernels instead of the host FrameMAP over the result files;
-        # FILES: the per-rank result files are written as well (reference format), False: no file, no host copy of the detections
+        # frame-mAP of validate_tuber_detection (AVA) and validate_tuber_ucf_detection (JHMDB / UCF101-24) computed on the device
+        # (device_map.py; not reference keys): ENABLE keeps detections and ground truth in device buffers and runs the frame_map.hip
+        # kernels instead of the host FrameMAP / FrameMAPUCF over the result files; FILES: the per-rank result files are written as
+        # well (reference format), False: no file, no host copy of the detections
         DEVICE_MAP=dict(ENABLE=False, FILES=True)), new_allowed=True)
     cfg.DATA = CfgNode(dict(
         DATASET_NAME="ava", NUM_CLASSES=80, IMG_SIZE=256, TEMP_LEN=32, FRAME_RATE=2), new_allowed=True)

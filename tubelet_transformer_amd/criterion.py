@@ -388,13 +388,20 @@ class SetCriterion(_SetCriterionBase):
 
 class PostProcess(nn.Module):
     @torch.no_grad()
-    def forward(self, outputs, target_sizes):
+    def decode(self, outputs, target_sizes):
+        """(class + no-object probabilities, xyxy boxes in pixels, visibility probabilities) as tensors on the outputs' device: what
+        ``forward`` copies to the host, for consumers that stay on the device (device_map.py)"""
         lg, bx, lb = outputs["pred_logits"].float(), outputs["pred_boxes"].float(), outputs["pred_logits_b"].float()
         assert len(lg) == len(target_sizes) and target_sizes.shape[1] == 2
         prob = F.softmax(lg, -1)
         h, w = target_sizes.to(bx.device).unbind(1)
         boxes = box_ops.box_cxcywh_to_xyxy(bx) * torch.stack([w, h, w, h], dim=1)[:, None, :]
-        return prob.cpu().numpy(), boxes.cpu().numpy(), lb.softmax(-1).cpu().numpy()[..., 1:]
+        return prob, boxes, lb.softmax(-1)[..., 1:]
+
+    @torch.no_grad()
+    def forward(self, outputs, target_sizes):
+        prob, boxes, pb = self.decode(outputs, target_sizes)
+        return prob.cpu().numpy(), boxes.cpu().numpy(), pb.cpu().numpy()
 
 
 class PostProcessAVA(nn.Module):

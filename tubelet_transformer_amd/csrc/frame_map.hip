@@ -5,6 +5,8 @@
 //   1. frame_match_kernel   a workgroup per frame, lanes over classes: greedy score-ordered matching of the frame's detections against its
 //                           ground-truth boxes, per class; writes one flag per (row, class): 1 true positive, 0 false positive, 2 not counted
 //                           (a box with x1 >= x2 or y1 >= y2, a class outside the mask), 3 a frame beyond the kernel's bounds (nothing decided)
+//   1b. frame_match_top1_kernel  the JHMDB / UCF101-24 counting rule (evaluation.FrameMAPUCF, evaluates/evaluate_ucf.py:109-126): a row counts once,
+//                           as its arg-max class; a wave per frame, a lane per detection, the matching in closed form (no sequential pass)
 //   2. ranked_ap_kernel     a workgroup per class over that class's flags in rank order: VOC average precision (area under the monotone
 //                           precision envelope) in fp64 from two sweeps over 4096-entry chunks with carries
 // No atomics, fixed reduction trees: the same input gives the same bits.  Both are bound by their flag / score traffic, not by arithmetic.
@@ -113,6 +115,76 @@ __global__ __launch_bounds__(FMAP_THREADS) void frame_match_kernel(const float* 
             }
             fl[(long)i * C] = tp;
         }
+    }
+}
+
+#define FTOP_WAVES 4              // frames per workgroup: a wave each
+
+// The UCF counting rule: a row is ONE detection, of its arg-max class a over the C + 1 columns (np.argmax: the first maximum, a NaN counting as
+// one), scored det_prob[r][a]; it is not counted when a is the no-object column C, when its box is not a box, or when its frame is on the
+// exclude list.  The greedy matching in closed form: the best candidate (bj, bv) of a row -- first arg-max of the IoU over the frame's
+// ground-truth rows of class a -- does not depend on the visiting order, and the sequential pass marks a box taken exactly when a row with
+// that best candidate and bv >= thr visits it first.  So a row is a true positive iff bv >= thr and no other counted row of the frame with
+// the same bj and bv >= thr has a larger order key (keys are distinct: their low word is the row).  A ground-truth row has one class, so an
+// equal bj implies an equal class.  Cross-lane reads over the wave; no LDS, no atomics.
+__global__ __launch_bounds__(64 * FTOP_WAVES) void frame_match_top1_kernel(const float* __restrict__ det_box, const float* __restrict__ det_prob,
+                                                                           const int* __restrict__ det_off, const double* __restrict__ gt_box,
+                                                                           const int* __restrict__ gt_cls, const int* __restrict__ gt_off,
+                                                                           const unsigned char* __restrict__ frame_skip, int F, int N, int G, int C,
+                                                                           double iou_thr, int* __restrict__ det_cls,
+                                                                           unsigned char* __restrict__ det_flag) {
+    const int lane = threadIdx.x & 63;
+    const int f = blockIdx.x * FTOP_WAVES + (threadIdx.x >> 6);                   // wave-uniform from here on
+    if (f >= F) return;
+    const int d0 = det_off[f], d1 = det_off[f + 1], g0 = gt_off[f], g1 = gt_off[f + 1];
+    if (d0 < 0 || d1 < d0 || d1 > N || g0 < 0 || g1 < g0 || g1 > G) return;       // not a CSR row of these arrays: touch nothing
+    const int n = d1 - d0, g = g1 - g0;
+    if (n > FMAP_MAX_DETS || g > FMAP_MAX_GT) {
+        for (int i = lane; i < n; i += 64) {
+            det_cls[d0 + i] = -1;
+            det_flag[d0 + i] = FMAP_BEYOND_BOUNDS;
+        }
+        return;
+    }
+    if (n == 0) return;
+    const bool skip = frame_skip ? frame_skip[f] != 0 : false;
+    const bool have = lane < n;
+    int a = C;
+    float score = 0.f;
+    bool counted = false;
+    int bj = -1;
+    bool hit = false;
+    if (have) {
+        const float* p = det_prob + (long)(d0 + lane) * (C + 1);
+        a = 0;
+        score = p[0];
+        for (int c = 1; c <= C; ++c) {
+            const float v = p[c];
+            if (score == score && (v > score || v != v)) { a = c; score = v; }
+        }
+        const float* d = det_box + (long)(d0 + lane) * 4;
+        counted = a != C && d[0] < d[2] && d[1] < d[3] && !skip;
+        if (counted) {
+            double bv = 0.0;
+            for (int j = 0; j < g; ++j) {                                         // the ground truth is read uniformly: the same address in every lane
+                if (gt_cls[g0 + j] != a) continue;
+                const double v = fmap_iou(d, gt_box + (long)(g0 + j) * 4);
+                if (bj < 0 || (bv == bv && (v > bv || v != v))) { bj = j; bv = v; }
+            }
+            hit = bj >= 0 && bv >= iou_thr;
+        }
+    }
+    const unsigned long long key = fmap_key(score, lane);
+    const int claim = hit ? bj : -1;                                              // the box this row would take
+    bool lost = false;
+    for (int m = 0; m < n; ++m) {                                                 // every lane of the wave is here: m is uniform
+        const int cm = __shfl(claim, m, 64);
+        const unsigned long long km = __shfl(key, m, 64);
+        lost |= cm == claim && km > key;
+    }
+    if (have) {
+        det_cls[d0 + lane] = a;
+        det_flag[d0 + lane] = !counted ? (unsigned char)FMAP_NOT_COUNTED : (unsigned char)((hit && !lost) ? 1 : 0);
     }
 }
 
@@ -266,6 +338,23 @@ int tuber_frame_match(const float* det_box, const float* det_score, const int* d
 }
 int tuber_frame_match_max_dets() { return FMAP_MAX_DETS; }
 int tuber_frame_match_max_gt() { return FMAP_MAX_GT; }
+
+// The matching step under the JHMDB / UCF101-24 counting rule (evaluation.FrameMAPUCF): det_prob [N][C + 1] fp32, columns [0, C) the classes and
+// column C no-object; gt_cls [G] the 0-based class of a ground-truth row (a class outside [0, C) matches nothing); frame_skip [F] bytes, non-zero =
+// the frame is on the exclude list (NULL: none).  det_cls [N] out: the row's arg-max column (C = no-object); det_flag [N] out: 1 true positive,
+// 0 false positive, 2 not counted, 3 (with det_cls -1) a frame beyond the bounds.  Offsets, bounds and refusals as tuber_frame_match.
+int tuber_frame_match_top1(const float* det_box, const float* det_prob, const int* det_off, const double* gt_box, const int* gt_cls,
+                           const int* gt_off, const unsigned char* frame_skip, int F, int N, int G, int C, double iou_thr, int* det_cls,
+                           unsigned char* det_flag, hipStream_t stream) {
+    if (F < 0 || N < 0 || G < 0 || C <= 0 || !(iou_thr == iou_thr)) return TUBER_EINVAL;
+    if ((long)N > (long)F * FMAP_MAX_DETS || (long)G > (long)F * FMAP_MAX_GT) return TUBER_EINVAL;
+    if (N == 0) return TUBER_OK;
+    if (!det_box || !det_prob || !det_off || !gt_off || !det_cls || !det_flag) return TUBER_EINVAL;
+    if (G > 0 && (!gt_box || !gt_cls)) return TUBER_EINVAL;
+    hipLaunchKernelGGL(frame_match_top1_kernel, dim3((F + FTOP_WAVES - 1) / FTOP_WAVES), dim3(64 * FTOP_WAVES), 0, stream, det_box, det_prob,
+                       det_off, gt_box, gt_cls, gt_off, frame_skip, F, N, G, C, iou_thr, det_cls, det_flag);
+    TUBER_RETURN_LAUNCH();
+}
 
 // VOC average precision per class from flags in rank order: flags_ranked [C][N] bytes (1 true positive, 0 false positive, anything else counts
 // nowhere), n_gt [C] ground-truth boxes of the class -> ap [C] fp64 (NaN where n_gt <= 0, 0.0 where nothing is counted) and n_tp [C] (NULL: not

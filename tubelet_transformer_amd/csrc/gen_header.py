@@ -316,6 +316,14 @@ DOC = {
                          "the fp64 IoU over the frame's ground-truth boxes labelled c, true positive iff iou[j] >= iou_thr and j not taken. flags [N][C] bytes: 1 true positive, 0 false "
                          "positive, 2 not counted (x1 >= x2 or y1 >= y2; class_mask[c] == 0, NULL mask: all classes), 3 a frame beyond the bounds (nothing decided). Sizes no frame list can "
                          "meet (N > F * max_dets, G > F * max_gt), bad sizes or pointers: negative, nothing launched. One workgroup per frame, lanes over classes, the n x g IoU table in LDS.",
+    "tuber_frame_match_top1": "validation frame-mAP on the device, matching step under the JHMDB / UCF101-24 counting rule (evaluates/evaluate_ucf.py:109-126 over the same PASCAL "
+                              "matching, evaluates/utils/per_image_evaluation.py:354-366,445-449): a row of det_prob [N][C + 1] fp32 (columns [0, C) the classes, column C no-object) is ONE "
+                              "detection, of its arg-max column a (np.argmax: the first maximum, a NaN counting as one) with score det_prob[r][a]. det_cls [N] out: a. det_flag [N] bytes out: "
+                              "2 not counted (a == C; x1 >= x2 or y1 >= y2; frame_skip[f] != 0, frame_skip [F] bytes or NULL: the frames a ground-truth box under 10 px^2 excludes, "
+                              "evaluate_ucf.py:60-62), else with (bj, bv) the first arg-max of the fp64 IoU over the frame's ground-truth rows with gt_cls [G] == a (0-based; a class outside "
+                              "[0, C) matches nothing): 1 iff bv >= iou_thr and no other counted row of the frame with the same bj and bv >= iou_thr ranks higher (score descending, equal scores by "
+                              "ascending row, NaN last) -- the sequential greedy matching in closed form -- else 0; no candidate: 0. Offsets (DEVICE int[F + 1]), bounds and refusals as "
+                              "tuber_frame_match; a frame beyond the bounds gets det_flag 3 and det_cls -1. One wave per frame, one lane per detection, four frames per workgroup, no LDS, no atomics.",
     "tuber_frame_match_max_dets": "detections per frame tuber_frame_match takes (64).",
     "tuber_frame_match_max_gt": "ground-truth boxes per frame tuber_frame_match takes (32).",
     "tuber_ranked_ap": "validation frame-mAP on the device, ranking step: VOC average precision per class (area under the monotone precision envelope, summed where recall changes; "

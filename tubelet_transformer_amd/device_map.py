@@ -13,6 +13,9 @@ class has two equal scores.  ``evaluate()`` leaves the number of rows per class 
 
 A store on the CPU, and a store with a frame beyond the kernel's bounds (``tuber_frame_match_max_dets`` detections,
 ``tuber_frame_match_max_gt`` ground-truth boxes), is evaluated by ``to_host_evaluator().evaluate()``: no frame is ever dropped or cut.
+
+``DeviceFrameMAPUCF`` is the same store under the JHMDB / UCF101-24 counting rule of ``evaluation.FrameMAPUCF`` (``validate_tuber_ucf_detection``):
+a row of C + 1 probabilities is one detection, of its arg-max class; the matching step is ``tuber_frame_match_top1``, the rest is shared.
 """
 import logging
 
@@ -20,7 +23,7 @@ import numpy as np
 import torch
 
 from . import lib
-from .evaluation import FrameMAP, mean_ap
+from .evaluation import FrameMAP, FrameMAPUCF, mean_ap
 
 log = logging.getLogger(__name__)
 
@@ -34,12 +37,17 @@ class DeviceFrameMAP:
         self.exclude = set(exclude_keys)
         self.gt_min_score = gt_min_score
         self.device = torch.device(device)
+        self._init_store(self.class_num, self.class_num)
+
+    def _init_store(self, score_width, label_width):
+        """the empty store: ``score_width`` columns per detection row, ``label_width`` per ground-truth line"""
+        self.score_width, self.label_width = score_width, label_width
         self.frame_ids, self.frame_keys = {}, []          # frames with detections: key -> id, in order of first appearance
         self.det_count = []                               # rows per frame id
         self.row_fid = []                                 # frame id per stored row (host)
         self.n = 0                                        # rows stored (the cursor: a host integer)
         self._box = torch.empty((0, 4), dtype=torch.float32, device=self.device)
-        self._score = torch.empty((0, self.class_num), dtype=torch.float32, device=self.device)
+        self._score = torch.empty((0, self.score_width), dtype=torch.float32, device=self.device)
         self.gt_keys, self._gt_box, self._gt_lab = [], [], []
         self.ties = None                                  # after evaluate(): {class_id: rows that share their score with another row}
         self.path = None                                  # after evaluate(): "device" or "host"
@@ -60,7 +68,7 @@ class DeviceFrameMAP:
             return
         cap = max(need, 2 * self._box.shape[0], 1024)
         box = torch.empty((cap, 4), dtype=torch.float32, device=self.device)
-        score = torch.empty((cap, self.class_num), dtype=torch.float32, device=self.device)
+        score = torch.empty((cap, self.score_width), dtype=torch.float32, device=self.device)
         box[:self.n] = self._box[:self.n]
         score[:self.n] = self._score[:self.n]
         self._box, self._score = box, score
@@ -77,7 +85,7 @@ class DeviceFrameMAP:
         """``keys``: one frame key per row; ``boxes`` [n, 4] fp32 xyxy, ``scores`` [n, C] fp32 on the store's device.  Rows of an excluded
         key are dropped (``FrameMAP.load_detections`` skips their lines).  No device read."""
         keys = list(keys)
-        assert boxes.shape == (len(keys), 4) and scores.shape == (len(keys), self.class_num), (boxes.shape, scores.shape, len(keys))
+        assert boxes.shape == (len(keys), 4) and scores.shape == (len(keys), self.score_width), (boxes.shape, scores.shape, len(keys))
         assert boxes.dtype == torch.float32 and scores.dtype == torch.float32
         keep = [i for i, k in enumerate(keys) if k not in self.exclude]
         if len(keep) != len(keys):
@@ -103,7 +111,7 @@ class DeviceFrameMAP:
         ``gt_min_score``).  Host data: take them from the loader's CPU tensors."""
         keys = list(keys)
         boxes = np.asarray(boxes.detach().cpu().numpy() if torch.is_tensor(boxes) else boxes, dtype=np.float64).reshape(-1, 4)
-        labels = np.asarray(labels.detach().cpu().numpy() if torch.is_tensor(labels) else labels, dtype=np.float64).reshape(-1, self.class_num)
+        labels = np.asarray(labels.detach().cpu().numpy() if torch.is_tensor(labels) else labels, dtype=np.float64).reshape(-1, self.label_width)
         assert len(boxes) == len(keys) == len(labels), (len(boxes), len(keys), len(labels))
         for i, k in enumerate(keys):
             if k in self.exclude:
@@ -115,7 +123,7 @@ class DeviceFrameMAP:
     def gt_arrays(self):
         """(boxes [m, 4] fp64, labels [m, C] fp64) in store order"""
         if not self.gt_keys:
-            return np.zeros((0, 4)), np.zeros((0, self.class_num))
+            return np.zeros((0, 4)), np.zeros((0, self.label_width))
         return np.stack(self._gt_box), np.stack(self._gt_lab)
 
     @classmethod
@@ -140,18 +148,18 @@ class DeviceFrameMAP:
         dist.all_gather_object(meta, dict(n=self.n, frame_keys=self.frame_keys, row_fid=self.row_fid, gt_keys=self.gt_keys, gt_box=gb, gt_lab=gl))
         nmax = max(m["n"] for m in meta)
         box = torch.zeros((nmax, 4), dtype=torch.float32, device=self.device)
-        score = torch.zeros((nmax, self.class_num), dtype=torch.float32, device=self.device)
+        score = torch.zeros((nmax, self.score_width), dtype=torch.float32, device=self.device)
         box[:self.n], score[:self.n] = self.boxes, self.scores
         boxes, scores = [torch.empty_like(box) for _ in range(world)], [torch.empty_like(score) for _ in range(world)]
         dist.all_gather(boxes, box)
         dist.all_gather(scores, score)
         parts = []
         for m, b, s in zip(meta, boxes, scores):
-            part = DeviceFrameMAP(device=self.device, **self._settings())
+            part = type(self)(device=self.device, **self._settings())
             part.add_detections([m["frame_keys"][f] for f in m["row_fid"]], b[:m["n"]], s[:m["n"]])
             part.add_ground_truth(m["gt_keys"], m["gt_box"], m["gt_lab"])
             parts.append(part)
-        return DeviceFrameMAP.merge(parts)
+        return type(self).merge(parts)
 
     # ------------------------------------------------------------------------------------------------------------------
     # evaluation
@@ -194,7 +202,7 @@ class DeviceFrameMAP:
     def _finish(self, ap, ties):
         per_class = {c + 1: float(ap[c]) for c in range(self.class_num) if self._wanted(c + 1) and not np.isnan(ap[c])}
         self.ties = {c + 1: int(ties[c]) for c in range(self.class_num) if self._wanted(c + 1)}
-        ncat = max(self.whitelist) if self.whitelist else self.class_num
+        ncat = getattr(self, "num_categories", None) or (max(self.whitelist) if self.whitelist else self.class_num)
         return mean_ap(per_class, ncat), per_class
 
     def _evaluate_host(self):
@@ -207,12 +215,13 @@ class DeviceFrameMAP:
         self.ties = {c + 1: int(ties[c]) for c in range(self.class_num) if self._wanted(c + 1)}
         return mAP, per_class
 
-    def device_arrays(self):
-        """The operands of ``tuber_frame_match`` on the store's device: rows stable-sorted by frame id, the two CSR offset arrays over all
-        frames (frames that only have ground truth come after those with detections), label bytes, class mask, boxes per class."""
-        C, dev = self.class_num, self.device
+    def _frame_layout(self, gt_keys):
+        """The frame-major layout both matching kernels read: frame ids over the detections' keys and then ``gt_keys`` (frames that only
+        have ground truth come last), the rows stable-sorted by frame id, per-frame counts and CSR offsets, the ground truth's frame ids and
+        their stable order."""
+        dev = self.device
         ids = dict(self.frame_ids)
-        gfid = np.asarray([ids.setdefault(k, len(ids)) for k in self.gt_keys], dtype=np.int64)
+        gfid = np.asarray([ids.setdefault(k, len(ids)) for k in gt_keys], dtype=np.int64)
         F = len(ids)
         fid = torch.tensor(self.row_fid, dtype=torch.int32).to(dev)
         order = torch.sort(fid, stable=True).indices if self.n else torch.zeros(0, dtype=torch.long, device=dev)
@@ -222,8 +231,15 @@ class DeviceFrameMAP:
         gt_n = np.bincount(gfid, minlength=F) if F else np.zeros(0, dtype=np.int64)
         det_off = np.concatenate([[0], np.cumsum(det_n)]).astype(np.int32)
         gt_off = np.concatenate([[0], np.cumsum(gt_n)]).astype(np.int32)
-        gb, gl = self.gt_arrays()
         gorder = np.argsort(gfid, kind="stable")
+        return ids, F, order, box, score, det_n, gt_n, det_off, gt_off, gfid, gorder
+
+    def device_arrays(self):
+        """The operands of ``tuber_frame_match`` on the store's device: rows stable-sorted by frame id, the two CSR offset arrays over all
+        frames (frames that only have ground truth come after those with detections), label bytes, class mask, boxes per class."""
+        C, dev = self.class_num, self.device
+        gb, gl = self.gt_arrays()
+        ids, F, order, box, score, det_n, gt_n, det_off, gt_off, gfid, gorder = self._frame_layout(self.gt_keys)
         mask = np.asarray([1 if self._wanted(c + 1) else 0 for c in range(C)], dtype=np.uint8)
         lab = ((gl[gorder] > self.gt_min_score) & (mask[None, :] != 0)).astype(np.uint8)
         n_gt = lab.sum(axis=0).astype(np.int32)
@@ -254,11 +270,20 @@ class DeviceFrameMAP:
                 marks.append((name, e))
         mark("start")
         a = self.device_arrays()
+        if self._beyond_bounds(a):
+            return self._evaluate_host()
+        self.path = "device"
+        return self._evaluate_device(a, mark, marks, timings)
+
+    def _beyond_bounds(self, a):
+        """a frame the matching kernels do not take: logged once, the store is evaluated on the host"""
         if a["max_dets"] > lib.query("tuber_frame_match_max_dets") or a["max_gt"] > lib.query("tuber_frame_match_max_gt"):
             log.warning("DeviceFrameMAP: a frame has %d detections / %d ground-truth boxes, beyond the kernel's %d / %d: evaluating on the host",
                         a["max_dets"], a["max_gt"], lib.query("tuber_frame_match_max_dets"), lib.query("tuber_frame_match_max_gt"))
-            return self._evaluate_host()
-        self.path = "device"
+            return True
+        return False
+
+    def _evaluate_device(self, a, mark, marks, timings):
         C, N = a["C"], a["N"]
         mark("frame_sort_and_uploads")
         flags = self.match_flags(a)
@@ -273,6 +298,9 @@ class DeviceFrameMAP:
         mark("tuber_ranked_ap")
         ties = self._tie_counts(ranked)
         mark("tie_count")
+        return self._read_back(ap, ties, marks, timings)
+
+    def _read_back(self, ap, ties, marks, timings):
         if timings is not None:
             import time
             torch.cuda.synchronize()
@@ -283,3 +311,124 @@ class DeviceFrameMAP:
             for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
                 timings[name + "_ms"] = e0.elapsed_time(e1)
         return self._finish(ap, ties)
+
+
+class DeviceFrameMAPUCF(DeviceFrameMAP):
+    """``evaluation.FrameMAPUCF`` on the store of ``DeviceFrameMAP``: a detection row is ``[C + 1]`` probabilities (the classes, then
+    no-object) and counts once, as its arg-max class with that probability, unless no-object is the arg-max; a ground-truth line is a box and
+    the one-hot row the loop writes to ``GT_*.txt``; a ground-truth box under 10 px^2 is dropped and puts its key on the exclude list -- decided
+    in ``evaluate()`` over everything stored, as the reference loads every ground-truth file before any detection file.  The mean runs over 24
+    categories whatever ``class_num`` is.
+
+    Equal scores keep store order: frames in order of first appearance in the store, then row order.  That is ``FrameMAPUCF(stable=True)`` on
+    files with the same lines whenever the first stored row of every frame is not behind a counted row of a later frame (always, when a
+    frame's rows arrive together), and the unmodified ``FrameMAPUCF()`` when no class has two equal scores."""
+
+    TINY = 10                                             # evaluate_ucf.py:60-62
+
+    def __init__(self, class_num=24, iou_threshold=0.5, label_width=None, device="cuda"):
+        self.class_num, self.iou = int(class_num), float(iou_threshold)
+        self.whitelist, self.exclude, self.gt_min_score = None, set(), 1e-2
+        self.num_categories = 24                          # evaluate_ucf.py:15-20
+        self.device = torch.device(device)
+        self._init_store(self.class_num + 1, int(label_width) if label_width else max(21, self.class_num))
+
+    def _settings(self):
+        return dict(class_num=self.class_num, iou_threshold=self.iou, label_width=self.label_width)
+
+    def ucf_ground_truth(self):
+        """-> (excluded keys, [(key, class 0-based, box)] in store order): ``FrameMAPUCF.load_gt`` over the stored lines"""
+        gb, gl = self.gt_arrays()
+        tiny = (gb[:, 2] - gb[:, 0]) * (gb[:, 3] - gb[:, 1]) < self.TINY
+        excluded = {k for k, t in zip(self.gt_keys, tiny) if t}
+        rows = [(k, int(x), gb[i]) for i, k in enumerate(self.gt_keys) if not tiny[i] for x in np.nonzero(~(gl[i] <= 1e-2))[0]]
+        return excluded, rows
+
+    def to_host_evaluator(self, stable=True):
+        """A ``FrameMAPUCF`` whose gt / det dictionaries hold the store in store order: what ``load_gt`` / ``load_detections`` build from
+        result files with the same lines."""
+        ev = FrameMAPUCF(self.class_num, iou_threshold=self.iou, stable=stable)
+        ev.exclude, rows = self.ucf_ground_truth()
+        for k, x, box in rows:
+            ev.gt.setdefault(k, []).append((x + 1, np.asarray(box, dtype=float)))
+        boxes = self.boxes.cpu().numpy().astype(np.float64)
+        probs = self.scores.cpu().numpy().astype(np.float64)
+        for k in self.frame_keys:
+            ev.det[k] = []
+        for r, fid in enumerate(self.row_fid):
+            k = self.frame_keys[fid]
+            if k in ev.exclude or int(np.argmax(probs[r])) == self.class_num:
+                continue
+            x = int(np.argmax(probs[r, :self.class_num]))
+            ev.det[k].append((x + 1, boxes[r], float(probs[r, x])))
+        ev.det = {k: d for k, d in ev.det.items() if d}
+        return ev
+
+    def _evaluate_host(self):
+        self.path = "host"
+        ev = self.to_host_evaluator(stable=True)
+        mAP, per_class = ev.evaluate()
+        _, scores, _ = ev.match()
+        self.ties = {}
+        for c in range(1, self.class_num + 1):
+            s = np.concatenate(scores[c]) if c in scores else np.zeros(0)
+            _, counts = np.unique(np.where(np.isnan(s), -np.inf, s), return_counts=True)
+            self.ties[c] = int(counts[counts > 1].sum())
+        return mAP, per_class
+
+    def device_arrays(self):
+        """The operands of ``tuber_frame_match_top1`` on the store's device: rows stable-sorted by frame id, the CSR offsets over all
+        frames, one ground-truth row per (kept line, class set in it), the exclude list as a byte per frame, boxes per class."""
+        C, dev = self.class_num, self.device
+        excluded, rows = self.ucf_ground_truth()
+        ids, F, order, box, prob, det_n, gt_n, det_off, gt_off, gfid, gorder = self._frame_layout([k for k, _, _ in rows])
+        gcls = np.asarray([x for _, x, _ in rows], dtype=np.int32)[gorder]
+        gbox = np.asarray([b for _, _, b in rows], dtype=np.float64).reshape(-1, 4)[gorder]
+        skip = np.zeros(F, dtype=np.uint8)
+        skip[np.asarray([ids[k] for k in excluded if k in ids], dtype=np.int64)] = 1
+        n_gt = np.bincount(gcls[(gcls >= 0) & (gcls < C)], minlength=C).astype(np.int32)
+        up = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        return dict(F=F, N=self.n, G=len(gfid), C=C, order=order, det_box=box, det_prob=prob, det_off=up(det_off), gt_box=up(gbox),
+                    gt_cls=up(gcls), gt_off=up(gt_off), frame_skip=up(skip), n_gt=up(n_gt), max_dets=int(det_n.max()) if F else 0,
+                    max_gt=int(gt_n.max()) if F else 0)
+
+    def match_flags(self, a=None):
+        """``tuber_frame_match_top1`` over the store: (det_cls [N] int32, det_flag [N] uint8) for the rows in frame order"""
+        a = a or self.device_arrays()
+        cls = torch.empty(a["N"], dtype=torch.int32, device=self.device)
+        flag = torch.empty(a["N"], dtype=torch.uint8, device=self.device)
+        lib.call("tuber_frame_match_top1", a["det_box"], a["det_prob"], a["det_off"], a["gt_box"], a["gt_cls"], a["gt_off"], a["frame_skip"],
+                 a["F"], a["N"], a["G"], a["C"], self.iou, cls, flag)
+        return cls, flag
+
+    def _evaluate_device(self, a, mark, marks, timings):
+        C, N, dev = a["C"], a["N"], self.device
+        mark("frame_sort_and_uploads")
+        cls, flag = self.match_flags(a)
+        mark("tuber_frame_match_top1")
+        # every class's ranking over its counted rows: one stable sort by score (descending, NaN last), one by class; the rows that are not
+        # counted go to a bucket of their own (row C of the [C + 1][N] layout, which tuber_ranked_ap does not read)
+        cls = cls.long()
+        score = self._nan_last(a["det_prob"].gather(1, cls.clamp(0, C)[:, None])[:, 0]) if N else torch.zeros(0, device=dev)
+        bucket = torch.where(flag == 2, torch.full_like(cls, C), cls)
+        ranked, by_score = torch.sort(score, descending=True, stable=True)
+        bucket, by_class = torch.sort(bucket[by_score], stable=True)
+        ranked, flag = ranked[by_class], flag[by_score][by_class]
+        count = torch.zeros(C + 1, dtype=torch.long, device=dev).scatter_add_(0, bucket, torch.ones_like(bucket))
+        pos = torch.arange(N, device=dev) - (count.cumsum(0) - count)[bucket]
+        flags_ranked = torch.full((C + 1, N), 2, dtype=torch.uint8, device=dev)
+        flags_ranked[bucket, pos] = flag
+        mark("rank_sort_and_scatter")
+        ap = torch.empty(C, dtype=torch.float64, device=dev)
+        n_tp = torch.empty(C, dtype=torch.int32, device=dev)
+        lib.call("tuber_ranked_ap", flags_ranked, a["n_gt"], C, N, ap, n_tp)
+        mark("tuber_ranked_ap")
+        ties = torch.zeros(C + 1, dtype=torch.long, device=dev)
+        if N > 1:
+            eq = (ranked[1:] == ranked[:-1]) & (bucket[1:] == bucket[:-1])
+            member = torch.zeros(N, dtype=torch.bool, device=dev)
+            member[1:] |= eq
+            member[:-1] |= eq
+            ties.scatter_add_(0, bucket, member.long())
+        mark("tie_count")
+        return self._read_back(ap, ties[:C], marks, timings)

@@ -357,10 +357,11 @@ class FrameMAPUCF(FrameMAP):
     ground-truth lines whose box is smaller than 10 px^2 put their image on an exclude list (:60-62); a detection line is
     ``[x1,y1,x2,y2, <C class probabilities>, <no-object probability>]`` and counts ONCE, as its arg-max class with that score,
     unless the no-object column is the overall arg-max (:109-126).  Pinned against the reference evaluator by
-    ``oracle/gen_eval_golden.py`` -> ``tests/golden/frame_map_ucf_case.json``."""
+    ``oracle/gen_eval_golden.py`` -> ``tests/golden/frame_map_ucf_case.json``.  ``stable``: as ``FrameMAP``; the rule
+    device_map.DeviceFrameMAPUCF computes by."""
 
-    def __init__(self, class_num=24, iou_threshold=0.5):
-        super().__init__(class_num, None, (), iou_threshold)
+    def __init__(self, class_num=24, iou_threshold=0.5, stable=False):
+        super().__init__(class_num, None, (), iou_threshold, stable=stable)
         self.num_categories = 24          # evaluate_ucf.py:15-20: the category list is the 24 UCF101-24 names whatever class_num is
 
     def load_gt(self, paths):
@@ -397,7 +398,9 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
     the HIP path, ``PostProcess``, the key frame's QUERY_NUM tubelet queries of every clip written to ``{rank}.txt`` (box + C+1
     class probabilities), ``binary_{rank}.txt`` (visibility probabilities) and ``GT_{rank}.txt`` (raw box + one-hot label), then
     frame-mAP@0.5 by ``FrameMAPUCF`` on rank 0.  Differences from the reference: barriers only when torch.distributed is
-    initialised; the one-hot width is max(21, NUM_CLASSES) (the reference hard-codes 21, :564, which UCF101-24 would overflow)."""
+    initialised; the one-hot width is max(21, NUM_CLASSES) (the reference hard-codes 21, :564, which UCF101-24 would overflow).
+    With ``CONFIG.VAL.DEVICE_MAP.ENABLE`` the same rows go from ``PostProcess.decode`` into a ``device_map.DeviceFrameMAPUCF`` and the
+    metric is computed on the device; the three files are written only with ``FILES``."""
     import torch.distributed as dist
     C = cfg.CONFIG
     ddp = dist.is_available() and dist.is_initialized()
@@ -414,18 +417,48 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
     Q, nc = C.MODEL.QUERY_NUM, C.DATA.NUM_CLASSES
     width = max(21, nc)
     buff_output, buff_anno, buff_id, buff_binary, gt_label, gt_anno, gt_id = [], [], [], [], [], [], []
+    dm = getattr(C.VAL, "DEVICE_MAP", None)
+    store, files = None, True
+    if dm is not None and dm.ENABLE:
+        from .device_map import DeviceFrameMAPUCF
+        store = DeviceFrameMAPUCF(class_num=nc, label_width=width, device=dev)
+        files = bool(dm.FILES)
+
+    def onehot_of(lab):
+        onehot = np.zeros((len(lab), width), dtype=np.int64)
+        for i in range(len(lab)):
+            onehot[i, int(lab[i])] = 1
+        return onehot
     meters = {k: [0.0, 0] for k in ("loss", "loss_bbox", "loss_giou", "loss_ce", "class_error")}
     end = time.time()
     for idx, data in enumerate(data_loader):
         samples, targets = data[0], data[1]
         samples = samples.to(dev)
         batch_id = [t["image_id"] for t in targets]
+        host_targets = targets               # the loader's own tensors: the device evaluator takes its ground truth from them, without a sync
         targets = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in t.items() if k != "image_id"} for t in targets]
         outputs = _forward_checked(model, samples)
         loss_dict = criterion(outputs, targets)
         sizes = torch.stack([t["size"] for t in targets], dim=0)
-        scores, boxes, output_b = postprocessors["bbox"](outputs, sizes)
-        for b in range(scores.shape[0]):
+        if store is None:
+            scores, boxes, output_b = postprocessors["bbox"](outputs, sizes)
+        else:
+            d_scores, d_boxes, d_binary = postprocessors["bbox"].decode(outputs, sizes)
+            if files:                        # what PostProcess.forward returns, bit for bit
+                scores, boxes, output_b = d_scores.cpu().numpy(), d_boxes.cpu().numpy(), d_binary.cpu().numpy()
+            first = None
+            for b in range(len(host_targets)):
+                raw = host_targets[b]["raw_boxes"]
+                if len(raw) == 0:
+                    continue
+                frame_id, key_pos = batch_id[b][0], int(batch_id[b][1])
+                store.add_detections([frame_id] * Q, d_boxes[b, key_pos * Q:(key_pos + 1) * Q, :], d_scores[b, key_pos * Q:(key_pos + 1) * Q, :])
+                raw = raw.reshape(-1, raw.shape[-1])
+                if first is None:
+                    first = float(host_targets[0]["raw_boxes"].reshape(-1, raw.shape[-1])[0, 0])
+                store.add_ground_truth([batch_id[int(float(raw[x, 0]) - first)][0] for x in range(len(raw))], raw[:, 2:6].double(),
+                                       onehot_of(host_targets[b]["labels"]))
+        for b in range(len(targets) if files else 0):
             raw = targets[b]["raw_boxes"]
             if len(raw) == 0:
                 continue
@@ -435,12 +468,8 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
             for _ in range(Q):
                 buff_id.append(frame_id)
                 buff_binary.append(output_b[..., 0])
-            lab = targets[b]["labels"]
-            onehot = np.zeros((len(lab), width), dtype=np.int64)
-            for i in range(len(lab)):
-                onehot[i, int(lab[i])] = 1
             raw = raw.reshape(-1, raw.shape[-1])
-            gt_label.append(onehot)
+            gt_label.append(onehot_of(targets[b]["labels"]))
             gt_anno.append(raw.detach().cpu().numpy())
             first = float(targets[0]["raw_boxes"].reshape(-1, raw.shape[-1])[0, 0])
             gt_id.extend(batch_id[int(float(raw[x, 0]) - first)][0] for x in range(len(raw)))
@@ -462,23 +491,29 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
     cat = lambda xs, w: np.concatenate(xs, axis=0) if xs else np.zeros((0, w))
     out_a, anno_a = cat(buff_output, nc + 1), cat(buff_anno, 4)
     gl, ga = cat(gt_label, width), cat(gt_anno, 6)
-    with open(os.path.join(res, "%d.txt" % rank), "w") as f:
-        for x in range(len(buff_id)):
-            f.write("{} {}\n".format(buff_id[x], np.concatenate([anno_a[x], out_a[x]]).tolist()))
-    with open(os.path.join(res, "binary_%d.txt" % rank), "w") as f:
-        for x in range(len(buff_id)):
-            f.write("{} {}\n".format(buff_id[x], np.asarray(buff_binary[x]).tolist()))
-    with open(os.path.join(res, "GT_%d.txt" % rank), "w") as f:
-        for x in range(len(gt_id)):
-            f.write("{} {}\n".format(gt_id[x], np.concatenate([ga[x], gl[x]]).tolist()))
+    if files:
+        with open(os.path.join(res, "%d.txt" % rank), "w") as f:
+            for x in range(len(buff_id)):
+                f.write("{} {}\n".format(buff_id[x], np.concatenate([anno_a[x], out_a[x]]).tolist()))
+        with open(os.path.join(res, "binary_%d.txt" % rank), "w") as f:
+            for x in range(len(buff_id)):
+                f.write("{} {}\n".format(buff_id[x], np.asarray(buff_binary[x]).tolist()))
+        with open(os.path.join(res, "GT_%d.txt" % rank), "w") as f:
+            for x in range(len(gt_id)):
+                f.write("{} {}\n".format(gt_id[x], np.concatenate([ga[x], gl[x]]).tolist()))
     if ddp:
         dist.barrier()
+    if store is not None and ddp:
+        store = store.all_gather_merge()     # every rank's rows in rank order: the order in which rank 0 loads the files
     mAP = 0
     if rank == 0:
-        ev = FrameMAPUCF(class_num=nc)
-        ev.load_gt([os.path.join(res, "GT_%d.txt" % r) for r in range(world)])
-        ev.load_detections([os.path.join(res, "%d.txt" % r) for r in range(world)])
-        mAP, per_class = ev.evaluate()
+        if store is not None:
+            mAP, per_class = store.evaluate()
+        else:
+            ev = FrameMAPUCF(class_num=nc)
+            ev.load_gt([os.path.join(res, "GT_%d.txt" % r) for r in range(world)])
+            ev.load_detections([os.path.join(res, "%d.txt" % r) for r in range(world)])
+            mAP, per_class = ev.evaluate()
         if verbose:
             print("mAP: %.5f" % mAP)
         if writer is not None:

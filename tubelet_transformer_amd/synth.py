@@ -213,3 +213,53 @@ def synthetic_frame_map_case(frames, dets=15, classes=80, seed=7, max_gt=5, gate
             det_keys.append(keys[f]); det_boxes.append(box)
     return dict(det_keys=det_keys, det_boxes=np.asarray(det_boxes, dtype=np.float32).reshape(n, 4), det_scores=scores, gt_keys=gt_keys,
                 gt_boxes=np.asarray(gt_boxes, dtype=np.float64).reshape(-1, 4), gt_labels=np.asarray(gt_labels, dtype=np.float64).reshape(-1, classes))
+
+
+def synthetic_frame_map_ucf_case(frames, dets=10, classes=21, seed=7, max_gt=3, tiny=0.05, no_object=0.25, near=0.6, hw=(240, 320)):
+    """A synthetic JHMDB / UCF101-24 validation result for evaluation.FrameMAPUCF and device_map.DeviceFrameMAPUCF: ``frames`` frames with
+    ``dets`` rows of ``classes + 1`` probabilities (the classes, then no-object) that sum to 1 and 0..``max_gt`` ground-truth boxes of one
+    class each.  The top value of row r is the fp32 number ``0.5 + 0.45 * (perm(n)[r] + 1) / (n + 1)``: distinct (their spacing is far above
+    an fp32 ulp), above 0.5 and therefore above every other entry of the row, so the arg-max is unambiguous, survives fp32 rounding, and no
+    class has two equal scores.  About ``no_object`` of the rows have no-object on top, about ``tiny`` of the ground-truth boxes measure
+    3 x 3 = 9 px^2 (their frame goes on the exclude list), about ``near`` of the detections sit near a ground-truth box of their frame (IoU
+    on both sides of 0.5) and mostly carry its class.  numpy arrays: ``det_keys`` [n], ``det_boxes`` [n, 4] fp32 xyxy, ``det_probs``
+    [n, C + 1] fp32, ``gt_keys`` [m], ``gt_boxes`` [m, 4] fp64, ``gt_labels`` [m, max(21, C)] fp64 one-hot."""
+    import numpy as np
+    n, C = frames * dets, classes
+    rng = np.random.default_rng(seed)
+    H, W = hw
+    width = max(21, C)
+    top = (0.5 + 0.45 * (rng.permutation(n) + 1.0) / (n + 1.0)).astype(np.float32)
+    keys = ["clip%03d_%05d" % (f // 40, 1 + f % 40) for f in range(frames)]
+    det_keys, det_boxes, det_top, gt_keys, gt_boxes, gt_labels = [], [], [], [], [], []
+    for f in range(frames):
+        g = int(rng.integers(0, max_gt + 1))
+        xy = rng.uniform(0, 0.6, (g, 2)) * [W, H]
+        wh = rng.uniform(0.15, 0.4, (g, 2)) * [W, H]
+        gb = np.concatenate([xy, xy + wh], axis=1).astype(np.float32).astype(np.float64)
+        gc = rng.integers(0, C, g)
+        for j in range(g):
+            if rng.random() < tiny:
+                gb[j, 2:] = gb[j, :2] + 3.0
+            lab = np.zeros(width)
+            lab[gc[j]] = 1.0
+            gt_keys.append(keys[f]); gt_boxes.append(gb[j].copy()); gt_labels.append(lab)
+        for i in range(dets):
+            a = int(rng.integers(0, C))
+            if g and rng.random() < near:
+                j = int(rng.integers(0, g))
+                box = gb[j] + rng.normal(0, 0.1, 4) * np.tile(gb[j, 2:] - gb[j, :2], 2)
+                if rng.random() < 0.8:
+                    a = int(gc[j])
+            else:
+                p = rng.uniform(0, 0.7, 2) * [W, H]
+                box = np.concatenate([p, p + rng.uniform(0.1, 0.3, 2) * [W, H]])
+            if rng.random() < no_object:
+                a = C
+            det_keys.append(keys[f]); det_boxes.append(box); det_top.append(a)
+    rest = rng.uniform(0.05, 1.0, (n, C + 1))
+    rest[np.arange(n), det_top] = 0.0
+    probs = ((1.0 - top.astype(np.float64))[:, None] * rest / rest.sum(axis=1, keepdims=True)).astype(np.float32)
+    probs[np.arange(n), det_top] = top
+    return dict(det_keys=det_keys, det_boxes=np.asarray(det_boxes, dtype=np.float32).reshape(n, 4), det_probs=probs, gt_keys=gt_keys,
+                gt_boxes=np.asarray(gt_boxes, dtype=np.float64).reshape(-1, 4), gt_labels=np.asarray(gt_labels, dtype=np.float64).reshape(-1, width))
