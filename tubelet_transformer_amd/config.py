@@ -154,7 +154,11 @@ def get_cfg_defaults():
         # (device_map.py; not reference keys): ENABLE keeps detections and ground truth in device buffers and runs the frame_map.hip
         # kernels instead of the host FrameMAP / FrameMAPUCF over the result files; FILES: the per-rank result files are written as
         # well (reference format), False: no file, no host copy of the detections
-        DEVICE_MAP=dict(ENABLE=False, FILES=True)), new_allowed=True)
+        DEVICE_MAP=dict(ENABLE=False, FILES=True),
+        # video-mAP of validate_tuber_ucf_detection over linked action tubes (evaluation.VideoMAP / device_map.DeviceVideoMAP; not reference
+        # keys): consecutive detections of a class link when their IoU is at least LINK_IOU, over at most MAX_GAP empty frames; tubes shorter
+        # than MIN_LEN are not counted; THRESHOLDS: spatio-temporal IoU thresholds, "0.5:0.95" the mean over 0.50, 0.55, ..., 0.95
+        VIDEO_MAP=dict(ENABLE=False, LINK_IOU=0.2, MAX_GAP=2, MIN_LEN=1, THRESHOLDS=[0.2, 0.5, 0.75, "0.5:0.95"])), new_allowed=True)
     cfg.DATA = CfgNode(dict(
         DATASET_NAME="ava", NUM_CLASSES=80, IMG_SIZE=256, TEMP_LEN=32, FRAME_RATE=2), new_allowed=True)
     cfg.MODEL = CfgNode(dict(
@@ -173,6 +177,33 @@ def get_cfg_defaults():
                            EVAL_DIR="", SAVE_FREQ=1, RES_DIR="tmp"), new_allowed=True)
     C.CONFIG = cfg
     return C
+
+
+def video_map_settings(cfg):
+    """CONFIG.VAL.VIDEO_MAP validated -> the keyword arguments of ``VideoMAP`` / ``DeviceVideoMAP``; a bad value raises ValueError naming its key"""
+    vm = cfg.CONFIG.VAL.VIDEO_MAP
+
+    def bad(key, why):
+        raise ValueError("CONFIG.VAL.VIDEO_MAP.%s = %r: %s" % (key, vm[key], why))
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v
+    if not isinstance(vm.ENABLE, bool):
+        bad("ENABLE", "must be True or False")
+    if not number(vm.LINK_IOU) or not 0.0 <= vm.LINK_IOU <= 1.0:
+        bad("LINK_IOU", "must be a number in [0, 1]")
+    if not isinstance(vm.MAX_GAP, int) or isinstance(vm.MAX_GAP, bool) or vm.MAX_GAP < 0:
+        bad("MAX_GAP", "must be an integer >= 0")
+    if not isinstance(vm.MIN_LEN, int) or isinstance(vm.MIN_LEN, bool) or vm.MIN_LEN < 1:
+        bad("MIN_LEN", "must be an integer >= 1")
+    thr = vm.THRESHOLDS
+    if not isinstance(thr, (list, tuple)) or len(thr) == 0:
+        bad("THRESHOLDS", "must be a non-empty list")
+    for t in thr:
+        if not (t == "0.5:0.95" or (number(t) and 0.0 < t <= 1.0)):
+            bad("THRESHOLDS", 'every entry must be a number in (0, 1] or "0.5:0.95" (got %r)' % (t,))
+    if len(set(thr)) != len(thr):
+        bad("THRESHOLDS", "entries must be distinct")
+    return dict(link_iou=float(vm.LINK_IOU), max_gap=int(vm.MAX_GAP), min_len=int(vm.MIN_LEN),
+                thresholds=tuple(t if t == "0.5:0.95" else float(t) for t in thr))
 
 
 def load_cfg(path):

@@ -10,11 +10,9 @@
 //   2. ranked_ap_kernel     a workgroup per class over that class's flags in rank order: VOC average precision (area under the monotone
 //                           precision envelope) in fp64 from two sweeps over 4096-entry chunks with carries
 // No atomics, fixed reduction trees: the same input gives the same bits.  Both are bound by their flag / score traffic, not by arithmetic.
-#include "common.h"
+#include "map_common.h"          // FMAP_MAX_DETS / FMAP_MAX_GT, fmap_iou, fmap_key, fmap_argmax: shared with tube_map.hip
 #include <float.h>
 
-#define FMAP_MAX_DETS 64          // detections per frame: the valid set is one 64-bit mask, a row index fits the low word of the order key
-#define FMAP_MAX_GT 32            // ground-truth boxes per frame: candidate and taken sets are 32-bit masks
 #define FMAP_THREADS 128          // two waves: C = 80 classes in one trip
 #define FMAP_NOT_COUNTED 2
 #define FMAP_BEYOND_BOUNDS 3
@@ -22,33 +20,6 @@
 #define RAP_THREADS 256
 #define RAP_PER 16                // flags per thread and chunk: one 16-byte load where the row is aligned
 #define RAP_CHUNK (RAP_THREADS * RAP_PER)
-
-// IoU of an fp32 detection box with an fp64 ground-truth box, expression for expression evaluation._iou_one_to_many in fp64; no FMA
-// contraction, so that a decision at exactly the threshold falls as it does on the host
-__device__ __forceinline__ double fmap_iou(const float* __restrict__ d, const double* __restrict__ g) {
-#pragma clang fp contract(off)
-    const double b0 = (double)d[0], b1 = (double)d[1], b2 = (double)d[2], b3 = (double)d[3];
-    const double g0 = g[0], g1 = g[1], g2 = g[2], g3 = g[3];
-    const double x1 = fmax(b0, g0), y1 = fmax(b1, g1), x2 = fmin(b2, g2), y2 = fmin(b3, g3);
-    const double w = fmax(x2 - x1, 0.0), h = fmax(y2 - y1, 0.0);
-    const double inter = w * h;
-    const double a = (b2 - b0) * (b3 - b1);
-    const double b = (g2 - g0) * (g3 - g1);
-    const double u = a + b;
-    return inter / (u - inter);
-}
-
-// order key of (score, row in frame): a larger key is visited earlier.  High word: the score as an order-preserving unsigned (-0 == +0, NaN below
-// everything: np.argsort(-score) puts NaN last); low word: ~row, so equal scores go by ascending row.
-__device__ __forceinline__ unsigned long long fmap_key(float s, int k) {
-    unsigned u = __float_as_uint(s);
-    if (s != s) u = 0u;
-    else {
-        if (s == 0.f) u = 0u;
-        u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-    }
-    return ((unsigned long long)u << 32) | (unsigned long long)(0xFFFFFFFFu - (unsigned)k);
-}
 
 __global__ __launch_bounds__(FMAP_THREADS) void frame_match_kernel(const float* __restrict__ det_box, const float* __restrict__ det_score,
                                                                    const int* __restrict__ det_off, const double* __restrict__ gt_box,
@@ -156,12 +127,7 @@ __global__ __launch_bounds__(64 * FTOP_WAVES) void frame_match_top1_kernel(const
     bool hit = false;
     if (have) {
         const float* p = det_prob + (long)(d0 + lane) * (C + 1);
-        a = 0;
-        score = p[0];
-        for (int c = 1; c <= C; ++c) {
-            const float v = p[c];
-            if (score == score && (v > score || v != v)) { a = c; score = v; }
-        }
+        a = fmap_argmax(p, C, score);
         const float* d = det_box + (long)(d0 + lane) * 4;
         counted = a != C && d[0] < d[2] && d[1] < d[3] && !skip;
         if (counted) {

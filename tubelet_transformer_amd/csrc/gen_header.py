@@ -330,6 +330,28 @@ DOC = {
                        "evaluates/utils/metrics.py compute_precision_recall + compute_average_precision) from flags_ranked [C][N] bytes in rank order (1 true positive, 0 false positive, "
                        "anything else counts nowhere) and n_gt [C]: ap [C] fp64, NaN where n_gt <= 0, 0.0 where nothing is counted; n_tp [C] true positives (NULL: not wanted). One workgroup "
                        "per class, fp64, two sweeps over 4096-entry chunks with carries in a fixed order: no atomics, the same bits every run. N == 0 is legal.",
+    "tuber_tube_link": "video-mAP on the device, linking step (evaluation.VideoMAP.link: the definition; the reference ships the frame-level evaluator "
+                       "evaluates/evaluate_ucf.py only): det_box [N][4] fp32 xyxy / det_prob [N][C + 1] fp32 in layout order (video, slot, store order), slot_off DEVICE "
+                       "int[S + 1] rows per slot, video_off DEVICE int[V + 1] slots per video. A row counts as one detection of its arg-max column (np.argmax; not when that "
+                       "is no-object, the box has x1 >= x2 or y1 >= y2, or the probability is NaN). Per (video, class), slots ascending: the tubes whose last detection is "
+                       "at most max_gap + 1 slots back are visited by descending mean score (fp64 sum of the fp32 scores / count), equal means by ascending head; each takes, "
+                       "among the slot's unclaimed rows of the class whose fp64 IoU with its last box is >= link_iou, the highest score (equal scores by ascending row); rows "
+                       "left over start tubes. Out: row_cls [N] the arg-max column, row_head [N] the layout row of the tube's first detection (-1: not counted), and at head "
+                       "rows tube_score (fp64 mean), tube_len, tube_last (last slot). max_rows: the largest number of rows in a slot (the caller knows it). max_rows > "
+                       "tuber_frame_match_max_dets(), max_rows * (max_gap + 1) > tuber_tube_link_max_active(), N > S * max_rows, bad sizes or pointers: negative, nothing "
+                       "launched. One wave per (video, class): a lane holds one active tube and one row of the slot; no LDS, no atomics.",
+    "tuber_tube_link_max_active": "simultaneously active tubes of one (video, class) tuber_tube_link takes: max rows per slot x (max_gap + 1) (64).",
+    "tuber_tube_match": "video-mAP on the device, matching step (evaluation.VideoMAP.match): the tuber_tube_link outputs against ground-truth tubes given as gt_box [G][4] fp64 / "
+                        "gt_cls [G] / gt_tube [G] (the rank of the row's tube among the tube ids of its (video, class), ascending; one row per (slot, class, tube)) in slot order "
+                        "with gt_off DEVICE int[S + 1]. stIoU(d, g) = sum over the shared slots of the fp64 IoU / |slots of d or g|, 0 without a shared slot. Per (video, class) the "
+                        "tubes of at least min_len detections are visited by descending score (equal scores by ascending head); per threshold (thresholds DEVICE double[T]) a tube "
+                        "takes the not yet taken ground-truth tube of largest stIoU (the first maximum) and is a true positive iff that stIoU >= threshold. tube_flag [T][N] bytes: "
+                        "1 true positive, 0 false positive, 2 not counted (not a head, shorter than min_len), 3 a (video, class) beyond the bounds. work: caller-owned "
+                        "double[N * max(max_gt_tubes, 1)]. max_rows / max_gt_rows / max_gt_tubes: largest rows and ground-truth rows per slot, ground-truth tubes per (video, "
+                        "class). T > tuber_tube_match_max_thresholds(), max_gt_tubes > tuber_tube_match_max_gt(), max_rows > tuber_frame_match_max_dets(), max_gt_rows > "
+                        "tuber_frame_match_max_gt(), bad sizes or pointers: negative, nothing launched. One wave per (video, class), sums in slot order: the same bits every run.",
+    "tuber_tube_match_max_gt": "ground-truth tubes per (video, class) tuber_tube_match takes (32).",
+    "tuber_tube_match_max_thresholds": "thresholds per call tuber_tube_match takes (16).",
     "tuber_tensor_stats_chunk": "largest number of elements in one chunk of tuber_tensor_stats (a multiple of 64).",
     "tuber_tensor_stats_tensor_bytes": "sizeof(TensorStatsTensor) as compiled (host-side layout check).",
     "tuber_tensor_stats_chunk_bytes": "sizeof(TensorStatsChunk) as compiled (host-side layout check).",

@@ -1,0 +1,341 @@
+// Video-mAP of the JHMDB / UCF101-24 validation loop on the device (gfx950): the two sequential steps behind device_map.DeviceVideoMAP.  They
+// restate evaluation.VideoMAP, which is the definition (the reference ships no tube linking and no video-level evaluator).
+//   1. tube_rows_kernel     a thread per row: the arg-max column of its C + 1 probabilities
+//      tube_link_kernel     a wave per (video, class) walks the video's slots in order.  A lane holds one active tube (last box, fp64 score sum,
+//                           count, last slot, head) AND one row of the current slot; the visiting order of the tubes is a rank over
+//                           (mean score, head), the pick of a tube a wave arg-max over the order keys of the rows it may take.
+//   2. tube_match_kernel    a wave per (video, class): walks the slots again with the live tubes in lanes and adds the per-slot IoU against the
+//                           ground-truth boxes of the class into a [64][32] table (tube lane x ground-truth tube), writes a tube's spatio-temporal
+//                           IoU row when the tube ends, then visits the counted tubes by descending score and matches them greedily, a lane per
+//                           threshold with its taken set in one 32-bit mask.
+// No floating-point atomics, every sum sequential in slot order: the same input gives the same bits.
+#include "map_common.h"
+
+#define TUBE_MAX_ACTIVE 64        // simultaneously active tubes of one (video, class): a lane each
+#define TUBE_MAX_GT 32            // ground-truth tubes of one (video, class): the taken set is one 32-bit mask
+#define TUBE_MAX_THR 16           // thresholds of one call
+#define TUBE_NOT_COUNTED 2
+#define TUBE_BEYOND_BOUNDS 3
+#define TLINK_WAVES 4             // (video, class) pairs per workgroup of the link kernel: a wave each
+#define TMATCH_LD 33              // leading dimension of the LDS tables of the match kernel
+
+__device__ __forceinline__ unsigned long long tube_wave_max(unsigned long long k) {
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long t = __shfl_xor(k, o, 64);
+        k = t > k ? t : k;
+    }
+    return k;
+}
+
+// a double as an order-preserving unsigned (-0 == +0, NaN below everything)
+__device__ __forceinline__ unsigned long long tube_ord(double s) {
+    unsigned long long u = (unsigned long long)__double_as_longlong(s);
+    if (s != s) return 0ull;
+    if (s == 0.0) u = 0ull;
+    return (u & 0x8000000000000000ull) ? ~u : (u | 0x8000000000000000ull);
+}
+
+__global__ __launch_bounds__(256) void tube_rows_kernel(const float* __restrict__ det_prob, int N, int C, int* __restrict__ row_cls,
+                                                        int* __restrict__ row_head) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= N) return;
+    float score;
+    row_cls[r] = fmap_argmax(det_prob + (long)r * (C + 1), C, score);
+    row_head[r] = -1;
+}
+
+__global__ __launch_bounds__(64 * TLINK_WAVES) void tube_link_kernel(const float* __restrict__ det_box, const float* __restrict__ det_prob,
+                                                                     const int* __restrict__ slot_off, const int* __restrict__ video_off, int V,
+                                                                     int S, int N, int C, double link_iou, int max_gap,
+                                                                     const int* __restrict__ row_cls, int* __restrict__ row_head,
+                                                                     double* __restrict__ tube_score, int* __restrict__ tube_len,
+                                                                     int* __restrict__ tube_last) {
+    const int lane = threadIdx.x & 63;
+    const long w = (long)blockIdx.x * TLINK_WAVES + (threadIdx.x >> 6);           // wave-uniform from here on
+    if (w >= (long)V * C) return;
+    const int v = (int)(w / C), c = (int)(w % C);
+    const int s0 = video_off[v], s1 = video_off[v + 1];
+    if (s0 < 0 || s1 < s0 || s1 > S) return;                                      // not a CSR row of these arrays: touch nothing
+    const int limit = max_gap + 1 > TUBE_MAX_ACTIVE ? 0 : TUBE_MAX_ACTIVE / (max_gap + 1);
+    // the tube this lane holds
+    bool valid = false;
+    float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
+    double sum = 0.0;
+    int cnt = 0, last = 0, head = 0;
+    for (int s = s0; s < s1; ++s) {
+        const int r0 = slot_off[s], r1 = slot_off[s + 1];
+        if (r0 < 0 || r1 < r0 || r1 > N) return;
+        const int n = r1 - r0;
+        if (n > limit) return;                                                    // the caller's bookkeeping should have kept this video away
+        if (n == 0) continue;
+        // the row this lane holds: counted rows of the wave's class
+        const int r = r0 + lane;
+        bool mine = false;
+        float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f, sc = 0.f;
+        if (lane < n && row_cls[r] == c) {
+            const float* d = det_box + (long)r * 4;
+            b0 = d[0]; b1 = d[1]; b2 = d[2]; b3 = d[3];
+            sc = det_prob[(long)r * (C + 1) + c];
+            mine = b0 < b2 && b1 < b3 && sc == sc;
+        }
+        if (!__ballot(mine)) continue;
+        // the active tubes in visiting order: rank = tubes in front of this one (mean score descending, then head ascending)
+        const bool active = valid && s - last <= max_gap + 1;
+        const unsigned long long amask = __ballot(active);
+        const double mean = active ? sum / (double)cnt : 0.0;
+        int rank = 0;
+        for (unsigned long long m = amask; m; m &= m - 1) {
+            const int j = __ffsll((long long)m) - 1;
+            const double mj = __shfl(mean, j, 64);
+            const int hj = __shfl(head, j, 64);
+            rank += (mj > mean || (mj == mean && hj < head)) ? 1 : 0;
+        }
+        const int na = __popcll(amask);
+        bool claimed = false;
+        for (int k = 0; k < na; ++k) {
+            const unsigned long long tm = __ballot(active && rank == k);
+            if (!tm) continue;
+            const int t = __ffsll((long long)tm) - 1;
+            const float l0 = __shfl(t0, t, 64), l1 = __shfl(t1, t, 64), l2 = __shfl(t2, t, 64), l3 = __shfl(t3, t, 64);
+            const double iou = fmap_iou_d((double)l0, (double)l1, (double)l2, (double)l3, (double)b0, (double)b1, (double)b2, (double)b3);
+            const bool elig = mine && !claimed && iou >= link_iou;
+            const unsigned long long best = tube_wave_max(elig ? fmap_key(sc, lane) : 0ull);   // a key is > 0: its low word is >= ~63
+            if (!best) continue;
+            const int p = (int)(0xFFFFFFFFu - (unsigned)(best & 0xFFFFFFFFull));
+            const float n0 = __shfl(b0, p, 64), n1 = __shfl(b1, p, 64), n2 = __shfl(b2, p, 64), n3 = __shfl(b3, p, 64);
+            const float ns = __shfl(sc, p, 64);
+            const int ht = __shfl(head, t, 64);
+            if (lane == p) {
+                claimed = true;
+                row_head[r] = ht;
+            }
+            if (lane == t) {
+                t0 = n0; t1 = n1; t2 = n2; t3 = n3;
+                sum += (double)ns;
+                cnt += 1;
+                last = s;
+                tube_score[head] = sum / (double)cnt;
+                tube_len[head] = cnt;
+                tube_last[head] = s;
+            }
+        }
+        // the rows nobody took start tubes, in the lanes of tubes that cannot be active at the next slot
+        unsigned long long um = __ballot(mine && !claimed);
+        unsigned long long fm = __ballot(!valid || s - last > max_gap);
+        for (; um; um &= um - 1) {
+            if (!fm) return;                                                      // cannot happen within the bounds the launcher checks
+            const int p = __ffsll((long long)um) - 1;
+            const int t = __ffsll((long long)fm) - 1;
+            fm &= fm - 1;
+            const float n0 = __shfl(b0, p, 64), n1 = __shfl(b1, p, 64), n2 = __shfl(b2, p, 64), n3 = __shfl(b3, p, 64);
+            const float ns = __shfl(sc, p, 64);
+            if (lane == p) row_head[r] = r;
+            if (lane == t) {
+                valid = true;
+                t0 = n0; t1 = n1; t2 = n2; t3 = n3;
+                sum = (double)ns;
+                cnt = 1;
+                last = s;
+                head = r0 + p;
+                tube_score[head] = sum;
+                tube_len[head] = 1;
+                tube_last[head] = s;
+            }
+        }
+    }
+}
+
+__global__ __launch_bounds__(64) void tube_match_kernel(const float* __restrict__ det_box, const int* __restrict__ slot_off,
+                                                        const int* __restrict__ video_off, const int* __restrict__ row_cls,
+                                                        const int* __restrict__ row_head, const double* __restrict__ tube_score,
+                                                        const int* __restrict__ tube_len, const int* __restrict__ tube_last,
+                                                        const double* __restrict__ gt_box, const int* __restrict__ gt_cls,
+                                                        const int* __restrict__ gt_tube, const int* __restrict__ gt_off,
+                                                        const double* __restrict__ thresholds, int S, int N, int G, int C, int T, int K, int min_len,
+                                                        double* __restrict__ work, unsigned char* __restrict__ tube_flag) {
+    __shared__ double s_acc[TUBE_MAX_ACTIVE * TMATCH_LD];                         // [tube lane][ground-truth tube]: sum of the per-slot IoU
+    __shared__ int s_cnt[TUBE_MAX_ACTIVE * TMATCH_LD];                            // slots the two share
+    __shared__ int s_glen[TUBE_MAX_GT];                                           // slots of a ground-truth tube; 0: no such tube
+    const int lane = threadIdx.x;
+    const int v = blockIdx.x / C, c = blockIdx.x % C;
+    const int s0 = video_off[v], s1 = video_off[v + 1];
+    if (s0 < 0 || s1 < s0 || s1 > S) return;
+    const int R0 = slot_off[s0], R1 = slot_off[s1], G0 = gt_off[s0], G1 = gt_off[s1];
+    if (R0 < 0 || R1 < R0 || R1 > N || G0 < 0 || G1 < G0 || G1 > G) return;
+    const int KS = K > 0 ? K : 1;
+    if (lane < TUBE_MAX_GT) s_glen[lane] = 0;
+    __syncthreads();
+    for (int i = G0 + lane; i < G1; i += 64) {
+        const int k = gt_tube[i];
+        if (gt_cls[i] == c && k >= 0 && k < K) atomicAdd(&s_glen[k], 1);          // integers: any order
+    }
+    __syncthreads();
+
+    // phase 1: the spatio-temporal IoU of every tube of the class with every ground-truth tube of the class
+    bool valid = false, beyond = false;
+    int head = -1, last = -1, len = 0;
+    for (int s = s0; s < s1 && !beyond; ++s) {
+        const int r0 = slot_off[s], r1 = slot_off[s + 1], g0 = gt_off[s], g1 = gt_off[s + 1];
+        if (r0 < R0 || r1 < r0 || r1 > R1 || g0 < G0 || g1 < g0 || g1 > G1) return;
+        const int n = r1 - r0, g = g1 - g0;
+        if (n > FMAP_MAX_DETS || g > FMAP_MAX_GT) { beyond = true; break; }
+        const int r = r0 + lane;
+        int rh = -1;
+        float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
+        if (lane < n && row_cls[r] == c) {
+            rh = row_head[r];
+            if (rh < R0 || rh > r) rh = -1;
+            if (rh >= 0) {
+                const float* d = det_box + (long)r * 4;
+                b0 = d[0]; b1 = d[1]; b2 = d[2]; b3 = d[3];
+            }
+        }
+        int gk = -1;
+        double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
+        if (lane < g && gt_cls[g0 + lane] == c) {
+            const int k = gt_tube[g0 + lane];
+            if (k >= 0 && k < K) {
+                const double* q = gt_box + (long)(g0 + lane) * 4;
+                gk = k; q0 = q[0]; q1 = q[1]; q2 = q[2]; q3 = q[3];
+            }
+        }
+        for (unsigned long long m = __ballot(rh >= 0); m; m &= m - 1) {
+            const int p = __ffsll((long long)m) - 1;
+            const int h = __shfl(rh, p, 64);
+            const unsigned long long tm = __ballot(valid && head == h);
+            int t;
+            if (tm) {
+                t = __ffsll((long long)tm) - 1;
+            } else {                                                              // a tube begins: a free lane, its table row zeroed
+                const unsigned long long fm = ~__ballot(valid);
+                if (!fm) { beyond = true; break; }
+                t = __ffsll((long long)fm) - 1;
+                if (lane == t) {
+                    valid = true;
+                    head = h;
+                    last = tube_last[h];
+                    len = tube_len[h];
+                }
+                if (lane < TUBE_MAX_GT) {
+                    s_acc[t * TMATCH_LD + lane] = 0.0;
+                    s_cnt[t * TMATCH_LD + lane] = 0;
+                }
+                __syncthreads();
+            }
+            const float p0 = __shfl(b0, p, 64), p1 = __shfl(b1, p, 64), p2 = __shfl(b2, p, 64), p3 = __shfl(b3, p, 64);
+            if (gk >= 0) {
+                s_acc[t * TMATCH_LD + gk] += fmap_iou_d((double)p0, (double)p1, (double)p2, (double)p3, q0, q1, q2, q3);
+                s_cnt[t * TMATCH_LD + gk] += 1;
+            }
+        }
+        if (beyond) break;
+        __syncthreads();
+        if (valid && last <= s) {                                                 // the tube ends here: its row of the overlap table
+            for (int k = 0; k < K; ++k) {
+                const int shared = s_cnt[lane * TMATCH_LD + k];
+                work[(long)head * KS + k] = shared > 0 ? s_acc[lane * TMATCH_LD + k] / (double)(len + s_glen[k] - shared) : 0.0;
+            }
+            valid = false;
+        }
+        __syncthreads();
+    }
+    if (beyond) {                                                                 // nothing decided for this (video, class)
+        for (int r = R0 + lane; r < R1; r += 64)
+            if (row_cls[r] == c && row_head[r] == r)
+                for (int i = 0; i < T; ++i) tube_flag[(long)i * N + r] = TUBE_BEYOND_BOUNDS;
+        return;
+    }
+    __threadfence();
+    __syncthreads();
+
+    // phase 2: the counted tubes by descending score (equal scores by ascending head), a lane per threshold
+    const double thr = lane < T ? thresholds[lane] : 0.0;
+    unsigned taken = 0u;
+    unsigned long long last_hi = ~0ull, last_lo = ~0ull;
+    for (;;) {
+        unsigned long long best_hi = 0ull, best_lo = 0ull;                        // a real key has lo > 0
+        for (int r = R0 + lane; r < R1; r += 64) {
+            if (row_cls[r] != c || row_head[r] != r || tube_len[r] < min_len) continue;
+            const unsigned long long hi = tube_ord(tube_score[r]), lo = 0xFFFFFFFFull - (unsigned long long)(r - R0);
+            if (!(hi < last_hi || (hi == last_hi && lo < last_lo))) continue;
+            if (hi > best_hi || (hi == best_hi && lo > best_lo)) { best_hi = hi; best_lo = lo; }
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long oh = __shfl_xor(best_hi, o, 64), ol = __shfl_xor(best_lo, o, 64);
+            if (oh > best_hi || (oh == best_hi && ol > best_lo)) { best_hi = oh; best_lo = ol; }
+        }
+        if (!best_lo) break;
+        last_hi = best_hi;
+        last_lo = best_lo;
+        const int h = R0 + (int)(0xFFFFFFFFull - best_lo);
+        if (lane < T) {
+            int bk = -1;                                                          // the largest overlap among the tubes not taken, the first one
+            double bv = 0.0;
+            for (int k = 0; k < K; ++k) {
+                if (s_glen[k] <= 0 || ((taken >> k) & 1u)) continue;
+                // read at device scope: the row was written by another lane of this wave, and a neighbouring workgroup on this CU may have
+                // pulled the cache line into the vector L1 before that
+                const double x = __longlong_as_double((long long)__hip_atomic_load((const unsigned long long*)(work + (long)h * KS + k),
+                                                                                 __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+                if (bk < 0 || x > bv) { bk = k; bv = x; }
+            }
+            const bool tp = bk >= 0 && bv >= thr;
+            if (tp) taken |= 1u << bk;
+            tube_flag[(long)lane * N + h] = tp ? 1 : 0;
+        }
+    }
+}
+
+extern "C" {
+
+// Linking of per-frame detections into action tubes (evaluation.VideoMAP.link).  det_box [N][4] fp32 xyxy / det_prob [N][C + 1] fp32 in layout order
+// (video, slot, store order); slot_off DEVICE int[S + 1]: rows per slot; video_off DEVICE int[V + 1]: slots per video.  max_rows: the largest
+// number of rows in one slot, which the caller knows.  Refused (negative, nothing launched): max_rows beyond tuber_frame_match_max_dets(),
+// max_rows * (max_gap + 1) beyond tuber_tube_link_max_active(), sizes no slot list can meet, bad sizes or pointers.
+int tuber_tube_link(const float* det_box, const float* det_prob, const int* slot_off, const int* video_off, int V, int S, int N, int C, int max_rows,
+                    double link_iou, int max_gap, int* row_cls, int* row_head, double* tube_score, int* tube_len, int* tube_last,
+                    hipStream_t stream) {
+    if (V < 0 || S < 0 || N < 0 || C <= 0 || max_rows < 0 || max_gap < 0 || !(link_iou == link_iou)) return TUBER_EINVAL;
+    if (max_rows > FMAP_MAX_DETS || (long)max_rows * ((long)max_gap + 1) > TUBE_MAX_ACTIVE) return TUBER_EINVAL;
+    if ((long)N > (long)S * max_rows || S < V) return TUBER_EINVAL;
+    if (N == 0) return TUBER_OK;
+    if ((long)V * C > 0x7FFFFFFFl) return TUBER_EINVAL;
+    if (!det_box || !det_prob || !slot_off || !video_off || !row_cls || !row_head || !tube_score || !tube_len || !tube_last) return TUBER_EINVAL;
+    hipLaunchKernelGGL(tube_rows_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, det_prob, N, C, row_cls, row_head);
+    const long waves = (long)V * C;
+    hipLaunchKernelGGL(tube_link_kernel, dim3((unsigned)((waves + TLINK_WAVES - 1) / TLINK_WAVES)), dim3(64 * TLINK_WAVES), 0, stream, det_box,
+                       det_prob, slot_off, video_off, V, S, N, C, link_iou, max_gap, row_cls, row_head, tube_score, tube_len, tube_last);
+    TUBER_RETURN_LAUNCH();
+}
+int tuber_tube_link_max_active() { return TUBE_MAX_ACTIVE; }
+
+// Spatio-temporal matching of the linked tubes against the ground-truth tubes (evaluation.VideoMAP.match).  The link outputs; gt_box [G][4] fp64,
+// gt_cls [G], gt_tube [G] (the rank of the row's tube among the tube ids of its (video, class), ascending; one row per (slot, class, tube)) in slot
+// order, gt_off DEVICE int[S + 1]; thresholds DEVICE double[T]; work: caller-owned double[N * max(max_gt_tubes, 1)].  max_rows, max_gt_rows,
+// max_gt_tubes: the largest rows / ground-truth rows per slot and ground-truth tubes per (video, class), which the caller knows.  tube_flag [T][N]
+// bytes out: 1 true positive, 0 false positive, 2 not counted (not a head, or shorter than min_len), 3 a (video, class) beyond the bounds.
+int tuber_tube_match(const float* det_box, const int* slot_off, const int* video_off, const int* row_cls, const int* row_head,
+                     const double* tube_score, const int* tube_len, const int* tube_last, const double* gt_box, const int* gt_cls,
+                     const int* gt_tube, const int* gt_off, const double* thresholds, int V, int S, int N, int G, int C, int T, int max_rows,
+                     int max_gt_rows, int max_gt_tubes, int min_len, double* work, unsigned char* tube_flag, hipStream_t stream) {
+    if (V < 0 || S < 0 || N < 0 || G < 0 || C <= 0 || T <= 0 || max_rows < 0 || max_gt_rows < 0 || max_gt_tubes < 0) return TUBER_EINVAL;
+    if (T > TUBE_MAX_THR || max_gt_tubes > TUBE_MAX_GT || max_rows > FMAP_MAX_DETS || max_gt_rows > FMAP_MAX_GT) return TUBER_EINVAL;
+    if ((long)N > (long)S * max_rows || (long)G > (long)S * max_gt_rows || S < V) return TUBER_EINVAL;
+    if (N == 0) return TUBER_OK;
+    if ((long)V * C > 0x7FFFFFFFl || (long)T * N > 0x7FFFFFFFl) return TUBER_EINVAL;
+    if (!det_box || !slot_off || !video_off || !row_cls || !row_head || !tube_score || !tube_len || !tube_last || !gt_off || !thresholds || !work ||
+        !tube_flag)
+        return TUBER_EINVAL;
+    if (G > 0 && (!gt_box || !gt_cls || !gt_tube)) return TUBER_EINVAL;
+    const hipError_t e = hipMemsetAsync(tube_flag, TUBE_NOT_COUNTED, (size_t)T * N, stream);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(tube_match_kernel, dim3((unsigned)(V * C)), dim3(64), 0, stream, det_box, slot_off, video_off, row_cls, row_head, tube_score,
+                       tube_len, tube_last, gt_box, gt_cls, gt_tube, gt_off, thresholds, S, N, G, C, T, max_gt_tubes, min_len, work, tube_flag);
+    TUBER_RETURN_LAUNCH();
+}
+int tuber_tube_match_max_gt() { return TUBE_MAX_GT; }
+int tuber_tube_match_max_thresholds() { return TUBE_MAX_THR; }
+
+}  // extern "C"

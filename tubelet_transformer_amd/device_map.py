@@ -16,6 +16,10 @@ A store on the CPU, and a store with a frame beyond the kernel's bounds (``tuber
 
 ``DeviceFrameMAPUCF`` is the same store under the JHMDB / UCF101-24 counting rule of ``evaluation.FrameMAPUCF`` (``validate_tuber_ucf_detection``):
 a row of C + 1 probabilities is one detection, of its arg-max class; the matching step is ``tuber_frame_match_top1``, the rest is shared.
+
+``DeviceVideoMAP`` is that store again with the tube id of every ground-truth line: besides frame-mAP it links the rows into action tubes
+(``tuber_tube_link``), matches them against the ground-truth tubes by spatio-temporal IoU (``tuber_tube_match``, csrc/tube_map.hip) and gives
+video-mAP at several thresholds -- ``evaluation.VideoMAP`` on the device.
 """
 import logging
 
@@ -24,6 +28,7 @@ import torch
 
 from . import lib
 from .evaluation import FrameMAP, FrameMAPUCF, mean_ap
+from . import evaluation as _ev
 
 log = logging.getLogger(__name__)
 
@@ -120,6 +125,10 @@ class DeviceFrameMAP:
             self._gt_box.append(boxes[i])
             self._gt_lab.append(labels[i])
 
+    def _gt_extra(self):
+        """further per-line ground truth a subclass stores, as keyword arguments of its ``add_ground_truth`` (``merge`` carries them)"""
+        return {}
+
     def gt_arrays(self):
         """(boxes [m, 4] fp64, labels [m, C] fp64) in store order"""
         if not self.gt_keys:
@@ -135,7 +144,7 @@ class DeviceFrameMAP:
         for s in stores:
             out.add_detections([s.frame_keys[f] for f in s.row_fid], s.boxes.to(out.device), s.scores.to(out.device))
             gb, gl = s.gt_arrays()
-            out.add_ground_truth(s.gt_keys, gb, gl)
+            out.add_ground_truth(s.gt_keys, gb, gl, **s._gt_extra())
         return out
 
     def all_gather_merge(self):
@@ -145,7 +154,8 @@ class DeviceFrameMAP:
         world = dist.get_world_size()
         gb, gl = self.gt_arrays()
         meta = [None] * world
-        dist.all_gather_object(meta, dict(n=self.n, frame_keys=self.frame_keys, row_fid=self.row_fid, gt_keys=self.gt_keys, gt_box=gb, gt_lab=gl))
+        dist.all_gather_object(meta, dict(n=self.n, frame_keys=self.frame_keys, row_fid=self.row_fid, gt_keys=self.gt_keys, gt_box=gb, gt_lab=gl,
+                                          gt_extra=self._gt_extra()))
         nmax = max(m["n"] for m in meta)
         box = torch.zeros((nmax, 4), dtype=torch.float32, device=self.device)
         score = torch.zeros((nmax, self.score_width), dtype=torch.float32, device=self.device)
@@ -157,7 +167,7 @@ class DeviceFrameMAP:
         for m, b, s in zip(meta, boxes, scores):
             part = type(self)(device=self.device, **self._settings())
             part.add_detections([m["frame_keys"][f] for f in m["row_fid"]], b[:m["n"]], s[:m["n"]])
-            part.add_ground_truth(m["gt_keys"], m["gt_box"], m["gt_lab"])
+            part.add_ground_truth(m["gt_keys"], m["gt_box"], m["gt_lab"], **m["gt_extra"])
             parts.append(part)
         return type(self).merge(parts)
 
@@ -432,3 +442,201 @@ class DeviceFrameMAPUCF(DeviceFrameMAP):
             ties.scatter_add_(0, bucket, member.long())
         mark("tie_count")
         return self._read_back(ap, ties[:C], marks, timings)
+
+
+class DeviceVideoMAP(DeviceFrameMAPUCF):
+    """``DeviceFrameMAPUCF`` that also links its rows into action tubes and computes video-mAP (``evaluation.VideoMAP``: the definition).
+    ``evaluate()`` is unchanged (frame-mAP); ``link()`` / ``tubes()`` give the tubes, ``evaluate_video()`` the video-mAPs.  Keys are
+    ``"<video>-<frame number>"``.  ``add_ground_truth(..., tubes=)`` takes one integer tube id per line; without it the id is the ordinal of
+    the line among its frame's lines of the same class.  A CPU store, a store beyond a kernel bound and a key that does not parse are evaluated
+    by ``to_video_host_evaluator()``: no row is ever dropped."""
+
+    def __init__(self, class_num=24, iou_threshold=0.5, label_width=None, device="cuda", link_iou=0.2, max_gap=2, min_len=1,
+                 thresholds=(0.2, 0.5, 0.75, "0.5:0.95")):
+        super().__init__(class_num, iou_threshold, label_width, device)
+        self.link_iou, self.max_gap, self.min_len, self.thresholds = float(link_iou), int(max_gap), int(min_len), tuple(thresholds)
+        self.video_path = None                            # after evaluate_video(): "device" or "host"
+
+    def _init_store(self, score_width, label_width):
+        super()._init_store(score_width, label_width)
+        self._gt_tube = []                                # per ground-truth line: its tube id or None
+
+    def _settings(self):
+        return dict(super()._settings(), link_iou=self.link_iou, max_gap=self.max_gap, min_len=self.min_len, thresholds=self.thresholds)
+
+    def _gt_extra(self):
+        return dict(tubes=list(self._gt_tube))
+
+    def add_ground_truth(self, keys, boxes, labels, tubes=None):
+        keys = list(keys)
+        tubes = [None] * len(keys) if tubes is None else [None if t is None else int(t) for t in tubes]
+        assert len(tubes) == len(keys), (len(tubes), len(keys))
+        super().add_ground_truth(keys, boxes, labels)
+        self._gt_tube.extend(tubes)
+        assert len(self._gt_tube) == len(self.gt_keys)
+
+    def video_ground_truth(self):
+        """-> (keys, [(class 0-based, box, tube id or None)]): one row per (line, class set in it), in store order; tiny boxes are kept"""
+        gb, gl = self.gt_arrays()
+        keys, rows = [], []
+        for i, k in enumerate(self.gt_keys):
+            for x in np.nonzero(~(gl[i] <= 1e-2))[0]:
+                keys.append(k)
+                rows.append((int(x), gb[i], self._gt_tube[i]))
+        return keys, rows
+
+    def to_video_host_evaluator(self):
+        """an ``evaluation.VideoMAP`` holding the store, in store order"""
+        ev = _ev.VideoMAP(self.class_num, self.link_iou, self.max_gap, self.min_len, self.thresholds)
+        ev.add_detections([self.frame_keys[f] for f in self.row_fid], self.boxes.cpu().numpy(), self.scores.cpu().numpy())
+        keys, rows = self.video_ground_truth()
+        ev.add_ground_truth(keys, [r[1] for r in rows], [r[0] for r in rows], [r[2] for r in rows])
+        return ev
+
+    def video_arrays(self):
+        """The operands of ``tuber_tube_link`` / ``tuber_tube_match`` on the store's device: the rows in layout order (video, slot, store
+        order), the CSR offsets of the slots and videos, one ground-truth row per (slot, class, tube) in slot order with the tube's rank among
+        the ids of its (video, class), tubes per class; ``beyond``: why the kernels cannot take the store, or None."""
+        C, dev = self.class_num, self.device
+        gkeys, grows = self.video_ground_truth()
+        frame_slot_keys = list(self.frame_keys)
+        lay = _ev.tube_layout(frame_slot_keys, gkeys)     # one detection "row" per frame id: rows of a frame share their slot
+        S, V = lay["S"], lay["V"]
+        fslot = torch.from_numpy(lay["det_slot"]).to(dev)
+        slot = fslot[torch.tensor(self.row_fid, dtype=torch.long).to(dev)] if self.n else torch.zeros(0, dtype=torch.long, device=dev)
+        order = torch.sort(slot, stable=True).indices
+        rows_per = np.zeros(S, dtype=np.int64)
+        np.add.at(rows_per, lay["det_slot"], np.asarray(self.det_count, dtype=np.int64))
+        gt = _ev.ground_truth_tubes(lay, grows)
+        rank, per_vc = {}, {}
+        for key in sorted(gt):
+            rank[key] = per_vc[key[:2]] = per_vc.get(key[:2], 0)
+            per_vc[key[:2]] += 1
+        flat = sorted((s, key[1], rank[key], key) for key, g in gt.items() if 0 <= key[1] < C for s in g)
+        gslot = np.asarray([f[0] for f in flat], dtype=np.int64)
+        gt_per = np.bincount(gslot, minlength=S) if S else np.zeros(0, dtype=np.int64)
+        n_gt = np.bincount(np.asarray([k[1] for k in gt if 0 <= k[1] < C], dtype=np.int64), minlength=C).astype(np.int32)
+        thr = _ev.expand_thresholds(self.thresholds)
+        a = dict(V=V, S=S, N=self.n, G=len(flat), C=C, T=len(thr), thr=thr, layout=lay, max_rows=int(rows_per.max()) if S else 0,
+                 max_gt_rows=int(gt_per.max()) if S else 0, max_gt_tubes=max(per_vc.values()) if per_vc else 0)
+        a["beyond"] = self._video_beyond(a)
+        if a["beyond"]:
+            return a
+        up = lambda x: torch.from_numpy(np.ascontiguousarray(x)).to(dev)
+        a.update(order=order, row_slot=slot.index_select(0, order), det_box=self.boxes.index_select(0, order).contiguous(),
+                 det_prob=self.scores.index_select(0, order).contiguous(),
+                 slot_off=up(np.concatenate([[0], np.cumsum(rows_per)]).astype(np.int32)), video_off=up(lay["video_off"].astype(np.int32)),
+                 gt_box=up(np.asarray([gt[f[3]][f[0]] for f in flat], dtype=np.float64).reshape(-1, 4)),
+                 gt_cls=up(np.asarray([f[1] for f in flat], dtype=np.int32)), gt_tube=up(np.asarray([f[2] for f in flat], dtype=np.int32)),
+                 gt_off=up(np.concatenate([[0], np.cumsum(gt_per)]).astype(np.int32)), thresholds=up(np.asarray(thr, dtype=np.float64)),
+                 n_gt=up(n_gt))
+        return a
+
+    def _video_beyond(self, a):
+        if not a["layout"]["parsed"]:
+            return "a key is not of the form <video>-<frame number>"
+        if a["max_rows"] > lib.query("tuber_frame_match_max_dets") or a["max_rows"] * (self.max_gap + 1) > lib.query("tuber_tube_link_max_active"):
+            return "%d rows in a frame with MAX_GAP %d: beyond %d rows or %d active tubes" % (
+                a["max_rows"], self.max_gap, lib.query("tuber_frame_match_max_dets"), lib.query("tuber_tube_link_max_active"))
+        if a["max_gt_rows"] > lib.query("tuber_frame_match_max_gt") or a["max_gt_tubes"] > lib.query("tuber_tube_match_max_gt"):
+            return "%d ground-truth boxes in a frame / %d ground-truth tubes in a (video, class): beyond %d / %d" % (
+                a["max_gt_rows"], a["max_gt_tubes"], lib.query("tuber_frame_match_max_gt"), lib.query("tuber_tube_match_max_gt"))
+        if a["T"] > lib.query("tuber_tube_match_max_thresholds"):
+            return "%d thresholds: beyond %d" % (a["T"], lib.query("tuber_tube_match_max_thresholds"))
+        if max(a["S"], a["V"] * a["C"], a["T"] * a["N"]) >= 2 ** 31:
+            return "sizes beyond 32-bit indices"
+        return None
+
+    def link(self, a=None):
+        """``tuber_tube_link`` over the store -> device tensors in layout order: ``order`` (layout row -> store row), ``det_box``, ``det_prob``,
+        ``row_slot``, ``row_cls``, ``row_head`` (-1: not counted), and at head rows ``tube_score`` (fp64), ``tube_len``, ``tube_last``; ``layout``.
+        A store the kernel cannot take gives the host's arrays (``evaluation.VideoMAP.link``) as CPU tensors."""
+        if self.device.type == "cuda":
+            a = a or self.video_arrays()
+        if self.device.type != "cuda" or a["beyond"]:
+            host = self.to_video_host_evaluator().link()
+            return {k: (torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v) for k, v in host.items() if k != "tubes"}
+        N, dev = a["N"], self.device
+        out = dict(order=a["order"], det_box=a["det_box"], det_prob=a["det_prob"], row_slot=a["row_slot"], layout=a["layout"],
+                   row_cls=torch.empty(N, dtype=torch.int32, device=dev), row_head=torch.empty(N, dtype=torch.int32, device=dev),
+                   tube_score=torch.zeros(N, dtype=torch.float64, device=dev), tube_len=torch.zeros(N, dtype=torch.int32, device=dev),
+                   tube_last=torch.full((N,), -1, dtype=torch.int32, device=dev))
+        lib.call("tuber_tube_link", a["det_box"], a["det_prob"], a["slot_off"], a["video_off"], a["V"], a["S"], N, a["C"], a["max_rows"],
+                 self.link_iou, self.max_gap, out["row_cls"], out["row_head"], out["tube_score"], out["tube_len"], out["tube_last"])
+        return out
+
+    def tubes(self):
+        """the linked tubes read back: a list of dict(video, cls (1-based), score, frames, boxes, head, rows) in head order"""
+        link = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in self.link().items()}
+        return _ev.tubes_from_link(link)
+
+    def match_video(self, a, link):
+        """``tuber_tube_match`` -> tube_flag [T, N] uint8 on the device (1 true positive, 0 false positive, 2 not counted)"""
+        N, dev = a["N"], self.device
+        flags = torch.empty((a["T"], N), dtype=torch.uint8, device=dev)
+        work = torch.empty(N * max(a["max_gt_tubes"], 1), dtype=torch.float64, device=dev)
+        lib.call("tuber_tube_match", a["det_box"], a["slot_off"], a["video_off"], link["row_cls"], link["row_head"], link["tube_score"],
+                 link["tube_len"], link["tube_last"], a["gt_box"], a["gt_cls"], a["gt_tube"], a["gt_off"], a["thresholds"], a["V"], a["S"], N,
+                 a["G"], a["C"], a["T"], a["max_rows"], a["max_gt_rows"], a["max_gt_tubes"], self.min_len, work, flags)
+        return flags
+
+    def evaluate_video(self, timings=None):
+        """-> {threshold: (video-mAP, {class_id: AP})} as ``VideoMAP.evaluate()``; ``video_path`` is set.  Bitwise reproducible run to run.
+        ``timings``: a dict that receives the device time of every stage in ms (HIP events) and the host time of the read-back."""
+        if self.device.type != "cuda":
+            return self._evaluate_video_host("the store is on the CPU")
+        marks = []
+
+        def mark(name):
+            if timings is not None:
+                e = torch.cuda.Event(enable_timing=True)
+                e.record()
+                marks.append((name, e))
+        mark("start")
+        a = self.video_arrays()
+        if a["beyond"]:
+            return self._evaluate_video_host(a["beyond"])
+        self.video_path = "device"
+        C, N, T, dev = a["C"], a["N"], a["T"], self.device
+        mark("layout_and_uploads")
+        link = self.link(a)
+        mark("tuber_tube_link")
+        flags = self.match_video(a, link)
+        mark("tuber_tube_match")
+        # every class's ranking over its counted tubes, the same for every threshold: one stable sort by score (descending, NaN last), one by
+        # class; rows that are no counted head go to a bucket of their own (row C of every [C + 1][N] slab, with n_gt 0)
+        cls = link["row_cls"].long()
+        score = self._nan_last(link["tube_score"].clone())
+        bucket = torch.where(flags[0] == 2, torch.full_like(cls, C), cls.clamp(0, C)) if N else cls
+        ranked, by_score = torch.sort(score, descending=True, stable=True)
+        bucket, by_class = torch.sort(bucket[by_score], stable=True)
+        perm = by_score[by_class]
+        count = torch.zeros(C + 1, dtype=torch.long, device=dev).scatter_add_(0, bucket, torch.ones_like(bucket))
+        pos = torch.arange(N, device=dev) - (count.cumsum(0) - count)[bucket]
+        flags_ranked = torch.full((T, C + 1, N), 2, dtype=torch.uint8, device=dev)
+        if N:
+            flags_ranked[:, bucket, pos] = flags[:, perm]
+        mark("rank_sort_and_scatter")
+        n_gt = torch.cat([a["n_gt"], torch.zeros(1, dtype=torch.int32, device=dev)]).repeat(T).contiguous()
+        ap = torch.empty(T * (C + 1), dtype=torch.float64, device=dev)
+        lib.call("tuber_ranked_ap", flags_ranked, n_gt, T * (C + 1), N, ap, None)
+        mark("tuber_ranked_ap")
+        if timings is not None:
+            import time
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        ap = ap.cpu().numpy().reshape(T, C + 1)
+        if timings is not None:
+            timings["read_back_ms"] = (time.perf_counter() - t0) * 1e3
+            for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
+                timings[name + "_ms"] = e0.elapsed_time(e1)
+        at = {}
+        for i, thr in enumerate(a["thr"]):
+            per_class = {c + 1: float(ap[i, c]) for c in range(C) if not np.isnan(ap[i, c])}
+            at[thr] = (mean_ap(per_class, self.num_categories), per_class)
+        return _ev.collect_thresholds(self.thresholds, at)
+
+    def _evaluate_video_host(self, why):
+        log.warning("DeviceVideoMAP: %s: evaluating video-mAP on the host", why)
+        self.video_path = "host"
+        return self.to_video_host_evaluator().evaluate()

@@ -391,16 +391,273 @@ class FrameMAPUCF(FrameMAP):
                 self.det.setdefault(key, []).append((x + 1, np.asarray(v[0:4], dtype=float), float(scores[x])))
 
 
+# ---------------------------------------------------------------------------------------------------------------------
+# video-mAP over linked action tubes (the definition; the reference ships the frame-level evaluator only)
+# ---------------------------------------------------------------------------------------------------------------------
+VIDEO_MAP_RANGE = tuple(round(0.5 + 0.05 * i, 2) for i in range(10))          # the members of "0.5:0.95"
+
+
+def expand_thresholds(thresholds):
+    """the numeric thresholds a list of settings needs, ascending: its numbers and, for "0.5:0.95", 0.50, 0.55, ..., 0.95"""
+    out = set()
+    for t in thresholds:
+        out.update(VIDEO_MAP_RANGE if t == "0.5:0.95" else (float(t),))
+    return sorted(out)
+
+
+def split_key(key):
+    """"<video>-<frame number>" -> (video, frame), split at the last "-"; None when the key is not of that form"""
+    video, sep, frame = str(key).rpartition("-")
+    if not sep or not video or not (frame.isascii() and frame.isdigit()):
+        return None
+    return video, int(frame)
+
+
+def tube_layout(det_keys, gt_keys):
+    """The slot layout of a store: videos in order of first appearance (detections first, then ground truth); a video's slots are the
+    consecutive frame numbers from its smallest to its largest; ``det_slot`` / ``gt_slot``: the global slot of every row.  A key that does
+    not parse is a one-slot video of its own name (``parsed`` is False then)."""
+    ids, lo, hi, parsed = {}, [], [], True
+    rows = []
+    for k in list(det_keys) + list(gt_keys):
+        p = split_key(k)
+        if p is None:
+            parsed, p = False, (str(k), 0)
+        v = ids.get(p[0])
+        if v is None:
+            v = ids[p[0]] = len(lo)
+            lo.append(p[1]); hi.append(p[1])
+        else:
+            lo[v] = min(lo[v], p[1]); hi[v] = max(hi[v], p[1])
+        rows.append((v, p[1]))
+    lo_a, hi_a = np.asarray(lo, dtype=np.int64).reshape(-1), np.asarray(hi, dtype=np.int64).reshape(-1)
+    video_off = np.concatenate([[0], np.cumsum(hi_a - lo_a + 1)]).astype(np.int64)
+    slot = np.asarray([video_off[v] + f - lo[v] for v, f in rows], dtype=np.int64)
+    nd = len(det_keys)
+    return dict(videos=list(ids), V=len(lo), S=int(video_off[-1]), video_off=video_off, first_frame=lo_a, det_slot=slot[:nd], gt_slot=slot[nd:],
+                parsed=parsed)
+
+
+def ground_truth_tubes(lay, gt_rows):
+    """``gt_rows``: [(class 0-based, box fp64, tube id or None)] aligned with ``lay['gt_slot']`` -> {(video, class, id): {slot: box}}.  A missing
+    id is the ordinal of the line among its slot's lines of the same class; a second line with the same (slot, class, id) is ignored."""
+    ordinal, tubes = {}, {}
+    for slot, (c, box, tid) in zip(lay["gt_slot"].tolist(), gt_rows):
+        o = ordinal.get((slot, c), 0)
+        ordinal[(slot, c)] = o + 1
+        tid = o if tid is None else int(tid)
+        v = int(np.searchsorted(lay["video_off"], slot, side="right")) - 1
+        tubes.setdefault((v, int(c), tid), {}).setdefault(slot, np.asarray(box, dtype=np.float64))
+    return tubes
+
+
+def tubes_from_link(link):
+    """the linked tubes of ``VideoMAP.link()`` (or of the device arrays read back) as a list of dict(video, cls (1-based), score, frames, boxes,
+    head, rows: the layout rows), in head order"""
+    lay, head, slot = link["layout"], np.asarray(link["row_head"]), np.asarray(link["row_slot"])
+    rows = {}
+    for r in np.nonzero(head >= 0)[0].tolist():
+        rows.setdefault(int(head[r]), []).append(r)
+    out = []
+    for h in sorted(rows):
+        v = int(np.searchsorted(lay["video_off"], slot[h], side="right")) - 1
+        frames = [int(lay["first_frame"][v] + slot[r] - lay["video_off"][v]) for r in rows[h]]
+        out.append(dict(video=lay["videos"][v], cls=int(link["row_cls"][h]) + 1, score=float(link["tube_score"][h]), frames=frames,
+                        boxes=np.asarray(link["det_box"])[rows[h]], head=h, rows=rows[h]))
+    return out
+
+
+class VideoMAP:
+    """Video-level mean average precision over action tubes: per (video, class) the per-frame detections are linked greedily into tubes
+    (``link``), the tubes are matched against the ground-truth tubes by spatio-temporal IoU (``match``), and the ranked flags give VOC AP per
+    class (``evaluate``).  Counting rule of ``FrameMAPUCF`` (a row of C + 1 probabilities is one detection of its arg-max class; not counted
+    when no-object is the arg-max, the box is not a box, or the arg-max probability is NaN); no exclude list.  Plain numpy / Python: the
+    definition ``device_map.DeviceVideoMAP`` reproduces, and its fallback."""
+
+    def __init__(self, class_num=24, link_iou=0.2, max_gap=2, min_len=1, thresholds=(0.2, 0.5, 0.75, "0.5:0.95")):
+        self.class_num, self.link_iou, self.max_gap, self.min_len = int(class_num), float(link_iou), int(max_gap), int(min_len)
+        self.thresholds = tuple(thresholds)
+        self.num_categories = 24
+        self.det_keys, self._box, self._prob = [], [], []
+        self.gt_keys, self.gt_rows = [], []
+
+    def add_detections(self, keys, boxes, probs):
+        """``keys``: one "<video>-<frame>" key per row; ``boxes`` [n, 4] fp32 xyxy, ``probs`` [n, C + 1] fp32"""
+        keys = list(keys)
+        boxes, probs = np.asarray(boxes, dtype=np.float32).reshape(-1, 4), np.asarray(probs, dtype=np.float32).reshape(-1, self.class_num + 1)
+        assert len(boxes) == len(keys) == len(probs), (len(boxes), len(keys), len(probs))
+        self.det_keys.extend(keys); self._box.append(boxes); self._prob.append(probs)
+
+    def add_ground_truth(self, keys, boxes, classes, tubes=None):
+        """one line per box: its key, box (fp64 xyxy), 0-based class and, with ``tubes``, the integer id of its tube"""
+        keys = list(keys)
+        boxes = np.asarray(boxes, dtype=np.float64).reshape(-1, 4)
+        tubes = [None] * len(keys) if tubes is None else [None if t is None else int(t) for t in tubes]
+        assert len(boxes) == len(keys) == len(classes) == len(tubes)
+        self.gt_keys.extend(keys)
+        self.gt_rows.extend((int(c), boxes[i], tubes[i]) for i, c in enumerate(classes))
+
+    def link(self):
+        """-> dict: ``order`` (layout row -> store row), ``det_box``, ``det_prob``, ``row_slot`` in layout order, ``row_cls`` (arg-max column),
+        ``row_head`` (layout row of the tube's first detection, -1 for a row that is not counted), at head rows ``tube_score`` (fp64 mean of
+        the fp32 scores), ``tube_len``, ``tube_last`` (last slot); ``layout``; ``tubes`` (``tubes_from_link``)."""
+        C, N = self.class_num, len(self.det_keys)
+        lay = tube_layout(self.det_keys, self.gt_keys)
+        box = np.concatenate(self._box) if self._box else np.zeros((0, 4), np.float32)
+        prob = np.concatenate(self._prob) if self._prob else np.zeros((0, C + 1), np.float32)
+        order = np.argsort(lay["det_slot"], kind="stable")
+        box, prob, slot = box[order], prob[order], lay["det_slot"][order]
+        cls = prob.argmax(axis=1) if N else np.zeros(0, dtype=np.int64)
+        score = prob[np.arange(N), cls]
+        counted = (cls != C) & (box[:, 0] < box[:, 2]) & (box[:, 1] < box[:, 3]) & ~np.isnan(score)
+        box64 = box.astype(np.float64)
+        video = np.searchsorted(lay["video_off"], slot, side="right") - 1
+        head = np.full(N, -1, dtype=np.int64)
+        tscore, tlen, tlast = np.zeros(N), np.zeros(N, dtype=np.int64), np.full(N, -1, dtype=np.int64)
+        groups = {}
+        for r in np.nonzero(counted)[0].tolist():
+            groups.setdefault((int(video[r]), int(cls[r])), []).append(r)
+        for rows in groups.values():
+            tubes, i = [], 0                              # a tube: [head, fp64 score sum, count, last slot, last row]
+            while i < len(rows):
+                s, j = slot[rows[i]], i
+                while j < len(rows) and slot[rows[j]] == s:
+                    j += 1
+                cur, i = rows[i:j], j
+                active = [t for t in tubes if s - t[3] <= self.max_gap + 1]
+                for t in tubes:
+                    if s - t[3] > self.max_gap + 1:
+                        tscore[t[0]], tlen[t[0]], tlast[t[0]] = t[1] / t[2], t[2], t[3]
+                active.sort(key=lambda t: (-(t[1] / t[2]), t[0]))
+                claimed = set()
+                for t in active:
+                    cand = [r for r in cur if r not in claimed]
+                    if not cand:
+                        break
+                    with np.errstate(all="ignore"):
+                        iou = _iou_one_to_many(box64[t[4]], box64[cand])
+                    best = None
+                    for r, u in zip(cand, iou):
+                        if u >= self.link_iou and (best is None or score[r] > score[best]):
+                            best = r
+                    if best is not None:
+                        claimed.add(best)
+                        head[best] = t[0]
+                        t[1] += float(score[best]); t[2] += 1; t[3] = s; t[4] = best
+                tubes = active
+                for r in cur:
+                    if r not in claimed:
+                        head[r] = r
+                        tubes.append([r, float(score[r]), 1, s, r])
+            for t in tubes:
+                tscore[t[0]], tlen[t[0]], tlast[t[0]] = t[1] / t[2], t[2], t[3]
+        link = dict(order=order, det_box=box, det_prob=prob, row_slot=slot, row_cls=cls, row_head=head, tube_score=tscore, tube_len=tlen,
+                    tube_last=tlast, layout=lay)
+        link["tubes"] = tubes_from_link(link)
+        return link
+
+    def st_iou(self, link=None):
+        """-> (gt, overlaps): the ground-truth tubes {(video, class, id): {slot: box}} and {head: {(video, class, id): stIoU}} over the
+        ground-truth tubes of the tube's (video, class)"""
+        link = link or self.link()
+        gt = ground_truth_tubes(link["layout"], self.gt_rows)
+        by_vc = {}
+        for key in sorted(gt):
+            by_vc.setdefault(key[:2], []).append(key)
+        box64, slot = link["det_box"].astype(np.float64), link["row_slot"]
+        videos = {name: v for v, name in enumerate(link["layout"]["videos"])}
+        overlaps = {}
+        for t in link["tubes"]:
+            mine = {int(slot[r]): r for r in t["rows"]}
+            row = overlaps[t["head"]] = {}
+            for key in by_vc.get((videos[t["video"]], t["cls"] - 1), []):
+                g = gt[key]
+                shared = sorted(set(mine) & set(g))
+                total = 0.0
+                for s in shared:
+                    with np.errstate(all="ignore"):
+                        total += float(_iou_one_to_many(box64[mine[s]], g[s][None, :])[0])
+                row[key] = total / (len(mine) + len(g) - len(shared)) if shared else 0.0
+        return gt, overlaps
+
+    def match(self, link=None):
+        """-> (n_gt {class 1-based: ground-truth tubes}, flags {threshold: uint8 [N] in layout order: 1 true positive, 0 false positive, 2 not
+        counted}, link) over ``expand_thresholds(self.thresholds)``"""
+        link = link or self.link()
+        gt, overlaps = self.st_iou(link)
+        n_gt = {}
+        for (_, c, _) in gt:
+            if 0 <= c < self.class_num:
+                n_gt[c + 1] = n_gt.get(c + 1, 0) + 1
+        N = len(link["row_head"])
+        groups = {}
+        for t in link["tubes"]:
+            if len(t["frames"]) >= self.min_len:
+                groups.setdefault((t["video"], t["cls"]), []).append(t)
+        flags = {}
+        for thr in expand_thresholds(self.thresholds):
+            fl = flags[thr] = np.full(N, 2, dtype=np.uint8)
+            for tubes in groups.values():
+                taken = set()
+                for t in sorted(tubes, key=lambda t: (-t["score"] if t["score"] == t["score"] else np.inf, t["head"])):
+                    bk, bv = None, 0.0
+                    for key, x in overlaps[t["head"]].items():             # ascending tube id
+                        if key not in taken and (bk is None or x > bv):
+                            bk, bv = key, x
+                    tp = bk is not None and bv >= thr
+                    if tp:
+                        taken.add(bk)
+                    fl[t["head"]] = 1 if tp else 0
+        return n_gt, flags, link
+
+    def evaluate(self):
+        """-> {threshold: (video-mAP, {class_id: AP})} for the configured thresholds; "0.5:0.95" is the mean over its ten members"""
+        n_gt, flags, link = self.match()
+        N = len(link["row_head"])
+        is_head = link["row_head"] == np.arange(N)
+        at = {}
+        for thr, fl in flags.items():
+            per_class = {}
+            for cls in range(1, self.class_num + 1):
+                if n_gt.get(cls, 0) == 0:
+                    continue
+                heads = np.nonzero(is_head & (link["row_cls"] == cls - 1) & (fl != 2))[0]
+                if len(heads) == 0:
+                    per_class[cls] = 0.0
+                    continue
+                t = (fl[heads] == 1)[np.argsort(-link["tube_score"][heads], kind="stable")]
+                ctp = np.cumsum(t).astype(float); cfp = np.cumsum(~t).astype(float)
+                per_class[cls] = _average_precision(ctp / np.maximum(ctp + cfp, np.finfo(np.float64).eps), ctp / n_gt[cls])
+            at[thr] = (mean_ap(per_class, self.num_categories), per_class)
+        return collect_thresholds(self.thresholds, at)
+
+
+def collect_thresholds(thresholds, at):
+    """{numeric threshold: (mAP, per_class)} -> the same for the configured ``thresholds``, "0.5:0.95" as the mean over its members"""
+    out = {}
+    for t in thresholds:
+        if t == "0.5:0.95":
+            members = [at[m] for m in VIDEO_MAP_RANGE]
+            per_class = {c: float(np.mean([m[1][c] for m in members])) for c in members[0][1]}
+            out[t] = (float(np.mean([m[0] for m in members])), per_class)
+        else:
+            out[t] = at[float(t)]
+    return out
+
+
 @_with_averaged_weights
 @torch.no_grad()
-def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loader, epoch, writer=None, verbose=True):
+def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loader, epoch, writer=None, verbose=True, results=None):
     """utils/video_action_recognition.py:456-689 (called by train_tuber_jhmdb.py:83 / eval_tuber_jhmdb.py:77): eval-mode forward on
     the HIP path, ``PostProcess``, the key frame's QUERY_NUM tubelet queries of every clip written to ``{rank}.txt`` (box + C+1
     class probabilities), ``binary_{rank}.txt`` (visibility probabilities) and ``GT_{rank}.txt`` (raw box + one-hot label), then
     frame-mAP@0.5 by ``FrameMAPUCF`` on rank 0.  Differences from the reference: barriers only when torch.distributed is
     initialised; the one-hot width is max(21, NUM_CLASSES) (the reference hard-codes 21, :564, which UCF101-24 would overflow).
     With ``CONFIG.VAL.DEVICE_MAP.ENABLE`` the same rows go from ``PostProcess.decode`` into a ``device_map.DeviceFrameMAPUCF`` and the
-    metric is computed on the device; the three files are written only with ``FILES``."""
+    metric is computed on the device; the three files are written only with ``FILES``.  With ``CONFIG.VAL.VIDEO_MAP.ENABLE`` the rows go
+    into a ``device_map.DeviceVideoMAP`` (``FILES`` keeps its meaning), the return value is still frame-mAP, and the video-mAPs over linked
+    tubes are printed, written to the writer as ``val/video_mAP@<thr>`` and left in ``results`` (a dict: ``results["video_mAP"][thr]``,
+    ``results["video_AP"][thr]``).  A DistributedSampler's padded repeat frames are not de-duplicated."""
     import torch.distributed as dist
     C = cfg.CONFIG
     ddp = dist.is_available() and dist.is_initialized()
@@ -418,8 +675,16 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
     width = max(21, nc)
     buff_output, buff_anno, buff_id, buff_binary, gt_label, gt_anno, gt_id = [], [], [], [], [], [], []
     dm = getattr(C.VAL, "DEVICE_MAP", None)
-    store, files = None, True
-    if dm is not None and dm.ENABLE:
+    store, files, frame_on_device = None, True, True
+    vm = getattr(C.VAL, "VIDEO_MAP", None)
+    video = vm is not None and vm.ENABLE
+    if video:
+        from .config import video_map_settings
+        from .device_map import DeviceVideoMAP
+        store = DeviceVideoMAP(class_num=nc, label_width=width, device=dev, **video_map_settings(cfg))
+        frame_on_device = dm is not None and bool(dm.ENABLE)      # without DEVICE_MAP frame-mAP still comes from the result files
+        files = bool(dm.FILES) if frame_on_device else True
+    elif dm is not None and dm.ENABLE:
         from .device_map import DeviceFrameMAPUCF
         store = DeviceFrameMAPUCF(class_num=nc, label_width=width, device=dev)
         files = bool(dm.FILES)
@@ -507,7 +772,7 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
         store = store.all_gather_merge()     # every rank's rows in rank order: the order in which rank 0 loads the files
     mAP = 0
     if rank == 0:
-        if store is not None:
+        if store is not None and frame_on_device:
             mAP, per_class = store.evaluate()
         else:
             ev = FrameMAPUCF(class_num=nc)
@@ -518,6 +783,16 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
             print("mAP: %.5f" % mAP)
         if writer is not None:
             writer.add_scalar("val/val_mAP_epoch", mAP, epoch)
+        if video:
+            vres = store.evaluate_video()
+            if results is not None:
+                results["video_mAP"] = {t: m for t, (m, _) in vres.items()}
+                results["video_AP"] = {t: ap for t, (_, ap) in vres.items()}
+            if verbose:
+                print("video-mAP: " + ", ".join("@%s %.5f" % (t, m) for t, (m, _) in vres.items()))
+            if writer is not None:
+                for t, (m, _) in vres.items():
+                    writer.add_scalar("val/video_mAP@%s" % t, m, epoch)
     if ddp:
         dist.barrier()
     return mAP

@@ -263,3 +263,62 @@ def synthetic_frame_map_ucf_case(frames, dets=10, classes=21, seed=7, max_gt=3, 
     probs[np.arange(n), det_top] = top
     return dict(det_keys=det_keys, det_boxes=np.asarray(det_boxes, dtype=np.float32).reshape(n, 4), det_probs=probs, gt_keys=gt_keys,
                 gt_boxes=np.asarray(gt_boxes, dtype=np.float64).reshape(-1, 4), gt_labels=np.asarray(gt_labels, dtype=np.float64).reshape(-1, width))
+
+
+def synthetic_video_map_case(videos, frames, dets=10, classes=24, seed=7, max_tubes=2, drop=0.15, jitter=0.05, echo=0.3, no_object=0.2,
+                             hw=(240, 320)):
+    """A synthetic JHMDB / UCF101-24 validation result with tubes, for evaluation.VideoMAP and device_map.DeviceVideoMAP: ``videos`` videos of
+    ``frames`` frames (keys ``"video%04d-<frame>"``, frames from 1) with exactly ``dets`` rows of ``classes + 1`` probabilities each.  A
+    video has 1..``max_tubes`` ground-truth tubes of one class each whose box drifts and breathes smoothly over at least half of the video;
+    for every ground-truth box a jittered copy is a detection of (mostly) its class unless it drops out (``drop``: the gaps linking has to
+    bridge), about ``echo`` of them come with a second, looser copy (a competing tube), and the remaining rows are spurious boxes that mostly
+    score lower.  Top probabilities as ``synthetic_frame_map_ucf_case``: distinct fp32 numbers above 0.5.  numpy arrays: ``det_keys`` [n], ``det_boxes`` [n, 4]
+    fp32 xyxy, ``det_probs`` [n, C + 1] fp32, ``gt_keys`` [m], ``gt_boxes`` [m, 4] fp64, ``gt_labels`` [m, max(21, C)] fp64 one-hot,
+    ``gt_tubes`` [m] integer tube ids."""
+    import numpy as np
+    n, C = videos * frames * dets, classes
+    rng = np.random.default_rng(seed)
+    H, W = hw
+    width = max(21, C)
+    det_keys, det_boxes, det_top, det_true, gt_keys, gt_boxes, gt_labels, gt_tubes = [], [], [], [], [], [], [], []
+    for v in range(videos):
+        tubes = []
+        for t in range(int(rng.integers(1, max_tubes + 1))):
+            span = int(rng.integers((frames + 1) // 2, frames + 1))
+            first = int(rng.integers(0, frames - span + 1))
+            c0 = rng.uniform(0.25, 0.6, 2) * [W, H]
+            tubes.append(dict(id=t, cls=int(rng.integers(0, C)), first=first, last=first + span - 1, c0=c0, vel=rng.uniform(-0.2, 0.2, 2) * [W, H],
+                              wh=rng.uniform(0.2, 0.35, 2) * [W, H], phase=rng.uniform(0, 6.28)))
+        for f in range(frames):
+            key = "video%04d-%d" % (v, f + 1)
+            rows = []
+            for t in tubes:
+                if not t["first"] <= f <= t["last"]:
+                    continue
+                u = f / max(frames - 1, 1)
+                ctr = t["c0"] + t["vel"] * u
+                wh = t["wh"] * (1.0 + 0.15 * np.sin(t["phase"] + 6.28 * u))
+                gb = np.concatenate([ctr - wh / 2, ctr + wh / 2]).astype(np.float32).astype(np.float64)
+                lab = np.zeros(width)
+                lab[t["cls"]] = 1.0
+                gt_keys.append(key); gt_boxes.append(gb); gt_labels.append(lab); gt_tubes.append(t["id"])
+                if rng.random() >= drop:
+                    rows.append((gb + rng.normal(0, jitter, 4) * np.tile(wh, 2), t["cls"] if rng.random() < 0.9 else int(rng.integers(0, C)), 1))
+                    if rng.random() < echo:
+                        rows.append((gb + rng.normal(0, 3 * jitter, 4) * np.tile(wh, 2), t["cls"], 0))
+            rows = rows[:dets]
+            while len(rows) < dets:
+                p = rng.uniform(0, 0.7, 2) * [W, H]
+                rows.append((np.concatenate([p, p + rng.uniform(0.1, 0.3, 2) * [W, H]]), C if rng.random() < no_object else int(rng.integers(0, C)), 0))
+            for i in rng.permutation(dets):
+                det_keys.append(key); det_boxes.append(rows[i][0]); det_top.append(rows[i][1]); det_true.append(rows[i][2])
+    # the copies of the ground truth mostly outrank the rest: a noisy rank, then distinct values as synthetic_frame_map_ucf_case has them
+    rank = np.argsort(np.argsort(np.asarray(det_true) * 0.5 + rng.uniform(0, 1, n), kind="stable"), kind="stable")
+    top = (0.5 + 0.45 * (rank + 1.0) / (n + 1.0)).astype(np.float32)
+    rest = rng.uniform(0.05, 1.0, (n, C + 1))
+    rest[np.arange(n), det_top] = 0.0
+    probs = ((1.0 - top.astype(np.float64))[:, None] * rest / rest.sum(axis=1, keepdims=True)).astype(np.float32)
+    probs[np.arange(n), det_top] = top
+    return dict(det_keys=det_keys, det_boxes=np.asarray(det_boxes, dtype=np.float32).reshape(n, 4), det_probs=probs, gt_keys=gt_keys,
+                gt_boxes=np.asarray(gt_boxes, dtype=np.float64).reshape(-1, 4), gt_labels=np.asarray(gt_labels, dtype=np.float64).reshape(-1, width),
+                gt_tubes=np.asarray(gt_tubes, dtype=np.int64))
