@@ -158,7 +158,12 @@ def get_cfg_defaults():
         # video-mAP of validate_tuber_ucf_detection over linked action tubes (evaluation.VideoMAP / device_map.DeviceVideoMAP; not reference
         # keys): consecutive detections of a class link when their IoU is at least LINK_IOU, over at most MAX_GAP empty frames; tubes shorter
         # than MIN_LEN are not counted; THRESHOLDS: spatio-temporal IoU thresholds, "0.5:0.95" the mean over 0.50, 0.55, ..., 0.95
-        VIDEO_MAP=dict(ENABLE=False, LINK_IOU=0.2, MAX_GAP=2, MIN_LEN=1, THRESHOLDS=[0.2, 0.5, 0.75, "0.5:0.95"])), new_allowed=True)
+        VIDEO_MAP=dict(ENABLE=False, LINK_IOU=0.2, MAX_GAP=2, MIN_LEN=1, THRESHOLDS=[0.2, 0.5, 0.75, "0.5:0.95"]),
+        # ranked detections decoded on the device (detect.Detector; not reference keys): a candidate scores at least SCORE_THR, the best TOPK
+        # per clip are kept; ACTOR_THR: the actor-probability gate of the AVA rule (the reference's 0.8)
+        DETECT=dict(SCORE_THR=0.05, TOPK=100, ACTOR_THR=0.8),
+        # both validation loops run the eval forward as a captured hipGraph per input shape (detect.GraphedEval; not a reference key)
+        GRAPHED=False), new_allowed=True)
     cfg.DATA = CfgNode(dict(
         DATASET_NAME="ava", NUM_CLASSES=80, IMG_SIZE=256, TEMP_LEN=32, FRAME_RATE=2), new_allowed=True)
     cfg.MODEL = CfgNode(dict(
@@ -204,6 +209,25 @@ def video_map_settings(cfg):
         bad("THRESHOLDS", "entries must be distinct")
     return dict(link_iou=float(vm.LINK_IOU), max_gap=int(vm.MAX_GAP), min_len=int(vm.MIN_LEN),
                 thresholds=tuple(t if t == "0.5:0.95" else float(t) for t in thr))
+
+
+def detect_settings(cfg):
+    """CONFIG.VAL.DETECT and CONFIG.VAL.GRAPHED validated -> dict(score_thr, topk, actor_thr, graphed); a bad value raises ValueError naming its key"""
+    val = cfg.CONFIG.VAL
+    d = val.DETECT
+
+    def bad(key, value, why):
+        raise ValueError("CONFIG.VAL.%s = %r: %s" % (key, value, why))
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v
+    if not number(d.SCORE_THR) or not 0.0 <= d.SCORE_THR <= 1.0:
+        bad("DETECT.SCORE_THR", d.SCORE_THR, "must be a number in [0, 1]")
+    if not isinstance(d.TOPK, int) or isinstance(d.TOPK, bool) or d.TOPK < 1:
+        bad("DETECT.TOPK", d.TOPK, "must be an integer >= 1")
+    if not number(d.ACTOR_THR) or not 0.0 <= d.ACTOR_THR < 1.0:
+        bad("DETECT.ACTOR_THR", d.ACTOR_THR, "must be a number in [0, 1)")
+    if not isinstance(val.GRAPHED, bool):
+        bad("GRAPHED", val.GRAPHED, "must be True or False")
+    return dict(score_thr=float(d.SCORE_THR), topk=int(d.TOPK), actor_thr=float(d.ACTOR_THR), graphed=val.GRAPHED)
 
 
 def load_cfg(path):

@@ -352,6 +352,19 @@ DOC = {
                         "tuber_frame_match_max_gt(), bad sizes or pointers: negative, nothing launched. One wave per (video, class), sums in slot order: the same bits every run.",
     "tuber_tube_match_max_gt": "ground-truth tubes per (video, class) tuber_tube_match takes (32).",
     "tuber_tube_match_max_thresholds": "thresholds per call tuber_tube_match takes (16).",
+    "tuber_detect_ava": "ranked detections of an AVA eval forward in ONE launch (PostProcessAVA, models/criterion.py:447-482, the post-processor models/tuber_ava.py builds; "
+                        "box_cxcywh_to_xyxy utils/box_ops.py:9-13; then threshold and top-K): pb = softmax(pred_logits_b)[1]; a query passes when pb > actor_thr; "
+                        "score(q, c) = sigmoid(logit) * pb; candidates: (q, c) of a passed query with a score that is not NaN and >= score_thr; the best K by score "
+                        "descending, then q, then c ascending. pred_logits [B][Qtot][C], pred_logits_b [B][lb_rows][NB] (lb_rows = Qtot or 1), pred_boxes [B][Qtot][4], each "
+                        "fp32 or bf16 by its bit of dtypes (1, 2, 4), converted on load; sizes [B][2] fp32 (h, w); q_begin DEVICE int[B] or NULL: where the clip's Qs "
+                        "queries start. Out: det_box [B][K][4] xyxy pixels (bit-identical to decode()'s), det_score, det_aux (pb) [B][K] fp32, det_label, det_query [B][K] "
+                        "int, det_count [B] = min(det_total, K), det_total [B]; rows from det_count on: box 0, score 0, aux 0, label -1, query -1. One workgroup per clip, "
+                        "the clip's order keys sorted in LDS: no atomics, no workspace, no host synchronisation. Beyond tuber_detect_limits: -2, nothing launched.",
+    "tuber_detect_top1": "ranked detections of a JHMDB / UCF101-24 eval forward in ONE launch (PostProcess, models/tuber_jhmdb.py:357-389, plus the counted-once rule of "
+                         "evaluates/evaluate_ucf.py:109-126): a query's label is the first maximum of its fp32 logit row over the C + 1 columns (a NaN counting as a maximum), "
+                         "its score that column's softmax probability; not a candidate when the label is the no-object column C, the score is NaN or < score_thr; the best K "
+                         "by score descending, then q ascending; det_aux: the visibility probability softmax(pred_logits_b)[1]. Arguments and outputs as tuber_detect_ava.",
+    "tuber_detect_limits": "bounds of tuber_detect_ava / tuber_detect_top1: which = 0 the largest Qs * C (4096), 1 the largest K (1024), 2 the largest NB (8).",
     "tuber_tensor_stats_chunk": "largest number of elements in one chunk of tuber_tensor_stats (a multiple of 64).",
     "tuber_tensor_stats_tensor_bytes": "sizeof(TensorStatsTensor) as compiled (host-side layout check).",
     "tuber_tensor_stats_chunk_bytes": "sizeof(TensorStatsChunk) as compiled (host-side layout check).",

@@ -197,16 +197,29 @@ def read_labelmap(path):
 # ---------------------------------------------------------------------------------------------------------------------
 # the loop
 # ---------------------------------------------------------------------------------------------------------------------
-def _forward_checked(model, samples):
+def _forward_checked(model, samples, graphed=None):
     """model(samples) of a validation iteration.  The cooperative decoder launch (csrc/decoder_coop.hip) fails safe -- a timed-out
     barrier leaves NaN outputs and an error word -- and the loop copies the outputs to the host right after this anyway, so the word is
     read here (16 bytes) every iteration: on a failure the engine switches to the launch chain and the batch is run again (ADVICE r05:
-    the evaluation path never looked at the word)."""
-    outputs = model(samples)
+    the evaluation path never looked at the word).  ``graphed``: the loop's detect.GraphedEval under CONFIG.VAL.GRAPHED -- the same
+    outputs from a hipGraph replay; the repeat after a failure is a new key there (``coop_off``), hence a new capture."""
+    forward = model if graphed is None else graphed
+    outputs = forward(samples)
     store = model.engine()[0]
     if not store.coop_off and store.coop_failed():
-        outputs = model(samples)
+        outputs = forward(samples)
     return outputs
+
+
+def _graphed_eval(cfg, model):
+    """CONFIG.VAL.GRAPHED: the loop's captured eval forward (built at the top of a validation loop, dropped with it), or None"""
+    graphed = getattr(cfg.CONFIG.VAL, "GRAPHED", False)
+    if graphed is False:                     # the default, or a config node built without the key: exactly the plain loop
+        return None
+    from .config import detect_settings
+    from .detect import GraphedEval
+    detect_settings(cfg)                     # anything but True / False raises, naming the key
+    return GraphedEval(model)
 
 
 def _with_averaged_weights(fn):
@@ -262,6 +275,7 @@ def validate_tuber_detection(cfg, model, criterion, postprocessors, data_loader,
         store = DeviceFrameMAP(C.DATA.NUM_CLASSES, class_whitelist=white, exclude_keys=excl, device=dev)
         files = bool(dm.FILES)
     meters = {k: [0.0, 0] for k in ("loss", "loss_bbox", "loss_giou", "loss_ce", "loss_ce_b", "class_error")}
+    graphed = _graphed_eval(cfg, model)
     end = time.time()
     for idx, data in enumerate(data_loader):
         samples, targets = data[0], data[1]
@@ -269,7 +283,7 @@ def validate_tuber_detection(cfg, model, criterion, postprocessors, data_loader,
         batch_id = [t["image_id"] for t in targets]
         host_targets = targets               # the loader's own tensors: the device evaluator takes its ground truth from them, without a sync
         targets = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in t.items() if k != "image_id"} for t in targets]
-        outputs = _forward_checked(model, samples)
+        outputs = _forward_checked(model, samples, graphed)
         loss_dict = criterion(outputs, targets)
         sizes = torch.stack([t["size"] for t in targets], dim=0)
         Q = C.MODEL.QUERY_NUM
@@ -318,6 +332,7 @@ def validate_tuber_detection(cfg, model, criterion, postprocessors, data_loader,
             print("Epoch: [%d][%d/%d]  batch time %.3f  " % (epoch, idx + 1, len(data_loader), time.time() - end) +
                   ", ".join("%s: %.3f" % (k, s / max(c, 1)) for k, (s, c) in meters.items()))
         end = time.time()
+    graphed = None                           # the captures and their private pools go with it
     cat = lambda xs, w: np.concatenate(xs, axis=0) if xs else np.zeros((0, w))
     nc = C.DATA.NUM_CLASSES
     if files:
@@ -695,6 +710,7 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
             onehot[i, int(lab[i])] = 1
         return onehot
     meters = {k: [0.0, 0] for k in ("loss", "loss_bbox", "loss_giou", "loss_ce", "class_error")}
+    graphed = _graphed_eval(cfg, model)
     end = time.time()
     for idx, data in enumerate(data_loader):
         samples, targets = data[0], data[1]
@@ -702,7 +718,7 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
         batch_id = [t["image_id"] for t in targets]
         host_targets = targets               # the loader's own tensors: the device evaluator takes its ground truth from them, without a sync
         targets = [{k: (v.to(dev) if torch.is_tensor(v) else v) for k, v in t.items() if k != "image_id"} for t in targets]
-        outputs = _forward_checked(model, samples)
+        outputs = _forward_checked(model, samples, graphed)
         loss_dict = criterion(outputs, targets)
         sizes = torch.stack([t["size"] for t in targets], dim=0)
         if store is None:
@@ -750,6 +766,7 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
             print("Epoch: [%d][%d/%d]  batch time %.3f  " % (epoch, idx + 1, len(data_loader), time.time() - end) +
                   ", ".join("%s: %.3f" % (k, s / max(c, 1)) for k, (s, c) in meters.items()))
         end = time.time()
+    graphed = None                           # the captures and their private pools go with it
     if writer is not None and rank == 0:
         for k, name in (("class_error", "class_error"), ("loss", "totall_loss"), ("loss_bbox", "loss_bbox"), ("loss_giou", "loss_giou"), ("loss_ce", "loss_ce")):
             writer.add_scalar("val/" + name, meters[k][0] / max(meters[k][1], 1), epoch)

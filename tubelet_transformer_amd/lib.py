@@ -121,6 +121,18 @@ def _call(name, *args):
     return rc
 
 
+def call_rc(name, *args):
+    """``call`` without the raise and without the launch hook: the launcher's return code (0, a negative argument-check code, or a
+    hipError_t), for callers that handle a refusal themselves"""
+    load()
+    sig = _sigs[name]
+    if len(args) == len(sig) - 1 and sig and sig[-1][0] == "hipStream_t":
+        args = args + (current_stream(),)
+    if len(args) != len(sig):
+        raise TypeError("%s expects %d args, got %d" % (name, len(sig), len(args)))
+    return getattr(_lib, name)(*[_conv(v, t) for v, (t, _) in zip(args, sig)])
+
+
 def query(name, *args):
     """Helper calls without a stream (workspace sizing); returns the integer result."""
     lib = load()
