@@ -543,7 +543,12 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
     const int t0 = tk * g.tc, t1 = min(g.T, t0 + g.tc);
 
     // ---- staging slots: thread -> (position, channel quad) of a plane, loop invariant over t (as in dwconv_tile_body) ----
-    int s_off[NLD];
+    // Addresses: everything the workgroup shares -- tensor, clip n, plane t, channel block c0 -- is ONE 64-bit base per tensor and plane
+    // (scalar registers); a thread keeps only unsigned 32-bit byte offsets inside the plane, so the loads and stores take the
+    // scalar-base + vector-offset form and no 64-bit address pair lives in vector registers across the plane loop (held as pairs, the
+    // eight output addresses alone pushed the kernel past 256 VGPRs: five were reloaded from scratch in front of their stores, each
+    // reload behind a wait for ALL memory traffic in flight).  The launcher rejects planes of 4 GiB and more.
+    uint32_t s_off[NLD];
     bool s_ok[NLD];
 #pragma unroll
     for (int i = 0; i < NLD; ++i) {
@@ -552,21 +557,28 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
         const int pr = pos / PW, pc = pos % PW;
         const int hi = h0 - 1 + pr, wi = w0 - 1 + pc;
         s_ok[i] = pos < NPOS && hi >= 0 && hi < g.H && wi >= 0 && wi < g.W;
-        s_off[i] = s_ok[i] ? (hi * g.W + wi) * g.C + c0 + q * 4 : 0;
+        s_off[i] = s_ok[i] ? ((uint32_t)(hi * g.W + wi) * (uint32_t)g.C + q * 4) * 2u : 0u;
     }
-    const long plane_elems = (long)g.H * g.W * g.C;
-    const bf16* in_n = a.in + (long)n * g.T * plane_elems;
-    const bf16* in2_n = FRZ ? nullptr : a.xu + (long)n * g.T * plane_elems;       // (frozen: cB = 0, xu is not read)
+    const size_t plane_bytes = (size_t)g.H * g.W * g.C * 2;
+    auto plane_base = [&](const bf16* p, int t) {           // workgroup-uniform: plane t of clip n, channel block c0
+        return (const char*)p + ((size_t)n * g.T + t) * plane_bytes + (size_t)c0 * 2;
+    };
+    // base + offset of one access.  The offset passes through an empty asm so that its widening to 64 bits stays next to the access (where
+    // the scalar-base form absorbs it) instead of being hoisted out of the plane loop as a 64-bit register pair.
+    auto at = [](const char* base, uint32_t off) {
+        asm volatile("" : "+v"(off));
+        return base + off;
+    };
     uint2 regs[NLD], regs_a[NLD], regs_b[NLD], regx[NLD], regx_a[NLD], regx_b[NLD];
     auto fetch = [&](int t, uint2 (&rg)[NLD], uint2 (&rx)[NLD]) {          // unconditional loads (see dwconv_tile_body)
         const bool tok = t >= 0 && t < g.T;
-        const bf16* p = in_n + (long)(tok ? t : 0) * plane_elems;
+        const char* p = plane_base(a.in, tok ? t : 0);
 #pragma unroll
-        for (int i = 0; i < NLD; ++i) rg[i] = *(const uint2*)(p + s_off[i]);
-        if constexpr (!FRZ) {
-            const bf16* p2 = in2_n + (long)(tok ? t : 0) * plane_elems;
+        for (int i = 0; i < NLD; ++i) rg[i] = *(const uint2*)at(p, s_off[i]);
+        if constexpr (!FRZ) {                                              // (frozen: cB = 0, xu is not read)
+            const char* p2 = plane_base(a.xu, tok ? t : 0);
 #pragma unroll
-            for (int i = 0; i < NLD; ++i) rx[i] = *(const uint2*)(p2 + s_off[i]);
+            for (int i = 0; i < NLD; ++i) rx[i] = *(const uint2*)at(p2, s_off[i]);
         }
     };
     auto park = [&](int t, const uint2 (&rg)[NLD], const uint2 (&rx)[NLD]) {      // g = cA*dzu + cB*xu + cC, fp32, zero outside the volume
@@ -622,21 +634,28 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
     const int dch = c0 + (tid & 63);
     const float d_mu = a.bmean[dch], d_rr = a.binvstd[dch], d_gm = a.bgamma[dch];      // used by threads 0 .. 63 below
     const float2 sc2 = *(const float2*)(a.sc + c), sh2 = *(const float2*)(a.sh + c);      // bn1 scale / shift of the channel pair
-    fetch(t0 - 1, regs_a, regx_a);
-    fetch(t0, regs_b, regx_b);
-    fetch(t0 + 1, regs, regx);
-
     // ---- x at this thread's output positions (mask + statistics operand of the data gradient, activation operand of the weight
-    // gradient): 4 B per column, fetched one plane ahead, the first ones together with the prologue planes ----
+    // gradient): 4 B per column, fetched one plane ahead.  Always issued IN FRONT of the plane fetch of the same step: vector loads
+    // complete in order, so the wait of the next park covers them, and no later wait for them can drain the plane fetch behind them ----
     const int ho = h0 + row, wo0 = w0 + cg * 8;
     const bool row_ok = ho < g.H;
+    // byte offset of column j inside a plane's channel block, clamped to the volume; the eight columns are one uniform stride apart, so
+    // an access derives its offset with an add (and the clamp) instead of holding it.  For a column inside the volume this is also the
+    // offset of the output element.
+    const uint32_t col_stride = (uint32_t)g.C * 2u;
+    const uint32_t row_off = (uint32_t)(min(ho, g.H - 1) * g.W) * col_stride + cp * 4;
+    const uint32_t col_first = (uint32_t)wo0 * col_stride, col_last = (uint32_t)(g.W - 1) * col_stride;
+    auto col_off = [&](int j) { return row_off + min(col_first + (uint32_t)j * col_stride, col_last); };
     auto side_fetch = [&](int t, uint32_t (&sd)[8]) {          // unconditional, from the clamped position
-        const long ob = (((long)n * g.T + t) * g.H + min(ho, g.H - 1)) * (long)g.W * g.C + c;
+        const char* p = plane_base(a.aux, t);
 #pragma unroll
-        for (int j = 0; j < 8; ++j) sd[j] = *(const uint32_t*)(a.aux + ob + (long)min(wo0 + j, g.W - 1) * g.C);
+        for (int j = 0; j < 8; ++j) sd[j] = *(const uint32_t*)at(p, col_off(j));
     };
     uint32_t side_nx[8];
     side_fetch(t0, side_nx);
+    fetch(t0 - 1, regs_a, regx_a);
+    fetch(t0, regs_b, regx_b);
+    fetch(t0 + 1, regs, regx);
 
     // ---- coefficients of the BatchNorm backward above, derived under the latency of the fetches just issued (identical arithmetic
     // to dwconv_tile_body<., BNG>: dgamma / dbeta and the coefficients are bit-identical) ----
@@ -718,12 +737,10 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
     }
     for (int t = t0; t < t1; ++t) {
         park(t + 1, regs, regx);
-        if (t + 1 < t1) fetch(t + 2, regs, regx);
         uint32_t side[8];
 #pragma unroll
         for (int j = 0; j < 8; ++j) side[j] = side_nx[j];
-        if (t + 1 < t1) side_fetch(t + 1, side_nx);
-        const long obase = (((long)n * g.T + t) * g.H + ho) * (long)g.W * g.C + c;
+        if (t + 1 < t1) { side_fetch(t + 1, side_nx); fetch(t + 2, regs, regx); }
         __syncthreads();
         f32x2 acc[8], av[8];
 #pragma unroll
@@ -771,6 +788,7 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
             for (int k = 0; k < 9; ++k) { const f32x2 g2 = wacc[18 + k] + w9[k]; wacc[18 + k] = wacc[9 + k]; wacc[9 + k] = wacc[k]; wacc[k] = g2; }
         }
         if (row_ok) {
+            char* const po = const_cast<char*>(plane_base(a.out, t));
 #pragma unroll
             for (int j = 0; j < 8; ++j) {
                 if (wo0 + j >= g.W) continue;
@@ -782,7 +800,7 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
                 o[0] = f2bf(d0); o[1] = f2bf(d1);
                 s0 = s0 + f32x2{d0, d1};
                 s1 = s1 + f32x2{d0 * x0, d1 * x1};
-                *(uint32_t*)(a.out + obase + (long)(wo0 + j) * g.C) = __builtin_bit_cast(uint32_t, o);
+                *(uint32_t*)at(po, col_off(j)) = __builtin_bit_cast(uint32_t, o);
             }
         }
         __syncthreads();                              // ring slot (t-1) mod 3 is overwritten by the next park
@@ -853,7 +871,7 @@ int launch_tile(TileArgs& a, hipStream_t stream) {
     TUBER_RETURN_LAUNCH();
 }
 
-// launch of dwconv_tile_bwd_both_kernel (arguments checked by the callers)
+// launch of dwconv_tile_bwd_both_kernel (pointers and R checked by the callers)
 template <bool FRZ>
 static int dwconv_tile_bwd_both(const void* dzu, const void* xu, const float* bst0, const float* bst1, int R, float count,
                                 const float* gamma, const float* mean, const float* invstd, float* dgamma, float* dbeta,
@@ -864,6 +882,9 @@ static int dwconv_tile_bwd_both(const void* dzu, const void* xu, const float* bs
     a.st0 = st0; a.st1 = st1; a.P = partial;
     a.bst0 = bst0; a.bst1 = bst1; a.bR = R; a.bcount = count; a.bgamma = gamma; a.bmean = mean; a.binvstd = invstd;
     a.bdgamma = dgamma; a.bdbeta = dbeta;
+    // the kernel addresses inside a plane with unsigned 32-bit byte offsets (columns are stepped up to one tile past the row's end
+    // before they are clamped)
+    if ((size_t)H * W * C * 2 > 0xFFFFFFFFull || (size_t)(W + TW) * C * 2 > 0xFFFFFFFFull) return TUBER_EINVAL;
     a.g = make_geom(N, T, H, W, C);
     const size_t lds = (3 * PLANE + 27 * 64 + 3 * 64) * sizeof(float);
     static LdsOptIn opt;
