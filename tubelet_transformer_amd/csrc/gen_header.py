@@ -177,7 +177,8 @@ DOC = {
                                      "operands: both are sums over the same (p, p - off) position pairs, so the ring of dc3 staged for the data gradient also feeds "
                                      "dW[off] = sum_p relu(bn1(x))[p] * dc3[p - off] -- 4 tensor passes (read dzu, xu, x; write dz). dz / dgamma / dbeta bit-identical to "
                                      "tuber_dwconv_tile_bwd_data_bn, statistics rows and weight gradient equal up to fp32 summation order; partial = "
-                                     "tuber_dwconv_tile_blocks(...) blocks of [27][C], reduced by the caller. autograd of models/backbones/ir_CSN_152.py:48-56,74-77.",
+                                     "tuber_dwconv_tile_blocks(...) blocks of [27][C], reduced by the caller. The kernel addresses a plane with 32-bit byte offsets: planes of "
+                                     "H * W * C * 2 >= 4 GiB are refused (TUBER_EINVAL), here and in the frozen form. autograd of models/backbones/ir_CSN_152.py:48-56,74-77.",
     "tuber_dwconv_tile_bwd_weight_bn": "tuber_dwconv_tile_bwd_weight with the same fold: the output-position gradient is formed from (dzu, xu, partial rows) on load.",
     "tuber_comm_init_timeout": "tuber_comm_init with a deadline: the bootstrap (a collective) runs on a helper thread and the call returns -3 with a message naming "
                                "the waiting rank when its peers have not arrived after timeout_ms -- a dead rank fails the job loudly instead of hanging it "
@@ -340,7 +341,19 @@ DOC = {
                        "rows tube_score (fp64 mean), tube_len, tube_last (last slot). max_rows: the largest number of rows in a slot (the caller knows it). max_rows > "
                        "tuber_frame_match_max_dets(), max_rows * (max_gap + 1) > tuber_tube_link_max_active(), N > S * max_rows, bad sizes or pointers: negative, nothing "
                        "launched. One wave per (video, class): a lane holds one active tube and one row of the slot; no LDS, no atomics.",
-    "tuber_tube_link_max_active": "simultaneously active tubes of one (video, class) tuber_tube_link takes: max rows per slot x (max_gap + 1) (64).",
+    "tuber_tube_link_ranked": "tuber_tube_link over ranked detections (detect.Detections / video.VideoDetections; evaluation.link_rows: the definition): a row's class and "
+                              "score are det_label [N] int (0-based; negative or >= C: the row is not counted) and det_score [N] fp32 instead of the arg-max of a "
+                              "[N][C + 1] row. Arguments, outputs, bounds, negative codes, the wave-per-(video, class) walk and the fp64 sequential mean are "
+                              "tuber_tube_link's, whose kernel body it shares; row_cls: the label, C for a row that is not counted. A padded [S][K] detection store "
+                              "is passed as it is: slot_off = arange(S + 1) * K, the rows behind a key's count carry label -1.",
+    "tuber_video_clips": "the clips of B key frames gathered from ONE resident video (datasets/ava_frame.py:43,143-150: every FRAME_RATE-th frame from "
+                         "max(key - T//2 * rate, 0), the indices clipped; datasets/jhmdb_frame.py:201-213; then ToTensor + Normalize, "
+                         "datasets/video_transforms.py:308-322): out[b][c][t][y][x] = lut[c][frames[clamp(index[b][t], 0, nframes - 1)][y1 + y][x1 + x][c]]. frames uint8 "
+                         "[nframes][H][W][3] packed at any byte alignment, index DEVICE int[B][T] (clamped by the kernel), (y1, x1, h, w) the window taken of every "
+                         "frame (Resize_Custom, video_transforms.py:210-227), lut fp32 [3][256], out fp32 [B][3][T][h][w]. 16-byte stores and dword loads from the "
+                         "enclosing aligned window when w % 4 == 0, byte loads and scalar stores otherwise; the table in LDS. A null pointer, a non-positive size "
+                         "or a window outside H x W: negative, nothing launched.",
+    "tuber_tube_link_max_active":"simultaneously active tubes of one (video, class) tuber_tube_link takes: max rows per slot x (max_gap + 1) (64).",
     "tuber_tube_match": "video-mAP on the device, matching step (evaluation.VideoMAP.match): the tuber_tube_link outputs against ground-truth tubes given as gt_box [G][4] fp64 / "
                         "gt_cls [G] / gt_tube [G] (the rank of the row's tube among the tube ids of its (video, class), ascending; one row per (slot, class, tube)) in slot order "
                         "with gt_off DEVICE int[S + 1]. stIoU(d, g) = sum over the shared slots of the fp64 IoU / |slots of d or g|, 0 without a shared slot. Per (video, class) the "

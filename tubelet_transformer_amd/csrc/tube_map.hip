@@ -1,6 +1,6 @@
 // Video-mAP of the JHMDB / UCF101-24 validation loop on the device (gfx950): the two sequential steps behind device_map.DeviceVideoMAP.  They
 // restate evaluation.VideoMAP, which is the definition (the reference ships no tube linking and no video-level evaluator).
-//   1. tube_rows_kernel     a thread per row: the arg-max column of its C + 1 probabilities
+//   1. tube_rows_kernel     a thread per row: the arg-max column of its C + 1 probabilities (tube_rows_ranked_kernel: the class the caller gives)
 //      tube_link_kernel     a wave per (video, class) walks the video's slots in order.  A lane holds one active tube (last box, fp64 score sum,
 //                           count, last slot, head) AND one row of the current slot; the visiting order of the tubes is a rank over
 //                           (mean score, head), the pick of a tube a wave arg-max over the order keys of the rows it may take.
@@ -45,6 +45,18 @@ __global__ __launch_bounds__(256) void tube_rows_kernel(const float* __restrict_
     row_head[r] = -1;
 }
 
+// the ranked form (tuber_tube_link_ranked): a row's class is what the caller gives, C where that is no class of the call
+__global__ __launch_bounds__(256) void tube_rows_ranked_kernel(const int* __restrict__ det_label, int N, int C, int* __restrict__ row_cls,
+                                                               int* __restrict__ row_head) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= N) return;
+    const int l = det_label[r];
+    row_cls[r] = (l >= 0 && l < C) ? l : C;
+    row_head[r] = -1;
+}
+
+// RANKED: det_prob is det_score [N], a row's score; otherwise [N][C + 1], the score being the wave's column of the row
+template <bool RANKED>
 __global__ __launch_bounds__(64 * TLINK_WAVES) void tube_link_kernel(const float* __restrict__ det_box, const float* __restrict__ det_prob,
                                                                      const int* __restrict__ slot_off, const int* __restrict__ video_off, int V,
                                                                      int S, int N, int C, double link_iou, int max_gap,
@@ -76,7 +88,7 @@ __global__ __launch_bounds__(64 * TLINK_WAVES) void tube_link_kernel(const float
         if (lane < n && row_cls[r] == c) {
             const float* d = det_box + (long)r * 4;
             b0 = d[0]; b1 = d[1]; b2 = d[2]; b3 = d[3];
-            sc = det_prob[(long)r * (C + 1) + c];
+            sc = RANKED ? det_prob[r] : det_prob[(long)r * (C + 1) + c];
             mine = b0 < b2 && b1 < b3 && sc == sc;
         }
         if (!__ballot(mine)) continue;
@@ -305,8 +317,28 @@ int tuber_tube_link(const float* det_box, const float* det_prob, const int* slot
     if (!det_box || !det_prob || !slot_off || !video_off || !row_cls || !row_head || !tube_score || !tube_len || !tube_last) return TUBER_EINVAL;
     hipLaunchKernelGGL(tube_rows_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, det_prob, N, C, row_cls, row_head);
     const long waves = (long)V * C;
-    hipLaunchKernelGGL(tube_link_kernel, dim3((unsigned)((waves + TLINK_WAVES - 1) / TLINK_WAVES)), dim3(64 * TLINK_WAVES), 0, stream, det_box,
+    hipLaunchKernelGGL(tube_link_kernel<false>, dim3((unsigned)((waves + TLINK_WAVES - 1) / TLINK_WAVES)), dim3(64 * TLINK_WAVES), 0, stream, det_box,
                        det_prob, slot_off, video_off, V, S, N, C, link_iou, max_gap, row_cls, row_head, tube_score, tube_len, tube_last);
+    TUBER_RETURN_LAUNCH();
+}
+
+// tuber_tube_link over ranked detections (detect.Detections, video.VideoDetections): a row's class and score are det_label [N] (0-based; negative or
+// >= C: the row is not counted) and det_score [N] fp32 instead of the arg-max of a [N][C + 1] row.  Everything else -- arguments, outputs, bounds,
+// negative codes, the walk and the fp64 sequential mean -- is tuber_tube_link's; row_cls: the label, C for a row that is not counted.
+int tuber_tube_link_ranked(const float* det_box, const int* det_label, const float* det_score, const int* slot_off, const int* video_off, int V, int S,
+                           int N, int C, int max_rows, double link_iou, int max_gap, int* row_cls, int* row_head, double* tube_score, int* tube_len,
+                           int* tube_last, hipStream_t stream) {
+    if (V < 0 || S < 0 || N < 0 || C <= 0 || max_rows < 0 || max_gap < 0 || !(link_iou == link_iou)) return TUBER_EINVAL;
+    if (max_rows > FMAP_MAX_DETS || (long)max_rows * ((long)max_gap + 1) > TUBE_MAX_ACTIVE) return TUBER_EINVAL;
+    if ((long)N > (long)S * max_rows || S < V) return TUBER_EINVAL;
+    if (N == 0) return TUBER_OK;
+    if ((long)V * C > 0x7FFFFFFFl) return TUBER_EINVAL;
+    if (!det_box || !det_label || !det_score || !slot_off || !video_off || !row_cls || !row_head || !tube_score || !tube_len || !tube_last)
+        return TUBER_EINVAL;
+    hipLaunchKernelGGL(tube_rows_ranked_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, det_label, N, C, row_cls, row_head);
+    const long waves = (long)V * C;
+    hipLaunchKernelGGL(tube_link_kernel<true>, dim3((unsigned)((waves + TLINK_WAVES - 1) / TLINK_WAVES)), dim3(64 * TLINK_WAVES), 0, stream, det_box,
+                       det_score, slot_off, video_off, V, S, N, C, link_iou, max_gap, row_cls, row_head, tube_score, tube_len, tube_last);
     TUBER_RETURN_LAUNCH();
 }
 int tuber_tube_link_max_active() { return TUBE_MAX_ACTIVE; }

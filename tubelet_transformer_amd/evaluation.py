@@ -482,6 +482,63 @@ def tubes_from_link(link):
     return out
 
 
+def link_rows(box, cls, score, slot, video_off, class_num, link_iou, max_gap):
+    """The greedy linking of per-frame detections into tubes, over rows in layout order (video, slot, store order): ``box`` [N, 4] fp32 xyxy,
+    ``cls`` [N] the 0-based class of a row, ``score`` [N] fp32, ``slot`` [N] the global slot, ``video_off`` [V + 1] the slots of every video.  A
+    row is counted unless its class is outside [0, class_num), its box has x1 >= x2 or y1 >= y2, or its score is NaN.  Per (video, class), slots
+    ascending: the tubes whose last detection is at most ``max_gap`` + 1 slots back are visited by descending mean score (fp64 sum of the fp32
+    scores / count), equal means by ascending head; each takes, among the slot's unclaimed rows whose fp64 IoU with its last box is >=
+    ``link_iou``, the highest score (equal scores: the first row); rows left over start tubes.  -> dict: ``row_head`` (layout row of the tube's
+    first detection, -1 for a row that is not counted) and, at head rows, ``tube_score`` (fp64 mean), ``tube_len``, ``tube_last`` (last slot).
+    The body of ``VideoMAP.link``, the definition of ``tuber_tube_link_ranked`` and the fallback of ``video.VideoDetections.tubes``."""
+    box = np.asarray(box, dtype=np.float32).reshape(-1, 4)
+    cls, score, slot = np.asarray(cls).reshape(-1), np.asarray(score).reshape(-1), np.asarray(slot).reshape(-1)
+    N, C = len(box), int(class_num)
+    counted = (cls >= 0) & (cls < C) & (box[:, 0] < box[:, 2]) & (box[:, 1] < box[:, 3]) & ~np.isnan(score)
+    box64 = box.astype(np.float64)
+    video = np.searchsorted(np.asarray(video_off), slot, side="right") - 1
+    head = np.full(N, -1, dtype=np.int64)
+    tscore, tlen, tlast = np.zeros(N), np.zeros(N, dtype=np.int64), np.full(N, -1, dtype=np.int64)
+    groups = {}
+    for r in np.nonzero(counted)[0].tolist():
+        groups.setdefault((int(video[r]), int(cls[r])), []).append(r)
+    for rows in groups.values():
+        tubes, i = [], 0                              # a tube: [head, fp64 score sum, count, last slot, last row]
+        while i < len(rows):
+            s, j = slot[rows[i]], i
+            while j < len(rows) and slot[rows[j]] == s:
+                j += 1
+            cur, i = rows[i:j], j
+            active = [t for t in tubes if s - t[3] <= max_gap + 1]
+            for t in tubes:
+                if s - t[3] > max_gap + 1:
+                    tscore[t[0]], tlen[t[0]], tlast[t[0]] = t[1] / t[2], t[2], t[3]
+            active.sort(key=lambda t: (-(t[1] / t[2]), t[0]))
+            claimed = set()
+            for t in active:
+                cand = [r for r in cur if r not in claimed]
+                if not cand:
+                    break
+                with np.errstate(all="ignore"):
+                    iou = _iou_one_to_many(box64[t[4]], box64[cand])
+                best = None
+                for r, u in zip(cand, iou):
+                    if u >= link_iou and (best is None or score[r] > score[best]):
+                        best = r
+                if best is not None:
+                    claimed.add(best)
+                    head[best] = t[0]
+                    t[1] += float(score[best]); t[2] += 1; t[3] = s; t[4] = best
+            tubes = active
+            for r in cur:
+                if r not in claimed:
+                    head[r] = r
+                    tubes.append([r, float(score[r]), 1, s, r])
+        for t in tubes:
+            tscore[t[0]], tlen[t[0]], tlast[t[0]] = t[1] / t[2], t[2], t[3]
+    return dict(row_head=head, tube_score=tscore, tube_len=tlen, tube_last=tlast)
+
+
 class VideoMAP:
     """Video-level mean average precision over action tubes: per (video, class) the per-frame detections are linked greedily into tubes
     (``link``), the tubes are matched against the ground-truth tubes by spatio-temporal IoU (``match``), and the ranked flags give VOC AP per
@@ -524,48 +581,8 @@ class VideoMAP:
         box, prob, slot = box[order], prob[order], lay["det_slot"][order]
         cls = prob.argmax(axis=1) if N else np.zeros(0, dtype=np.int64)
         score = prob[np.arange(N), cls]
-        counted = (cls != C) & (box[:, 0] < box[:, 2]) & (box[:, 1] < box[:, 3]) & ~np.isnan(score)
-        box64 = box.astype(np.float64)
-        video = np.searchsorted(lay["video_off"], slot, side="right") - 1
-        head = np.full(N, -1, dtype=np.int64)
-        tscore, tlen, tlast = np.zeros(N), np.zeros(N, dtype=np.int64), np.full(N, -1, dtype=np.int64)
-        groups = {}
-        for r in np.nonzero(counted)[0].tolist():
-            groups.setdefault((int(video[r]), int(cls[r])), []).append(r)
-        for rows in groups.values():
-            tubes, i = [], 0                              # a tube: [head, fp64 score sum, count, last slot, last row]
-            while i < len(rows):
-                s, j = slot[rows[i]], i
-                while j < len(rows) and slot[rows[j]] == s:
-                    j += 1
-                cur, i = rows[i:j], j
-                active = [t for t in tubes if s - t[3] <= self.max_gap + 1]
-                for t in tubes:
-                    if s - t[3] > self.max_gap + 1:
-                        tscore[t[0]], tlen[t[0]], tlast[t[0]] = t[1] / t[2], t[2], t[3]
-                active.sort(key=lambda t: (-(t[1] / t[2]), t[0]))
-                claimed = set()
-                for t in active:
-                    cand = [r for r in cur if r not in claimed]
-                    if not cand:
-                        break
-                    with np.errstate(all="ignore"):
-                        iou = _iou_one_to_many(box64[t[4]], box64[cand])
-                    best = None
-                    for r, u in zip(cand, iou):
-                        if u >= self.link_iou and (best is None or score[r] > score[best]):
-                            best = r
-                    if best is not None:
-                        claimed.add(best)
-                        head[best] = t[0]
-                        t[1] += float(score[best]); t[2] += 1; t[3] = s; t[4] = best
-                tubes = active
-                for r in cur:
-                    if r not in claimed:
-                        head[r] = r
-                        tubes.append([r, float(score[r]), 1, s, r])
-            for t in tubes:
-                tscore[t[0]], tlen[t[0]], tlast[t[0]] = t[1] / t[2], t[2], t[3]
+        rows = link_rows(box, cls, score, slot, lay["video_off"], C, self.link_iou, self.max_gap)
+        head, tscore, tlen, tlast = rows["row_head"], rows["tube_score"], rows["tube_len"], rows["tube_last"]
         link = dict(order=order, det_box=box, det_prob=prob, row_slot=slot, row_cls=cls, row_head=head, tube_score=tscore, tube_len=tlen,
                     tube_last=tlast, layout=lay)
         link["tubes"] = tubes_from_link(link)

@@ -1,0 +1,276 @@
+"""Whole-video inference: frames in, detections per key frame and action tubes out.
+
+The reference reaches its model through a dataset loader that cuts one clip per annotated key frame on CPU workers
+(``datasets/ava_frame.py:37-74,133-152``, ``datasets/jhmdb_frame.py:194-223``); it has no path from a video to detections.  Here a video is
+resident ONCE on the device at working resolution (``tuber_frames_resize``, every frame resized once), the overlapping clips of a batch of key
+frames are gathered from it by one launch (``tuber_video_clips``, csrc/video_clips.hip) reading a frame-index table (``clip_indices``), the
+captured ``detect.Detector`` runs over them, and the ranked detections of all key frames are linked into tubes by the wave-per-(video, class)
+linker in its ranked form (``tuber_tube_link_ranked``, csrc/tube_map.hip; ``evaluation.link_rows`` is its definition and its fallback).
+"""
+import sys
+
+import numpy as np
+import torch
+
+from . import input_pipeline as ip
+from . import lib
+from .detect import FIELDS, Detector
+from .misc import NestedTensor
+
+RULES = ("ava", "jhmdb", "edge")
+
+
+def clip_indices(n_frames, keys, T, rate=1, rule="ava"):
+    """The frames of the clip around every key frame: int32 [len(keys), T] of 0-based frame numbers in [0, n_frames).
+
+    ``rule="ava"`` (datasets/ava_frame.py:43,143-145): ``start = max(key - T//2 * rate, 0)``, then
+    ``clip(range(start, start + T * rate, rate), 0, n - 1)`` -- a clip at the front of a video starts at frame 0, so its key frame sits before
+    position T//2.  ``rule="jhmdb"`` (datasets/jhmdb_frame.py:201-208, ids 0-based; ``rate`` is not used): ``start = max(key - T//2, 0)``,
+    ``end = min(key + T - T//2, n - 1)``, ``range(start, end)``; a short clip gets ``(T - len) // 2`` copies of frame 0 in front -- the
+    reference's pad, whatever ``start`` is -- and copies of ``end`` behind.  ``rule="edge"`` is not a reference rule: it keeps the key frame
+    at position T//2, ``clamp(key + (i - T//2) * rate, 0, n - 1)``."""
+    n, T, rate = int(n_frames), int(T), int(rate)
+    if n < 1 or T < 1 or rate < 1:
+        raise ValueError("clip_indices: n_frames = %d, T = %d, rate = %d must be >= 1" % (n, T, rate))
+    if rule not in RULES:
+        raise ValueError("clip_indices: rule %r is not one of %s" % (rule, ", ".join(RULES)))
+    keys = [int(k) for k in keys]
+    out = np.zeros((len(keys), T), dtype=np.int32)
+    for i, key in enumerate(keys):
+        if not 0 <= key < n:
+            raise ValueError("clip_indices: key frame %d outside the video's %d frames" % (key, n))
+        if rule == "ava":
+            start = max(key - T // 2 * rate, 0)
+            out[i] = np.clip(np.arange(start, start + T * rate, rate), 0, n - 1)
+        elif rule == "jhmdb":
+            start = max(key - T // 2, 0)
+            end = min(key + T - T // 2, n - 1)
+            ids = list(range(start, end))
+            if len(ids) < T:
+                front = (T - len(ids)) // 2
+                ids = [0] * front + ids + [end] * (T - len(ids) - front)
+            out[i] = ids[:T]
+        else:
+            out[i] = np.clip(key + (np.arange(T) - T // 2) * rate, 0, n - 1)
+    return out
+
+
+def working_geometry(H0, W0, size):
+    """(nh, nw, y1, x1, h, w) of the reference's val pipeline for a H0 x W0 video: the short side resized to ``size``
+    (datasets/ava_frame.py:86-91,127,149: ``int`` of the float sizes), then the window of ``Resize_Custom(size)``
+    (datasets/video_transforms.py:210-227) in the resized frame"""
+    oh, ow, size = int(H0), int(W0), int(size)
+    if oh <= ow:
+        nh, nw = size, size * (ow / oh)
+    else:
+        nw, nh = size, size * (oh / ow)
+    H, W = int(nh), int(nw)
+    if W < H:
+        w, h = size, int(size * (H / W))
+    else:
+        h, w = size, int(size * (W / H))
+    h, w = min(h, H), min(w, W)
+    return H, W, int(round((H - h) / 2.0)), int(round((W - w) / 2.0)), h, w
+
+
+class VideoDetections:
+    """The ranked detections of a video's key frames: ``keys`` (frame numbers) and, as tensors on one device, ``boxes`` [n, K, 4] fp32 xyxy in
+    source-video pixels, ``scores`` / ``aux`` [n, K] fp32, ``labels`` / ``queries`` [n, K] int32 (-1 in the rows behind ``count``), ``count`` /
+    ``total`` [n] int32 -- the fields of ``detect.Detections``, a row per key frame."""
+
+    def __init__(self, keys, boxes, scores, labels, queries, aux, count, total, class_num, settings=None, store=None):
+        self.keys = [int(k) for k in keys]
+        self.boxes, self.scores, self.labels, self.queries, self.aux, self.count, self.total = boxes, scores, labels, queries, aux, count, total
+        self.class_num = int(class_num)
+        self.settings = dict(settings or dict(link_iou=0.2, max_gap=2, min_len=1))      # the defaults of tubes(): CONFIG.VAL.VIDEO_MAP
+        self.tubes_path = None                                                         # "device" or "host" after tubes()
+        self._store = store                                                            # the engine's ParamStore: to_host reads its error word
+        if not (len(self.keys) == boxes.shape[0] == scores.shape[0] == count.shape[0]):
+            raise ValueError("VideoDetections: %d keys, %d rows" % (len(self.keys), boxes.shape[0]))
+
+    def tensors(self):
+        return tuple(getattr(self, k) for k in FIELDS)
+
+    def _fetch(self, extra=()):
+        """every field (and ``extra`` tensors) as numpy arrays, in ONE device-to-host copy"""
+        parts = [t.contiguous() for t in list(self.tensors()) + list(extra)]
+        if self.boxes.device.type != "cuda":
+            return [t.numpy() for t in parts]
+        blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
+        host, o = [], 0
+        for t in parts:
+            n = t.numel() * t.element_size()
+            host.append(blob[o:o + n].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape)))
+            o += n
+        return host
+
+    def to_host(self):
+        """a list, per key frame, of dicts of numpy arrays trimmed to ``count`` (``key``, ``boxes``, ``scores``, ``labels``, ``queries``, ``aux``,
+        ``count``, ``total``): one copy, the place that synchronises.  A cooperative decoder launch that timed out during the video leaves empty
+        key frames (detect.py, "Fail-safe"); its error word travels in the same copy and raises here, the engine having switched to the launch
+        chain: run the video again."""
+        word = [self._store.coop_sync] if self._store is not None and self.boxes.device.type == "cuda" else []
+        host = self._fetch(word)
+        if word and host[-1][2] and not self._store.coop_off:
+            self._store.check_coop()
+        host = dict(zip(FIELDS, host))
+        out = []
+        for i, key in enumerate(self.keys):
+            n = int(host["count"][i])
+            d = {k: host[k][i, :n].copy() for k in ("boxes", "scores", "labels", "queries", "aux")}
+            d["key"], d["count"], d["total"] = key, n, int(host["total"][i])
+            out.append(d)
+        return out
+
+    # -- tubes ------------------------------------------------------------------------------------------------------------
+    def _link_device(self, link_iou, max_gap):
+        """``tuber_tube_link_ranked`` over the padded store as it is, or None where the linker's bounds refuse it"""
+        S, K = self.scores.shape
+        if self.boxes.device.type != "cuda":
+            return None, "the store is on the CPU"
+        if K > lib.query("tuber_frame_match_max_dets") or K * (max_gap + 1) > lib.query("tuber_tube_link_max_active"):
+            return None, "%d rows per key frame with max_gap %d: beyond %d rows or %d active tubes" % (
+                K, max_gap, lib.query("tuber_frame_match_max_dets"), lib.query("tuber_tube_link_max_active"))
+        dev, N = self.boxes.device, S * K
+        slot_off = torch.arange(S + 1, dtype=torch.int32, device=dev) * K               # rows behind a key's count carry label -1: not counted
+        video_off = torch.tensor([0, S], dtype=torch.int32).to(dev)
+        out = dict(row_cls=torch.empty(N, dtype=torch.int32, device=dev), row_head=torch.empty(N, dtype=torch.int32, device=dev),
+                   tube_score=torch.zeros(N, dtype=torch.float64, device=dev), tube_len=torch.zeros(N, dtype=torch.int32, device=dev),
+                   tube_last=torch.full((N,), -1, dtype=torch.int32, device=dev))
+        lib.call("tuber_tube_link_ranked", self.boxes.contiguous(), self.labels.contiguous(), self.scores.contiguous(), slot_off, video_off, 1, S, N,
+                 self.class_num, K, float(link_iou), int(max_gap), out["row_cls"], out["row_head"], out["tube_score"], out["tube_len"], out["tube_last"])
+        names = ("row_head", "tube_score", "tube_len", "tube_last")
+        host = self._fetch([out[k] for k in names])
+        return dict(zip(FIELDS + names, host)), None
+
+    def tubes(self, link_iou=None, max_gap=None, min_len=None):
+        """The action tubes of the video: a list of ``dict(cls, score, frames, boxes, length)`` in head order (the order of the tubes' first
+        detections) -- ``cls`` 1-based as in ``evaluation.tubes_from_link``, ``score`` the fp64 mean of the linked fp32 scores, ``frames`` the key
+        frame numbers, ``boxes`` [length, 4] in source pixels; tubes shorter than ``min_len`` are dropped.  The slots of the linker are key
+        ORDINALS, so ``max_gap`` counts key frames.  Defaults: ``CONFIG.VAL.VIDEO_MAP``.  Linked on the device by ``tuber_tube_link_ranked``;
+        beyond its bounds (K > 64 rows per key frame or K * (max_gap + 1) > ``tuber_tube_link_max_active()`` = 64) or on a CPU store
+        ``evaluation.link_rows`` answers, one line says so, and ``tubes_path`` is "host" instead of "device".  ``VideoDetector``'s default
+        ``topk`` is 21 = 64 // (MAX_GAP + 1) with the shipped MAX_GAP of 2, so that the default path is the device's."""
+        from .evaluation import link_rows, tubes_from_link
+        link_iou = float(self.settings["link_iou"] if link_iou is None else link_iou)
+        max_gap = int(self.settings["max_gap"] if max_gap is None else max_gap)
+        min_len = int(self.settings["min_len"] if min_len is None else min_len)
+        S, K = self.scores.shape
+        slot = np.repeat(np.arange(S, dtype=np.int64), K)
+        host, why = self._link_device(link_iou, max_gap)
+        if host is None:
+            print("[tuber] VideoDetections.tubes: %s; linking on the host" % why, file=sys.stderr, flush=True)
+            host = dict(zip(FIELDS, self._fetch()))
+            host.update(link_rows(host["boxes"].reshape(-1, 4), host["labels"].reshape(-1), host["scores"].reshape(-1), slot, [0, S], self.class_num,
+                                  link_iou, max_gap))
+        self.tubes_path = "host" if why else "device"
+        layout = dict(videos=["video"], video_off=np.asarray([0, S]), first_frame=np.asarray([0]))
+        link = dict(layout=layout, row_head=host["row_head"], row_slot=slot, row_cls=host["labels"].reshape(-1), tube_score=host["tube_score"],
+                    det_box=host["boxes"].reshape(-1, 4))
+        out = []
+        for t in tubes_from_link(link):
+            if len(t["frames"]) >= min_len:
+                out.append(dict(cls=t["cls"], score=t["score"], frames=[self.keys[s] for s in t["frames"]], boxes=t["boxes"], length=len(t["frames"])))
+        return out
+
+
+class VideoDetector:
+    """``VideoDetector(cfg, model)(frames)`` -> ``VideoDetections``: every key frame of a video through the captured ``detect.Detector``.
+
+    ``frames``: uint8 [N, H0, W0, 3] (numpy, a host tensor or a device tensor).  They are uploaded ``chunk`` frames at a time and each frame is
+    resized ONCE (``tuber_frames_resize``) to the reference's val size (``working_geometry``); the raw frames never need to be resident.
+    ``keys``: frame numbers, by default ``range(0, N, stride)``; ``stride`` defaults to one second's worth for AVA (30 frames: the reference's
+    ``timef * 30``, datasets/ava_frame.py:43) and 1 for JHMDB / UCF101-24.  Per batch of ``batch`` keys: one ``tuber_video_clips`` launch over a
+    slice of the one index table (``clip_indices``, uploaded up front), the one ``Detector`` with ``key_pos = T // 2`` and ``sizes = (H0, W0)``,
+    and the seven fields copied device-to-device into the video's store.  The last batch is padded by repeating its last key -- one graph
+    shape -- and its surplus rows are dropped.  Once the first call has captured its graph, a call synchronises nowhere.
+
+    ``rule``: ``clip_indices``' rule, by default the model's ``dataset_mode`` ("ava", otherwise "jhmdb").  ``topk``: by default
+    ``min(CONFIG.VAL.DETECT.TOPK, tuber_tube_link_max_active() // (CONFIG.VAL.VIDEO_MAP.MAX_GAP + 1))`` -- 21 with the shipped settings (TOPK 100,
+    64 active tubes, MAX_GAP 2) -- so that ``tubes()`` with its defaults links on the device.  ``score_thr`` / ``actor_thr`` / ``graphed``: as
+    ``Detector``."""
+
+    def __init__(self, cfg, model, batch=2, score_thr=None, topk=None, actor_thr=None, graphed=True, rule=None):
+        from .config import detect_settings, video_map_settings
+        self.cfg, self.model = cfg, model
+        self.batch = int(batch)
+        if self.batch < 1:
+            raise ValueError("VideoDetector: batch = %r must be >= 1" % (batch,))
+        vm = video_map_settings(cfg)
+        self.settings = dict(link_iou=float(vm["link_iou"]), max_gap=int(vm["max_gap"]), min_len=int(vm["min_len"]))
+        if topk is None:
+            topk = max(1, min(detect_settings(cfg)["topk"], lib.query("tuber_tube_link_max_active") // (self.settings["max_gap"] + 1)))
+        self.detector = Detector(cfg, model, score_thr=score_thr, topk=topk, actor_thr=actor_thr, graphed=graphed)
+        self.mode = model.dataset_mode
+        self.rule = rule if rule is not None else ("ava" if self.mode == "ava" else "jhmdb")
+        if self.rule not in RULES:
+            raise ValueError("VideoDetector: rule %r is not one of %s" % (rule, ", ".join(RULES)))
+        D = cfg.CONFIG.DATA
+        self.T, self.rate, self.size, self.class_num = int(D.TEMP_LEN), int(D.FRAME_RATE), int(D.IMG_SIZE), int(D.NUM_CLASSES)
+        self._bufs = {}
+
+    def _resident(self, frames, dev, chunk):
+        """the video at working resolution on the device, uint8 [N, nh, nw, 3]: uploaded and resized ``chunk`` frames at a time"""
+        N, H0, W0 = (int(v) for v in frames.shape[:3])
+        nh, nw = working_geometry(H0, W0, self.size)[:2]
+        out = torch.empty(N, nh, nw, 3, dtype=torch.uint8, device=dev)
+        same = (nh, nw) == (H0, W0)
+        if not same:
+            (bh, kh, bv, kv), ksh, ksv, y0, rows = ip._device_coeffs(dev, H0, W0, nh, nw)
+            tmp = torch.empty(chunk * rows * nw * 3, dtype=torch.uint8, device=dev) if (nw != W0 and nh != H0) else None
+        for i in range(0, N, chunk):
+            src = frames[i:i + chunk].to(dev, non_blocking=True).contiguous()
+            if same:
+                out[i:i + chunk].copy_(src)
+            else:
+                lib.call("tuber_frames_resize", src, tmp, out[i:], src.shape[0], H0, W0, nh, nw, bh, kh, ksh, bv, kv, ksv, y0, rows)
+        return out
+
+    @torch.no_grad()
+    def __call__(self, frames, keys=None, stride=None, chunk=256):
+        if self.model.training:
+            raise RuntimeError("VideoDetector runs an eval forward: call model.eval() first")
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
+            raise ValueError("VideoDetector wants uint8 frames [N, H, W, 3], got %s %s" % (frames.dtype, tuple(frames.shape)))
+        chunk = int(chunk)
+        if chunk < 1:
+            raise ValueError("VideoDetector: chunk = %r must be >= 1" % (chunk,))
+        store, _ = self.model.engine()
+        dev = store.device
+        N, H0, W0 = (int(v) for v in frames.shape[:3])
+        if keys is None:
+            stride = int(stride) if stride is not None else (30 if self.mode == "ava" else 1)
+            if stride < 1:
+                raise ValueError("VideoDetector: stride = %r must be >= 1" % (stride,))
+            keys = range(0, N, stride)
+        keys = [int(k) for k in keys]
+        if not keys:
+            raise ValueError("VideoDetector: no key frames")
+        n, B, T = len(keys), self.batch, self.T
+        nb = (n + B - 1) // B
+        table = clip_indices(N, keys + [keys[-1]] * (nb * B - n), T, self.rate, self.rule)      # the padded last batch repeats its last key
+        table = torch.from_numpy(table).to(dev, non_blocking=True)
+        resident = self._resident(frames, dev, chunk)
+        nh, nw, y1, x1, h, w = working_geometry(H0, W0, self.size)
+        lut = ip._device_tables(dev, (ip.MEAN, ip.STD))[0]
+        bufs = self._bufs.get((str(dev), h, w))
+        if bufs is None:                       # one clip buffer, one zero mask (every frame of a video has one size), the per-batch constants
+            bufs = self._bufs[str(dev), h, w] = (torch.empty(B, 3, T, h, w, dtype=torch.float32, device=dev),
+                                                 torch.zeros(B, h, w, dtype=torch.bool, device=dev),
+                                                 torch.full((B,), T // 2, dtype=torch.int64, device=dev))
+        clips, mask, key_pos = bufs
+        sizes = torch.tensor([[H0, W0]] * B, dtype=torch.float32).to(dev, non_blocking=True)
+        K = self.detector.topk
+        f32, i32 = torch.float32, torch.int32
+        full = [torch.empty(nb * B, K, 4, dtype=f32, device=dev), torch.empty(nb * B, K, dtype=f32, device=dev), torch.empty(nb * B, K, dtype=i32, device=dev),
+                torch.empty(nb * B, K, dtype=i32, device=dev), torch.empty(nb * B, K, dtype=f32, device=dev), torch.empty(nb * B, dtype=i32, device=dev),
+                torch.empty(nb * B, dtype=i32, device=dev)]
+        samples = NestedTensor(clips, mask)
+        for b in range(nb):
+            lib.call("tuber_video_clips", resident, N, nh, nw, table[b * B:], B, T, y1, x1, h, w, lut, clips)
+            det = self.detector(samples, sizes, key_pos)
+            for dst, src in zip(full, det.tensors()):
+                dst[b * B:(b + 1) * B].copy_(src)
+        return VideoDetections(keys, *[t[:n] for t in full], class_num=self.class_num, settings=self.settings, store=store)
