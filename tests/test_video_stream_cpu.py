@@ -1,0 +1,208 @@
+"""Streaming video inference on the host (tubelet_transformer_amd/video.py ``VideoStream``): ``evaluation.TubeLinker`` -- the
+resumable form of ``link_rows`` and the definition of ``tuber_tube_link_stream`` -- against ``link_rows`` in one piece and cut at every slot and
+pair of slots, ``frames_needed`` against ``clip_indices`` evaluated for every longer video, and the ring size of ``ring_frames`` against a replay
+of ``StreamSchedule`` on host integers.  Every comparison is exact."""
+import itertools
+
+import numpy as np
+import pytest
+
+from tubelet_transformer_amd.evaluation import TubeLinker, link_rows
+from tubelet_transformer_amd.video import RULES, StreamSchedule, clip_indices, clip_span, frames_needed, ring_frames
+
+LINK_IOU = 0.25
+A = (0, 0, 10, 10)
+PAD = ((0, 0, 0, 0), -1, 0.0)
+
+
+def ranked_fixture():
+    """the fixture of tests/test_video_gpu.py, restated: S = 6 slots of K = 4 rows, C = 3, two videos (slots 0-3 and 4-5), max_gap = 1"""
+    nan = float("nan")
+    slots = [
+        [(A, 0, 0.8), ((100, 0, 110, 10), 0, 0.8), (A, 1, 0.7), PAD],                   # two tubes of class 0 with equal means (0.8)
+        [PAD, PAD, PAD, PAD],                                                           # an empty slot, inside the gap of both
+        [((6, 0, 16, 10), 0, 0.6),                                                      # IoU with A exactly 0.25 = LINK_IOU: linked
+         ((101, 0, 111, 10), 0, 0.5), ((99, 0, 109, 10), 0, 0.5),                       # two equal scores for one tube: it takes the first
+         ((2, 0, 12, 10), 0, nan)],                                                     # a NaN score: not counted
+        [(A, 1, 0.9),                                                                   # class 1 again after two slots without it: beyond the gap
+         ((5, 0, 5, 10), 0, 0.9),                                                       # x1 >= x2: not counted
+         ((7, 0, 17, 10), 0, 0.7), PAD],
+        [(A, 2, 0.6), ((2, 0, 12, 10), 2, 0.9), PAD, PAD],
+        [((1, 0, 11, 10), 2, 0.7), ((3, 0, 13, 10), 2, 0.7), (A, 5, 0.9), PAD],         # equal scores again; a label >= C
+    ]
+    box = np.array([r[0] for s in slots for r in s], dtype=np.float32)
+    label = np.array([r[1] for s in slots for r in s], dtype=np.int32)
+    score = np.array([r[2] for s in slots for r in s], dtype=np.float32)
+    return dict(box=box, label=label, score=score, S=6, K=4, C=3, max_gap=1, link_iou=LINK_IOU, videos=((0, 4), (4, 6)))
+
+
+def lattice_fixture():
+    """S = 9 slots of K = 6 rows of ONE video, C = 4, max_gap = 2: boxes around three anchors, scores on a lattice (equal scores within and across
+    slots), one empty slot, NaN scores, labels of no class"""
+    rng = np.random.default_rng(5)
+    S, K, C = 9, 6, 4
+    rows_per = rng.integers(2, K + 1, S)
+    rows_per[3] = 0
+    anchors = np.array([[10, 10, 50, 60], [30, 15, 70, 65], [100, 20, 140, 80]], dtype=np.float32)
+    box = anchors[rng.integers(3, size=S * K)] + rng.integers(-6, 7, (S * K, 4)).astype(np.float32)
+    label = rng.integers(0, C + 1, S * K).astype(np.int32)                                  # C: no class of the call
+    label[rng.random(S * K) < 0.5] = 1                                                      # one crowded class: tubes that compete
+    score = (rng.integers(1, 10, S * K) / 10.0).astype(np.float32)
+    score[[2, 31]] = np.nan
+    for s in range(S):
+        label[s * K + rows_per[s]:(s + 1) * K] = -1                                         # the rows behind a slot's count
+        box[s * K + rows_per[s]:(s + 1) * K] = 0
+        score[s * K + rows_per[s]:(s + 1) * K] = 0
+    return dict(box=box, label=label, score=score, S=S, K=K, C=C, max_gap=2, link_iou=0.2, videos=((0, S),))
+
+
+FIXTURES = {"ranked": ranked_fixture, "lattice": lattice_fixture}
+
+
+def video_rows(fx, v):
+    s0, s1 = fx["videos"][v]
+    K = fx["K"]
+    return fx["box"][s0 * K:s1 * K], fx["label"][s0 * K:s1 * K], fx["score"][s0 * K:s1 * K], s1 - s0
+
+
+def one_shot(fx, v):
+    """``link_rows`` over one video of a fixture"""
+    box, label, score, S = video_rows(fx, v)
+    return link_rows(box, label, score, np.repeat(np.arange(S), fx["K"]), [0, S], fx["C"], fx["link_iou"], fx["max_gap"])
+
+
+def pushed(linker, fx, v, cuts=()):
+    """the records of one video pushed in the pieces that ``cuts`` (slot numbers) make, concatenated"""
+    box, label, score, S = video_rows(fx, v)
+    K = fx["K"]
+    edges = [0] + sorted(cuts) + [S]
+    parts = [linker.push(box[a * K:b * K], label[a * K:b * K], score[a * K:b * K], K) for a, b in zip(edges[:-1], edges[1:])]
+    return {k: np.concatenate([p[k] for p in parts]) for k in ("row_head", "row_score", "row_len")}
+
+
+def last_rows(row_head):
+    """head -> the last row of its tube"""
+    return {int(h): r for r, h in enumerate(row_head.tolist()) if h >= 0}
+
+
+def assert_agrees_with_link_rows(got, want):
+    assert np.array_equal(got["row_head"], want["row_head"])
+    ends = last_rows(want["row_head"])
+    assert len(ends) >= 2
+    for h, r in ends.items():
+        assert got["row_len"][r] == want["tube_len"][h]
+        assert got["row_score"][r:r + 1].view(np.int64)[0] == want["tube_score"][h:h + 1].view(np.int64)[0]
+    off = want["row_head"] < 0
+    assert (got["row_score"][off] == 0).all() and (got["row_len"][off] == 0).all()
+
+
+def same_records(a, b):
+    return (np.array_equal(a["row_head"], b["row_head"]) and np.array_equal(a["row_len"], b["row_len"])
+            and np.array_equal(a["row_score"].view(np.int64), b["row_score"].view(np.int64)))
+
+
+@pytest.mark.parametrize("name", sorted(FIXTURES))
+def test_tube_linker_in_one_push_equals_link_rows(name):
+    fx = FIXTURES[name]()
+    linker = TubeLinker(fx["C"], fx["link_iou"], fx["max_gap"])
+    for v in range(len(fx["videos"])):                                  # the second video after reset(): heads count from 0 again
+        assert_agrees_with_link_rows(pushed(linker, fx, v), one_shot(fx, v))
+        linker.reset()
+    if name == "lattice":
+        label, score = fx["label"], fx["score"]
+        ok = label >= 0
+        assert np.isnan(score).any() and (label == fx["C"]).any() and not ok.reshape(fx["S"], fx["K"])[3].any()
+        assert len(set(score[ok & ~np.isnan(score)].tolist())) < ok.sum() - 1          # equal scores
+        assert one_shot(fx, 0)["tube_len"].max() >= 3
+
+
+@pytest.mark.parametrize("name", sorted(FIXTURES))
+def test_tube_linker_split_at_every_cut_and_pair_of_cuts_gives_the_same_records(name):
+    fx = FIXTURES[name]()
+    linker = TubeLinker(fx["C"], fx["link_iou"], fx["max_gap"])
+    S, K = fx["videos"][0][1], fx["K"]
+    want = one_shot(fx, 0)
+    head = want["row_head"]
+    # before comparing: the fixture holds a tube that spans a cut across an empty slot, and one that closes exactly at a cut
+    slot_of = lambda r: r // K
+    rows_of = {}
+    for r, h in enumerate(head.tolist()):
+        if h >= 0:
+            rows_of.setdefault(h, []).append(r)
+    empty = [s for s in range(S) if (head[s * K:(s + 1) * K] < 0).all()]
+    assert empty
+    assert any(slot_of(a) < e < slot_of(b) for rows in rows_of.values() for a, b in zip(rows[:-1], rows[1:]) for e in empty)    # cuts e and e + 1 split it
+    stale = fx["max_gap"] + 2                                                        # slots after its last one at which a tube is no longer active
+    assert any(1 <= slot_of(rows[-1]) + stale <= S - 1 for rows in rows_of.values())  # a cut there: the tube closes exactly at the cut
+    whole = pushed(linker, fx, 0)
+    assert_agrees_with_link_rows(whole, want)
+    cuts = [()] + [(c,) for c in range(1, S)] + list(itertools.combinations(range(1, S), 2))
+    for cut in cuts:
+        linker.reset()
+        assert same_records(pushed(linker, fx, 0, cut), whole), cut
+    with pytest.raises(ValueError):
+        linker.push(fx["box"][:K + 1], fx["label"][:K + 1], fx["score"][:K + 1], K + 1)      # another K inside a video
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# readiness and the ring
+# ------------------------------------------------------------------------------------------------------------------------------
+NMAX = 23
+
+
+@pytest.mark.parametrize("rule", RULES)
+@pytest.mark.parametrize("rate", (1, 2))
+def test_a_key_is_ready_exactly_when_no_longer_video_changes_its_clip(rule, rate):
+    T = 4
+    rows = {n: clip_indices(n, range(n), T, rate, rule) for n in range(1, NMAX + 1)}
+    seen = set()
+    for n in range(1, NMAX):
+        for key in range(n):
+            same = all(np.array_equal(rows[n][key], rows[m][key]) for m in range(n + 1, NMAX + 1))
+            assert (frames_needed(key, T, rate, rule) <= n) == same, (key, n)
+            seen.add(same)
+    assert seen == {True, False}
+    # the schedule decides a prefix of the keys: readiness grows with the key
+    need = [frames_needed(k, T, rate, rule) for k in range(NMAX)]
+    assert need == sorted(need) and all(f > k for k, f in enumerate(need))
+
+
+@pytest.mark.parametrize("rule", RULES)
+@pytest.mark.parametrize("T,rate,batch,stride,max_chunk,pushes", [
+    (4, 1, 2, 3, 5, (23,)), (4, 2, 3, 2, 4, (1, 9, 13)), (4, 2, 1, 1, 1, (7,) * 4), (8, 2, 2, 9, 16, (1, 50, 49)), (5, 1, 2, 1, 3, (2,) * 15),
+    (4, 2, 2, 30, 2, (64,))])
+def test_the_ring_holds_every_frame_a_key_needs_when_it_runs(rule, T, rate, batch, stride, max_chunk, pushes):
+    sch = StreamSchedule(T, rate, rule, batch, stride, max_chunk)
+    R = sch.R
+    assert R == ring_frames(T, rate, rule, batch, stride, max_chunk) == clip_span(T, rate, rule) + (batch - 1) * stride + max_chunk
+    total = sum(pushes)
+    slot = {}                                                           # ring slot -> the frame it holds
+    ran = []
+
+    def run(first, keys, n_total):
+        for key in [(first + i) * stride for i in range(keys)]:
+            row = clip_indices(n_total if n_total > 0 else key + 4 * T * rate, [key], T, rate, rule)[0]
+            if n_total < 0:
+                assert np.array_equal(row, clip_indices(total, [key], T, rate, rule)[0])            # decided: what the whole video gives
+            for f in row.tolist():
+                assert f == 0 or slot.get(f % R) == f, (key, f, R)      # frame 0 has a slot of its own
+            ran.append(key)
+    n = 0
+    for m in pushes:
+        for off, length, batches in sch.push(m):
+            assert length <= max_chunk
+            for f in range(n, n + length):
+                slot[f % R] = f
+            n += length
+            for k in batches:
+                run(k, batch, -1)
+    overwritten = n > R
+    n_total, batches = sch.finish()
+    assert n_total == total
+    for k, keys in batches:
+        assert 1 <= keys <= batch
+        run(k, keys, n_total)
+    assert ran == list(range(0, total, stride))                         # every key once, in order, in VideoDetector's batches
+    assert (sch.frames, sch.decided) == (0, 0)
+    if max_chunk < total and (T, stride) != (4, 30):
+        assert overwritten

@@ -353,6 +353,23 @@ DOC = {
                          "frame (Resize_Custom, video_transforms.py:210-227), lut fp32 [3][256], out fp32 [B][3][T][h][w]. 16-byte stores and dword loads from the "
                          "enclosing aligned window when w % 4 == 0, byte loads and scalar stores otherwise; the table in LDS. A null pointer, a non-positive size "
                          "or a window outside H x W: negative, nothing launched.",
+    "tuber_video_clips_ring": "tuber_video_clips over a ring of the last R frames (video.VideoStream), the frame-index rule evaluated in the kernel: no index table is "
+                              "built or uploaded. ring uint8 [R + 1][H][W][3] packed at any byte alignment: frame f sits in slot f % R, and frame 0 in the fixed slot R "
+                              "as well (the jhmdb rule pads a short clip at the END of a video with frame 0, datasets/jhmdb_frame.py:205-208). Key b of the batch is "
+                              "first_key + min(b, n_keys - 1) * key_step (the last batch repeats its last key); rule 0 ava (datasets/ava_frame.py:43,143-145), 1 jhmdb "
+                              "(datasets/jhmdb_frame.py:201-208), 2 edge: video.clip_indices restated in closed form; n_total the video's frame count, < 0 while it is "
+                              "not known (no end clamp). Window, lut, out and the load / store body are tuber_video_clips', the buffer bounds those of the R + 1 slots. "
+                              "The caller guarantees that the ring holds every frame a key needs. A null pointer, a non-positive size, R < 1, an unknown rule, a "
+                              "negative key or a window outside H x W: negative, nothing launched.",
+    "tuber_tube_link_stream": "tuber_tube_link_ranked for ONE video whose slots arrive in pieces (evaluation.TubeLinker: the definition; video.VideoStream): links the S "
+                              "new slots with the ordinals slot_base .. slot_base + S - 1, K rows each (det_box [S * K][4], det_label / det_score [S * K]; rows behind a "
+                              "key's count carry label -1). state: caller-owned, tuber_tube_link_state_bytes(C) bytes, 16-byte aligned, all zero = no tubes: per (class, "
+                              "lane) what a lane of the link kernel holds (valid, last box, fp64 sum, count, last ordinal, head), loaded before the walk and stored after "
+                              "it with plain vector stores. Out, per row: row_head the GLOBAL row (ordinal * K + position) of the tube's first detection, row_score the "
+                              "tube's fp64 mean and row_len its count after taking the row; -1, 0, 0 for a row that is not counted: a tube's score and length are those "
+                              "of its last row. The walk is tuber_tube_link's kernel body. K > tuber_frame_match_max_dets(), K * (max_gap + 1) > "
+                              "tuber_tube_link_max_active(), (slot_base + S) * K beyond an int32, bad sizes or pointers: negative, nothing launched, the state untouched.",
+    "tuber_tube_link_state_bytes": "bytes of the state buffer of tuber_tube_link_stream for C classes (40 per (class, lane): C * 64 * 40); 0 for C <= 0.",
     "tuber_tube_link_max_active":"simultaneously active tubes of one (video, class) tuber_tube_link takes: max rows per slot x (max_gap + 1) (64).",
     "tuber_tube_match": "video-mAP on the device, matching step (evaluation.VideoMAP.match): the tuber_tube_link outputs against ground-truth tubes given as gt_box [G][4] fp64 / "
                         "gt_cls [G] / gt_tube [G] (the rank of the row's tube among the tube ids of its (video, class), ascending; one row per (slot, class, tube)) in slot order "

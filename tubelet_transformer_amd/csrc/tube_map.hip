@@ -4,6 +4,8 @@
 //      tube_link_kernel     a wave per (video, class) walks the video's slots in order.  A lane holds one active tube (last box, fp64 score sum,
 //                           count, last slot, head) AND one row of the current slot; the visiting order of the tubes is a rank over
 //                           (mean score, head), the pick of a tube a wave arg-max over the order keys of the rows it may take.
+//                           Its STREAM form (tuber_tube_link_stream, video.VideoStream) links one video whose slots arrive in pieces: the
+//                           lanes are loaded from and stored to a caller-owned state around the walk.
 //   2. tube_match_kernel    a wave per (video, class): walks the slots again with the live tubes in lanes and adds the per-slot IoU against the
 //                           ground-truth boxes of the class into a [64][32] table (tube lane x ground-truth tube), writes a tube's spatio-temporal
 //                           IoU row when the tube ends, then visits the counted tubes by descending score and matches them greedily, a lane per
@@ -55,28 +57,54 @@ __global__ __launch_bounds__(256) void tube_rows_ranked_kernel(const int* __rest
     row_head[r] = -1;
 }
 
-// RANKED: det_prob is det_score [N], a row's score; otherwise [N][C + 1], the score being the wave's column of the row
-template <bool RANKED>
+// the linker's state of one video between two tuber_tube_link_stream calls: per (class, lane) what a lane of tube_link_kernel holds, in plain
+// arrays of C * 64 entries one behind the other (all zero: no tubes)
+struct TubeLinkState {
+    double* sum;
+    float4* box;
+    int *valid, *cnt, *last, *head;
+    __host__ __device__ TubeLinkState(unsigned char* p, long lanes)
+        : sum((double*)p), box((float4*)(p + 8 * lanes)), valid((int*)(p + 24 * lanes)), cnt((int*)(p + 28 * lanes)), last((int*)(p + 32 * lanes)),
+          head((int*)(p + 36 * lanes)) {}
+};
+#define TUBE_STATE_LANE_BYTES 40
+
+// RANKED: det_prob is det_score [N], a row's score; otherwise [N][C + 1], the score being the wave's column of the row.
+// STREAM (tuber_tube_link_stream): ONE video whose S slots of K rows each carry the ordinals slot_base .. slot_base + S - 1; the lanes are loaded
+// from `state` and stored back to it; row_cls is det_label; a head is the global row ordinal * K + position; tube_score / tube_len are PER ROW
+// (the tube's mean and count after taking the row) and tube_last is not written.
+template <bool RANKED, bool STREAM>
 __global__ __launch_bounds__(64 * TLINK_WAVES) void tube_link_kernel(const float* __restrict__ det_box, const float* __restrict__ det_prob,
                                                                      const int* __restrict__ slot_off, const int* __restrict__ video_off, int V,
                                                                      int S, int N, int C, double link_iou, int max_gap,
                                                                      const int* __restrict__ row_cls, int* __restrict__ row_head,
                                                                      double* __restrict__ tube_score, int* __restrict__ tube_len,
-                                                                     int* __restrict__ tube_last) {
+                                                                     int* __restrict__ tube_last, int K, int slot_base,
+                                                                     unsigned char* __restrict__ state) {
     const int lane = threadIdx.x & 63;
     const long w = (long)blockIdx.x * TLINK_WAVES + (threadIdx.x >> 6);           // wave-uniform from here on
     if (w >= (long)V * C) return;
     const int v = (int)(w / C), c = (int)(w % C);
-    const int s0 = video_off[v], s1 = video_off[v + 1];
+    const int s0 = STREAM ? 0 : video_off[v], s1 = STREAM ? S : video_off[v + 1];
     if (s0 < 0 || s1 < s0 || s1 > S) return;                                      // not a CSR row of these arrays: touch nothing
+    const int hbase = STREAM ? slot_base * K : 0;                                 // global row of this call's row 0
     const int limit = max_gap + 1 > TUBE_MAX_ACTIVE ? 0 : TUBE_MAX_ACTIVE / (max_gap + 1);
     // the tube this lane holds
     bool valid = false;
     float t0 = 0.f, t1 = 0.f, t2 = 0.f, t3 = 0.f;
     double sum = 0.0;
     int cnt = 0, last = 0, head = 0;
-    for (int s = s0; s < s1; ++s) {
-        const int r0 = slot_off[s], r1 = slot_off[s + 1];
+    const TubeLinkState st(state, (long)C * 64);
+    if (STREAM) {
+        const int i = c * 64 + lane;
+        const float4 b = st.box[i];
+        valid = st.valid[i] != 0;
+        t0 = b.x; t1 = b.y; t2 = b.z; t3 = b.w;
+        sum = st.sum[i]; cnt = st.cnt[i]; last = st.last[i]; head = st.head[i];
+    }
+    for (int sl = s0; sl < s1; ++sl) {
+        const int s = STREAM ? slot_base + sl : sl;                               // the slot's ordinal in its video's numbering
+        const int r0 = STREAM ? sl * K : slot_off[sl], r1 = STREAM ? r0 + K : slot_off[sl + 1];
         if (r0 < 0 || r1 < r0 || r1 > N) return;
         const int n = r1 - r0;
         if (n > limit) return;                                                    // the caller's bookkeeping should have kept this video away
@@ -127,9 +155,10 @@ __global__ __launch_bounds__(64 * TLINK_WAVES) void tube_link_kernel(const float
                 sum += (double)ns;
                 cnt += 1;
                 last = s;
-                tube_score[head] = sum / (double)cnt;
-                tube_len[head] = cnt;
-                tube_last[head] = s;
+                const int at = STREAM ? r0 + p : head;
+                tube_score[at] = sum / (double)cnt;
+                tube_len[at] = cnt;
+                if (!STREAM) tube_last[head] = s;
             }
         }
         // the rows nobody took start tubes, in the lanes of tubes that cannot be active at the next slot
@@ -142,20 +171,37 @@ __global__ __launch_bounds__(64 * TLINK_WAVES) void tube_link_kernel(const float
             fm &= fm - 1;
             const float n0 = __shfl(b0, p, 64), n1 = __shfl(b1, p, 64), n2 = __shfl(b2, p, 64), n3 = __shfl(b3, p, 64);
             const float ns = __shfl(sc, p, 64);
-            if (lane == p) row_head[r] = r;
+            if (lane == p) row_head[r] = hbase + r;
             if (lane == t) {
                 valid = true;
                 t0 = n0; t1 = n1; t2 = n2; t3 = n3;
                 sum = (double)ns;
                 cnt = 1;
                 last = s;
-                head = r0 + p;
-                tube_score[head] = sum;
-                tube_len[head] = 1;
-                tube_last[head] = s;
+                head = hbase + r0 + p;
+                const int at = STREAM ? r0 + p : head;
+                tube_score[at] = sum;
+                tube_len[at] = 1;
+                if (!STREAM) tube_last[head] = s;
             }
         }
     }
+    if (STREAM) {
+        const int i = c * 64 + lane;
+        st.box[i] = make_float4(t0, t1, t2, t3);
+        st.valid[i] = valid ? 1 : 0;
+        st.sum[i] = sum; st.cnt[i] = cnt; st.last[i] = last; st.head[i] = head;
+    }
+}
+
+// every row of a tuber_tube_link_stream call starts as "not counted"
+__global__ __launch_bounds__(256) void tube_rows_stream_kernel(int N, int* __restrict__ row_head, double* __restrict__ row_score,
+                                                               int* __restrict__ row_len) {
+    const int r = blockIdx.x * 256 + threadIdx.x;
+    if (r >= N) return;
+    row_head[r] = -1;
+    row_score[r] = 0.0;
+    row_len[r] = 0;
 }
 
 __global__ __launch_bounds__(64) void tube_match_kernel(const float* __restrict__ det_box, const int* __restrict__ slot_off,
@@ -317,8 +363,9 @@ int tuber_tube_link(const float* det_box, const float* det_prob, const int* slot
     if (!det_box || !det_prob || !slot_off || !video_off || !row_cls || !row_head || !tube_score || !tube_len || !tube_last) return TUBER_EINVAL;
     hipLaunchKernelGGL(tube_rows_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, det_prob, N, C, row_cls, row_head);
     const long waves = (long)V * C;
-    hipLaunchKernelGGL(tube_link_kernel<false>, dim3((unsigned)((waves + TLINK_WAVES - 1) / TLINK_WAVES)), dim3(64 * TLINK_WAVES), 0, stream, det_box,
-                       det_prob, slot_off, video_off, V, S, N, C, link_iou, max_gap, row_cls, row_head, tube_score, tube_len, tube_last);
+    hipLaunchKernelGGL((tube_link_kernel<false, false>), dim3((unsigned)((waves + TLINK_WAVES - 1) / TLINK_WAVES)), dim3(64 * TLINK_WAVES), 0, stream, det_box,
+                       det_prob, slot_off, video_off, V, S, N, C, link_iou, max_gap, row_cls, row_head, tube_score, tube_len, tube_last, 0, 0,
+                       (unsigned char*)nullptr);
     TUBER_RETURN_LAUNCH();
 }
 
@@ -337,11 +384,36 @@ int tuber_tube_link_ranked(const float* det_box, const int* det_label, const flo
         return TUBER_EINVAL;
     hipLaunchKernelGGL(tube_rows_ranked_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, det_label, N, C, row_cls, row_head);
     const long waves = (long)V * C;
-    hipLaunchKernelGGL(tube_link_kernel<true>, dim3((unsigned)((waves + TLINK_WAVES - 1) / TLINK_WAVES)), dim3(64 * TLINK_WAVES), 0, stream, det_box,
-                       det_score, slot_off, video_off, V, S, N, C, link_iou, max_gap, row_cls, row_head, tube_score, tube_len, tube_last);
+    hipLaunchKernelGGL((tube_link_kernel<true, false>), dim3((unsigned)((waves + TLINK_WAVES - 1) / TLINK_WAVES)), dim3(64 * TLINK_WAVES), 0, stream, det_box,
+                       det_score, slot_off, video_off, V, S, N, C, link_iou, max_gap, row_cls, row_head, tube_score, tube_len, tube_last, 0, 0,
+                       (unsigned char*)nullptr);
     TUBER_RETURN_LAUNCH();
 }
 int tuber_tube_link_max_active() { return TUBE_MAX_ACTIVE; }
+
+// tuber_tube_link_ranked for ONE video whose slots arrive in pieces (evaluation.TubeLinker: the definition; video.VideoStream).  This call links
+// the S new slots with the ordinals slot_base .. slot_base + S - 1, K rows each (det_box [S * K][4], det_label / det_score [S * K]; the rows
+// behind a key's count carry label -1).  state: caller-owned, tuber_tube_link_state_bytes(C) bytes, 16-byte aligned, all zero = no tubes; loaded
+// before the walk and stored after it.  Out, per row: row_head the GLOBAL row (ordinal * K + position) of the tube's first detection, row_score
+// the tube's fp64 mean and row_len its count after taking the row; -1, 0, 0 for a row that is not counted.  Refused (TUBER_EINVAL, nothing
+// launched, the state untouched): K > tuber_frame_match_max_dets(), K * (max_gap + 1) > tuber_tube_link_max_active(), (slot_base + S) * K beyond
+// an int32, bad sizes or pointers.
+int tuber_tube_link_stream(const float* det_box, const int* det_label, const float* det_score, int S, int K, int slot_base, int C, double link_iou,
+                           int max_gap, void* state, int* row_head, double* row_score, int* row_len, hipStream_t stream) {
+    if (S < 0 || K <= 0 || slot_base < 0 || C <= 0 || max_gap < 0 || !(link_iou == link_iou)) return TUBER_EINVAL;
+    if (K > FMAP_MAX_DETS || (long)K * ((long)max_gap + 1) > TUBE_MAX_ACTIVE) return TUBER_EINVAL;
+    if (((long)slot_base + S) * K > 0x7FFFFFFFl || (long)C * 64 * TUBE_STATE_LANE_BYTES > 0x7FFFFFFFl) return TUBER_EINVAL;
+    if (!state || ((uintptr_t)state & 15)) return TUBER_EINVAL;
+    if (S == 0) return TUBER_OK;
+    if (!det_box || !det_label || !det_score || !row_head || !row_score || !row_len) return TUBER_EINVAL;
+    const int N = S * K;
+    hipLaunchKernelGGL(tube_rows_stream_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, N, row_head, row_score, row_len);
+    hipLaunchKernelGGL((tube_link_kernel<true, true>), dim3((unsigned)((C + TLINK_WAVES - 1) / TLINK_WAVES)), dim3(64 * TLINK_WAVES), 0, stream, det_box,
+                       det_score, (const int*)nullptr, (const int*)nullptr, 1, S, N, C, link_iou, max_gap, det_label, row_head, row_score, row_len,
+                       (int*)nullptr, K, slot_base, (unsigned char*)state);
+    TUBER_RETURN_LAUNCH();
+}
+long tuber_tube_link_state_bytes(int C) { return C > 0 ? (long)C * 64 * TUBE_STATE_LANE_BYTES : 0; }
 
 // Spatio-temporal matching of the linked tubes against the ground-truth tubes (evaluation.VideoMAP.match).  The link outputs; gt_box [G][4] fp64,
 // gt_cls [G], gt_tube [G] (the rank of the row's tube among the tube ids of its (video, class), ascending; one row per (slot, class, tube)) in slot

@@ -539,6 +539,77 @@ def link_rows(box, cls, score, slot, video_off, class_num, link_iou, max_gap):
     return dict(row_head=head, tube_score=tscore, tube_len=tlen, tube_last=tlast)
 
 
+class TubeLinker:
+    """``link_rows`` for ONE video whose slots arrive in pieces: ``push(box, cls, score, K)`` links the next ``len(cls) // K`` slots of ``K`` rows
+    each (rows behind a slot's count: class -1) and returns, per new row, ``row_head`` (the GLOBAL row ``ordinal * K + position`` of the tube's
+    first detection, -1 for a row that is not counted), ``row_score`` (the tube's fp64 mean after taking the row) and ``row_len`` (its count
+    after taking the row); a tube's score and length are those of its last row.  Between pushes a class keeps what ``link_rows`` keeps between
+    slots: per tube the head, the fp64 score sum, the count, the last slot and the last box.  Pushing everything at once gives ``link_rows``'
+    ``row_head`` and, at a tube's last row, its ``tube_score`` (bit for bit) and ``tube_len``.  ``K`` is the same for every push of a video.
+    The definition of ``tuber_tube_link_stream`` and the fallback of ``video.VideoStream`` beyond the linker's bounds."""
+
+    def __init__(self, class_num, link_iou, max_gap):
+        self.class_num, self.link_iou, self.max_gap = int(class_num), float(link_iou), int(max_gap)
+        self.reset()
+
+    def reset(self):
+        """the next push is slot 0 of a new video"""
+        self.slots, self.K = 0, None
+        self._tubes = {}                              # class -> [[head, fp64 score sum, count, last slot, last box fp64], ...]
+
+    def push(self, box, cls, score, K):
+        box = np.asarray(box, dtype=np.float32).reshape(-1, 4)
+        cls, score, K = np.asarray(cls).reshape(-1), np.asarray(score).reshape(-1), int(K)
+        N, C = len(box), self.class_num
+        if K < 1 or N % K or len(cls) != N or len(score) != N:
+            raise ValueError("TubeLinker.push: %d boxes, %d classes, %d scores in slots of %d rows" % (N, len(cls), len(score), K))
+        if self.K not in (None, K):
+            raise ValueError("TubeLinker.push: %d rows per slot after %d" % (K, self.K))
+        self.K = K
+        base = self.slots * K                         # the global row of this push's row 0
+        counted = (cls >= 0) & (cls < C) & (box[:, 0] < box[:, 2]) & (box[:, 1] < box[:, 3]) & ~np.isnan(score)
+        box64 = box.astype(np.float64)
+        head = np.full(N, -1, dtype=np.int64)
+        rscore, rlen = np.zeros(N), np.zeros(N, dtype=np.int64)
+        groups = {}
+        for r in np.nonzero(counted)[0].tolist():
+            groups.setdefault(int(cls[r]), []).append(r)
+        for c, rows in groups.items():
+            tubes, i = self._tubes.get(c, []), 0
+            while i < len(rows):
+                s, j = self.slots + rows[i] // K, i
+                while j < len(rows) and self.slots + rows[j] // K == s:
+                    j += 1
+                cur, i = rows[i:j], j
+                active = [t for t in tubes if s - t[3] <= self.max_gap + 1]
+                active.sort(key=lambda t: (-(t[1] / t[2]), t[0]))
+                claimed = set()
+                for t in active:
+                    cand = [r for r in cur if r not in claimed]
+                    if not cand:
+                        break
+                    with np.errstate(all="ignore"):
+                        iou = _iou_one_to_many(t[4], box64[cand])
+                    best = None
+                    for r, u in zip(cand, iou):
+                        if u >= self.link_iou and (best is None or score[r] > score[best]):
+                            best = r
+                    if best is not None:
+                        claimed.add(best)
+                        head[best] = t[0]
+                        t[1] += float(score[best]); t[2] += 1; t[3] = s; t[4] = box64[best].copy()
+                        rscore[best], rlen[best] = t[1] / t[2], t[2]
+                tubes = active
+                for r in cur:
+                    if r not in claimed:
+                        head[r] = base + r
+                        tubes.append([base + r, float(score[r]), 1, s, box64[r].copy()])
+                        rscore[r], rlen[r] = float(score[r]), 1
+            self._tubes[c] = tubes
+        self.slots += N // K
+        return dict(row_head=head, row_score=rscore, row_len=rlen)
+
+
 class VideoMAP:
     """Video-level mean average precision over action tubes: per (video, class) the per-frame detections are linked greedily into tubes
     (``link``), the tubes are matched against the ground-truth tubes by spatio-temporal IoU (``match``), and the ranked flags give VOC AP per

@@ -6,7 +6,13 @@ resident ONCE on the device at working resolution (``tuber_frames_resize``, ever
 frames are gathered from it by one launch (``tuber_video_clips``, csrc/video_clips.hip) reading a frame-index table (``clip_indices``), the
 captured ``detect.Detector`` runs over them, and the ranked detections of all key frames are linked into tubes by the wave-per-(video, class)
 linker in its ranked form (``tuber_tube_link_ranked``, csrc/tube_map.hip; ``evaluation.link_rows`` is its definition and its fallback).
+
+``VideoStream`` is the same computation for a video that arrives in pieces: a ring of the last R frames instead of the
+resident video (``tuber_video_clips_ring`` evaluates the index rule itself), the same batches of key frames as soon as their clips can no longer
+change, and the linker resumed push by push (``tuber_tube_link_stream``; ``evaluation.TubeLinker`` is its definition and its fallback).
+``VideoDetector`` is the definition the stream is held to.
 """
+import functools
 import sys
 
 import numpy as np
@@ -85,6 +91,7 @@ class VideoDetections:
         self.settings = dict(settings or dict(link_iou=0.2, max_gap=2, min_len=1))      # the defaults of tubes(): CONFIG.VAL.VIDEO_MAP
         self.tubes_path = None                                                         # "device" or "host" after tubes()
         self._store = store                                                            # the engine's ParamStore: to_host reads its error word
+        self.row_head = self.row_score = self.row_len = None                           # the link records of a VideoStream push (link=True)
         if not (len(self.keys) == boxes.shape[0] == scores.shape[0] == count.shape[0]):
             raise ValueError("VideoDetections: %d keys, %d rows" % (len(self.keys), boxes.shape[0]))
 
@@ -274,3 +281,343 @@ class VideoDetector:
             for dst, src in zip(full, det.tensors()):
                 dst[b * B:(b + 1) * B].copy_(src)
         return VideoDetections(keys, *[t[:n] for t in full], class_num=self.class_num, settings=self.settings, store=store)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# a video that arrives in pieces
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def clip_span(T, rate=1, rule="ava"):
+    """the largest number of consecutive frame numbers between the first and the last frame one key's clip may read, both included: the rule's
+    look-back + look-ahead + 1.  ava / edge: T frames ``rate`` apart, ``(T - 1) * rate + 1``; jhmdb: ``key - T//2 .. key + T - T//2``, the
+    last one being the pad behind a clip whose start was clamped: ``T + 1``.  Frame 0 as jhmdb's front pad does not count: the ring keeps it in
+    a slot of its own."""
+    if rule not in RULES:
+        raise ValueError("clip_span: rule %r is not one of %s" % (rule, ", ".join(RULES)))
+    T, rate = int(T), int(rate)
+    return T + 1 if rule == "jhmdb" else (T - 1) * rate + 1
+
+
+@functools.lru_cache(maxsize=4096)
+def frames_needed(key, T, rate=1, rule="ava"):
+    """the smallest frame count n > key from which on ``clip_indices(n, [key], ...)`` no longer changes: a stream of n frames can run this key
+    frame.  ava / edge: the clip's last frame has arrived.  jhmdb: ``key + T - T//2`` frames always do (``end`` is no longer clamped); one
+    fewer do as well when the clip is not clamped at the front, the missing frame being the pad that repeats ``end``."""
+    key, T, rate = int(key), int(T), int(rate)
+    if rule == "ava":
+        return max(key - T // 2 * rate, 0) + (T - 1) * rate + 1
+    if rule == "edge":
+        return key + max(T - 1 - T // 2, 0) * rate + 1
+    n = key + T - T // 2 + 1
+    final = clip_indices(n, [key], T, rate, rule)
+    while n - 1 > key and np.array_equal(clip_indices(n - 1, [key], T, rate, rule), final):
+        n -= 1
+    return n
+
+
+def ring_frames(T, rate, rule, batch, stride, max_chunk):
+    """R, the frames the ring of a ``VideoStream`` holds: ``clip_span`` (the rule's look-back + look-ahead) + ``(batch - 1) * stride`` +
+    ``max_chunk``.  Why that is enough: key frames run in full batches, so the oldest frame still needed is the first frame of the clip of the
+    first key of the batch that waits, and the batch waits only while its LAST key, ``(batch - 1) * stride`` frames on, lacks a frame of its
+    clip; the frames pushed so far therefore end inside that clip, at most ``clip_span - 1 + (batch - 1) * stride`` frames after the oldest
+    one needed.  A piece adds at most ``max_chunk`` frames before the batches that became ready are run."""
+    return clip_span(T, rate, rule) + (int(batch) - 1) * int(stride) + int(max_chunk)
+
+
+class StreamSchedule:
+    """The host integers of a ``VideoStream``: which ring slots the next frames go to and which batches of key frames run after them.
+    ``push(m)`` -> ``[(offset, length, [first key ordinal of a batch, ...]), ...]``: the pieces of at most ``max_chunk`` frames a push of m
+    frames is cut into and the full batches that are ready after each; ``finish()`` -> ``(n_total, [(first key ordinal, keys), ...])``: the
+    batches that remain once the frame count is known, the last one possibly short, and the schedule is reset for the next video."""
+
+    def __init__(self, T, rate, rule, batch, stride, max_chunk):
+        self.T, self.rate, self.rule, self.batch, self.stride, self.max_chunk = int(T), int(rate), rule, int(batch), int(stride), int(max_chunk)
+        self.R = ring_frames(self.T, self.rate, rule, self.batch, self.stride, self.max_chunk)
+        self.frames = self.decided = self._scan = 0      # frames pushed; key frames run (the next key ordinal); key frames known to be ready
+
+    def ready(self, n):
+        """key frames of a stream of n frames whose clips can no longer change: a prefix of the keys, ``frames_needed`` growing with the key"""
+        k = self._scan
+        while k * self.stride < n and frames_needed(k * self.stride, self.T, self.rate, self.rule) <= n:
+            k += 1
+        self._scan = k
+        return k
+
+    def push(self, m):
+        plan = []
+        for i in range(0, int(m), self.max_chunk):
+            length = min(self.max_chunk, int(m) - i)
+            self.frames += length
+            batches = []
+            while self.ready(self.frames) - self.decided >= self.batch:
+                batches.append(self.decided)
+                self.decided += self.batch
+            plan.append((i, length, batches))
+        return plan
+
+    def finish(self):
+        n_total = self.frames
+        keys = (n_total - 1) // self.stride + 1 if n_total else 0          # len(range(0, n_total, stride))
+        batches = [(k, min(self.batch, keys - k)) for k in range(self.decided, keys, self.batch)]
+        self.frames = self.decided = self._scan = 0
+        return n_total, batches
+
+
+class VideoStream:
+    """``VideoDetector`` for a video that arrives in pieces: ``push(frames)`` as they come, ``finish()`` at the end, ``tubes()`` whenever wanted.
+    The rows of every ``push`` and of ``finish``, concatenated, are ``VideoDetector(cfg, model, batch, ...)(video, stride=stride)``'s, bit for
+    bit, and so are the tubes.
+
+    ``push(frames)``: uint8 [n, H0, W0, 3] (numpy, a host tensor or a device tensor), H0 x W0 fixed by the first push of a video.  The frames
+    are resized (``tuber_frames_resize``) into the slots ``f % R`` of a ring of R = ``ring_frames(...)`` frames at working resolution, at most
+    ``max_chunk`` at a time; frame 0 is kept in a slot of its own as well.  After each piece every key frame (``range(0, inf, stride)``) whose
+    clip can no longer change (``frames_needed``) is decided, and the decided keys run in the batches ``VideoDetector`` forms -- keys
+    ``i * batch .. i * batch + batch - 1``, full batches only, a remainder waits -- each one ``tuber_video_clips_ring`` launch and the captured
+    ``Detector``.  Returns the ``VideoDetections`` of the keys this push decided, or None.  With ``link=True`` it also carries, as device
+    tensors, ``row_head`` [n, K] int32 (the tube's first detection as key ordinal * K + position, -1: not counted), ``row_score`` [n, K] fp64
+    and ``row_len`` [n, K] int32 (the tube's mean score and length after taking the row): one ``tuber_tube_link_stream`` launch per push, or
+    ``evaluation.TubeLinker`` on the host beyond the linker's bounds (one line says so).  Readiness and ring arithmetic are host integers:
+    once the first push has captured its graph, ``push`` synchronises nowhere.
+
+    ``finish()``: the end of the video.  The remaining keys run with the frame count known (the end clamps, jhmdb's end pad), the last batch
+    padded by repeating its last key; returns their ``VideoDetections`` or None, then resets the frame counter, the key ordinal and the link
+    state (a memset) for the next video, which allocates and captures nothing new when it has the same size.
+
+    ``tubes()``: the tubes that CLOSED since the last call -- no key frame still to come can extend them: the next key ordinal is more than
+    ``max_gap`` + 1 past their last one -- and after ``finish()`` all that remain; ``dict(cls, score, frames, boxes, length, head)`` in head
+    order, as ``VideoDetections.tubes`` (``head``: key ordinal * K + position of the first detection).  It runs on the host and makes one
+    device-to-host copy per call; the rows of open tubes are kept on the host in between.
+
+    Device memory does not grow with the video: the ring, (R + 1) * nh * nw * 3 bytes; the link state, ``tuber_tube_link_state_bytes(C)`` =
+    2560 * C bytes; one batch of clips; and the ``VideoDetections`` of the pushes since the last ``tubes()`` call (``link=False``: none are
+    kept).  ``rule`` / ``topk`` / ``score_thr`` / ``actor_thr`` / ``graphed`` / ``stride``: as ``VideoDetector``."""
+
+    def __init__(self, cfg, model, batch=2, stride=None, rule=None, max_chunk=64, score_thr=None, topk=None, actor_thr=None, graphed=True,
+                 link=True):
+        from .config import detect_settings, video_map_settings
+        self.cfg, self.model = cfg, model
+        self.batch, self.max_chunk, self.link = int(batch), int(max_chunk), bool(link)
+        if self.batch < 1 or self.max_chunk < 1:
+            raise ValueError("VideoStream: batch = %r and max_chunk = %r must be >= 1" % (batch, max_chunk))
+        vm = video_map_settings(cfg)
+        self.settings = dict(link_iou=float(vm["link_iou"]), max_gap=int(vm["max_gap"]), min_len=int(vm["min_len"]))
+        if topk is None:
+            topk = max(1, min(detect_settings(cfg)["topk"], lib.query("tuber_tube_link_max_active") // (self.settings["max_gap"] + 1)))
+        self.detector = Detector(cfg, model, score_thr=score_thr, topk=topk, actor_thr=actor_thr, graphed=graphed)
+        self.mode = model.dataset_mode
+        self.rule = rule if rule is not None else ("ava" if self.mode == "ava" else "jhmdb")
+        if self.rule not in RULES:
+            raise ValueError("VideoStream: rule %r is not one of %s" % (rule, ", ".join(RULES)))
+        self.stride = int(stride) if stride is not None else (30 if self.mode == "ava" else 1)
+        if self.stride < 1:
+            raise ValueError("VideoStream: stride = %r must be >= 1" % (stride,))
+        D = cfg.CONFIG.DATA
+        self.T, self.rate, self.size, self.class_num = int(D.TEMP_LEN), int(D.FRAME_RATE), int(D.IMG_SIZE), int(D.NUM_CLASSES)
+        self.schedule = StreamSchedule(self.T, self.rate, self.rule, self.batch, self.stride, self.max_chunk)
+        self.R = self.schedule.R
+        K, gap = self.detector.topk, self.settings["max_gap"]
+        self._why_host = None
+        if K > lib.query("tuber_frame_match_max_dets") or K * (gap + 1) > lib.query("tuber_tube_link_max_active"):
+            self._why_host = "%d rows per key frame with max_gap %d: beyond %d rows or %d active tubes" % (
+                K, gap, lib.query("tuber_frame_match_max_dets"), lib.query("tuber_tube_link_max_active"))
+        self._host_linker, self._said = None, False
+        self._bufs = {}                    # (device, H0, W0) -> the buffers of a video size
+        self._cur = None                   # the current video's buffers
+        self.wrapped = False               # whether a ring slot has been overwritten in the current video
+        self._pending = []                 # link records since the last tubes() call; None marks the end of a video
+        self._open = {}                    # head -> the rows of an open tube, on the host
+
+    # -- buffers ----------------------------------------------------------------------------------------------------------
+    def _buffers(self, dev, H0, W0):
+        key = (str(dev), H0, W0)
+        b = self._bufs.get(key)
+        if b is None:
+            nh, nw, y1, x1, h, w = working_geometry(H0, W0, self.size)
+            B, T, R = self.batch, self.T, self.R
+            b = dict(H0=H0, W0=W0, nh=nh, nw=nw, window=(y1, x1, h, w), same=(nh, nw) == (H0, W0),
+                     ring=torch.empty(R + 1, nh, nw, 3, dtype=torch.uint8, device=dev),
+                     clips=torch.empty(B, 3, T, h, w, dtype=torch.float32, device=dev), mask=torch.zeros(B, h, w, dtype=torch.bool, device=dev),
+                     key_pos=torch.full((B,), T // 2, dtype=torch.int64, device=dev),
+                     sizes=torch.tensor([[H0, W0]] * B, dtype=torch.float32).to(dev, non_blocking=True),
+                     lut=ip._device_tables(dev, (ip.MEAN, ip.STD))[0],
+                     state=torch.zeros(lib.query("tuber_tube_link_state_bytes", self.class_num), dtype=torch.uint8, device=dev))
+            if not b["same"]:
+                b["coeffs"] = ip._device_coeffs(dev, H0, W0, nh, nw)
+                rows = b["coeffs"][4]
+                b["tmp"] = torch.empty(self.max_chunk * rows * nw * 3, dtype=torch.uint8, device=dev) if (nw != W0 and nh != H0) else None
+            self._bufs[key] = b
+        return b
+
+    def device_bytes(self):
+        """bytes of the current video size's ring and link state: what the stream holds instead of the resident video"""
+        b = self._cur
+        return 0 if b is None else b["ring"].numel() + b["state"].numel()
+
+    def _store_frames(self, b, src, first):
+        """frames ``first .. first + len(src) - 1`` into their ring slots: a run that crosses the ring's end is two calls"""
+        R, m = self.R, int(src.shape[0])
+        s0 = first % R
+        for lo, hi, slot in ((0, min(m, R - s0), s0), (min(m, R - s0), m, 0)):
+            if hi <= lo:
+                continue
+            if b["same"]:
+                b["ring"][slot:slot + hi - lo].copy_(src[lo:hi])
+            else:
+                (bh, kh, bv, kv), ksh, ksv, y0, rows = b["coeffs"]
+                lib.call("tuber_frames_resize", src[lo:hi], b["tmp"], b["ring"][slot:], hi - lo, b["H0"], b["W0"], b["nh"], b["nw"], bh, kh, ksh, bv, kv,
+                         ksv, y0, rows)
+        if first == 0:
+            b["ring"][R].copy_(b["ring"][0])                   # frame 0 in its fixed slot as well
+        self.wrapped = self.wrapped or first + m > R
+
+    # -- key frames -------------------------------------------------------------------------------------------------------
+    def _run(self, b, full, row, first_ord, n_keys, n_total):
+        """one batch: the keys ``first_ord .. first_ord + n_keys - 1`` (the last one repeated up to ``batch``) into rows ``row ..`` of ``full``"""
+        B = self.batch
+        lib.call("tuber_video_clips_ring", b["ring"], self.R, b["nh"], b["nw"], first_ord * self.stride, self.stride, n_keys, B, self.T, self.rate,
+                 RULES.index(self.rule), n_total, *b["window"], b["lut"], b["clips"])
+        det = self.detector(NestedTensor(b["clips"], b["mask"]), b["sizes"], b["key_pos"])
+        for dst, src in zip(full, det.tensors()):
+            dst[row:row + B].copy_(src)
+
+    def _result(self, b, full, first_ord, n, store):
+        """the ``VideoDetections`` of the keys ``first_ord .. first_ord + n - 1`` in the first n rows of ``full``, linked"""
+        if n == 0:
+            return None
+        vd = VideoDetections([(first_ord + i) * self.stride for i in range(n)], *[t[:n] for t in full], class_num=self.class_num,
+                             settings=self.settings, store=store)
+        if self.link:
+            self._link(b, vd, first_ord)
+            self._pending.append((first_ord, vd))
+        return vd
+
+    def _link(self, b, vd, first_ord):
+        n, K = vd.scores.shape
+        dev = vd.scores.device
+        why = self._why_host
+        if why is None and (first_ord + n) * K > 0x7FFFFFFF:
+            why = "key ordinal %d with %d rows per key frame: row numbers beyond 32 bits" % (first_ord + n, K)
+        if why is None:
+            vd.row_head = torch.empty(n, K, dtype=torch.int32, device=dev)
+            vd.row_score = torch.empty(n, K, dtype=torch.float64, device=dev)
+            vd.row_len = torch.empty(n, K, dtype=torch.int32, device=dev)
+            lib.call("tuber_tube_link_stream", vd.boxes.contiguous(), vd.labels.contiguous(), vd.scores.contiguous(), n, K, first_ord, self.class_num,
+                     self.settings["link_iou"], self.settings["max_gap"], b["state"], vd.row_head, vd.row_score, vd.row_len)
+            return
+        from .evaluation import TubeLinker
+        if not self._said:
+            print("[tuber] VideoStream: %s; linking on the host" % why, file=sys.stderr, flush=True)
+            self._said = True
+        if self._host_linker is None:
+            self._host_linker = TubeLinker(self.class_num, self.settings["link_iou"], self.settings["max_gap"])
+        host = dict(zip(FIELDS, vd._fetch()))
+        got = self._host_linker.push(host["boxes"].reshape(-1, 4), host["labels"].reshape(-1), host["scores"].reshape(-1), K)
+        vd.row_head = torch.from_numpy(got["row_head"].reshape(n, K).astype(np.int32)).to(dev)
+        vd.row_score = torch.from_numpy(got["row_score"].reshape(n, K)).to(dev)
+        vd.row_len = torch.from_numpy(got["row_len"].reshape(n, K).astype(np.int32)).to(dev)
+
+    def _empty(self, rows, dev):
+        K, f32, i32 = self.detector.topk, torch.float32, torch.int32
+        return [torch.empty(rows, K, 4, dtype=f32, device=dev), torch.empty(rows, K, dtype=f32, device=dev), torch.empty(rows, K, dtype=i32, device=dev),
+                torch.empty(rows, K, dtype=i32, device=dev), torch.empty(rows, K, dtype=f32, device=dev), torch.empty(rows, dtype=i32, device=dev),
+                torch.empty(rows, dtype=i32, device=dev)]
+
+    @torch.no_grad()
+    def push(self, frames):
+        if self.model.training:
+            raise RuntimeError("VideoStream runs an eval forward: call model.eval() first")
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
+            raise ValueError("VideoStream wants uint8 frames [n, H, W, 3], got %s %s" % (frames.dtype, tuple(frames.shape)))
+        m, H0, W0 = (int(v) for v in frames.shape[:3])
+        sch = self.schedule
+        if sch.frames and (H0, W0) != (self._cur["H0"], self._cur["W0"]):
+            raise ValueError("VideoStream: frames of %d x %d in a video of %d x %d" % (H0, W0, self._cur["H0"], self._cur["W0"]))
+        if m == 0:
+            return None
+        store, _ = self.model.engine()
+        dev = store.device
+        if not sch.frames:
+            self._cur = self._buffers(dev, H0, W0)
+        b, B = self._cur, self.batch
+        first_frame, first_ord = sch.frames, sch.decided
+        plan = sch.push(m)                                      # host integers first: the pieces, and the batches ready after each
+        total = sum(len(batches) for _, _, batches in plan)
+        full = self._empty(total * B, dev) if total else None
+        row = 0
+        for i, length, batches in plan:
+            src = frames[i:i + length].to(dev, non_blocking=True).contiguous()
+            self._store_frames(b, src, first_frame + i)
+            for k in batches:
+                self._run(b, full, row, k, B, -1)
+                row += B
+        return self._result(b, full, first_ord, row, store)
+
+    @torch.no_grad()
+    def finish(self):
+        if self.model.training:
+            raise RuntimeError("VideoStream runs an eval forward: call model.eval() first")
+        n_total, batches = self.schedule.finish()
+        self.wrapped = False
+        if not n_total:
+            return None
+        b, B = self._cur, self.batch
+        store, _ = self.model.engine()
+        out = None
+        if batches:
+            full = self._empty(len(batches) * B, store.device)
+            for i, (k, n_keys) in enumerate(batches):
+                self._run(b, full, i * B, k, n_keys, n_total)
+            out = self._result(b, full, batches[0][0], batches[-1][0] + batches[-1][1] - batches[0][0], store)
+        b["state"].zero_()
+        if self._host_linker is not None:
+            self._host_linker.reset()
+        if self.link:
+            self._pending.append(None)
+        return out
+
+    # -- tubes ------------------------------------------------------------------------------------------------------------
+    def tubes(self):
+        if not self.link:
+            raise RuntimeError("VideoStream(link=False) keeps no link records: no tubes")
+        pending, self._pending = self._pending, []
+        recs = [p for p in pending if p is not None]
+        names = ("boxes", "labels", "row_head", "row_score", "row_len")
+        parts = [getattr(vd, k).contiguous() for _, vd in recs for k in names]
+        host, o = [], 0
+        if parts:                                               # one copy for every record
+            blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
+            for t in parts:
+                nbytes = t.numel() * t.element_size()
+                host.append(blob[o:o + nbytes].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape)))
+                o += nbytes
+        gap, min_len, out, i = self.settings["max_gap"], self.settings["min_len"], [], 0
+        next_ord = None
+
+        def close(everything):
+            for h in sorted(self._open):
+                t = self._open[h]
+                if everything or next_ord - t["last"] > gap + 1:
+                    del self._open[h]
+                    if t["length"] >= min_len:
+                        out.append(dict(cls=t["cls"], score=t["score"], frames=t["frames"], boxes=np.stack(t["boxes"]), length=t["length"], head=h))
+        for p in pending:
+            if p is None:                                       # the end of a video: whatever is open closes
+                close(True)
+                next_ord = None
+                continue
+            first_ord, vd = p
+            boxes, labels, head, score, length = host[5 * i:5 * i + 5]
+            i += 1
+            for s, q in zip(*np.nonzero(head >= 0)):
+                h = int(head[s, q])
+                t = self._open.get(h)
+                if t is None:
+                    t = self._open[h] = dict(cls=int(labels[s, q]) + 1, frames=[], boxes=[])
+                t["frames"].append(vd.keys[s])
+                t["boxes"].append(boxes[s, q].copy())
+                t["score"], t["length"], t["last"] = float(score[s, q]), int(length[s, q]), first_ord + int(s)
+            next_ord = first_ord + len(vd.keys)
+        if next_ord is not None:
+            close(False)
+        return out
