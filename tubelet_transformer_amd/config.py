@@ -162,6 +162,11 @@ def get_cfg_defaults():
         # ranked detections decoded on the device (detect.Detector; not reference keys): a candidate scores at least SCORE_THR, the best TOPK
         # per clip are kept; ACTOR_THR: the actor-probability gate of the AVA rule (the reference's 0.8)
         DETECT=dict(SCORE_THR=0.05, TOPK=100, ACTOR_THR=0.8),
+        # actor tracks of an AVA video (detect.Detector(actors=...), video.VideoActors.tracks; not reference keys): the best TOPK actors of a key
+        # frame are kept, linked class-agnostically (LINK_IOU, MAX_GAP, MIN_LEN as in VIDEO_MAP), a row's action scores smoothed over the rows of
+        # its track at most WINDOW key frames away, a track labelled with the classes whose mean score is at least LABEL_THR.  None: TOPK =
+        # min(MODEL.QUERY_NUM, 64 active tubes // (MAX_GAP + 1)), LINK_IOU / MAX_GAP / MIN_LEN = VIDEO_MAP's, LABEL_THR = DETECT.SCORE_THR
+        ACTORS=dict(TOPK=None, LINK_IOU=None, MAX_GAP=None, MIN_LEN=None, WINDOW=1, LABEL_THR=None),
         # both validation loops run the eval forward as a captured hipGraph per input shape (detect.GraphedEval; not a reference key)
         GRAPHED=False), new_allowed=True)
     cfg.DATA = CfgNode(dict(
@@ -228,6 +233,38 @@ def detect_settings(cfg):
     if not isinstance(val.GRAPHED, bool):
         bad("GRAPHED", val.GRAPHED, "must be True or False")
     return dict(score_thr=float(d.SCORE_THR), topk=int(d.TOPK), actor_thr=float(d.ACTOR_THR), graphed=val.GRAPHED)
+
+
+def actor_settings(cfg):
+    """CONFIG.VAL.ACTORS validated, its None entries resolved -> dict(topk, link_iou, max_gap, min_len, window, label_thr); a bad value raises
+    ValueError naming its key"""
+    a = cfg.CONFIG.VAL.ACTORS
+    vm, d = video_map_settings(cfg), detect_settings(cfg)
+
+    def bad(key, why):
+        raise ValueError("CONFIG.VAL.ACTORS.%s = %r: %s" % (key, a[key], why))
+    number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v
+    integer = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    if a.LINK_IOU is not None and (not number(a.LINK_IOU) or not 0.0 <= a.LINK_IOU <= 1.0):
+        bad("LINK_IOU", "must be None or a number in [0, 1]")
+    if a.MAX_GAP is not None and (not integer(a.MAX_GAP) or a.MAX_GAP < 0):
+        bad("MAX_GAP", "must be None or an integer >= 0")
+    if a.MIN_LEN is not None and (not integer(a.MIN_LEN) or a.MIN_LEN < 1):
+        bad("MIN_LEN", "must be None or an integer >= 1")
+    if not integer(a.WINDOW) or a.WINDOW < 0:
+        bad("WINDOW", "must be an integer >= 0")
+    if a.LABEL_THR is not None and (not number(a.LABEL_THR) or not 0.0 <= a.LABEL_THR <= 1.0):
+        bad("LABEL_THR", "must be None or a number in [0, 1]")
+    if a.TOPK is not None and (not integer(a.TOPK) or a.TOPK < 1):
+        bad("TOPK", "must be None or an integer >= 1")
+    max_gap = int(vm["max_gap"] if a.MAX_GAP is None else a.MAX_GAP)
+    topk = a.TOPK
+    if topk is None:
+        from . import lib
+        topk = max(1, min(int(cfg.CONFIG.MODEL.QUERY_NUM), lib.query("tuber_tube_link_max_active") // (max_gap + 1)))
+    return dict(topk=int(topk), link_iou=float(vm["link_iou"] if a.LINK_IOU is None else a.LINK_IOU), max_gap=max_gap,
+                min_len=int(vm["min_len"] if a.MIN_LEN is None else a.MIN_LEN), window=int(a.WINDOW),
+                label_thr=float(d["score_thr"] if a.LABEL_THR is None else a.LABEL_THR))
 
 
 def load_cfg(path):

@@ -6,6 +6,8 @@
 //   detect_kernel<1>   JHMDB / UCF101-24 rule (counted once, evaluates/evaluate_ucf.py:109-126): a query's label is the first maximum of its fp32 logit
 //                      row over the C + 1 columns (a NaN counting as a maximum, fmap_argmax), its score that column's softmax probability; not a
 //                      candidate when the label is the no-object column C, the score is NaN or < score_thr; order: score descending, then q ascending
+//   detect_actors_kernel   AVA rule per ACTOR (tuber_detect_actors): the queries with pb > actor_thr ranked by pb descending, then q ascending, the best A kept,
+//                      each with its box and its whole action row sigmoid(logit) * pb -- detect_kernel<0>'s score of every (q, c), unthresholded
 // The candidates' order keys (fmap_key: the score as an order-preserving unsigned over ~index) sit in LDS, non-candidates as key 0, and a bitonic
 // network sorts them descending: keys are distinct, so the result is a function of the inputs alone -- no atomics anywhere.  The score is recovered
 // from the key's high word bit for bit.  Inputs are read in the dtype the forward produced (fp32 or bf16, converted on load: no cast launch).
@@ -186,6 +188,129 @@ __global__ __launch_bounds__(DET_THREADS) void detect_kernel(const void* __restr
     }
 }
 
+// Actor decode (AVA rule; detect.decode_actors_host is the definition): the clip's ACTORS -- queries with pb = softmax(logits_b)[1] > actor_thr --
+// ranked by pb descending, then query ascending (fmap_key(pb, q) sorted in LDS as above), the best A kept, each with its box and its WHOLE action
+// row sigmoid(logit) * pb, unthresholded: det_actions[a][c] is the number detect_kernel<0> calls the score of (query, c), bit for bit.
+#define DETA_MAX_QS 1024          // queries of a clip: 8 KB of keys
+#define DETA_MAX_A 1024
+
+__global__ __launch_bounds__(DET_THREADS) void detect_actors_kernel(const void* __restrict__ logits, const void* __restrict__ logits_b,
+                                                                    const void* __restrict__ boxes, const float* __restrict__ sizes,
+                                                                    const int* __restrict__ q_begin, int Qtot, int Qs, int C, int NB, int lb_rows,
+                                                                    int dtypes, float actor_thr, int A, float* __restrict__ det_box,
+                                                                    float* __restrict__ det_actor, int* __restrict__ det_query,
+                                                                    float* __restrict__ det_actions, int* __restrict__ det_count,
+                                                                    int* __restrict__ det_total) {
+    __shared__ unsigned long long keys[DETA_MAX_QS];
+    __shared__ float s_pb[DETA_MAX_QS];
+    __shared__ int s_cnt[DET_THREADS / 64];
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const bool bf_lg = dtypes & DET_BF16_LOGITS, bf_lb = dtypes & DET_BF16_LOGITS_B, bf_bx = dtypes & DET_BF16_BOXES;
+    int n2 = 2;
+    while (n2 < Qs) n2 <<= 1;                           // <= DETA_MAX_QS (the launcher checked Qs)
+    int q0 = q_begin ? q_begin[b] : 0;
+    const bool slice_ok = q0 >= 0 && q0 <= Qtot - Qs;   // a slice outside the clip's queries: an empty result, nothing read
+    if (!slice_ok) q0 = 0;
+    const long qrow0 = (long)b * Qtot + q0;
+
+    // ---- per query: the actor probability and its order key ----
+    int mine = 0;
+    for (int q = tid; q < n2; q += DET_THREADS) {
+        unsigned long long key = 0ull;
+        if (q < Qs && slice_ok) {
+            const float pb = det_prob1(logits_b, lb_rows == 1 ? (long)b : qrow0 + q, NB, bf_lb);
+            s_pb[q] = pb;
+            if (pb > actor_thr) { key = fmap_key(pb, q); ++mine; }          // a NaN is no actor
+        }
+        keys[q] = key;
+    }
+#pragma unroll
+    for (int s = 1; s < 64; s <<= 1) mine += __shfl_xor(mine, s, 64);
+    if ((tid & 63) == 0) s_cnt[tid >> 6] = mine;
+    __syncthreads();
+    int total = 0;
+#pragma unroll
+    for (int w = 0; w < DET_THREADS / 64; ++w) total += s_cnt[w];
+    const int count = total < A ? total : A;
+
+    // ---- bitonic sort of keys[0, n2) descending ----
+    for (int k = 2; k <= n2; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (n2 >> 1); t += DET_THREADS) {
+                const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+                const unsigned long long x = keys[lo], y = keys[hi];
+                const bool desc = (lo & k) == 0;
+                if (desc ? x < y : x > y) { keys[lo] = y; keys[hi] = x; }
+            }
+            __syncthreads();
+        }
+    }
+
+    // ---- rows [0, count): box, actor probability, query; rows [count, A): the empty row ----
+    const float H = sizes[2 * b], W = sizes[2 * b + 1];
+    for (int r = tid; r < A; r += DET_THREADS) {
+        const long o = (long)b * A + r;
+        float bx[4] = {0.f, 0.f, 0.f, 0.f}, actor = 0.f;
+        int query = -1;
+        if (r < count) {
+            const unsigned long long key = keys[r];
+            query = (int)(0xFFFFFFFFu - (unsigned)(key & 0xFFFFFFFFull));
+            actor = det_score_of(key);
+            const long br = (qrow0 + query) * 4;
+            const float cx = det_ld(boxes, br, bf_bx), cy = det_ld(boxes, br + 1, bf_bx), w = det_ld(boxes, br + 2, bf_bx),
+                        h = det_ld(boxes, br + 3, bf_bx);
+            {
+#pragma clang fp contract(off)
+                const float hw = 0.5f * w, hh = 0.5f * h;
+                const float x1 = cx - hw, y1 = cy - hh, x2 = cx + hw, y2 = cy + hh;
+                bx[0] = x1 * W; bx[1] = y1 * H; bx[2] = x2 * W; bx[3] = y2 * H;
+            }
+        }
+        *(f32x4*)(det_box + o * 4) = f32x4{bx[0], bx[1], bx[2], bx[3]};
+        det_actor[o] = actor;
+        det_query[o] = query;
+    }
+
+    // ---- the action rows [A][C], consecutive threads on consecutive classes; rows behind count are zero ----
+    float* __restrict__ act = det_actions + (long)b * A * C;
+    if ((C & 3) == 0 && ((uintptr_t)det_actions & 15) == 0) {           // rows of whole 16-byte groups, each aligned
+        const int C4 = C >> 2;
+        for (int g = tid; g < A * C4; g += DET_THREADS) {
+            const int r = g / C4, c0 = (g - r * C4) << 2;
+            float v[4] = {0.f, 0.f, 0.f, 0.f};
+            if (r < count) {
+                const int query = (int)(0xFFFFFFFFu - (unsigned)(keys[r] & 0xFFFFFFFFull));
+                const float pb = s_pb[query];
+                const long base = (qrow0 + query) * C + c0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    const float x = det_ld(logits, base + j, bf_lg);
+                    const float s = (1.f / (1.f + expf(-x))) * pb;
+                    v[j] = s;
+                }
+            }
+            *(f32x4*)(act + (long)r * C + c0) = f32x4{v[0], v[1], v[2], v[3]};
+        }
+    } else {
+        for (int i = tid; i < A * C; i += DET_THREADS) {
+            const int r = i / C, c = i - r * C;
+            float v = 0.f;
+            if (r < count) {
+                const int query = (int)(0xFFFFFFFFu - (unsigned)(keys[r] & 0xFFFFFFFFull));
+                const float pb = s_pb[query];
+                const float x = det_ld(logits, (qrow0 + query) * C + c, bf_lg);
+                const float s = (1.f / (1.f + expf(-x))) * pb;
+                v = s;
+            }
+            act[i] = v;
+        }
+    }
+    if (tid == 0) {
+        det_count[b] = count;
+        det_total[b] = total;
+    }
+}
+
 static int detect_check(const void* logits, const void* logits_b, const void* boxes, const float* sizes, int B, int Qtot, int Qs, int C, int NB,
                         int lb_rows, int dtypes, float actor_thr, float score_thr, int K, const void* o0, const void* o1, const void* o2,
                         const void* o3, const void* o4, const void* o5, const void* o6) {
@@ -233,6 +358,33 @@ int tuber_detect_top1(const void* pred_logits, const void* pred_logits_b, const 
 // the bounds of the two entries: which = 0 the largest Qs * C, 1 the largest K, 2 the largest NB; anything else -1
 int tuber_detect_limits(int which) {
     return which == 0 ? DET_MAX_KEYS : which == 1 ? DET_MAX_K : which == 2 ? DET_MAX_NB : -1;
+}
+
+// Actor decode, AVA rule (detect.decode_actors_host: the definition).  Inputs as tuber_detect_ava.  An ACTOR is a query of the clip's slice whose
+// pb = softmax(pred_logits_b)[1] is not NaN and > actor_thr; the best A by pb descending, then query ascending, are kept.  Out: det_box [B][A][4]
+// fp32 xyxy pixels, det_actor [B][A] fp32 (pb), det_query [B][A] int (query in the slice), det_actions [B][A][C] fp32 = sigmoid(logit) * pb for
+// EVERY class (bit-identical to tuber_detect_ava's score of the same (query, class); a NaN logit stays NaN), det_count [B] = min(det_total, A),
+// det_total [B]; rows from det_count on: box 0, actor 0, query -1, actions 0.  Qs, A or NB beyond tuber_detect_actors_limits, or A * C beyond an
+// int32: -2, nothing launched, nothing written; bad sizes or pointers, a NaN threshold: -1.
+int tuber_detect_actors(const void* pred_logits, const void* pred_logits_b, const void* pred_boxes, const float* sizes, const int* q_begin, int B,
+                        int Qtot, int Qs, int C, int NB, int lb_rows, int dtypes, float actor_thr, int A, float* det_box, float* det_actor,
+                        int* det_query, float* det_actions, int* det_count, int* det_total, hipStream_t stream) {
+    if (B < 1 || Qtot < 1 || Qs < 1 || Qs > Qtot || C < 1 || A < 1 || NB < 2) return TUBER_EINVAL;
+    if (lb_rows != 1 && lb_rows != Qtot) return TUBER_EINVAL;
+    if (dtypes & ~(DET_BF16_LOGITS | DET_BF16_LOGITS_B | DET_BF16_BOXES)) return TUBER_EINVAL;
+    if (!(actor_thr == actor_thr)) return TUBER_EINVAL;
+    if (!pred_logits || !pred_logits_b || !pred_boxes || !sizes || !det_box || !det_actor || !det_query || !det_actions || !det_count || !det_total)
+        return TUBER_EINVAL;
+    if (((uintptr_t)det_box & 15)) return TUBER_EINVAL;
+    if (Qs > DETA_MAX_QS || A > DETA_MAX_A || NB > DET_MAX_NB || (long)A * C > 0x7FFFFFFFl) return DET_EBOUNDS;
+    hipLaunchKernelGGL(detect_actors_kernel, dim3(B), dim3(DET_THREADS), 0, stream, pred_logits, pred_logits_b, pred_boxes, sizes, q_begin, Qtot, Qs, C,
+                       NB, lb_rows, dtypes, actor_thr, A, det_box, det_actor, det_query, det_actions, det_count, det_total);
+    TUBER_RETURN_LAUNCH();
+}
+
+// the bounds of tuber_detect_actors: which = 0 the largest Qs, 1 the largest A, 2 the largest NB; anything else -1
+int tuber_detect_actors_limits(int which) {
+    return which == 0 ? DETA_MAX_QS : which == 1 ? DETA_MAX_A : which == 2 ? DET_MAX_NB : -1;
 }
 
 }  // extern "C"

@@ -395,7 +395,25 @@ DOC = {
                          "its score that column's softmax probability; not a candidate when the label is the no-object column C, the score is NaN or < score_thr; the best K "
                          "by score descending, then q ascending; det_aux: the visibility probability softmax(pred_logits_b)[1]. Arguments and outputs as tuber_detect_ava.",
     "tuber_detect_limits": "bounds of tuber_detect_ava / tuber_detect_top1: which = 0 the largest Qs * C (4096), 1 the largest K (1024), 2 the largest NB (8).",
-    "tuber_tensor_stats_chunk": "largest number of elements in one chunk of tuber_tensor_stats (a multiple of 64).",
+    "tuber_detect_actors": "actor decode of an AVA eval forward in ONE launch (detect.decode_actors_host: the definition; the reference has no such path, its "
+                           "PostProcessAVA, models/criterion.py:447-482, returns the dense table): an ACTOR is a query of the clip's slice whose pb = "
+                           "softmax(pred_logits_b)[1] is not NaN and > actor_thr; the best A by pb descending, then query ascending, are kept, each with its box and "
+                           "its WHOLE action row. Inputs as tuber_detect_ava. Out: det_box [B][A][4] xyxy pixels (bit-identical to decode()'s), det_actor [B][A] fp32 "
+                           "(pb), det_query [B][A] int, det_actions [B][A][C] fp32 = sigmoid(logit) * pb for EVERY class, unthresholded, bit-identical to "
+                           "tuber_detect_ava's score of the same (query, class), a NaN logit staying NaN; det_count [B] = min(det_total, A), det_total [B]; rows from "
+                           "det_count on: box 0, actor 0, query -1, actions 0. One workgroup per clip, the order keys fmap_key(pb, q) sorted in LDS, the action rows "
+                           "written by the whole workgroup with 16-byte stores where C % 4 == 0: no atomics. Beyond tuber_detect_actors_limits (or A * C beyond an "
+                           "int32): -2, nothing launched; bad sizes or pointers, a NaN threshold: -1.",
+    "tuber_detect_actors_limits": "bounds of tuber_detect_actors: which = 0 the largest Qs (1024), 1 the largest A (1024), 2 the largest NB (8).",
+    "tuber_track_actions": "per-track and temporally smoothed action scores of ONE video's linked actor rows (evaluation.actor_tracks: the definition): actions "
+                           "[S * A][C] fp32 with row r = slot * A + a; row_head / tube_last [S * A] as tuber_tube_link_ranked wrote them with class_num = 1. Out: "
+                           "row_smooth [S * A][C] fp64: the mean over the rows of the row's track at most `window` slots away; at head rows track_mean [S * A][C] "
+                           "fp64 and track_peak [S * A][C] fp32 (the maximum, a NaN staying); zeros at rows with head -1 and, for the track outputs, at rows that are "
+                           "no head. Every sum is fp64, sequential in slot order, then one division: the definition's bits. A workgroup per row, a wave per 64 "
+                           "classes, a row's track member in a slot found by one ballot over the slot's A heads; no atomics. A or C beyond "
+                           "tuber_track_actions_limits, S * A beyond an int32, bad sizes or pointers: negative, nothing launched.",
+    "tuber_track_actions_limits": "bounds of tuber_track_actions: which = 0 the largest A (64, the linker's), 1 the largest C (4096).",
+    "tuber_tensor_stats_chunk":"largest number of elements in one chunk of tuber_tensor_stats (a multiple of 64).",
     "tuber_tensor_stats_tensor_bytes": "sizeof(TensorStatsTensor) as compiled (host-side layout check).",
     "tuber_tensor_stats_chunk_bytes": "sizeof(TensorStatsChunk) as compiled (host-side layout check).",
     "tuber_grad_accum": "gradient accumulation over m micro-batches (DistributedDataParallel's mean over ranks reproduced on fewer GPUs: the mean of "

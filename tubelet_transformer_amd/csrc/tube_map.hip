@@ -10,6 +10,9 @@
 //                           ground-truth boxes of the class into a [64][32] table (tube lane x ground-truth tube), writes a tube's spatio-temporal
 //                           IoU row when the tube ends, then visits the counted tubes by descending score and matches them greedily, a lane per
 //                           threshold with its taken set in one 32-bit mask.
+//   3. track_actions_kernel (tuber_track_actions, actor tracks of an AVA video): behind tube_link_kernel run with one class over a [S][A] actor store, a
+//                           workgroup per row averages the action rows of the row's track -- over the whole track at its head, over a window of slots
+//                           at every row -- in fp64, sequentially in slot order.
 // No floating-point atomics, every sum sequential in slot order: the same input gives the same bits.
 #include "map_common.h"
 
@@ -346,7 +349,96 @@ __global__ __launch_bounds__(64) void tube_match_kernel(const float* __restrict_
     }
 }
 
+// Actor tracks (evaluation.actor_tracks: the definition): per-track and temporally smoothed action scores over ONE video's [S][A] actor store
+// linked class-agnostically by tube_link_kernel.  A workgroup per row r = slot * A + a, a wave per 64 classes; a row's track is the rows with its
+// row_head, at most one per slot, found by comparing the slot's A heads in the lanes of the wave (one ballot).  Every sum is fp64, sequential in
+// slot order, followed by one division: the numpy definition's bits.
+#define TRACK_THREADS 256
+#define TRACK_MAX_C 4096          // classes of an action row
+
+// the position in slot t of the row whose head is h, -1 when the slot has none (wave-uniform)
+__device__ __forceinline__ int track_member(const int* __restrict__ row_head, int t, int A, int h, int lane) {
+    const unsigned long long m = __ballot(lane < A && row_head[t * A + lane] == h);
+    return m ? __ffsll((long long)m) - 1 : -1;
+}
+
+__global__ __launch_bounds__(TRACK_THREADS) void track_actions_kernel(const float* __restrict__ actions, const int* __restrict__ row_head,
+                                                                      const int* __restrict__ tube_last, int S, int A, int C, int window,
+                                                                      double* __restrict__ row_smooth, double* __restrict__ track_mean,
+                                                                      float* __restrict__ track_peak) {
+    const int r = blockIdx.x, lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int s = r / A;
+    int h = row_head[r];
+    if (h < 0 || h > r) h = -1;                                                   // a head is its track's first row
+    const bool is_head = h == r;
+    const int lo = window >= s ? 0 : s - window;
+    const int hi = window >= S - 1 - s ? S - 1 : s + window;
+    int last = s;
+    if (is_head) {
+        last = tube_last[r];
+        last = last < s ? s : (last > S - 1 ? S - 1 : last);
+    }
+    for (int c0 = wave * 64; c0 < C; c0 += TRACK_THREADS) {                       // wave-uniform: every lane takes part in the ballots
+        const int c = c0 + lane;
+        const bool live = c < C;
+        double smooth = 0.0, mean = 0.0;
+        float peak = 0.f;
+        if (h >= 0) {
+            double sum = 0.0;
+            int n = 0;
+            for (int t = lo; t <= hi; ++t) {
+                const int a = track_member(row_head, t, A, h, lane);
+                if (a < 0) continue;
+                ++n;
+                if (live) sum += (double)actions[((long)t * A + a) * C + c];
+            }
+            smooth = sum / (double)n;                                             // n >= 1: the row itself
+            if (is_head) {
+                double tot = 0.0;
+                int len = 0;
+                for (int t = s; t <= last; ++t) {
+                    const int a = track_member(row_head, t, A, h, lane);
+                    if (a < 0) continue;
+                    ++len;
+                    if (live) {
+                        const float v = actions[((long)t * A + a) * C + c];
+                        tot += (double)v;
+                        if (len == 1) peak = v;
+                        else if (peak == peak && (v != v || v > peak)) peak = v;  // np.max: a NaN stays
+                    }
+                }
+                mean = tot / (double)len;
+            }
+        }
+        if (live) {
+            const long o = (long)r * C + c;
+            row_smooth[o] = smooth;
+            track_mean[o] = mean;
+            track_peak[o] = peak;
+        }
+    }
+}
+
 extern "C" {
+
+// Per-track and temporally smoothed action scores of linked actor rows (evaluation.actor_tracks: the definition).  actions [S * A][C] fp32, row
+// r = slot * A + a; row_head [S * A] / tube_last [S * A] as tuber_tube_link_ranked wrote them for this ONE video with class_num = 1.  Out:
+// row_smooth [S * A][C] fp64, the mean over the rows of the row's track at most `window` slots away (fp64 sum in slot order / their number);
+// at head rows track_mean [S * A][C] fp64 (fp64 sum in slot order / length) and track_peak [S * A][C] fp32 (maximum); zeros at rows with head
+// -1 and, for track_mean / track_peak, at rows that are no head.  A > tuber_track_actions_limits(0), C > tuber_track_actions_limits(1), S * A
+// beyond an int32, bad sizes or pointers: TUBER_EINVAL, nothing launched, nothing written.
+int tuber_track_actions(const float* actions, const int* row_head, const int* tube_last, int S, int A, int C, int window, double* row_smooth,
+                        double* track_mean, float* track_peak, hipStream_t stream) {
+    if (S < 0 || A < 1 || C < 1 || window < 0) return TUBER_EINVAL;
+    if (A > TUBE_MAX_ACTIVE || C > TRACK_MAX_C || (long)S * A > 0x7FFFFFFFl) return TUBER_EINVAL;
+    if (S == 0) return TUBER_OK;
+    if (!actions || !row_head || !tube_last || !row_smooth || !track_mean || !track_peak) return TUBER_EINVAL;
+    hipLaunchKernelGGL(track_actions_kernel, dim3((unsigned)(S * A)), dim3(TRACK_THREADS), 0, stream, actions, row_head, tube_last, S, A, C, window,
+                       row_smooth, track_mean, track_peak);
+    TUBER_RETURN_LAUNCH();
+}
+// the bounds of tuber_track_actions: which = 0 the largest A, 1 the largest C; anything else -1
+int tuber_track_actions_limits(int which) { return which == 0 ? TUBE_MAX_ACTIVE : which == 1 ? TRACK_MAX_C : -1; }
 
 // Linking of per-frame detections into action tubes (evaluation.VideoMAP.link).  det_box [N][4] fp32 xyxy / det_prob [N][C + 1] fp32 in layout order
 // (video, slot, store order); slot_off DEVICE int[S + 1]: rows per slot; video_off DEVICE int[V + 1]: slots per video.  max_rows: the largest

@@ -32,6 +32,7 @@ from . import ab, lib
 from .misc import NestedTensor, nested_tensor_from_tensor_list
 
 FIELDS = ("boxes", "scores", "labels", "queries", "aux", "count", "total")
+ACTOR_FIELDS = ("boxes", "actor", "queries", "actions", "count", "total")
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -146,6 +147,78 @@ def _decode_topk_torch(logits, logits_b, boxes, sizes, mode, actor_thr, score_th
             zero(torch.gather(s, 1, idx).float()), minus(c), minus(q), zero(torch.gather(pb, 1, q).float()), count, total)
 
 
+def decode_actors_host(logits, logits_b, boxes, sizes, actor_thr, A, q_begin=None, Qs=None):
+    """The ACTORS of a batch under the AVA rule, in numpy: the DEFINITION of ``tuber_detect_actors``.  ``decode_topk_host``
+    ranks (query, class) pairs, so a person doing three things is three rows; here a row is a person.  A query of the clip's slice is an actor
+    when ``pb = softmax(logits_b)[1]`` is not NaN and ``pb > actor_thr`` (the gate of ``decode_topk_host``); actors are ranked by ``pb`` descending,
+    then query ascending (``fmap_key(pb, q)``), and the best ``A`` kept, each with its WHOLE action row ``sigmoid(logit) * pb`` -- the number
+    ``decode_topk_host`` calls the score of (q, c) -- unthresholded, a NaN logit staying NaN.  Probabilities in fp64 from the fp32 inputs, boxes in
+    fp32.  logits [B, Qtot, C]; logits_b [B, Qtot, NB] or [B, NB]; boxes [B, Qtot, 4] cxcywh; sizes [B, 2] (h, w).  Returns a dict of the
+    ``ACTOR_FIELDS`` arrays: boxes [B, A, 4] f32, actor [B, A] f32, queries [B, A] i32, actions [B, A, C] f32, count / total [B] i32; rows at and
+    after ``count[b]``: box 0, actor 0, query -1, actions 0."""
+    lg = np.asarray(logits, dtype=np.float32)
+    lb = np.asarray(logits_b, dtype=np.float32)
+    B, Qtot, C = lg.shape
+    Qs = Qtot if Qs is None else int(Qs)
+    A = int(A)
+    qb = np.zeros(B, dtype=np.int64) if q_begin is None else np.asarray(q_begin, dtype=np.int64).reshape(B)
+    pix = boxes_xyxy_f32(boxes, sizes)
+    pb_all = _softmax64(lb)[..., 1]                                    # [B, Qtot] or [B]
+    out = dict(boxes=np.zeros((B, A, 4), np.float32), actor=np.zeros((B, A), np.float32), queries=np.full((B, A), -1, np.int32),
+               actions=np.zeros((B, A, C), np.float32), count=np.zeros(B, np.int32), total=np.zeros(B, np.int32))
+    for b in range(B):
+        q0 = int(qb[b])
+        if q0 < 0 or q0 + Qs > Qtot:                                   # a slice outside the clip's queries: an empty result
+            continue
+        rows = lg[b, q0:q0 + Qs]
+        pb = pb_all[b, q0:q0 + Qs] if pb_all.ndim == 2 else np.full(Qs, pb_all[b])
+        with np.errstate(invalid="ignore"):
+            qq = np.nonzero(~np.isnan(pb) & (pb > actor_thr))[0]       # query ascending
+        order = np.argsort(-pb[qq], kind="stable")[:A]                 # pb descending, equal pb in query order
+        n = len(order)
+        out["total"][b], out["count"][b] = len(qq), n
+        qq = qq[order]
+        with np.errstate(over="ignore"):
+            s = (1.0 / (1.0 + np.exp(-rows[qq].astype(np.float64)))) * pb[qq][:, None]
+        out["boxes"][b, :n] = pix[b, q0 + qq]
+        out["actor"][b, :n] = pb[qq].astype(np.float32)
+        out["queries"][b, :n] = qq
+        out["actions"][b, :n] = s.astype(np.float32)
+    return out
+
+
+def _decode_actors_torch(logits, logits_b, boxes, sizes, actor_thr, A, q_begin, Qs):
+    """``decode_actors_host`` restated in torch on the inputs' device (fp64 probabilities, a stable sort): the path of shapes beyond
+    ``tuber_detect_actors_limits``.  No host synchronisation.  Returns the ``ACTOR_FIELDS`` tensors."""
+    from . import box_ops
+    dev = logits.device
+    B, Qtot, C = logits.shape
+    lg, lb, bx = logits.float(), logits_b.float(), boxes.float()
+    h, w = sizes.to(dev, torch.float32).unbind(1)
+    pix = box_ops.box_cxcywh_to_xyxy(bx) * torch.stack([w, h, w, h], dim=1)[:, None, :]
+    qb = torch.zeros(B, dtype=torch.int64, device=dev) if q_begin is None else q_begin.to(dev, torch.int64)
+    valid = (qb >= 0) & (qb + Qs <= Qtot)
+    rows = (torch.where(valid, qb, torch.zeros_like(qb))[:, None] + torch.arange(Qs, device=dev)[None, :])          # [B, Qs]
+    lg = torch.gather(lg, 1, rows[:, :, None].expand(B, Qs, C))
+    pix = torch.gather(pix, 1, rows[:, :, None].expand(B, Qs, 4))
+    pb = lb.double().softmax(-1)[..., 1]
+    pb = torch.gather(pb, 1, rows) if pb.dim() == 2 else pb[:, None].expand(B, Qs)
+    ok = ~torch.isnan(pb) & (pb > actor_thr) & valid[:, None]
+    key = torch.where(ok, pb, torch.full_like(pb, float("-inf")))
+    idx = torch.sort(key, dim=1, descending=True, stable=True).indices
+    if Qs < A:
+        idx = torch.cat([idx, torch.zeros(B, A - Qs, dtype=idx.dtype, device=dev)], dim=1)
+    q = idx[:, :A]
+    total = ok.sum(1).to(torch.int32)
+    count = total.clamp(max=A)
+    live = torch.arange(A, device=dev)[None, :] < count[:, None]
+    pa = torch.gather(pb, 1, q)                                                                                      # [B, A] fp64
+    act = torch.gather(lg, 1, q[:, :, None].expand(B, A, C)).double().sigmoid() * pa[:, :, None]
+    zero = torch.zeros((), device=dev)
+    return (torch.where(live[:, :, None], torch.gather(pix, 1, q[:, :, None].expand(B, A, 4)), zero), torch.where(live, pa.float(), zero),
+            torch.where(live, q, torch.full_like(q, -1)).to(torch.int32), torch.where(live[:, :, None], act.float(), zero), count, total)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # captured eval forward
 # ---------------------------------------------------------------------------------------------------------------------
@@ -251,11 +324,12 @@ class GraphedEval:
 class Detections:
     """Ranked detections of a batch as device tensors: boxes [B, K, 4] f32 xyxy pixels, scores / aux [B, K] f32, labels / queries [B, K]
     i32 (-1 in empty rows), count [B] = min(total, K), total [B].  A detector's result is a view of its buffers: valid until its next call."""
-    __slots__ = FIELDS + ("_retry",)
+    __slots__ = FIELDS + ("_retry", "actors")
 
     def __init__(self, boxes, scores, labels, queries, aux, count, total):
         self.boxes, self.scores, self.labels, self.queries, self.aux, self.count, self.total = boxes, scores, labels, queries, aux, count, total
         self._retry = None           # (ParamStore, callable -> Detections of the same batch): set by Detector, consumed by to_host
+        self.actors = None           # the ``Actors`` of the same batch: ``Detector(..., actors=A)``
 
     def tensors(self):
         return tuple(getattr(self, k) for k in FIELDS)
@@ -286,6 +360,90 @@ class Detections:
             d["count"], d["total"] = n, int(host["total"][b])
             out.append(d)
         return out
+
+
+def _host_parts(parts):
+    """the tensors ``parts`` as numpy arrays, in ONE device-to-host copy (it synchronises with the producing stream)"""
+    blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
+    host, o = [], 0
+    for t in parts:
+        n = t.numel() * t.element_size()
+        host.append(blob[o:o + n].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape)))
+        o += n
+    return host
+
+
+class Actors:
+    """The actors of a batch as device tensors (``decode_actors_host``): boxes [B, A, 4] f32 xyxy pixels, actor [B, A] f32 (the actor probability),
+    queries [B, A] i32 (-1 in empty rows), actions [B, A, C] f32 (every class's score ``sigmoid(logit) * actor``), count [B] = min(total, A),
+    total [B].  A detector's result is a view of its buffers: valid until its next call."""
+    __slots__ = ACTOR_FIELDS + ("_retry",)
+
+    def __init__(self, boxes, actor, queries, actions, count, total):
+        self.boxes, self.actor, self.queries, self.actions, self.count, self.total = boxes, actor, queries, actions, count, total
+        self._retry = None           # (ParamStore, callable -> Actors of the same batch): set by Detector, consumed by to_host
+
+    def tensors(self):
+        return tuple(getattr(self, k) for k in ACTOR_FIELDS)
+
+    def _fetch(self, store):
+        host = _host_parts(list(self.tensors()) + ([store.coop_sync] if store is not None else []))
+        return dict(zip(ACTOR_FIELDS, host)), (host[-1] if store is not None else None)
+
+    def to_host(self):
+        """a list, per clip, of dicts of numpy arrays trimmed to ``count`` (``boxes``, ``actor``, ``queries``, ``actions`` [count, C], ``count``,
+        ``total``): one copy, the only place that synchronises.  The fail-safe of ``Detections.to_host``: a poisoned forward has NaN actor
+        probabilities, hence no actor; the error word travels in the same copy and the batch runs once more on the launch chain."""
+        retry, self._retry = self._retry, None
+        store, again = retry if retry is not None else (None, None)
+        host, word = self._fetch(store)
+        if word is not None and word[2] and not store.coop_off and store.coop_failed():
+            host, _ = again()._fetch(None)
+        out = []
+        for b in range(len(host["count"])):
+            n = int(host["count"][b])
+            d = {k: host[k][b, :n].copy() for k in ("boxes", "actor", "queries", "actions")}
+            d["count"], d["total"] = n, int(host["total"][b])
+            out.append(d)
+        return out
+
+
+def empty_actors(B, A, C, device):
+    f32, i32 = torch.float32, torch.int32
+    return Actors(torch.zeros(B, A, 4, dtype=f32, device=device), torch.zeros(B, A, dtype=f32, device=device),
+                  torch.full((B, A), -1, dtype=i32, device=device), torch.zeros(B, A, C, dtype=f32, device=device),
+                  torch.zeros(B, dtype=i32, device=device), torch.zeros(B, dtype=i32, device=device))
+
+
+def actors_launch(logits, logits_b, boxes, sizes, q_begin, Qs, actor_thr, A, out=None):
+    """one ``tuber_detect_actors`` launch on the current stream over AVA head outputs as the forward produced them (fp32 or bf16, contiguous);
+    arguments as ``detect_launch``.  ``out``: the ``Actors`` to write (allocated when None).  Beyond the kernel's bounds
+    (``tuber_detect_actors_limits``) the torch restatement of ``decode_actors_host`` answers."""
+    dev = logits.device
+    B, Qtot, C = logits.shape
+    NB = logits_b.shape[-1]
+    lb_rows = Qtot if logits_b.dim() == 3 else 1
+    if out is None:
+        out = empty_actors(B, A, C, dev)
+    lim = [lib.query("tuber_detect_actors_limits", w) for w in (0, 1, 2)]
+    if Qs > lim[0] or A > lim[1] or NB > lim[2] or A * C > 0x7FFFFFFF:
+        res = _decode_actors_torch(logits, logits_b, boxes, sizes, actor_thr, A, q_begin, Qs)
+        for dst, src in zip(out.tensors(), res):
+            dst.copy_(src)
+        return out
+    dtypes = 0
+    for t, bit in ((logits, 1), (logits_b, 2), (boxes, 4)):
+        if t.dtype == torch.bfloat16:
+            dtypes |= bit
+        elif t.dtype != torch.float32:
+            raise TypeError("actors_launch: head outputs are fp32 or bf16, got %s" % t.dtype)
+        if not t.is_contiguous():
+            raise ValueError("actors_launch: head outputs must be contiguous")
+    if sizes.dtype != torch.float32 or (q_begin is not None and q_begin.dtype != torch.int32):
+        raise TypeError("actors_launch: sizes is fp32 [B, 2], q_begin int32 [B]")
+    lib.call("tuber_detect_actors", logits, logits_b, boxes, sizes, q_begin, B, Qtot, Qs, C, NB, lb_rows, dtypes, float(actor_thr), int(A),
+             *out.tensors())
+    return out
 
 
 def detect_launch(mode, logits, logits_b, boxes, sizes, q_begin, Qs, actor_thr, score_thr, K, out=None):
@@ -332,9 +490,13 @@ class Detector:
     ``graphed=True``: the forward and the decode launch replay as one hipGraph per input shape (``GraphedEval``), ``sizes`` / the key-frame
     slice being static inputs; ``graphed=False``: the eager forward plus the one launch.  The rule comes from ``model.dataset_mode``, the
     defaults from ``CONFIG.VAL.DETECT``.  ``key_pos`` [B]: the key frame of each clip, needed when the model carries QUERY_NUM queries per
-    frame (``SINGLE_FRAME: False``, JHMDB / UCF101-24): the detections are those of that frame's queries."""
+    frame (``SINGLE_FRAME: False``, JHMDB / UCF101-24): the detections are those of that frame's queries.
 
-    def __init__(self, cfg, model, score_thr=None, topk=None, actor_thr=None, graphed=True, max_shapes=4):
+    ``actors=A`` (AVA models; default None: off): a second launch behind the first one, ``tuber_detect_actors`` over the same head outputs, and the
+    result carries ``.actors``, the ``Actors`` of the batch: the best A queries by actor probability, each with its whole action row.  The
+    JHMDB / UCF101-24 models carry one label per query -- their ranked detections already are per actor -- so ``actors`` raises there."""
+
+    def __init__(self, cfg, model, score_thr=None, topk=None, actor_thr=None, graphed=True, max_shapes=4, actors=None):
         from .config import detect_settings
         d = detect_settings(cfg)
         self.cfg, self.model = cfg, model
@@ -344,6 +506,12 @@ class Detector:
         if self.topk < 1:
             raise ValueError("Detector: topk = %r must be >= 1" % (topk,))
         self.mode = model.dataset_mode
+        if actors is not None:
+            if self.mode != "ava":
+                raise ValueError("Detector: actors = %r needs an AVA model; a %s model carries one label per query: use tubes()" % (actors, self.mode))
+            if isinstance(actors, bool) or int(actors) != actors or actors < 1:
+                raise ValueError("Detector: actors = %r must be an integer >= 1" % (actors,))
+        self.actors = None if actors is None else int(actors)
         self.graphed = bool(graphed)
         self.Q = int(cfg.CONFIG.MODEL.QUERY_NUM)
         self.sliced = model.query_embed.num_embeddings != self.Q       # QUERY_NUM queries per frame: a call names its key frames
@@ -353,13 +521,20 @@ class Detector:
     def statics(self, outputs):
         lg = outputs["pred_logits"]
         B, dev = lg.shape[0], lg.device
-        return {"sizes": torch.zeros(B, 2, dtype=torch.float32, device=dev), "q_begin": torch.zeros(B, dtype=torch.int32, device=dev),
-                "out": empty_detections(B, self.topk, dev)}
+        statics = {"sizes": torch.zeros(B, 2, dtype=torch.float32, device=dev), "q_begin": torch.zeros(B, dtype=torch.int32, device=dev),
+                   "out": empty_detections(B, self.topk, dev)}
+        if self.actors is not None:
+            statics["out"].actors = empty_actors(B, self.actors, lg.shape[2], dev)
+        return statics
 
     def launch(self, outputs, statics):
         lg = outputs["pred_logits"]
-        return detect_launch(self.mode, lg, outputs["pred_logits_b"], outputs["pred_boxes"], statics["sizes"], statics["q_begin"] if self.sliced else None,
-                             self.Q if self.sliced else lg.shape[1], self.actor_thr, self.score_thr, self.topk, out=statics["out"])
+        qb, Qs = statics["q_begin"] if self.sliced else None, self.Q if self.sliced else lg.shape[1]
+        det = detect_launch(self.mode, lg, outputs["pred_logits_b"], outputs["pred_boxes"], statics["sizes"], qb, Qs, self.actor_thr, self.score_thr,
+                            self.topk, out=statics["out"])
+        if self.actors is not None:
+            actors_launch(lg, outputs["pred_logits_b"], outputs["pred_boxes"], statics["sizes"], qb, Qs, self.actor_thr, self.actors, out=det.actors)
+        return det
 
     def _q_begin(self, key_pos):
         """first query of the key frame's slice: evaluation.py's ``key_pos // DS_RATE * Q`` (AVA, SINGLE_FRAME: False) / ``key_pos * Q``"""
@@ -387,4 +562,6 @@ class Detector:
             return self.eval.run(samples, feed)[1]
         det = run()
         det._retry = (self.model.engine()[0], run)
+        if det.actors is not None:
+            det.actors._retry = (det._retry[0], lambda: run().actors)
         return det

@@ -539,6 +539,47 @@ def link_rows(box, cls, score, slot, video_off, class_num, link_iou, max_gap):
     return dict(row_head=head, tube_score=tscore, tube_len=tlen, tube_last=tlast)
 
 
+def actor_tracks(box, actor, queries, actions, S, A, link_iou, max_gap, window):
+    """Actor tracks of ONE video: the definition of ``tuber_track_actions`` and the fallback of ``video.VideoActors.tracks``.
+    The rows are a padded [S][A] actor store (``detect.decode_actors_host`` per key frame): ``box`` [S * A, 4] fp32 xyxy, ``actor`` [S * A] fp32,
+    ``queries`` [S * A] (-1: a row behind its key's count), ``actions`` [S * A, C] fp32; row r = slot * A + a, the slots being key ordinals.
+
+    1. Link, class-agnostic: ``link_rows`` with ``class_num = 1``, the class 0 for an actor row and -1 for a row behind the count, the score the
+       actor probability -> ``row_head``, ``tube_score`` (the track's mean actor probability), ``tube_len``, ``tube_last``, unchanged.
+    2. Aggregate.  A track has the rows r_0 < ... < r_{L-1} at the slots s_i.  Per class: ``track_mean`` [S * A, C] fp64 at the head row, the fp64
+       sum of ``float64(actions[r_i])`` in slot order divided by L; ``track_peak`` [S * A, C] fp32 at the head row, the maximum; ``row_smooth``
+       [S * A, C] fp64 at every row of a track, the fp64 sum in slot order over the rows j of the track with ``|s_j - s_i| <= window`` divided by
+       their number (``window`` counts key frames, like ``max_gap``).  A NaN propagates as in numpy's sum and max.  Rows with ``row_head`` -1
+       hold zeros, and so do the track fields at rows that are no head."""
+    S, A, window = int(S), int(A), int(window)
+    N = S * A
+    box = np.asarray(box, dtype=np.float32).reshape(N, 4)
+    actor = np.asarray(actor, dtype=np.float32).reshape(N)
+    queries = np.asarray(queries).reshape(N)
+    actions = np.asarray(actions, dtype=np.float32).reshape(N, -1)
+    C = actions.shape[1]
+    slot = np.repeat(np.arange(S, dtype=np.int64), A)
+    out = link_rows(box, np.where(queries >= 0, 0, -1), actor, slot, [0, S], 1, link_iou, max_gap)
+    smooth, mean, peak = np.zeros((N, C)), np.zeros((N, C)), np.zeros((N, C), dtype=np.float32)
+    members = {}
+    for r in np.nonzero(out["row_head"] >= 0)[0].tolist():
+        members.setdefault(int(out["row_head"][r]), []).append(r)          # ascending rows: slot order, one row per slot
+    for h, rows in members.items():
+        acc = np.zeros(C)
+        for r in rows:
+            acc = acc + actions[r].astype(np.float64)
+        mean[h] = acc / len(rows)
+        peak[h] = np.max(actions[rows], axis=0)
+        for r in rows:
+            near = [j for j in rows if abs(int(slot[j]) - int(slot[r])) <= window]
+            acc = np.zeros(C)
+            for j in near:
+                acc = acc + actions[j].astype(np.float64)
+            smooth[r] = acc / len(near)
+    out.update(row_smooth=smooth, track_mean=mean, track_peak=peak)
+    return out
+
+
 class TubeLinker:
     """``link_rows`` for ONE video whose slots arrive in pieces: ``push(box, cls, score, K)`` links the next ``len(cls) // K`` slots of ``K`` rows
     each (rows behind a slot's count: class -1) and returns, per new row, ``row_head`` (the GLOBAL row ``ordinal * K + position`` of the tube's

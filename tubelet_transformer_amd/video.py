@@ -20,7 +20,7 @@ import torch
 
 from . import input_pipeline as ip
 from . import lib
-from .detect import FIELDS, Detector
+from .detect import ACTOR_FIELDS, FIELDS, Detector
 from .misc import NestedTensor
 
 RULES = ("ava", "jhmdb", "edge")
@@ -92,6 +92,7 @@ class VideoDetections:
         self.tubes_path = None                                                         # "device" or "host" after tubes()
         self._store = store                                                            # the engine's ParamStore: to_host reads its error word
         self.row_head = self.row_score = self.row_len = None                           # the link records of a VideoStream push (link=True)
+        self.actors = None                                                             # the ``VideoActors`` of ``VideoDetector(..., actors=A)``
         if not (len(self.keys) == boxes.shape[0] == scores.shape[0] == count.shape[0]):
             raise ValueError("VideoDetections: %d keys, %d rows" % (len(self.keys), boxes.shape[0]))
 
@@ -181,6 +182,131 @@ class VideoDetections:
         return out
 
 
+class VideoActors:
+    """The actors of a video's key frames (``VideoDetector(..., actors=A)``): ``keys`` (frame numbers) and, as tensors on one
+    device, ``boxes`` [n, A, 4] fp32 xyxy in source-video pixels, ``actor`` [n, A] fp32 (the actor probability), ``queries`` [n, A] int32 (-1 in
+    the rows behind ``count``), ``actions`` [n, A, C] fp32 (every class's score), ``count`` / ``total`` [n] int32 -- the fields of
+    ``detect.Actors``, a row per key frame."""
+
+    def __init__(self, keys, boxes, actor, queries, actions, count, total, settings=None, store=None):
+        self.keys = [int(k) for k in keys]
+        self.boxes, self.actor, self.queries, self.actions, self.count, self.total = boxes, actor, queries, actions, count, total
+        self.class_num = int(actions.shape[2])
+        # the defaults of tracks(): CONFIG.VAL.ACTORS
+        self.settings = dict(settings or dict(link_iou=0.2, max_gap=2, min_len=1, window=1, label_thr=0.05))
+        self.tracks_path = None                                                        # "device" or "host" after tracks()
+        self._store = store
+        if not (len(self.keys) == boxes.shape[0] == actor.shape[0] == actions.shape[0] == count.shape[0]):
+            raise ValueError("VideoActors: %d keys, %d rows" % (len(self.keys), boxes.shape[0]))
+
+    def tensors(self):
+        return tuple(getattr(self, k) for k in ACTOR_FIELDS)
+
+    def _fetch(self, extra=()):
+        """every field (and ``extra`` tensors) as numpy arrays, in ONE device-to-host copy"""
+        parts = [t.contiguous() for t in list(self.tensors()) + list(extra)]
+        if self.boxes.device.type != "cuda":
+            return [t.numpy() for t in parts]
+        blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
+        host, o = [], 0
+        for t in parts:
+            n = t.numel() * t.element_size()
+            host.append(blob[o:o + n].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape)))
+            o += n
+        return host
+
+    def to_host(self):
+        """a list, per key frame, of dicts of numpy arrays trimmed to ``count`` (``key``, ``boxes``, ``actor``, ``queries``, ``actions``,
+        ``count``, ``total``): one copy, the place that synchronises; the cooperative decoder's error word travels in it and raises here, as in
+        ``VideoDetections.to_host``."""
+        word = [self._store.coop_sync] if self._store is not None and self.boxes.device.type == "cuda" else []
+        host = self._fetch(word)
+        if word and host[-1][2] and not self._store.coop_off:
+            self._store.check_coop()
+        host = dict(zip(ACTOR_FIELDS, host))
+        out = []
+        for i, key in enumerate(self.keys):
+            n = int(host["count"][i])
+            d = {k: host[k][i, :n].copy() for k in ("boxes", "actor", "queries", "actions")}
+            d["key"], d["count"], d["total"] = key, n, int(host["total"][i])
+            out.append(d)
+        return out
+
+    # -- tracks -----------------------------------------------------------------------------------------------------------
+    NAMES = ("row_head", "tube_score", "tube_len", "tube_last", "row_smooth", "track_mean", "track_peak")
+
+    def _tracks_device(self, link_iou, max_gap, window):
+        """``tuber_tube_link_ranked`` with one class and ``tuber_track_actions`` over the padded store as it is, everything read back in one copy;
+        or None where the kernels' bounds refuse it"""
+        S, A, C = self.actions.shape
+        if self.boxes.device.type != "cuda":
+            return None, "the store is on the CPU"
+        rows, active = lib.query("tuber_frame_match_max_dets"), lib.query("tuber_tube_link_max_active")
+        max_a, max_c = lib.query("tuber_track_actions_limits", 0), lib.query("tuber_track_actions_limits", 1)
+        if A > min(rows, max_a) or A * (max_gap + 1) > active or C > max_c:
+            return None, "%d actors per key frame with max_gap %d and %d classes: beyond %d rows, %d active tracks or %d classes" % (
+                A, max_gap, C, min(rows, max_a), active, max_c)
+        dev, N = self.boxes.device, S * A
+        f64, i32 = torch.float64, torch.int32
+        slot_off = torch.arange(S + 1, dtype=i32, device=dev) * A
+        video_off = torch.tensor([0, S], dtype=i32).to(dev)
+        label = torch.where(self.queries >= 0, 0, -1).to(i32).contiguous()               # one class; a row behind its key's count is not counted
+        out = dict(row_cls=torch.empty(N, dtype=i32, device=dev), row_head=torch.empty(N, dtype=i32, device=dev),
+                   tube_score=torch.zeros(N, dtype=f64, device=dev), tube_len=torch.zeros(N, dtype=i32, device=dev),
+                   tube_last=torch.full((N,), -1, dtype=i32, device=dev), row_smooth=torch.empty(N, C, dtype=f64, device=dev),
+                   track_mean=torch.empty(N, C, dtype=f64, device=dev), track_peak=torch.empty(N, C, dtype=torch.float32, device=dev))
+        lib.call("tuber_tube_link_ranked", self.boxes.contiguous(), label, self.actor.contiguous(), slot_off, video_off, 1, S, N, 1, A, float(link_iou),
+                 int(max_gap), out["row_cls"], out["row_head"], out["tube_score"], out["tube_len"], out["tube_last"])
+        lib.call("tuber_track_actions", self.actions.contiguous(), out["row_head"], out["tube_last"], S, A, C, int(window), out["row_smooth"],
+                 out["track_mean"], out["track_peak"])
+        host = self._fetch([out[k] for k in self.NAMES])
+        return dict(zip(ACTOR_FIELDS + self.NAMES, host)), None
+
+    def tracks(self, link_iou=None, max_gap=None, min_len=None, window=None, label_thr=None):
+        """The actor tracks of the video -- who is there, from when to when, doing what: a list, in head order (the order of the tracks' first
+        rows), of ``dict(score, frames, boxes, actor, queries, actions, smooth, mean, peak, labels, length)``: ``score`` the fp64 mean actor
+        probability, ``frames`` the key frame numbers, ``boxes`` [L, 4] in source pixels, ``actor`` / ``queries`` [L], ``actions`` [L, C] fp32 the
+        action scores per key, ``smooth`` [L, C] fp64 those scores averaged over the track's keys at most ``window`` key frames away, ``mean``
+        [C] fp64 / ``peak`` [C] fp32 over the track, ``labels`` the 0-based classes with ``mean >= label_thr`` by mean descending, then class;
+        tracks shorter than ``min_len`` are dropped.  ``evaluation.actor_tracks`` is the definition.  Defaults: ``CONFIG.VAL.ACTORS``.  On the
+        device: ``tuber_tube_link_ranked`` with one class, ``tuber_track_actions``, one copy back.  Beyond their bounds (A > 64,
+        A * (max_gap + 1) > 64, C > 4096) or on a CPU store the definition answers on the host, one line says so, and ``tracks_path`` is "host"
+        instead of "device"."""
+        from .evaluation import actor_tracks
+        st = self.settings
+        link_iou = float(st["link_iou"] if link_iou is None else link_iou)
+        max_gap = int(st["max_gap"] if max_gap is None else max_gap)
+        min_len = int(st["min_len"] if min_len is None else min_len)
+        window = int(st["window"] if window is None else window)
+        label_thr = float(st["label_thr"] if label_thr is None else label_thr)
+        if max_gap < 0 or window < 0:
+            raise ValueError("VideoActors.tracks: max_gap = %d and window = %d must be >= 0" % (max_gap, window))
+        S, A, C = self.actions.shape
+        host, why = self._tracks_device(link_iou, max_gap, window)
+        if host is None:
+            print("[tuber] VideoActors.tracks: %s; tracks on the host" % why, file=sys.stderr, flush=True)
+            host = dict(zip(ACTOR_FIELDS, self._fetch()))
+            host.update(actor_tracks(host["boxes"], host["actor"], host["queries"], host["actions"], S, A, link_iou, max_gap, window))
+        self.tracks_path = "host" if why else "device"
+        head = np.asarray(host["row_head"]).reshape(-1)
+        box, actor, query, act = host["boxes"].reshape(-1, 4), host["actor"].reshape(-1), host["queries"].reshape(-1), host["actions"].reshape(-1, C)
+        members = {}
+        for r in np.nonzero(head >= 0)[0].tolist():
+            members.setdefault(int(head[r]), []).append(r)
+        out = []
+        for h in sorted(members):
+            rows = members[h]
+            if len(rows) < min_len:
+                continue
+            mean = np.array(host["track_mean"][h], dtype=np.float64)
+            with np.errstate(invalid="ignore"):
+                labels = sorted(np.nonzero(mean >= label_thr)[0].tolist(), key=lambda c: (-mean[c], c))
+            out.append(dict(score=float(host["tube_score"][h]), frames=[self.keys[r // A] for r in rows], boxes=box[rows].copy(), actor=actor[rows].copy(),
+                            queries=query[rows].copy(), actions=act[rows].copy(), smooth=np.array(host["row_smooth"][rows], dtype=np.float64), mean=mean,
+                            peak=np.array(host["track_peak"][h], dtype=np.float32), labels=labels, length=len(rows)))
+        return out
+
+
 class VideoDetector:
     """``VideoDetector(cfg, model)(frames)`` -> ``VideoDetections``: every key frame of a video through the captured ``detect.Detector``.
 
@@ -195,10 +321,12 @@ class VideoDetector:
     ``rule``: ``clip_indices``' rule, by default the model's ``dataset_mode`` ("ava", otherwise "jhmdb").  ``topk``: by default
     ``min(CONFIG.VAL.DETECT.TOPK, tuber_tube_link_max_active() // (CONFIG.VAL.VIDEO_MAP.MAX_GAP + 1))`` -- 21 with the shipped settings (TOPK 100,
     64 active tubes, MAX_GAP 2) -- so that ``tubes()`` with its defaults links on the device.  ``score_thr`` / ``actor_thr`` / ``graphed``: as
-    ``Detector``."""
+    ``Detector``.  ``actors=A`` (AVA models; default None: off): the ``Detector``'s actor decode as well, its six tensors copied device-to-device
+    into the video's store beside the seven; the result carries ``.actors``, a ``VideoActors``, whose ``tracks()`` answers "who is there, from
+    when to when, doing what" (DESIGN.md section 6i)."""
 
-    def __init__(self, cfg, model, batch=2, score_thr=None, topk=None, actor_thr=None, graphed=True, rule=None):
-        from .config import detect_settings, video_map_settings
+    def __init__(self, cfg, model, batch=2, score_thr=None, topk=None, actor_thr=None, graphed=True, rule=None, actors=None):
+        from .config import actor_settings, detect_settings, video_map_settings
         self.cfg, self.model = cfg, model
         self.batch = int(batch)
         if self.batch < 1:
@@ -207,7 +335,11 @@ class VideoDetector:
         self.settings = dict(link_iou=float(vm["link_iou"]), max_gap=int(vm["max_gap"]), min_len=int(vm["min_len"]))
         if topk is None:
             topk = max(1, min(detect_settings(cfg)["topk"], lib.query("tuber_tube_link_max_active") // (self.settings["max_gap"] + 1)))
-        self.detector = Detector(cfg, model, score_thr=score_thr, topk=topk, actor_thr=actor_thr, graphed=graphed)
+        self.detector = Detector(cfg, model, score_thr=score_thr, topk=topk, actor_thr=actor_thr, graphed=graphed, actors=actors)
+        self.actor_settings = None
+        if actors is not None:
+            st = actor_settings(cfg)
+            self.actor_settings = {k: st[k] for k in ("link_iou", "max_gap", "min_len", "window", "label_thr")}
         self.mode = model.dataset_mode
         self.rule = rule if rule is not None else ("ava" if self.mode == "ava" else "jhmdb")
         if self.rule not in RULES:
@@ -274,13 +406,24 @@ class VideoDetector:
         full = [torch.empty(nb * B, K, 4, dtype=f32, device=dev), torch.empty(nb * B, K, dtype=f32, device=dev), torch.empty(nb * B, K, dtype=i32, device=dev),
                 torch.empty(nb * B, K, dtype=i32, device=dev), torch.empty(nb * B, K, dtype=f32, device=dev), torch.empty(nb * B, dtype=i32, device=dev),
                 torch.empty(nb * B, dtype=i32, device=dev)]
+        A, full_a = self.detector.actors, None
+        if A is not None:
+            full_a = [torch.empty(nb * B, A, 4, dtype=f32, device=dev), torch.empty(nb * B, A, dtype=f32, device=dev),
+                      torch.empty(nb * B, A, dtype=i32, device=dev), torch.empty(nb * B, A, self.class_num, dtype=f32, device=dev),
+                      torch.empty(nb * B, dtype=i32, device=dev), torch.empty(nb * B, dtype=i32, device=dev)]
         samples = NestedTensor(clips, mask)
         for b in range(nb):
             lib.call("tuber_video_clips", resident, N, nh, nw, table[b * B:], B, T, y1, x1, h, w, lut, clips)
             det = self.detector(samples, sizes, key_pos)
             for dst, src in zip(full, det.tensors()):
                 dst[b * B:(b + 1) * B].copy_(src)
-        return VideoDetections(keys, *[t[:n] for t in full], class_num=self.class_num, settings=self.settings, store=store)
+            if full_a is not None:
+                for dst, src in zip(full_a, det.actors.tensors()):
+                    dst[b * B:(b + 1) * B].copy_(src)
+        vd = VideoDetections(keys, *[t[:n] for t in full], class_num=self.class_num, settings=self.settings, store=store)
+        if full_a is not None:
+            vd.actors = VideoActors(keys, *[t[:n] for t in full_a], settings=self.actor_settings, store=store)
+        return vd
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------
