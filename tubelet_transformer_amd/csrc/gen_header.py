@@ -413,6 +413,26 @@ DOC = {
                            "classes, a row's track member in a slot found by one ballot over the slot's A heads; no atomics. A or C beyond "
                            "tuber_track_actions_limits, S * A beyond an int32, bad sizes or pointers: negative, nothing launched.",
     "tuber_track_actions_limits": "bounds of tuber_track_actions: which = 0 the largest A (64, the linker's), 1 the largest C (4096).",
+    "tuber_track_actions_stream": "tuber_track_actions for ONE video whose key frames arrive in pieces (evaluation.ActorTracker: the definition; "
+                                  "video.VideoStream(actors=A)). This call takes the S new slots slot_base .. slot_base + S - 1 of A rows each: actions [S * A][C] fp32, "
+                                  "row_head [S * A] as tuber_tube_link_stream wrote it for the same slots with C = 1, K = A and the same slot_base. Out: row_mean "
+                                  "[S * A][C] fp64 / row_peak [S * A][C] fp32, the track's running mean (fp64 sum in slot order / count) and maximum (a NaN staying) "
+                                  "after taking the row: at a track's last row tuber_track_actions' track_mean / track_peak, bit for bit; smooth [(hi - lo) * A][C] "
+                                  "fp64: tuber_track_actions' row_smooth of the slots lo = max(slot_base - window, 0) .. hi = flush ? slot_base + S : "
+                                  "max(slot_base + S - window, lo) (evaluation.smooth_range) -- a smoothed row looks window slots ahead, so it is emitted window slots "
+                                  "late; flush != 0 marks the end of the video. Zeros at rows with head -1. state: caller-owned, "
+                                  "tuber_track_stream_state_bytes(A, C, max_gap, window) bytes, 16-byte aligned, all zero = a new video: a ring of the last H = max(2 * "
+                                  "window, max_gap + 1) + 1 slots, entry ordinal % H, per row the head and the count, per (row, class) the running fp64 sum, the fp32 "
+                                  "peak and the fp32 action. Every pushed slot, an empty one included, writes its entry and the kernel knows slot_base, so an entry "
+                                  "of an ordinal below 0 or of a slot not yet pushed is never consulted. One wave per 64 classes, each with its OWN copy of the head "
+                                  "/ count records in front of its class columns: no workgroup reads what another one writes, no atomics, plain vector stores. A, C "
+                                  "or window beyond tuber_track_stream_limits, A * (max_gap + 1) > tuber_tube_link_max_active(), (slot_base + S) * A beyond an int32, "
+                                  "bad sizes, a null or misaligned pointer, negative arguments: TUBER_EINVAL, nothing launched, the state untouched, nothing written. "
+                                  "S == 0 without flush: 0, no launch; with flush: the last min(window, slot_base) slots.",
+    "tuber_track_stream_state_bytes": "bytes of the state buffer of tuber_track_actions_stream: per 64 classes, H * A head and count records (rounded up to 16 "
+                                      "bytes) and H * A * 64 columns of 16 bytes, H = max(2 * window, max_gap + 1) + 1; 0 for arguments outside the bounds.",
+    "tuber_track_stream_limits": "bounds of tuber_track_actions_stream: which = 0 the largest A (64, the linker's), 1 the largest C (4096), 2 the largest window "
+                                 "(31: a ring of 63 slots); anything else -1.",
     "tuber_tensor_stats_chunk":"largest number of elements in one chunk of tuber_tensor_stats (a multiple of 64).",
     "tuber_tensor_stats_tensor_bytes": "sizeof(TensorStatsTensor) as compiled (host-side layout check).",
     "tuber_tensor_stats_chunk_bytes": "sizeof(TensorStatsChunk) as compiled (host-side layout check).",

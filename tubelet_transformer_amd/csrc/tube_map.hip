@@ -419,7 +419,182 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_actions_kernel(const floa
     }
 }
 
+// Actor tracks of a video whose key frames arrive in pieces (evaluation.ActorTracker: the definition; tuber_track_actions_stream).  Given the
+// heads every class is independent: a workgroup is ONE wave that owns 64 class columns, a lane per column, and walks the S new slots in order.
+// Between calls it keeps the last H = max(2 * window, max_gap + 1) + 1 slots in a caller-owned ring, entry ordinal % H: per row the head and the
+// count, per (row, class) the running fp64 sum, the fp32 peak and the fp32 action value.  The ring is laid out PER WAVE -- its own copy of the
+// head / count records in front of its own class columns -- so no workgroup reads what another one writes: the entry of slot s overwrites that
+// of slot s - H while a neighbouring wave may still be looking rows up in it, and with one copy each that cannot matter.  Inside a wave a
+// column is read and written by its own lane only; the head / count records live in LDS during the walk (barriers of one wave), are loaded
+// from the ring before it and stored slot by slot.
+#define TSTREAM_MAX_WINDOW 31                        // 2 * 31 + 1 = 63 ring slots
+#define TSTREAM_MAX_ENTRIES (64 * 63)                // H * A: A * (max_gap + 2) <= 128 and A * (2 * window + 1) <= 64 * 63
+#define TSTREAM_COLS 64                              // class columns of a wave
+
+__host__ __device__ inline int tstream_slots(int max_gap, int window) {
+    return (2 * window > max_gap + 1 ? 2 * window : max_gap + 1) + 1;
+}
+// bytes of the head + count records of one wave (16-byte multiple), and of one wave's whole ring
+__host__ __device__ inline long tstream_record_bytes(int entries) { return ((long)entries * 8 + 15) & ~15l; }
+__host__ __device__ inline long tstream_wave_bytes(int entries) {
+    return tstream_record_bytes(entries) + (long)entries * TSTREAM_COLS * 16;
+}
+
+// the position in ring entry e of the row whose head is h, -1 when the slot has none (wave-uniform)
+__device__ __forceinline__ int tstream_member(const int* s_head, int e, int A, int h, int lane) {
+    const unsigned long long m = __ballot(lane < A && s_head[e * A + lane] == h);
+    return m ? __ffsll((long long)m) - 1 : -1;
+}
+
+__global__ __launch_bounds__(64) void track_actions_stream_kernel(const float* __restrict__ actions, const int* __restrict__ row_head, int S,
+                                                                  int A, int C, int slot_base, int max_gap, int window, int flush, int H,
+                                                                  unsigned char* __restrict__ state, double* __restrict__ row_mean,
+                                                                  float* __restrict__ row_peak, double* __restrict__ smooth) {
+    __shared__ int s_head[TSTREAM_MAX_ENTRIES];
+    __shared__ int s_cnt[TSTREAM_MAX_ENTRIES];
+    const int lane = threadIdx.x;
+    const int c = blockIdx.x * TSTREAM_COLS + lane;
+    const bool live = c < C;
+    const int entries = H * A;
+    unsigned char* mine = state + (long)blockIdx.x * tstream_wave_bytes(entries);
+    int* g_head = (int*)mine;
+    int* g_cnt = g_head + entries;
+    double* g_sum = (double*)(mine + tstream_record_bytes(entries));             // [entry][64]
+    float* g_peak = (float*)(g_sum + (long)entries * TSTREAM_COLS);
+    float* g_act = g_peak + (long)entries * TSTREAM_COLS;
+    for (int i = lane; i < entries; i += 64) {
+        s_head[i] = g_head[i];
+        s_cnt[i] = g_cnt[i];
+    }
+    __syncthreads();
+    const int lo = slot_base - window > 0 ? slot_base - window : 0;              // the first slot whose smoothed rows this call emits
+
+    // the smoothed rows of slot t, the newest slot in the ring being `newest`: t - window .. min(t + window, newest) are all in the ring
+    auto emit = [&](int t, int newest) {
+        const int first = t - window > 0 ? t - window : 0;
+        const int last = window >= newest - t ? newest : t + window;
+        for (int a = 0; a < A; ++a) {
+            const int h = s_head[(t % H) * A + a];
+            double sum = 0.0;
+            int n = 1;
+            if (h >= 0) {
+                n = 0;
+                for (int u = first; u <= last; ++u) {
+                    const int e = u % H;
+                    const int j = tstream_member(s_head, e, A, h, lane);
+                    if (j < 0) continue;
+                    ++n;
+                    if (live) sum += (double)g_act[(long)(e * A + j) * TSTREAM_COLS + lane];
+                }
+            }
+            if (live) smooth[((long)(t - lo) * A + a) * C + c] = h >= 0 ? sum / (double)n : 0.0;      // n >= 1: the row itself
+        }
+    };
+
+    for (int sl = 0; sl < S; ++sl) {
+        const int s = slot_base + sl, e = s % H;
+        __syncthreads();                                                          // the lookups of the slot before are done with entry e
+        if (lane < A) {
+            int h = row_head[sl * A + lane];
+            if (h < 0 || h > s * A + lane) h = -1;                                // a head is its track's first row
+            s_head[e * A + lane] = h;
+            s_cnt[e * A + lane] = 0;
+        }
+        __syncthreads();
+        for (int a = 0; a < A; ++a) {
+            const int h = s_head[e * A + a];
+            const long r = (long)sl * A + a;
+            const long at = (long)(e * A + a) * TSTREAM_COLS + lane;
+            if (h < 0) {
+                if (live) {
+                    row_mean[r * C + c] = 0.0;
+                    row_peak[r * C + c] = 0.f;
+                }
+                continue;
+            }
+            int pe = -1, pa = -1;                                                 // the predecessor: the same head at most max_gap + 1 slots back
+            for (int t = s - 1; t >= 0 && t >= s - max_gap - 1; --t) {
+                pa = tstream_member(s_head, t % H, A, h, lane);
+                if (pa >= 0) { pe = t % H; break; }
+            }
+            int len = 1;
+            if (pe >= 0) len = s_cnt[pe * A + pa] + 1;
+            if (lane == a) s_cnt[e * A + a] = len;                                // read at later slots only: a barrier lies in between
+            if (live) {
+                const float v = actions[r * C + c];
+                double tot = 0.0;
+                float peak = 0.f;
+                if (pe >= 0) {
+                    const long from = (long)(pe * A + pa) * TSTREAM_COLS + lane;
+                    tot = g_sum[from];
+                    peak = g_peak[from];
+                }
+                tot += (double)v;
+                if (len == 1) peak = v;
+                else if (peak == peak && (v != v || v > peak)) peak = v;          // np.max: a NaN stays
+                g_sum[at] = tot;
+                g_peak[at] = peak;
+                g_act[at] = v;
+                row_mean[r * C + c] = tot / (double)len;
+                row_peak[r * C + c] = peak;
+            }
+        }
+        __syncthreads();
+        if (lane < A) {
+            g_head[e * A + lane] = s_head[e * A + lane];
+            g_cnt[e * A + lane] = s_cnt[e * A + lane];
+        }
+        if (s - window >= 0) emit(s - window, s);                                 // slot s - window has its whole window now
+    }
+    if (flush) {                                                                  // the end of the video: the last slots take what is there
+        const int end = slot_base + S;
+        for (int t = end - window > lo ? end - window : lo; t < end; ++t) emit(t, end - 1);
+    }
+}
+
 extern "C" {
+
+// tuber_track_actions for ONE video whose key frames arrive in pieces (evaluation.ActorTracker: the definition; video.VideoStream(actors=A)).
+// This call takes the S new slots slot_base .. slot_base + S - 1 of A rows each: actions [S * A][C] fp32 and row_head [S * A] as
+// tuber_tube_link_stream wrote it for the same slots with C = 1, K = A and the same slot_base.  Out: row_mean [S * A][C] fp64 / row_peak
+// [S * A][C] fp32, the track's running mean and maximum after taking the row, and smooth [(hi - lo) * A][C] fp64, the smoothed rows of the slots
+// lo = max(slot_base - window, 0) .. hi = flush ? slot_base + S : max(slot_base + S - window, lo) (evaluation.smooth_range); zeros at rows with
+// head -1.  state: caller-owned, tuber_track_stream_state_bytes(A, C, max_gap, window) bytes, 16-byte aligned, all zero = a new video; every
+// slot writes its ring entry and the kernel knows slot_base, so an entry of an ordinal below 0 or not yet pushed is never consulted.  Refused
+// (TUBER_EINVAL, nothing launched, the state untouched, nothing written): A, C or window beyond tuber_track_stream_limits, A * (max_gap + 1)
+// beyond tuber_tube_link_max_active(), (slot_base + S) * A beyond an int32, bad sizes, a null or misaligned pointer, negative arguments.
+// S == 0 without flush: TUBER_OK, no launch; with flush: the last min(window, slot_base) slots.
+int tuber_track_actions_stream(const float* actions, const int* row_head, int S, int A, int C, int slot_base, int max_gap, int window, int flush,
+                               void* state, double* row_mean, float* row_peak, double* smooth, hipStream_t stream) {
+    if (S < 0 || A < 1 || C < 1 || slot_base < 0 || max_gap < 0 || window < 0 || flush < 0) return TUBER_EINVAL;
+    if (A > TUBE_MAX_ACTIVE || C > TRACK_MAX_C || window > TSTREAM_MAX_WINDOW) return TUBER_EINVAL;
+    if ((long)A * ((long)max_gap + 1) > TUBE_MAX_ACTIVE || ((long)slot_base + S) * A > 0x7FFFFFFFl) return TUBER_EINVAL;
+    const int H = tstream_slots(max_gap, window);
+    if ((long)H * A > TSTREAM_MAX_ENTRIES) return TUBER_EINVAL;                   // cannot happen within the bounds above
+    if (!state || ((uintptr_t)state & 15)) return TUBER_EINVAL;
+    const long lo = slot_base - window > 0 ? slot_base - window : 0;
+    const long end = (long)slot_base + S;
+    const long hi = flush ? end : (end - window > lo ? end - window : lo);
+    if (S > 0 && (!actions || !row_head || !row_mean || !row_peak)) return TUBER_EINVAL;
+    if (hi > lo && !smooth) return TUBER_EINVAL;
+    if (S == 0 && hi == lo) return TUBER_OK;                                      // nothing to take and nothing to emit
+    hipLaunchKernelGGL(track_actions_stream_kernel, dim3((unsigned)((C + TSTREAM_COLS - 1) / TSTREAM_COLS)), dim3(64), 0, stream, actions, row_head, S,
+                       A, C, slot_base, max_gap, window, flush ? 1 : 0, H, (unsigned char*)state, row_mean, row_peak, smooth);
+    TUBER_RETURN_LAUNCH();
+}
+// bytes of the state of tuber_track_actions_stream: per 64 classes H * A head and count records and H * A * 64 (fp64 sum, fp32 peak, fp32
+// action) columns, H = max(2 * window, max_gap + 1) + 1; 0 for arguments outside the bounds
+long tuber_track_stream_state_bytes(int A, int C, int max_gap, int window) {
+    if (A < 1 || C < 1 || max_gap < 0 || window < 0 || A > TUBE_MAX_ACTIVE || C > TRACK_MAX_C || window > TSTREAM_MAX_WINDOW) return 0;
+    if ((long)A * ((long)max_gap + 1) > TUBE_MAX_ACTIVE) return 0;
+    const long entries = (long)tstream_slots(max_gap, window) * A;
+    if (entries > TSTREAM_MAX_ENTRIES) return 0;
+    return (long)((C + TSTREAM_COLS - 1) / TSTREAM_COLS) * tstream_wave_bytes((int)entries);
+}
+// the bounds of tuber_track_actions_stream: which = 0 the largest A, 1 the largest C, 2 the largest window; anything else -1
+int tuber_track_stream_limits(int which) {
+    return which == 0 ? TUBE_MAX_ACTIVE : which == 1 ? TRACK_MAX_C : which == 2 ? TSTREAM_MAX_WINDOW : -1;
+}
 
 // Per-track and temporally smoothed action scores of linked actor rows (evaluation.actor_tracks: the definition).  actions [S * A][C] fp32, row
 // r = slot * A + a; row_head [S * A] / tube_last [S * A] as tuber_tube_link_ranked wrote them for this ONE video with class_num = 1.  Out:

@@ -651,6 +651,132 @@ class TubeLinker:
         return dict(row_head=head, row_score=rscore, row_len=rlen)
 
 
+def smooth_range(base, n, window, flush=False):
+    """``[lo, hi)``: the key-frame slots whose smoothed rows a push of the slots ``[base, base + n)`` emits.  A smoothed
+    row looks ``window`` slots ahead, so it is emitted ``window`` slots late: ``lo = max(base - window, 0)``; ``hi = base + n`` when ``flush``
+    (the end of the video: what is there is all there will be), else ``max(base + n - window, lo)``.  Over the pushes of a video the ranges
+    partition ``[0, S)`` in order.  Host integer arithmetic: ``video.VideoStream`` sizes its buffers with it and synchronises nowhere."""
+    base, n, window = int(base), int(n), int(window)
+    if base < 0 or n < 0 or window < 0:
+        raise ValueError("smooth_range: base = %d, n = %d, window = %d must be >= 0" % (base, n, window))
+    lo = max(base - window, 0)
+    return lo, (base + n if flush else max(base + n - window, lo))
+
+
+def track_ring_slots(max_gap, window):
+    """H, the key-frame slots an ``ActorTracker`` (and ``tuber_track_actions_stream``) keeps between pushes: ``max(2 * window, max_gap + 1) + 1``.
+    A new row looks for its predecessor at most ``max_gap + 1`` slots back; the smoothed slot ``t`` is emitted when slot ``t + window`` has
+    arrived and reads back to ``t - window``: 2 * window + 1 slots, the newest one included."""
+    return max(2 * int(window), int(max_gap) + 1) + 1
+
+
+class ActorTracker:
+    """``actor_tracks`` for ONE video whose key frames arrive in pieces: the definition of ``tuber_track_actions_stream``
+    and the fallback of ``video.VideoStream(..., actors=A)`` beyond its bounds.
+
+    ``push(box, actor, queries, actions, A, flush=False)`` takes the next ``n = len(queries) // A`` slots of a padded [n][A] actor store
+    (``actor_tracks``' layout) and returns, per new row, ``row_head`` / ``row_score`` / ``row_len`` -- exactly
+    ``TubeLinker(1, link_iou, max_gap).push(box, where(queries >= 0, 0, -1), actor, A)``, heads being global rows ``ordinal * A + position``
+    -- and ``row_mean`` [n * A, C] fp64 / ``row_peak`` [n * A, C] fp32: the track's running mean (the fp64 sum of ``float64(actions)`` over the
+    track's rows so far, in slot order, divided by their count) and running maximum (``np.max``: a NaN stays) after taking the row; zeros at
+    rows with head -1.  At a track's last row they are ``actor_tracks``' ``track_mean`` / ``track_peak`` bit for bit.
+
+    ``smooth`` [(hi - lo) * A, C] fp64 with ``smooth_lo`` / ``smooth_hi`` = ``smooth_range(base, n, window, flush)``: ``actor_tracks``'
+    ``row_smooth`` of the slots ``[lo, hi)``, emitted ``window`` slots late because it is centred -- per row the fp64 sum, in slot order, over
+    the members of its track at the slots ``[t - window, min(t + window, newest)]`` divided by their number.  ``flush=True`` marks the end of
+    the video (a push without rows is legal then); ``reset()`` starts a new video.
+
+    Between pushes the tracker keeps the last H = ``track_ring_slots(max_gap, window)`` slots in a ring, entry ``ordinal % H``: per row the head,
+    the count, the running fp64 sum, the fp32 peak and the fp32 action row.  Every pushed slot, an empty one included, writes its entry, so an
+    entry of an ordinal below 0 or not yet pushed is never consulted."""
+
+    def __init__(self, link_iou, max_gap, window):
+        self.link_iou, self.max_gap, self.window = float(link_iou), int(max_gap), int(window)
+        if self.max_gap < 0 or self.window < 0:
+            raise ValueError("ActorTracker: max_gap = %d and window = %d must be >= 0" % (self.max_gap, self.window))
+        self.H = track_ring_slots(self.max_gap, self.window)
+        self.linker = TubeLinker(1, self.link_iou, self.max_gap)
+        self.reset()
+
+    def reset(self):
+        """the next push is slot 0 of a new video"""
+        self.linker.reset()
+        self.slots, self.A, self.C = 0, None, None
+        self._head = self._cnt = self._sum = self._peak = self._act = None
+
+    def _member(self, t, h):
+        """the position in slot t of the row whose head is h, -1 when the slot has none"""
+        hit = np.nonzero(self._head[t % self.H] == h)[0]
+        return int(hit[0]) if len(hit) else -1
+
+    def _smooth_slot(self, t, newest, out):
+        """the smoothed rows of slot t into ``out`` [A, C], the newest slot pushed being ``newest``"""
+        w, H = self.window, self.H
+        for a in range(self.A):
+            h = int(self._head[t % H, a])
+            if h < 0:
+                continue
+            acc, n = np.zeros(self.C), 0
+            for u in range(max(t - w, 0), min(t + w, newest) + 1):
+                j = self._member(u, h)
+                if j >= 0:
+                    acc = acc + self._act[u % H, j].astype(np.float64)
+                    n += 1
+            out[a] = acc / n
+
+    def push(self, box, actor, queries, actions, A, flush=False):
+        A = int(A)
+        queries = np.asarray(queries).reshape(-1)
+        N = len(queries)
+        if A < 1 or N % A:
+            raise ValueError("ActorTracker.push: %d rows in slots of %d" % (N, A))
+        actions = np.asarray(actions, dtype=np.float32)
+        actions = actions.reshape(N, -1) if N else actions.reshape(0, self.C or 0)
+        C = actions.shape[1] if N else (self.C or 0)
+        if self.A is None and N:
+            self.A, self.C, H = A, C, self.H
+            self._head = np.full((H, A), -1, dtype=np.int64)
+            self._cnt = np.zeros((H, A), dtype=np.int64)
+            self._sum, self._peak, self._act = np.zeros((H, A, C)), np.zeros((H, A, C), dtype=np.float32), np.zeros((H, A, C), dtype=np.float32)
+        elif N and (A, C) != (self.A, self.C):
+            raise ValueError("ActorTracker.push: slots of %d rows with %d classes after %d with %d" % (A, C, self.A, self.C))
+        n, base, w, H = N // A, self.slots, self.window, self.H
+        link = self.linker.push(box, np.where(queries >= 0, 0, -1), np.asarray(actor, dtype=np.float32).reshape(-1), A) if N else dict(
+            row_head=np.zeros(0, dtype=np.int64), row_score=np.zeros(0), row_len=np.zeros(0, dtype=np.int64))
+        lo, hi = smooth_range(base, n, w, flush)
+        mean, peak = np.zeros((N, C)), np.zeros((N, C), dtype=np.float32)
+        smooth = np.zeros(((hi - lo) * A, C))
+        for i in range(n):
+            s, e = base + i, (base + i) % H
+            self._head[e] = link["row_head"][i * A:(i + 1) * A]      # the entry of slot s - H goes: nothing looks that far back
+            self._cnt[e] = 0
+            for a in range(A):
+                h, r = int(self._head[e, a]), i * A + a
+                if h < 0:
+                    self._sum[e, a], self._peak[e, a], self._act[e, a] = 0.0, 0.0, 0.0
+                    continue
+                v = actions[r]
+                cnt, acc, top = 1, np.zeros(C) + v.astype(np.float64), v.copy()
+                for t in range(s - 1, max(s - self.max_gap - 1, 0) - 1, -1):      # the predecessor: the same head at most max_gap + 1 slots back
+                    j = self._member(t, h)
+                    if j >= 0:
+                        cnt = int(self._cnt[t % H, j]) + 1
+                        acc = self._sum[t % H, j] + v.astype(np.float64)
+                        with np.errstate(invalid="ignore"):
+                            top = np.max(np.stack([self._peak[t % H, j], v]), axis=0)
+                        break
+                self._cnt[e, a], self._sum[e, a], self._peak[e, a], self._act[e, a] = cnt, acc, top, v
+                mean[r], peak[r] = acc / cnt, top
+            if s - w >= 0:                                            # slot s - window has its whole window now
+                self._smooth_slot(s - w, s, smooth[(s - w - lo) * A:(s - w - lo + 1) * A])
+        self.slots = base + n
+        if flush:                                                     # the end: the last slots take what is there
+            for t in range(max(self.slots - w, lo), self.slots):
+                self._smooth_slot(t, self.slots - 1, smooth[(t - lo) * A:(t - lo + 1) * A])
+        return dict(row_head=link["row_head"], row_score=link["row_score"], row_len=link["row_len"], row_mean=mean, row_peak=peak, smooth=smooth,
+                    smooth_lo=lo, smooth_hi=hi)
+
+
 class VideoMAP:
     """Video-level mean average precision over action tubes: per (video, class) the per-frame detections are linked greedily into tubes
     (``link``), the tubes are matched against the ground-truth tubes by spatio-temporal IoU (``match``), and the ranked flags give VOC AP per

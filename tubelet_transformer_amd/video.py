@@ -10,7 +10,9 @@ linker in its ranked form (``tuber_tube_link_ranked``, csrc/tube_map.hip; ``eval
 ``VideoStream`` is the same computation for a video that arrives in pieces: a ring of the last R frames instead of the
 resident video (``tuber_video_clips_ring`` evaluates the index rule itself), the same batches of key frames as soon as their clips can no longer
 change, and the linker resumed push by push (``tuber_tube_link_stream``; ``evaluation.TubeLinker`` is its definition and its fallback).
-``VideoDetector`` is the definition the stream is held to.
+``VideoDetector`` is the definition the stream is held to.  With ``actors=A`` the stream carries the actor tracks of section 6i as well
+(DESIGN.md section 6j): per-track action sums resumed push by push (``tuber_track_actions_stream``; ``evaluation.ActorTracker`` is its
+definition and its fallback) and ``VideoStream.tracks()``.
 """
 import functools
 import sys
@@ -196,6 +198,9 @@ class VideoActors:
         self.settings = dict(settings or dict(link_iou=0.2, max_gap=2, min_len=1, window=1, label_thr=0.05))
         self.tracks_path = None                                                        # "device" or "host" after tracks()
         self._store = store
+        # the track records of a VideoStream(actors=A) push: row_head / row_score / row_len [n, A], row_mean / row_peak [n, A, C], smooth [m, A, C]
+        self.row_head = self.row_score = self.row_len = self.row_mean = self.row_peak = self.smooth = None
+        self.smooth_first = None                                                       # the key ordinal of smooth's first slot (a host int)
         if not (len(self.keys) == boxes.shape[0] == actor.shape[0] == actions.shape[0] == count.shape[0]):
             raise ValueError("VideoActors: %d keys, %d rows" % (len(self.keys), boxes.shape[0]))
 
@@ -532,20 +537,37 @@ class VideoStream:
 
     Device memory does not grow with the video: the ring, (R + 1) * nh * nw * 3 bytes; the link state, ``tuber_tube_link_state_bytes(C)`` =
     2560 * C bytes; one batch of clips; and the ``VideoDetections`` of the pushes since the last ``tubes()`` call (``link=False``: none are
-    kept).  ``rule`` / ``topk`` / ``score_thr`` / ``actor_thr`` / ``graphed`` / ``stride``: as ``VideoDetector``."""
+    kept).  ``rule`` / ``topk`` / ``score_thr`` / ``actor_thr`` / ``graphed`` / ``stride``: as ``VideoDetector``.
+
+    ``actors=A`` (AVA models, ``link=True``; default None: off): ``VideoDetector(..., actors=A)`` for the stream.  The
+    ``VideoDetections`` of a push carries ``.actors``, the ``VideoActors`` of the decided keys -- ``VideoDetector``'s rows bit for bit -- and on
+    it, as device tensors, ``row_head`` / ``row_score`` / ``row_len`` [n, A] (the actors' own ``tuber_tube_link_stream`` call with one class),
+    ``row_mean`` [n, A, C] fp64 / ``row_peak`` [n, A, C] fp32 (what the row's track has been doing SO FAR: its running mean and maximum) and
+    ``smooth`` [m, A, C] fp64 with ``smooth_first``, the key ordinal of its first slot: ``actor_tracks``' ``row_smooth``, which looks
+    ``window`` keys ahead and therefore comes ``window`` keys late (``evaluation.smooth_range``; ``finish()`` flushes, and returns a
+    ``VideoDetections`` without keys when only smoothed rows were left) -- one ``tuber_track_actions_stream`` call per push.  ``tracks()``
+    returns the actor tracks that closed since the last call.  The stream then also holds the actors' link state (2560 bytes) and the track
+    ring (``tuber_track_stream_state_bytes``); beyond the kernel's bounds ``evaluation.ActorTracker`` answers on the host, one line says so,
+    and ``tracks_path`` is "host" instead of "device"."""
 
     def __init__(self, cfg, model, batch=2, stride=None, rule=None, max_chunk=64, score_thr=None, topk=None, actor_thr=None, graphed=True,
-                 link=True):
-        from .config import detect_settings, video_map_settings
+                 link=True, actors=None):
+        from .config import actor_settings, detect_settings, video_map_settings
         self.cfg, self.model = cfg, model
         self.batch, self.max_chunk, self.link = int(batch), int(max_chunk), bool(link)
         if self.batch < 1 or self.max_chunk < 1:
             raise ValueError("VideoStream: batch = %r and max_chunk = %r must be >= 1" % (batch, max_chunk))
+        if actors is not None and not self.link:
+            raise ValueError("VideoStream: actors = %r needs link=True: the actor tracks are link records" % (actors,))
         vm = video_map_settings(cfg)
         self.settings = dict(link_iou=float(vm["link_iou"]), max_gap=int(vm["max_gap"]), min_len=int(vm["min_len"]))
         if topk is None:
             topk = max(1, min(detect_settings(cfg)["topk"], lib.query("tuber_tube_link_max_active") // (self.settings["max_gap"] + 1)))
-        self.detector = Detector(cfg, model, score_thr=score_thr, topk=topk, actor_thr=actor_thr, graphed=graphed)
+        self.detector = Detector(cfg, model, score_thr=score_thr, topk=topk, actor_thr=actor_thr, graphed=graphed, actors=actors)
+        self.actor_settings = None
+        if actors is not None:
+            st = actor_settings(cfg)
+            self.actor_settings = {k: st[k] for k in ("link_iou", "max_gap", "min_len", "window", "label_thr")}
         self.mode = model.dataset_mode
         self.rule = rule if rule is not None else ("ava" if self.mode == "ava" else "jhmdb")
         if self.rule not in RULES:
@@ -568,6 +590,19 @@ class VideoStream:
         self.wrapped = False               # whether a ring slot has been overwritten in the current video
         self._pending = []                 # link records since the last tubes() call; None marks the end of a video
         self._open = {}                    # head -> the rows of an open tube, on the host
+        # actor tracks (actors=A): their own pending list and their own open rows; tubes() and tracks() consume neither the other's
+        self.tracks_path = None            # "device" or "host" once a push has decided keys
+        self._why_host_tracks, self._host_tracker, self._said_tracks = None, None, False
+        self._pending_tracks, self._assembler = [], None
+        self._video_keys = 0               # keys decided in the current video
+        if actors is not None:
+            A, st = self.detector.actors, self.actor_settings
+            self._assembler = TrackAssembler(A, st["max_gap"], st["window"], st["min_len"], st["label_thr"])
+            self._track_bytes = lib.query("tuber_track_stream_state_bytes", A, self.class_num, st["max_gap"], st["window"])
+            if A > lib.query("tuber_frame_match_max_dets") or not self._track_bytes:
+                self._why_host_tracks = "%d actors per key frame with max_gap %d, window %d and %d classes: beyond %d rows, %d active tracks, window %d or %d classes" % (
+                    A, st["max_gap"], st["window"], self.class_num, min(lib.query("tuber_frame_match_max_dets"), lib.query("tuber_track_stream_limits", 0)),
+                    lib.query("tuber_tube_link_max_active"), lib.query("tuber_track_stream_limits", 2), lib.query("tuber_track_stream_limits", 1))
 
     # -- buffers ----------------------------------------------------------------------------------------------------------
     def _buffers(self, dev, H0, W0):
@@ -587,13 +622,17 @@ class VideoStream:
                 b["coeffs"] = ip._device_coeffs(dev, H0, W0, nh, nw)
                 rows = b["coeffs"][4]
                 b["tmp"] = torch.empty(self.max_chunk * rows * nw * 3, dtype=torch.uint8, device=dev) if (nw != W0 and nh != H0) else None
+            if self.detector.actors is not None and self._why_host_tracks is None:      # the actors' own link state (one class) and the track ring
+                b["actor_state"] = torch.zeros(lib.query("tuber_tube_link_state_bytes", 1), dtype=torch.uint8, device=dev)
+                b["track_state"] = torch.zeros(self._track_bytes, dtype=torch.uint8, device=dev)
             self._bufs[key] = b
         return b
 
     def device_bytes(self):
-        """bytes of the current video size's ring and link state: what the stream holds instead of the resident video"""
+        """bytes of the current video size's ring and link state -- with ``actors``, of the actors' link state and the track ring as well: what the
+        stream holds instead of the resident video"""
         b = self._cur
-        return 0 if b is None else b["ring"].numel() + b["state"].numel()
+        return 0 if b is None else b["ring"].numel() + b["state"].numel() + sum(b[k].numel() for k in ("actor_state", "track_state") if k in b)
 
     def _store_frames(self, b, src, first):
         """frames ``first .. first + len(src) - 1`` into their ring slots: a run that crosses the ring's end is two calls"""
@@ -613,25 +652,72 @@ class VideoStream:
         self.wrapped = self.wrapped or first + m > R
 
     # -- key frames -------------------------------------------------------------------------------------------------------
-    def _run(self, b, full, row, first_ord, n_keys, n_total):
-        """one batch: the keys ``first_ord .. first_ord + n_keys - 1`` (the last one repeated up to ``batch``) into rows ``row ..`` of ``full``"""
+    def _run(self, b, full, row, first_ord, n_keys, n_total, full_a=None):
+        """one batch: the keys ``first_ord .. first_ord + n_keys - 1`` (the last one repeated up to ``batch``) into rows ``row ..`` of ``full``
+        (and of ``full_a``: the six actor fields)"""
         B = self.batch
         lib.call("tuber_video_clips_ring", b["ring"], self.R, b["nh"], b["nw"], first_ord * self.stride, self.stride, n_keys, B, self.T, self.rate,
                  RULES.index(self.rule), n_total, *b["window"], b["lut"], b["clips"])
         det = self.detector(NestedTensor(b["clips"], b["mask"]), b["sizes"], b["key_pos"])
         for dst, src in zip(full, det.tensors()):
             dst[row:row + B].copy_(src)
+        if full_a is not None:
+            for dst, src in zip(full_a, det.actors.tensors()):
+                dst[row:row + B].copy_(src)
 
-    def _result(self, b, full, first_ord, n, store):
-        """the ``VideoDetections`` of the keys ``first_ord .. first_ord + n - 1`` in the first n rows of ``full``, linked"""
-        if n == 0:
-            return None
+    def _result(self, b, full, first_ord, n, store, full_a=None, flush=False):
+        """the ``VideoDetections`` of the keys ``first_ord .. first_ord + n - 1`` in the first n rows of ``full``, linked; with ``full_a`` its
+        ``.actors`` as well, tracked (``flush``: these are the video's last keys)"""
+        if n == 0 and not (full_a is not None and flush and self._video_keys and self.actor_settings["window"]):
+            return None                    # (with actors, a finish() that runs no key still emits the smoothed rows that waited for it)
         vd = VideoDetections([(first_ord + i) * self.stride for i in range(n)], *[t[:n] for t in full], class_num=self.class_num,
                              settings=self.settings, store=store)
-        if self.link:
+        if self.link and n:
             self._link(b, vd, first_ord)
             self._pending.append((first_ord, vd))
+        if full_a is not None:
+            vd.actors = VideoActors(vd.keys, *[t[:n] for t in full_a], settings=self.actor_settings, store=store)
+            self._track(b, vd.actors, first_ord, flush)
+            self._pending_tracks.append((first_ord, vd.actors))
+            self._video_keys += n
         return vd
+
+    def _track(self, b, va, first_ord, flush):
+        """the track records of the keys ``first_ord ..`` onto ``va``: ``tuber_tube_link_stream`` with one class, the label derived from
+        ``queries`` on the device, then ``tuber_track_actions_stream``; ``evaluation.ActorTracker`` on the host beyond their bounds"""
+        from .evaluation import ActorTracker, smooth_range
+        n, A, C = va.actions.shape
+        st, dev = self.actor_settings, va.actions.device
+        if (first_ord + n) * A > 0x7FFFFFFF:
+            raise RuntimeError("VideoStream: key ordinal %d with %d actors per key frame: row numbers beyond 32 bits" % (first_ord + n, A))
+        lo, hi = smooth_range(first_ord, n, st["window"], flush)
+        va.smooth_first = lo
+        f64, i32 = torch.float64, torch.int32
+        if self._why_host_tracks is None:
+            self.tracks_path = "device"
+            va.row_head, va.row_score, va.row_len = torch.empty(n, A, dtype=i32, device=dev), torch.empty(n, A, dtype=f64, device=dev), torch.empty(n, A, dtype=i32, device=dev)
+            va.row_mean, va.row_peak = torch.empty(n, A, C, dtype=f64, device=dev), torch.empty(n, A, C, dtype=torch.float32, device=dev)
+            va.smooth = torch.empty(hi - lo, A, C, dtype=f64, device=dev)
+            if n:
+                label = torch.where(va.queries >= 0, 0, -1).to(i32).contiguous()         # one class; a row behind its key's count is not counted
+                lib.call("tuber_tube_link_stream", va.boxes.contiguous(), label, va.actor.contiguous(), n, A, first_ord, 1, st["link_iou"], st["max_gap"],
+                         b["actor_state"], va.row_head, va.row_score, va.row_len)
+            lib.call("tuber_track_actions_stream", va.actions.contiguous(), va.row_head, n, A, C, first_ord, st["max_gap"], st["window"], 1 if flush else 0,
+                     b["track_state"], va.row_mean, va.row_peak, va.smooth)
+            return
+        if not self._said_tracks:
+            print("[tuber] VideoStream: %s; tracks on the host" % self._why_host_tracks, file=sys.stderr, flush=True)
+            self._said_tracks = True
+        self.tracks_path = "host"
+        if self._host_tracker is None:
+            self._host_tracker = ActorTracker(st["link_iou"], st["max_gap"], st["window"])
+        host = dict(zip(ACTOR_FIELDS, va._fetch()))
+        got = self._host_tracker.push(host["boxes"].reshape(-1, 4), host["actor"].reshape(-1), host["queries"].reshape(-1), host["actions"].reshape(n * A, C), A,
+                                      flush=flush)
+        up = lambda a, dtype, *shape: torch.from_numpy(np.ascontiguousarray(a.astype(dtype))).reshape(*shape).to(dev)
+        va.row_head, va.row_score, va.row_len = up(got["row_head"], np.int32, n, A), up(got["row_score"], np.float64, n, A), up(got["row_len"], np.int32, n, A)
+        va.row_mean, va.row_peak = up(got["row_mean"], np.float64, n, A, C), up(got["row_peak"], np.float32, n, A, C)
+        va.smooth = up(got["smooth"], np.float64, hi - lo, A, C)
 
     def _link(self, b, vd, first_ord):
         n, K = vd.scores.shape
@@ -664,6 +750,14 @@ class VideoStream:
                 torch.empty(rows, K, dtype=i32, device=dev), torch.empty(rows, K, dtype=f32, device=dev), torch.empty(rows, dtype=i32, device=dev),
                 torch.empty(rows, dtype=i32, device=dev)]
 
+    def _empty_actors(self, rows, dev):
+        A = self.detector.actors
+        if A is None:
+            return None
+        f32, i32 = torch.float32, torch.int32
+        return [torch.empty(rows, A, 4, dtype=f32, device=dev), torch.empty(rows, A, dtype=f32, device=dev), torch.empty(rows, A, dtype=i32, device=dev),
+                torch.empty(rows, A, self.class_num, dtype=f32, device=dev), torch.empty(rows, dtype=i32, device=dev), torch.empty(rows, dtype=i32, device=dev)]
+
     @torch.no_grad()
     def push(self, frames):
         if self.model.training:
@@ -687,19 +781,21 @@ class VideoStream:
         plan = sch.push(m)                                      # host integers first: the pieces, and the batches ready after each
         total = sum(len(batches) for _, _, batches in plan)
         full = self._empty(total * B, dev) if total else None
+        full_a = self._empty_actors(total * B, dev) if total else None
         row = 0
         for i, length, batches in plan:
             src = frames[i:i + length].to(dev, non_blocking=True).contiguous()
             self._store_frames(b, src, first_frame + i)
             for k in batches:
-                self._run(b, full, row, k, B, -1)
+                self._run(b, full, row, k, B, -1, full_a)
                 row += B
-        return self._result(b, full, first_ord, row, store)
+        return self._result(b, full, first_ord, row, store, full_a) if row else None
 
     @torch.no_grad()
     def finish(self):
         if self.model.training:
             raise RuntimeError("VideoStream runs an eval forward: call model.eval() first")
+        decided = self.schedule.decided
         n_total, batches = self.schedule.finish()
         self.wrapped = False
         if not n_total:
@@ -708,15 +804,25 @@ class VideoStream:
         store, _ = self.model.engine()
         out = None
         if batches:
-            full = self._empty(len(batches) * B, store.device)
+            full, full_a = self._empty(len(batches) * B, store.device), self._empty_actors(len(batches) * B, store.device)
             for i, (k, n_keys) in enumerate(batches):
-                self._run(b, full, i * B, k, n_keys, n_total)
-            out = self._result(b, full, batches[0][0], batches[-1][0] + batches[-1][1] - batches[0][0], store)
+                self._run(b, full, i * B, k, n_keys, n_total, full_a)
+            out = self._result(b, full, batches[0][0], batches[-1][0] + batches[-1][1] - batches[0][0], store, full_a, flush=True)
+        elif self.detector.actors is not None:                  # no key left to run: the smoothed rows that waited for the end (S = 0, flush)
+            out = self._result(b, self._empty(0, store.device), decided, 0, store, self._empty_actors(0, store.device), flush=True)
         b["state"].zero_()
+        for k in ("actor_state", "track_state"):
+            if k in b:
+                b[k].zero_()
         if self._host_linker is not None:
             self._host_linker.reset()
+        if self._host_tracker is not None:
+            self._host_tracker.reset()
         if self.link:
             self._pending.append(None)
+        if self.detector.actors is not None:
+            self._pending_tracks.append(None)
+            self._video_keys = 0
         return out
 
     # -- tubes ------------------------------------------------------------------------------------------------------------
@@ -763,4 +869,93 @@ class VideoStream:
             next_ord = first_ord + len(vd.keys)
         if next_ord is not None:
             close(False)
+        return out
+
+    # -- actor tracks -----------------------------------------------------------------------------------------------------
+    TRACK_NAMES = ("boxes", "actor", "queries", "actions", "row_head", "row_score", "row_len", "row_mean", "row_peak", "smooth")
+
+    def tracks(self):
+        """The actor tracks (``actors=A``) that CLOSED since the last call: the next key ordinal is more than ``max(max_gap + 1, window)`` past
+        their last one -- no key frame still to come can extend them, and the smoothed row of their last key has been emitted -- and after
+        ``finish()`` all that remain.  ``VideoActors.tracks``' dicts plus ``head`` (key ordinal * A + position of the first row), in head
+        order; ``score`` / ``mean`` / ``peak`` are the records of the track's last row.  One device-to-host copy per call; the rows of open
+        tracks are kept on the host in between (``TrackAssembler``).  ``tubes()`` keeps its own records: neither consumes the other's."""
+        if self._assembler is None:
+            raise RuntimeError("VideoStream without actors=A keeps no actor records: no tracks")
+        pending, self._pending_tracks = self._pending_tracks, []
+        recs = [p for p in pending if p is not None]
+        parts = [getattr(va, k).contiguous() for _, va in recs for k in self.TRACK_NAMES]
+        host, o = [], 0
+        if parts:                                               # one copy for every record
+            blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
+            for t in parts:
+                nbytes = t.numel() * t.element_size()
+                host.append(blob[o:o + nbytes].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape)))
+                o += nbytes
+        out, i, m = [], 0, len(self.TRACK_NAMES)
+        for p in pending:
+            if p is None:                                       # the end of a video: whatever is open closes
+                self._assembler.end()
+                out += self._assembler.take()
+                continue
+            first_ord, va = p
+            self._assembler.add(first_ord, va.keys, *host[m * i:m * i + m], va.smooth_first)
+            i += 1
+        return out + self._assembler.take()
+
+
+class TrackAssembler:
+    """The host side of ``VideoStream.tracks()``: the per-push records of a stream's actors (host arrays) in, closed actor tracks out.
+    ``add(first_ord, keys, boxes, actor, queries, actions, row_head, row_score, row_len, row_mean, row_peak, smooth, smooth_first)`` takes the
+    records of the keys ``first_ord ..`` ([n, A, ...] arrays; ``smooth`` [m, A, C] belongs to the slots ``smooth_first ..``, which lag
+    ``window`` keys behind); ``end()`` marks the end of the video; ``take()`` returns the tracks closed since the last call, in head order: after
+    ``end()`` all of them, before it those whose last key lies more than ``max(max_gap + 1, window)`` ordinals behind the next one.  A track
+    is ``VideoActors.tracks``' dict plus ``head``; tracks shorter than ``min_len`` are dropped."""
+
+    def __init__(self, A, max_gap, window, min_len=1, label_thr=0.05):
+        self.A, self.max_gap, self.window, self.min_len, self.label_thr = int(A), int(max_gap), int(window), int(min_len), float(label_thr)
+        self._open, self._waiting, self._closed, self._next = {}, {}, [], 0
+
+    def add(self, first_ord, keys, boxes, actor, queries, actions, row_head, row_score, row_len, row_mean, row_peak, smooth, smooth_first):
+        head = np.asarray(row_head)
+        for s, a in zip(*np.nonzero(head >= 0)):
+            h, o = int(head[s, a]), int(first_ord) + int(s)
+            t = self._open.get(h)
+            if t is None:
+                t = self._open[h] = dict(frames=[], boxes=[], actor=[], queries=[], actions=[], smooth=[])
+            t["frames"].append(int(keys[s]))
+            for k, src in (("boxes", boxes), ("actor", actor), ("queries", queries), ("actions", actions)):
+                t[k].append(np.array(src[s, a]))
+            t["score"], t["length"], t["last"] = float(row_score[s, a]), int(row_len[s, a]), o
+            t["mean"], t["peak"] = np.array(row_mean[s, a], dtype=np.float64), np.array(row_peak[s, a], dtype=np.float32)
+            self._waiting.setdefault(o, []).append((int(a), h))           # the row's smoothed scores come `window` keys later
+        for j in range(len(smooth)):                                      # slots in order: a track's smoothed rows arrive in slot order
+            for a, h in self._waiting.pop(int(smooth_first) + j, []):
+                self._open[h]["smooth"].append(np.array(smooth[j, a], dtype=np.float64))
+        self._next = int(first_ord) + len(keys)
+        self._close(False)
+
+    def end(self):
+        self._close(True)
+        self._waiting, self._next = {}, 0
+
+    def _close(self, everything):
+        for h in sorted(self._open):
+            t = self._open[h]
+            if not (everything or self._next - t["last"] > max(self.max_gap + 1, self.window)):
+                continue
+            del self._open[h]
+            if t["length"] < self.min_len:
+                continue
+            if len(t["smooth"]) != len(t["frames"]):
+                raise RuntimeError("TrackAssembler: track %d closes with %d of its %d smoothed rows" % (h, len(t["smooth"]), len(t["frames"])))
+            mean = t["mean"]
+            with np.errstate(invalid="ignore"):
+                labels = sorted(np.nonzero(mean >= self.label_thr)[0].tolist(), key=lambda c: (-mean[c], c))
+            self._closed.append(dict(score=t["score"], frames=t["frames"], boxes=np.stack(t["boxes"]), actor=np.stack(t["actor"]),
+                                     queries=np.stack(t["queries"]), actions=np.stack(t["actions"]), smooth=np.stack(t["smooth"]), mean=mean,
+                                     peak=t["peak"], labels=labels, length=t["length"], head=h))
+
+    def take(self):
+        out, self._closed = sorted(self._closed, key=lambda t: t["head"]), []
         return out
