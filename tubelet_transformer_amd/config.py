@@ -167,6 +167,10 @@ def get_cfg_defaults():
         # its track at most WINDOW key frames away, a track labelled with the classes whose mean score is at least LABEL_THR.  None: TOPK =
         # min(MODEL.QUERY_NUM, 64 active tubes // (MAX_GAP + 1)), LINK_IOU / MAX_GAP / MIN_LEN = VIDEO_MAP's, LABEL_THR = DETECT.SCORE_THR
         ACTORS=dict(TOPK=None, LINK_IOU=None, MAX_GAP=None, MIN_LEN=None, WINDOW=1, LABEL_THR=None),
+        # spatio-temporal NMS over linked tubes (evaluation.tube_nms / tuber_tube_nms; not reference keys): per (video, class) a tube whose
+        # spatio-temporal IoU with a higher-scored kept tube exceeds IOU is dropped -- before video-mAP in validate_tuber_ucf_detection and in
+        # video.VideoDetections.tubes(); ACTORS_IOU: the same, class-agnostic, for video.VideoActors.tracks().  None: off.  0.3 is customary
+        TUBE_NMS=dict(IOU=None, ACTORS_IOU=None),
         # both validation loops run the eval forward as a captured hipGraph per input shape (detect.GraphedEval; not a reference key)
         GRAPHED=False), new_allowed=True)
     cfg.DATA = CfgNode(dict(
@@ -214,6 +218,18 @@ def video_map_settings(cfg):
         bad("THRESHOLDS", "entries must be distinct")
     return dict(link_iou=float(vm.LINK_IOU), max_gap=int(vm.MAX_GAP), min_len=int(vm.MIN_LEN),
                 thresholds=tuple(t if t == "0.5:0.95" else float(t) for t in thr))
+
+
+def tube_nms_settings(cfg):
+    """CONFIG.VAL.TUBE_NMS validated -> dict(iou, actors_iou), each None (off) or a float in [0, 1]; a bad value raises ValueError naming its key"""
+    t = cfg.CONFIG.VAL.TUBE_NMS
+    out = {}
+    for key in ("IOU", "ACTORS_IOU"):
+        v = t[key]
+        if v is not None and (not isinstance(v, (int, float)) or isinstance(v, bool) or v != v or not 0.0 <= v <= 1.0):
+            raise ValueError("CONFIG.VAL.TUBE_NMS.%s = %r: must be None or a number in [0, 1]" % (key, v))
+        out[key.lower()] = None if v is None else float(v)
+    return out
 
 
 def detect_settings(cfg):

@@ -380,6 +380,20 @@ DOC = {
                         "double[N * max(max_gt_tubes, 1)]. max_rows / max_gt_rows / max_gt_tubes: largest rows and ground-truth rows per slot, ground-truth tubes per (video, "
                         "class). T > tuber_tube_match_max_thresholds(), max_gt_tubes > tuber_tube_match_max_gt(), max_rows > tuber_frame_match_max_dets(), max_gt_rows > "
                         "tuber_frame_match_max_gt(), bad sizes or pointers: negative, nothing launched. One wave per (video, class), sums in slot order: the same bits every run.",
+    "tuber_tube_nms": "spatio-temporal tube NMS on the device (evaluation.tube_nms: the definition; the 3-D NMS the ACT-detector protocol runs over the tubes of a "
+                      "(video, class) before video-mAP): the tuber_tube_link / tuber_tube_link_ranked outputs as tuber_tube_match reads them -- the validation store in "
+                      "layout order, or a padded [S][K] store with slot_off = arange(S + 1) * K and V = 1. stIoU(d, e) = sum over the slots both tubes have a row in, "
+                      "ascending, of the fp64 IoU of the two fp32 boxes / |slots of d or e|, 0 without a shared slot. Per (video, class) the tubes of at least min_len "
+                      "detections are visited by descending score (NaN last, equal scores by ascending head); a tube is suppressed iff its stIoU with a tube KEPT "
+                      "before it is > nms_iou (strictly), so a suppressed tube suppresses nothing. tube_keep [N] bytes: 1 kept head, 0 suppressed head, 2 not a head "
+                      "or shorter than min_len, 3 at the heads of a (video, class) in which more than tuber_tube_link_max_active() tubes are live (head <= slot <= "
+                      "tube_last) at one slot: nothing decided there. A row whose row_head lies outside [first row of its video, the row] or is no head row of the "
+                      "row's class is not counted. work: caller-owned, tuber_tube_nms_work_bytes(N) bytes, 16-byte aligned. One wave per (video, class): the live "
+                      "tubes in lanes, the pair sums in a [64][64] LDS table accumulated in slot order, a pair recorded when the first of its tubes ends, then the "
+                      "greedy pass; no atomics on floating-point data, plain vector stores, the same bits every run. max_rows > tuber_frame_match_max_dets(), "
+                      "min_len < 1, nms_iou NaN or outside [0, 1], N > S * max_rows, negative sizes, a null pointer or a misaligned work: negative, nothing launched, "
+                      "nothing written. N == 0 or V == 0: 0, nothing written.",
+    "tuber_tube_nms_work_bytes": "bytes of the scratch of tuber_tube_nms for N rows: 64 partner heads and one status word (int32) per row, rounded up to 16; 0 for N <= 0.",
     "tuber_tube_match_max_gt": "ground-truth tubes per (video, class) tuber_tube_match takes (32).",
     "tuber_tube_match_max_thresholds": "thresholds per call tuber_tube_match takes (16).",
     "tuber_detect_ava": "ranked detections of an AVA eval forward in ONE launch (PostProcessAVA, models/criterion.py:447-482, the post-processor models/tuber_ava.py builds; "

@@ -13,6 +13,9 @@
 //   3. track_actions_kernel (tuber_track_actions, actor tracks of an AVA video): behind tube_link_kernel run with one class over a [S][A] actor store, a
 //                           workgroup per row averages the action rows of the row's track -- over the whole track at its head, over a window of slots
 //                           at every row -- in fp64, sequentially in slot order.
+//   4. tube_nms_kernel      (tuber_tube_nms, evaluation.tube_nms: the definition) between steps 1 and 2, or behind step 1 over a padded store: a wave
+//                           per (video, class) adds the per-slot IoU of every two live tubes into a [64][64] table, records the pairs above the
+//                           threshold when the first of the two ends, and visits the tubes by descending score: suppressed iff a kept one overlaps.
 // No floating-point atomics, every sum sequential in slot order: the same input gives the same bits.
 #include "map_common.h"
 
@@ -346,6 +349,160 @@ __global__ __launch_bounds__(64) void tube_match_kernel(const float* __restrict_
             if (tp) taken |= 1u << bk;
             tube_flag[(long)lane * N + h] = tp ? 1 : 0;
         }
+    }
+}
+
+// Spatio-temporal NMS over the linked tubes (evaluation.tube_nms: the definition; tuber_tube_nms).  A wave per (video, class), tube_match_kernel's
+// tube-against-tube twin.  Phase 1 walks the slots with the live tubes in lanes and adds, per slot, the fp64 IoU of every two rows of the class
+// into a [64][64] table (tube lane x tube lane; a row's lane writes only its own table row); when a tube ends, every pair it forms with a
+// tube that is still live is final, and its lane writes the heads of the partners whose stIoU is above nms_iou into its 64-entry row of
+// `work`.  A pair is thus recorded in the row of the tube that ends first, or in both rows.  Phase 2 visits the tubes of at least min_len
+// detections by descending score (equal scores by ascending head): a tube is suppressed iff a kept tube marked it or a partner in its own
+// row is kept; a kept tube marks the partners in its row.  The status words (2 not visited, 1 kept, 0 suppressed or marked) follow the
+// partner rows in `work`.
+#define TNMS_LD 65                // leading dimension of the LDS tables: a lane reads its own row without bank conflicts
+#define TNMS_ROW 64               // partner entries per tube in `work`
+
+__device__ __forceinline__ int tnms_get(const int* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+__device__ __forceinline__ void tnms_put(int* p, int v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+
+__global__ __launch_bounds__(64) void tube_nms_kernel(const float* __restrict__ det_box, const int* __restrict__ slot_off,
+                                                      const int* __restrict__ video_off, const int* __restrict__ row_cls,
+                                                      const int* __restrict__ row_head, const double* __restrict__ tube_score,
+                                                      const int* __restrict__ tube_len, const int* __restrict__ tube_last, int S, int N, int C,
+                                                      int min_len, double nms_iou, int* __restrict__ work, unsigned char* __restrict__ tube_keep) {
+    __shared__ double s_acc[TUBE_MAX_ACTIVE * TNMS_LD];                           // [tube lane][tube lane]: sum of the per-slot IoU
+    __shared__ int s_cnt[TUBE_MAX_ACTIVE * TNMS_LD];                              // slots the two share
+    __shared__ int s_head[TUBE_MAX_ACTIVE], s_len[TUBE_MAX_ACTIVE];               // the tube a lane holds
+    const int lane = threadIdx.x;
+    const int v = blockIdx.x / C, c = blockIdx.x % C;
+    const int s0 = video_off[v], s1 = video_off[v + 1];
+    if (s0 < 0 || s1 < s0 || s1 > S) return;
+    const int R0 = slot_off[s0], R1 = slot_off[s1];
+    if (R0 < 0 || R1 < R0 || R1 > N) return;
+    int* status = work + (long)N * TNMS_ROW;
+
+    // phase 1: the partners of every tube of the class
+    bool valid = false, beyond = false;
+    int head = -1, last = -1, len = 0, seen = -1;
+    for (int s = s0; s < s1 && !beyond; ++s) {
+        const int r0 = slot_off[s], r1 = slot_off[s + 1];
+        if (r0 < R0 || r1 < r0 || r1 > R1) return;
+        const int n = r1 - r0;
+        if (n > FMAP_MAX_DETS) { beyond = true; break; }
+        const int r = r0 + lane;
+        int rh = -1, mine = -1;                                                   // the row's head, and the lane that holds its tube
+        float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
+        if (lane < n && row_cls[r] == c) {
+            rh = row_head[r];
+            if (rh < R0 || rh > r) rh = -1;
+            if (rh >= 0 && (row_cls[rh] != c || row_head[rh] != rh)) rh = -1;     // a head is a head row of this class: its work row is this wave's
+            if (rh >= 0) {
+                const float* d = det_box + (long)r * 4;
+                b0 = d[0]; b1 = d[1]; b2 = d[2]; b3 = d[3];
+            }
+        }
+        for (unsigned long long m = __ballot(rh >= 0); m; m &= m - 1) {
+            const int p = __ffsll((long long)m) - 1;
+            const int h = __shfl(rh, p, 64);
+            const unsigned long long tm = __ballot(valid && head == h);
+            int t;
+            if (tm) {
+                t = __ffsll((long long)tm) - 1;
+                if (__shfl(seen, t, 64) == s) {                                   // a second row of one tube in one slot: the first one counts
+                    if (lane == p) rh = -1;
+                    continue;
+                }
+            } else {                                                              // a tube begins: a free lane, its table row and column zeroed
+                const unsigned long long fm = ~__ballot(valid);
+                if (!fm) { beyond = true; break; }
+                t = __ffsll((long long)fm) - 1;
+                if (lane == t) {
+                    valid = true;
+                    head = h;
+                    last = tube_last[h];
+                    last = last > s1 - 1 ? s1 - 1 : last;
+                    len = tube_len[h];
+                    s_head[t] = h;
+                    s_len[t] = len;
+                }
+                s_acc[t * TNMS_LD + lane] = 0.0;
+                s_cnt[t * TNMS_LD + lane] = 0;
+                s_acc[lane * TNMS_LD + t] = 0.0;
+                s_cnt[lane * TNMS_LD + t] = 0;
+                work[(long)h * TNMS_ROW + lane] = -1;
+                if (lane == 0) status[h] = 2;
+                __syncthreads();
+            }
+            if (lane == t) seen = s;
+            if (lane == p) mine = t;
+        }
+        if (beyond) break;
+        const unsigned long long rows = __ballot(mine >= 0);
+        for (unsigned long long m = rows; m; m &= m - 1) {                        // every row against every other row of the slot
+            const int p = __ffsll((long long)m) - 1;
+            const int tp = __shfl(mine, p, 64);
+            const float p0 = __shfl(b0, p, 64), p1 = __shfl(b1, p, 64), p2 = __shfl(b2, p, 64), p3 = __shfl(b3, p, 64);
+            if (mine >= 0 && lane != p) {
+                s_acc[mine * TNMS_LD + tp] += fmap_iou_d((double)b0, (double)b1, (double)b2, (double)b3, (double)p0, (double)p1, (double)p2, (double)p3);
+                s_cnt[mine * TNMS_LD + tp] += 1;
+            }
+        }
+        __syncthreads();
+        const unsigned long long live = __ballot(valid);
+        if (valid && last <= s) {                                                 // the tube ends here: its pairs with the live tubes are final
+            if (len >= min_len) {
+                for (unsigned long long m = live & ~(1ull << lane); m; m &= m - 1) {
+                    const int j = __ffsll((long long)m) - 1;
+                    const int shared = s_cnt[lane * TNMS_LD + j];
+                    if (shared <= 0 || s_len[j] < min_len) continue;
+                    if (s_acc[lane * TNMS_LD + j] / (double)(len + s_len[j] - shared) > nms_iou) work[(long)head * TNMS_ROW + j] = s_head[j];
+                }
+            }
+            valid = false;
+        }
+        __syncthreads();
+    }
+    if (beyond) {                                                                 // nothing decided for this (video, class)
+        for (int r = R0 + lane; r < R1; r += 64)
+            if (row_cls[r] == c && row_head[r] == r) tube_keep[r] = TUBE_BEYOND_BOUNDS;
+        return;
+    }
+    __threadfence();
+    __syncthreads();
+
+    // phase 2: the counted tubes by descending score (equal scores by ascending head)
+    unsigned long long last_hi = ~0ull, last_lo = ~0ull;
+    for (;;) {
+        unsigned long long best_hi = 0ull, best_lo = 0ull;                        // a real key has lo > 0
+        for (int r = R0 + lane; r < R1; r += 64) {
+            if (row_cls[r] != c || row_head[r] != r || tube_len[r] < min_len) continue;
+            const unsigned long long hi = tube_ord(tube_score[r]), lo = 0xFFFFFFFFull - (unsigned long long)(r - R0);
+            if (!(hi < last_hi || (hi == last_hi && lo < last_lo))) continue;
+            if (hi > best_hi || (hi == best_hi && lo > best_lo)) { best_hi = hi; best_lo = lo; }
+        }
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const unsigned long long oh = __shfl_xor(best_hi, o, 64), ol = __shfl_xor(best_lo, o, 64);
+            if (oh > best_hi || (oh == best_hi && ol > best_lo)) { best_hi = oh; best_lo = ol; }
+        }
+        if (!best_lo) break;
+        last_hi = best_hi;
+        last_lo = best_lo;
+        const int h = R0 + (int)(0xFFFFFFFFull - best_lo);
+        // read at device scope: the words were written by other lanes of this wave, and a neighbouring workgroup on this CU may have pulled
+        // their cache lines into the vector L1 before that (tube_match_kernel's work rows)
+        const int p = tnms_get(work + (long)h * TNMS_ROW + lane);
+        const bool partner = p >= R0 && p < R1;
+        const bool hit = partner && tnms_get(status + p) == 1;
+        const bool suppressed = tnms_get(status + h) == 0 || __ballot(hit) != 0ull;
+        if (!suppressed && partner) tnms_put(status + p, 0);                    // p is not kept, or this tube would be suppressed
+        if (lane == 0) {
+            tnms_put(status + h, suppressed ? 0 : 1);
+            tube_keep[h] = suppressed ? 0 : 1;
+        }
+        __threadfence();
+        __syncthreads();
     }
 }
 
@@ -706,6 +863,34 @@ int tuber_tube_match(const float* det_box, const int* slot_off, const int* video
                        tube_len, tube_last, gt_box, gt_cls, gt_tube, gt_off, thresholds, S, N, G, C, T, max_gt_tubes, min_len, work, tube_flag);
     TUBER_RETURN_LAUNCH();
 }
+// Spatio-temporal NMS over linked tubes (evaluation.tube_nms: the definition).  The operands are the link outputs as tuber_tube_match reads them:
+// the validation store in layout order, or a padded [S][K] store with slot_off = arange(S + 1) * K and V = 1.  Two tubes of one (video, class)
+// overlap by stIoU = sum over the shared slots, ascending, of the fp64 IoU / |slots of either|; the tubes of at least min_len detections are
+// visited by descending score (NaN last, equal scores by ascending head) and one is suppressed iff its stIoU with a tube kept before it is
+// > nms_iou.  tube_keep [N] bytes out: 1 kept head, 0 suppressed head, 2 not a head or shorter than min_len, 3 at the heads of a (video, class)
+// with more than tuber_tube_link_max_active() tubes live at one slot.  work: caller-owned, tuber_tube_nms_work_bytes(N) bytes, 16-byte aligned.
+// Refused (negative, nothing launched, nothing written): max_rows > tuber_frame_match_max_dets(), min_len < 1, nms_iou NaN or outside [0, 1],
+// N > S * max_rows, bad sizes, a null pointer or a misaligned work.
+int tuber_tube_nms(const float* det_box, const int* slot_off, const int* video_off, const int* row_cls, const int* row_head,
+                   const double* tube_score, const int* tube_len, const int* tube_last, int V, int S, int N, int C, int max_rows, int min_len,
+                   double nms_iou, void* work, unsigned char* tube_keep, hipStream_t stream) {
+    if (V < 0 || S < 0 || N < 0 || C <= 0 || max_rows < 0 || min_len < 1) return TUBER_EINVAL;
+    if (!(nms_iou >= 0.0 && nms_iou <= 1.0)) return TUBER_EINVAL;                // a NaN fails both comparisons
+    if (max_rows > FMAP_MAX_DETS || (long)N > (long)S * max_rows || S < V) return TUBER_EINVAL;
+    if ((long)V * C > 0x7FFFFFFFl) return TUBER_EINVAL;
+    if (N == 0 || V == 0) return TUBER_OK;
+    if (!det_box || !slot_off || !video_off || !row_cls || !row_head || !tube_score || !tube_len || !tube_last || !work || !tube_keep)
+        return TUBER_EINVAL;
+    if ((uintptr_t)work & 15) return TUBER_EINVAL;
+    const hipError_t e = hipMemsetAsync(tube_keep, TUBE_NOT_COUNTED, (size_t)N, stream);
+    if (e != hipSuccess) return (int)e;
+    hipLaunchKernelGGL(tube_nms_kernel, dim3((unsigned)(V * C)), dim3(64), 0, stream, det_box, slot_off, video_off, row_cls, row_head, tube_score,
+                       tube_len, tube_last, S, N, C, min_len, nms_iou, (int*)work, tube_keep);
+    TUBER_RETURN_LAUNCH();
+}
+// bytes of the scratch of tuber_tube_nms: per row 64 partner heads and one status word (int32), rounded up to 16 bytes; 0 for N <= 0
+long tuber_tube_nms_work_bytes(long N) { return N > 0 ? (N * (TNMS_ROW + 1) * 4 + 15) & ~15l : 0; }
+
 int tuber_tube_match_max_gt() { return TUBE_MAX_GT; }
 int tuber_tube_match_max_thresholds() { return TUBE_MAX_THR; }
 

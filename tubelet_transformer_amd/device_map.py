@@ -19,7 +19,8 @@ a row of C + 1 probabilities is one detection, of its arg-max class; the matchin
 
 ``DeviceVideoMAP`` is that store again with the tube id of every ground-truth line: besides frame-mAP it links the rows into action tubes
 (``tuber_tube_link``), matches them against the ground-truth tubes by spatio-temporal IoU (``tuber_tube_match``, csrc/tube_map.hip) and gives
-video-mAP at several thresholds -- ``evaluation.VideoMAP`` on the device.
+video-mAP at several thresholds -- ``evaluation.VideoMAP`` on the device.  With ``tube_nms`` set, duplicate tubes are removed between the two
+steps (``tuber_tube_nms``; ``evaluation.tube_nms`` is the definition).
 """
 import logging
 
@@ -449,12 +450,15 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
     ``evaluate()`` is unchanged (frame-mAP); ``link()`` / ``tubes()`` give the tubes, ``evaluate_video()`` the video-mAPs.  Keys are
     ``"<video>-<frame number>"``.  ``add_ground_truth(..., tubes=)`` takes one integer tube id per line; without it the id is the ordinal of
     the line among its frame's lines of the same class.  A CPU store, a store beyond a kernel bound and a key that does not parse are evaluated
-    by ``to_video_host_evaluator()``: no row is ever dropped."""
+    by ``to_video_host_evaluator()``: no row is ever dropped.  ``tube_nms`` (default None: off): the spatio-temporal IoU above which a tube
+    is a duplicate of a higher-scored kept tube of its (video, class) and is neither matched nor ranked (``tuber_tube_nms``,
+    ``evaluation.tube_nms``: the definition); ``tubes()`` drops such tubes."""
 
     def __init__(self, class_num=24, iou_threshold=0.5, label_width=None, device="cuda", link_iou=0.2, max_gap=2, min_len=1,
-                 thresholds=(0.2, 0.5, 0.75, "0.5:0.95")):
+                 thresholds=(0.2, 0.5, 0.75, "0.5:0.95"), tube_nms=None):
         super().__init__(class_num, iou_threshold, label_width, device)
         self.link_iou, self.max_gap, self.min_len, self.thresholds = float(link_iou), int(max_gap), int(min_len), tuple(thresholds)
+        self.tube_nms = None if tube_nms is None else float(tube_nms)
         self.video_path = None                            # after evaluate_video(): "device" or "host"
 
     def _init_store(self, score_width, label_width):
@@ -462,7 +466,8 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
         self._gt_tube = []                                # per ground-truth line: its tube id or None
 
     def _settings(self):
-        return dict(super()._settings(), link_iou=self.link_iou, max_gap=self.max_gap, min_len=self.min_len, thresholds=self.thresholds)
+        return dict(super()._settings(), link_iou=self.link_iou, max_gap=self.max_gap, min_len=self.min_len, thresholds=self.thresholds,
+                    tube_nms=self.tube_nms)
 
     def _gt_extra(self):
         return dict(tubes=list(self._gt_tube))
@@ -487,7 +492,7 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
 
     def to_video_host_evaluator(self):
         """an ``evaluation.VideoMAP`` holding the store, in store order"""
-        ev = _ev.VideoMAP(self.class_num, self.link_iou, self.max_gap, self.min_len, self.thresholds)
+        ev = _ev.VideoMAP(self.class_num, self.link_iou, self.max_gap, self.min_len, self.thresholds, tube_nms=self.tube_nms)
         ev.add_detections([self.frame_keys[f] for f in self.row_fid], self.boxes.cpu().numpy(), self.scores.cpu().numpy())
         keys, rows = self.video_ground_truth()
         ev.add_ground_truth(keys, [r[1] for r in rows], [r[0] for r in rows], [r[2] for r in rows])
@@ -565,10 +570,30 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
                  self.link_iou, self.max_gap, out["row_cls"], out["row_head"], out["tube_score"], out["tube_len"], out["tube_last"])
         return out
 
+    def nms(self, a, link):
+        """``tuber_tube_nms`` over a device link record -> tube_keep [N] uint8 on the device (1 kept head, 0 suppressed head, 2 not a head or
+        shorter than ``min_len``, 3 a (video, class) beyond the kernel's bound)"""
+        N, dev = a["N"], self.device
+        keep = torch.full((N,), 2, dtype=torch.uint8, device=dev)
+        work = torch.empty(max(lib.query("tuber_tube_nms_work_bytes", N), 16), dtype=torch.uint8, device=dev)
+        lib.call("tuber_tube_nms", a["det_box"], a["slot_off"], a["video_off"], link["row_cls"], link["row_head"], link["tube_score"],
+                 link["tube_len"], link["tube_last"], a["V"], a["S"], N, a["C"], a["max_rows"], self.min_len, self.tube_nms, work, keep)
+        return keep
+
     def tubes(self):
-        """the linked tubes read back: a list of dict(video, cls (1-based), score, frames, boxes, head, rows) in head order"""
-        link = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in self.link().items()}
-        return _ev.tubes_from_link(link)
+        """the linked tubes read back: a list of dict(video, cls (1-based), score, frames, boxes, head, rows) in head order; with ``tube_nms``
+        set, without the suppressed ones"""
+        if self.tube_nms is None:
+            link = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in self.link().items()}
+            return _ev.tubes_from_link(link)
+        a = self.video_arrays() if self.device.type == "cuda" else None
+        link = self.link(a)
+        on_device = link["row_head"].device.type == "cuda"
+        keep = self.nms(a, link).cpu().numpy() if on_device else None
+        link = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in link.items()}
+        if keep is None or (keep == 3).any():
+            keep = _ev.tube_nms(link, self.tube_nms, self.min_len)
+        return [t for t in _ev.tubes_from_link(link) if keep[t["head"]] != 0]
 
     def match_video(self, a, link):
         """``tuber_tube_match`` -> tube_flag [T, N] uint8 on the device (1 true positive, 0 false positive, 2 not counted)"""
@@ -601,6 +626,13 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
         mark("layout_and_uploads")
         link = self.link(a)
         mark("tuber_tube_link")
+        keep = None
+        if self.tube_nms is not None:
+            # the match kernel sees a suppressed tube as one of no detections: with min_len >= 1 its phase 2 skips the head (flag 2, no
+            # ground-truth tube taken, its work row never read); phase 1 reads tube_len only into a divisor of that row
+            keep = self.nms(a, link)
+            link = dict(link, tube_len=link["tube_len"].masked_fill(keep == 0, 0))
+            mark("tuber_tube_nms")
         flags = self.match_video(a, link)
         mark("tuber_tube_match")
         # every class's ranking over its counted tubes, the same for every threshold: one stable sort by score (descending, NaN last), one by
@@ -618,14 +650,21 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
             flags_ranked[:, bucket, pos] = flags[:, perm]
         mark("rank_sort_and_scatter")
         n_gt = torch.cat([a["n_gt"], torch.zeros(1, dtype=torch.int32, device=dev)]).repeat(T).contiguous()
-        ap = torch.empty(T * (C + 1), dtype=torch.float64, device=dev)
+        ap = torch.empty(T * (C + 1) + (0 if keep is None else 1), dtype=torch.float64, device=dev)
         lib.call("tuber_ranked_ap", flags_ranked, n_gt, T * (C + 1), N, ap, None)
+        if keep is not None:
+            ap[-1] = (keep == 3).any()                    # the kernel's escape travels with the APs: no read-back of its own
         mark("tuber_ranked_ap")
         if timings is not None:
             import time
             torch.cuda.synchronize()
             t0 = time.perf_counter()
-        ap = ap.cpu().numpy().reshape(T, C + 1)
+        ap = ap.cpu().numpy()
+        if keep is not None:
+            if ap[-1] != 0.0:
+                return self._evaluate_video_host("more than %d tubes of a (video, class) live at one frame" % lib.query("tuber_tube_link_max_active"))
+            ap = ap[:-1]
+        ap = ap.reshape(T, C + 1)
         if timings is not None:
             timings["read_back_ms"] = (time.perf_counter() - t0) * 1e3
             for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):

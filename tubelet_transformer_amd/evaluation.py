@@ -539,6 +539,53 @@ def link_rows(box, cls, score, slot, video_off, class_num, link_iou, max_gap):
     return dict(row_head=head, tube_score=tscore, tube_len=tlen, tube_last=tlast)
 
 
+def tube_nms(link, nms_iou, min_len=1):
+    """Spatio-temporal NMS over linked tubes: the definition of ``tuber_tube_nms``.  ``link``: a link record as
+    ``VideoMAP.link()`` or ``link_rows`` leave it (``det_box``, ``row_slot``, ``row_cls``, ``row_head``, ``tube_score``, ``layout``).  A tube is
+    the rows of its head's class that carry its head, one per slot (the first one); it is a candidate with at least ``min_len`` rows.
+    ``stIoU(d, e)`` of two tubes of one (video, class): the fp64 sum, over the slots both have a row in, ascending, of ``_iou_one_to_many`` on the
+    two fp32 boxes promoted to fp64, divided by the number of slots either has a row in; 0 without a shared slot (gap slots belong to neither).
+    Per (video, class) the candidates are visited in ``VideoMAP.match``'s order -- descending score, NaN last, equal scores by ascending head
+    -- and one is suppressed iff its stIoU with a tube KEPT before it is strictly greater than ``nms_iou``; a suppressed tube suppresses
+    nothing.  -> ``tube_keep`` uint8 [N] in layout order: 1 kept head, 0 suppressed head, 2 not a head or shorter than ``min_len``."""
+    nms_iou, min_len = float(nms_iou), int(min_len)
+    if not 0.0 <= nms_iou <= 1.0 or min_len < 1:
+        raise ValueError("tube_nms: nms_iou = %r must lie in [0, 1] and min_len = %r be >= 1" % (nms_iou, min_len))
+    head, slot, cls = np.asarray(link["row_head"]).reshape(-1), np.asarray(link["row_slot"]).reshape(-1), np.asarray(link["row_cls"]).reshape(-1)
+    score = np.asarray(link["tube_score"], dtype=np.float64).reshape(-1)
+    box64 = np.asarray(link["det_box"], dtype=np.float32).reshape(-1, 4).astype(np.float64)
+    video_off = np.asarray(link["layout"]["video_off"])
+    N = len(head)
+    keep = np.full(N, 2, dtype=np.uint8)
+    video = np.searchsorted(video_off, slot, side="right") - 1
+    rows = {}                                                  # head -> {slot: row}
+    for r in np.nonzero(head >= 0)[0].tolist():
+        h = int(head[r])
+        if h <= r and head[h] == h and cls[h] == cls[r] and video[h] == video[r]:
+            rows.setdefault(h, {}).setdefault(int(slot[r]), r)
+    groups = {}
+    for h in sorted(rows):
+        if len(rows[h]) >= min_len:
+            groups.setdefault((int(video[h]), int(cls[h])), []).append(h)
+
+    def st_iou(d, e):
+        shared = sorted(set(d) & set(e))
+        total = 0.0
+        for s in shared:
+            with np.errstate(all="ignore"):
+                total += float(_iou_one_to_many(box64[d[s]], box64[e[s]][None, :])[0])
+        return total / (len(d) + len(e) - len(shared)) if shared else 0.0
+
+    for heads in groups.values():
+        kept = []
+        for h in sorted(heads, key=lambda h: (-score[h] if score[h] == score[h] else np.inf, h)):
+            suppressed = any(st_iou(rows[h], rows[k]) > nms_iou for k in kept)
+            keep[h] = 0 if suppressed else 1
+            if not suppressed:
+                kept.append(h)
+    return keep
+
+
 def actor_tracks(box, actor, queries, actions, S, A, link_iou, max_gap, window):
     """Actor tracks of ONE video: the definition of ``tuber_track_actions`` and the fallback of ``video.VideoActors.tracks``.
     The rows are a padded [S][A] actor store (``detect.decode_actors_host`` per key frame): ``box`` [S * A, 4] fp32 xyxy, ``actor`` [S * A] fp32,
@@ -784,9 +831,10 @@ class VideoMAP:
     when no-object is the arg-max, the box is not a box, or the arg-max probability is NaN); no exclude list.  Plain numpy / Python: the
     definition ``device_map.DeviceVideoMAP`` reproduces, and its fallback."""
 
-    def __init__(self, class_num=24, link_iou=0.2, max_gap=2, min_len=1, thresholds=(0.2, 0.5, 0.75, "0.5:0.95")):
+    def __init__(self, class_num=24, link_iou=0.2, max_gap=2, min_len=1, thresholds=(0.2, 0.5, 0.75, "0.5:0.95"), tube_nms=None):
         self.class_num, self.link_iou, self.max_gap, self.min_len = int(class_num), float(link_iou), int(max_gap), int(min_len)
         self.thresholds = tuple(thresholds)
+        self.tube_nms = None if tube_nms is None else float(tube_nms)     # the stIoU above which a lower-ranked tube is a duplicate (``tube_nms``)
         self.num_categories = 24
         self.det_keys, self._box, self._prob = [], [], []
         self.gt_keys, self.gt_rows = [], []
@@ -810,7 +858,8 @@ class VideoMAP:
     def link(self):
         """-> dict: ``order`` (layout row -> store row), ``det_box``, ``det_prob``, ``row_slot`` in layout order, ``row_cls`` (arg-max column),
         ``row_head`` (layout row of the tube's first detection, -1 for a row that is not counted), at head rows ``tube_score`` (fp64 mean of
-        the fp32 scores), ``tube_len``, ``tube_last`` (last slot); ``layout``; ``tubes`` (``tubes_from_link``)."""
+        the fp32 scores), ``tube_len``, ``tube_last`` (last slot); ``layout``; ``tubes`` (``tubes_from_link``); with ``tube_nms`` set,
+        ``tube_keep`` (``tube_nms``)."""
         C, N = self.class_num, len(self.det_keys)
         lay = tube_layout(self.det_keys, self.gt_keys)
         box = np.concatenate(self._box) if self._box else np.zeros((0, 4), np.float32)
@@ -824,6 +873,8 @@ class VideoMAP:
         link = dict(order=order, det_box=box, det_prob=prob, row_slot=slot, row_cls=cls, row_head=head, tube_score=tscore, tube_len=tlen,
                     tube_last=tlast, layout=lay)
         link["tubes"] = tubes_from_link(link)
+        if self.tube_nms is not None:
+            link["tube_keep"] = tube_nms(link, self.tube_nms, self.min_len)
         return link
 
     def st_iou(self, link=None):
@@ -852,7 +903,8 @@ class VideoMAP:
 
     def match(self, link=None):
         """-> (n_gt {class 1-based: ground-truth tubes}, flags {threshold: uint8 [N] in layout order: 1 true positive, 0 false positive, 2 not
-        counted}, link) over ``expand_thresholds(self.thresholds)``"""
+        counted}, link) over ``expand_thresholds(self.thresholds)``.  With ``tube_nms`` set, a suppressed tube is treated exactly like one shorter
+        than ``min_len``: flag 2, it takes no ground-truth tube and is not ranked."""
         link = link or self.link()
         gt, overlaps = self.st_iou(link)
         n_gt = {}
@@ -861,8 +913,11 @@ class VideoMAP:
                 n_gt[c + 1] = n_gt.get(c + 1, 0) + 1
         N = len(link["row_head"])
         groups = {}
+        keep = None
+        if self.tube_nms is not None:
+            keep = link["tube_keep"] if "tube_keep" in link else tube_nms(link, self.tube_nms, self.min_len)
         for t in link["tubes"]:
-            if len(t["frames"]) >= self.min_len:
+            if len(t["frames"]) >= self.min_len and (keep is None or keep[t["head"]] == 1):
                 groups.setdefault((t["video"], t["cls"]), []).append(t)
         flags = {}
         for thr in expand_thresholds(self.thresholds):
@@ -927,7 +982,8 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
     metric is computed on the device; the three files are written only with ``FILES``.  With ``CONFIG.VAL.VIDEO_MAP.ENABLE`` the rows go
     into a ``device_map.DeviceVideoMAP`` (``FILES`` keeps its meaning), the return value is still frame-mAP, and the video-mAPs over linked
     tubes are printed, written to the writer as ``val/video_mAP@<thr>`` and left in ``results`` (a dict: ``results["video_mAP"][thr]``,
-    ``results["video_AP"][thr]``).  A DistributedSampler's padded repeat frames are not de-duplicated."""
+    ``results["video_AP"][thr]``); with ``CONFIG.VAL.TUBE_NMS.IOU`` the tubes of a (video, class) go through ``tube_nms`` before they are
+    matched.  A DistributedSampler's padded repeat frames are not de-duplicated."""
     import torch.distributed as dist
     C = cfg.CONFIG
     ddp = dist.is_available() and dist.is_initialized()
@@ -949,9 +1005,9 @@ def validate_tuber_ucf_detection(cfg, model, criterion, postprocessors, data_loa
     vm = getattr(C.VAL, "VIDEO_MAP", None)
     video = vm is not None and vm.ENABLE
     if video:
-        from .config import video_map_settings
+        from .config import tube_nms_settings, video_map_settings
         from .device_map import DeviceVideoMAP
-        store = DeviceVideoMAP(class_num=nc, label_width=width, device=dev, **video_map_settings(cfg))
+        store = DeviceVideoMAP(class_num=nc, label_width=width, device=dev, tube_nms=tube_nms_settings(cfg)["iou"], **video_map_settings(cfg))
         frame_on_device = dm is not None and bool(dm.ENABLE)      # without DEVICE_MAP frame-mAP still comes from the result files
         files = bool(dm.FILES) if frame_on_device else True
     elif dm is not None and dm.ENABLE:

@@ -81,13 +81,33 @@ def working_geometry(H0, W0, size):
     return H, W, int(round((H - h) / 2.0)), int(round((W - w) / 2.0)), h, w
 
 
+def _nms_value(who, nms):
+    """None, or the NMS threshold as a float in [0, 1]"""
+    if nms is None:
+        return None
+    nms = float(nms)
+    if not 0.0 <= nms <= 1.0:
+        raise ValueError("%s: nms = %r must be None or a number in [0, 1]" % (who, nms))
+    return nms
+
+
+def _nms_device(boxes, slot_off, video_off, link, S, N, C, K, min_len, nms):
+    """``tuber_tube_nms`` behind ``tuber_tube_link_ranked`` over a padded [S][K] store -> tube_keep [N] uint8 on the device"""
+    keep = torch.full((N,), 2, dtype=torch.uint8, device=boxes.device)
+    work = torch.empty(max(lib.query("tuber_tube_nms_work_bytes", N), 16), dtype=torch.uint8, device=boxes.device)
+    lib.call("tuber_tube_nms", boxes, slot_off, video_off, link["row_cls"], link["row_head"], link["tube_score"], link["tube_len"], link["tube_last"], 1,
+             S, N, int(C), K, max(int(min_len), 1), float(nms), work, keep)
+    return keep
+
+
 class VideoDetections:
     """The ranked detections of a video's key frames: ``keys`` (frame numbers) and, as tensors on one device, ``boxes`` [n, K, 4] fp32 xyxy in
     source-video pixels, ``scores`` / ``aux`` [n, K] fp32, ``labels`` / ``queries`` [n, K] int32 (-1 in the rows behind ``count``), ``count`` /
     ``total`` [n] int32 -- the fields of ``detect.Detections``, a row per key frame."""
 
-    def __init__(self, keys, boxes, scores, labels, queries, aux, count, total, class_num, settings=None, store=None):
+    def __init__(self, keys, boxes, scores, labels, queries, aux, count, total, class_num, settings=None, store=None, nms_iou=None):
         self.keys = [int(k) for k in keys]
+        self.nms_iou = None if nms_iou is None else float(nms_iou)                      # the default of tubes(nms=): CONFIG.VAL.TUBE_NMS.IOU
         self.boxes, self.scores, self.labels, self.queries, self.aux, self.count, self.total = boxes, scores, labels, queries, aux, count, total
         self.class_num = int(class_num)
         self.settings = dict(settings or dict(link_iou=0.2, max_gap=2, min_len=1))      # the defaults of tubes(): CONFIG.VAL.VIDEO_MAP
@@ -133,8 +153,9 @@ class VideoDetections:
         return out
 
     # -- tubes ------------------------------------------------------------------------------------------------------------
-    def _link_device(self, link_iou, max_gap):
-        """``tuber_tube_link_ranked`` over the padded store as it is, or None where the linker's bounds refuse it"""
+    def _link_device(self, link_iou, max_gap, nms=None, min_len=1):
+        """``tuber_tube_link_ranked`` (and, with ``nms``, ``tuber_tube_nms`` behind it) over the padded store as it is, or None where the
+        linker's bounds refuse it"""
         S, K = self.scores.shape
         if self.boxes.device.type != "cuda":
             return None, "the store is on the CPU"
@@ -150,24 +171,31 @@ class VideoDetections:
         lib.call("tuber_tube_link_ranked", self.boxes.contiguous(), self.labels.contiguous(), self.scores.contiguous(), slot_off, video_off, 1, S, N,
                  self.class_num, K, float(link_iou), int(max_gap), out["row_cls"], out["row_head"], out["tube_score"], out["tube_len"], out["tube_last"])
         names = ("row_head", "tube_score", "tube_len", "tube_last")
+        if nms is not None:
+            out["tube_keep"] = _nms_device(self.boxes.contiguous(), slot_off, video_off, out, S, N, self.class_num, K, min_len, nms)
+            names += ("tube_keep",)
         host = self._fetch([out[k] for k in names])
         return dict(zip(FIELDS + names, host)), None
 
-    def tubes(self, link_iou=None, max_gap=None, min_len=None):
+    def tubes(self, link_iou=None, max_gap=None, min_len=None, nms=None):
         """The action tubes of the video: a list of ``dict(cls, score, frames, boxes, length)`` in head order (the order of the tubes' first
         detections) -- ``cls`` 1-based as in ``evaluation.tubes_from_link``, ``score`` the fp64 mean of the linked fp32 scores, ``frames`` the key
         frame numbers, ``boxes`` [length, 4] in source pixels; tubes shorter than ``min_len`` are dropped.  The slots of the linker are key
         ORDINALS, so ``max_gap`` counts key frames.  Defaults: ``CONFIG.VAL.VIDEO_MAP``.  Linked on the device by ``tuber_tube_link_ranked``;
         beyond its bounds (K > 64 rows per key frame or K * (max_gap + 1) > ``tuber_tube_link_max_active()`` = 64) or on a CPU store
         ``evaluation.link_rows`` answers, one line says so, and ``tubes_path`` is "host" instead of "device".  ``VideoDetector``'s default
-        ``topk`` is 21 = 64 // (MAX_GAP + 1) with the shipped MAX_GAP of 2, so that the default path is the device's."""
-        from .evaluation import link_rows, tubes_from_link
+        ``topk`` is 21 = 64 // (MAX_GAP + 1) with the shipped MAX_GAP of 2, so that the default path is the device's.  ``nms`` (default:
+        ``CONFIG.VAL.TUBE_NMS.IOU``; None: off): per class a tube whose spatio-temporal IoU with a higher-scored kept tube exceeds it is
+        dropped -- one more launch, ``tuber_tube_nms``, whose bytes travel in the same copy; on the host path
+        ``evaluation.tube_nms``."""
+        from .evaluation import link_rows, tube_nms, tubes_from_link
+        nms = _nms_value("VideoDetections.tubes", self.nms_iou if nms is None else nms)
         link_iou = float(self.settings["link_iou"] if link_iou is None else link_iou)
         max_gap = int(self.settings["max_gap"] if max_gap is None else max_gap)
         min_len = int(self.settings["min_len"] if min_len is None else min_len)
         S, K = self.scores.shape
         slot = np.repeat(np.arange(S, dtype=np.int64), K)
-        host, why = self._link_device(link_iou, max_gap)
+        host, why = self._link_device(link_iou, max_gap, nms, min_len)
         if host is None:
             print("[tuber] VideoDetections.tubes: %s; linking on the host" % why, file=sys.stderr, flush=True)
             host = dict(zip(FIELDS, self._fetch()))
@@ -177,9 +205,14 @@ class VideoDetections:
         layout = dict(videos=["video"], video_off=np.asarray([0, S]), first_frame=np.asarray([0]))
         link = dict(layout=layout, row_head=host["row_head"], row_slot=slot, row_cls=host["labels"].reshape(-1), tube_score=host["tube_score"],
                     det_box=host["boxes"].reshape(-1, 4))
+        keep = None
+        if nms is not None:
+            keep = host.get("tube_keep")
+            if keep is None or (keep == 3).any():                                      # the host path, or the kernel's escape
+                keep = tube_nms(link, nms, max(min_len, 1))
         out = []
         for t in tubes_from_link(link):
-            if len(t["frames"]) >= min_len:
+            if len(t["frames"]) >= min_len and (keep is None or keep[t["head"]] != 0):
                 out.append(dict(cls=t["cls"], score=t["score"], frames=[self.keys[s] for s in t["frames"]], boxes=t["boxes"], length=len(t["frames"])))
         return out
 
@@ -190,8 +223,9 @@ class VideoActors:
     the rows behind ``count``), ``actions`` [n, A, C] fp32 (every class's score), ``count`` / ``total`` [n] int32 -- the fields of
     ``detect.Actors``, a row per key frame."""
 
-    def __init__(self, keys, boxes, actor, queries, actions, count, total, settings=None, store=None):
+    def __init__(self, keys, boxes, actor, queries, actions, count, total, settings=None, store=None, nms_iou=None):
         self.keys = [int(k) for k in keys]
+        self.nms_iou = None if nms_iou is None else float(nms_iou)                      # the default of tracks(nms=): CONFIG.VAL.TUBE_NMS.ACTORS_IOU
         self.boxes, self.actor, self.queries, self.actions, self.count, self.total = boxes, actor, queries, actions, count, total
         self.class_num = int(actions.shape[2])
         # the defaults of tracks(): CONFIG.VAL.ACTORS
@@ -240,9 +274,9 @@ class VideoActors:
     # -- tracks -----------------------------------------------------------------------------------------------------------
     NAMES = ("row_head", "tube_score", "tube_len", "tube_last", "row_smooth", "track_mean", "track_peak")
 
-    def _tracks_device(self, link_iou, max_gap, window):
-        """``tuber_tube_link_ranked`` with one class and ``tuber_track_actions`` over the padded store as it is, everything read back in one copy;
-        or None where the kernels' bounds refuse it"""
+    def _tracks_device(self, link_iou, max_gap, window, nms=None, min_len=1):
+        """``tuber_tube_link_ranked`` with one class and ``tuber_track_actions`` (and, with ``nms``, ``tuber_tube_nms``) over the padded store as
+        it is, everything read back in one copy; or None where the kernels' bounds refuse it"""
         S, A, C = self.actions.shape
         if self.boxes.device.type != "cuda":
             return None, "the store is on the CPU"
@@ -264,10 +298,14 @@ class VideoActors:
                  int(max_gap), out["row_cls"], out["row_head"], out["tube_score"], out["tube_len"], out["tube_last"])
         lib.call("tuber_track_actions", self.actions.contiguous(), out["row_head"], out["tube_last"], S, A, C, int(window), out["row_smooth"],
                  out["track_mean"], out["track_peak"])
-        host = self._fetch([out[k] for k in self.NAMES])
-        return dict(zip(ACTOR_FIELDS + self.NAMES, host)), None
+        names = self.NAMES
+        if nms is not None:
+            out["tube_keep"] = _nms_device(self.boxes.contiguous(), slot_off, video_off, out, S, N, 1, A, min_len, nms)
+            names += ("tube_keep",)
+        host = self._fetch([out[k] for k in names])
+        return dict(zip(ACTOR_FIELDS + names, host)), None
 
-    def tracks(self, link_iou=None, max_gap=None, min_len=None, window=None, label_thr=None):
+    def tracks(self, link_iou=None, max_gap=None, min_len=None, window=None, label_thr=None, nms=None):
         """The actor tracks of the video -- who is there, from when to when, doing what: a list, in head order (the order of the tracks' first
         rows), of ``dict(score, frames, boxes, actor, queries, actions, smooth, mean, peak, labels, length)``: ``score`` the fp64 mean actor
         probability, ``frames`` the key frame numbers, ``boxes`` [L, 4] in source pixels, ``actor`` / ``queries`` [L], ``actions`` [L, C] fp32 the
@@ -276,8 +314,11 @@ class VideoActors:
         tracks shorter than ``min_len`` are dropped.  ``evaluation.actor_tracks`` is the definition.  Defaults: ``CONFIG.VAL.ACTORS``.  On the
         device: ``tuber_tube_link_ranked`` with one class, ``tuber_track_actions``, one copy back.  Beyond their bounds (A > 64,
         A * (max_gap + 1) > 64, C > 4096) or on a CPU store the definition answers on the host, one line says so, and ``tracks_path`` is "host"
-        instead of "device"."""
-        from .evaluation import actor_tracks
+        instead of "device".  ``nms`` (default: ``CONFIG.VAL.TUBE_NMS.ACTORS_IOU``; None: off): a track whose spatio-temporal IoU with a
+        kept track of higher mean actor probability exceeds it is dropped, class-agnostically: ``tuber_tube_nms`` on
+        the device, ``evaluation.tube_nms`` on the host path.  The aggregates of the kept tracks are unchanged."""
+        from .evaluation import actor_tracks, tube_nms
+        nms = _nms_value("VideoActors.tracks", self.nms_iou if nms is None else nms)
         st = self.settings
         link_iou = float(st["link_iou"] if link_iou is None else link_iou)
         max_gap = int(st["max_gap"] if max_gap is None else max_gap)
@@ -287,7 +328,7 @@ class VideoActors:
         if max_gap < 0 or window < 0:
             raise ValueError("VideoActors.tracks: max_gap = %d and window = %d must be >= 0" % (max_gap, window))
         S, A, C = self.actions.shape
-        host, why = self._tracks_device(link_iou, max_gap, window)
+        host, why = self._tracks_device(link_iou, max_gap, window, nms, min_len)
         if host is None:
             print("[tuber] VideoActors.tracks: %s; tracks on the host" % why, file=sys.stderr, flush=True)
             host = dict(zip(ACTOR_FIELDS, self._fetch()))
@@ -298,10 +339,16 @@ class VideoActors:
         members = {}
         for r in np.nonzero(head >= 0)[0].tolist():
             members.setdefault(int(head[r]), []).append(r)
+        keep = None
+        if nms is not None:
+            keep = host.get("tube_keep")
+            if keep is None or (keep == 3).any():                                      # the host path, or the kernel's escape
+                keep = tube_nms(dict(layout=dict(video_off=np.asarray([0, S])), row_head=head, row_slot=np.repeat(np.arange(S, dtype=np.int64), A),
+                                     row_cls=np.where(query >= 0, 0, -1), tube_score=host["tube_score"], det_box=box), nms, max(min_len, 1))
         out = []
         for h in sorted(members):
             rows = members[h]
-            if len(rows) < min_len:
+            if len(rows) < min_len or (keep is not None and keep[h] == 0):
                 continue
             mean = np.array(host["track_mean"][h], dtype=np.float64)
             with np.errstate(invalid="ignore"):
@@ -331,8 +378,9 @@ class VideoDetector:
     when to when, doing what" (DESIGN.md section 6i)."""
 
     def __init__(self, cfg, model, batch=2, score_thr=None, topk=None, actor_thr=None, graphed=True, rule=None, actors=None):
-        from .config import actor_settings, detect_settings, video_map_settings
+        from .config import actor_settings, detect_settings, tube_nms_settings, video_map_settings
         self.cfg, self.model = cfg, model
+        self.nms = tube_nms_settings(cfg)                  # the defaults of tubes(nms=) / tracks(nms=): kept out of ``settings``
         self.batch = int(batch)
         if self.batch < 1:
             raise ValueError("VideoDetector: batch = %r must be >= 1" % (batch,))
@@ -425,9 +473,9 @@ class VideoDetector:
             if full_a is not None:
                 for dst, src in zip(full_a, det.actors.tensors()):
                     dst[b * B:(b + 1) * B].copy_(src)
-        vd = VideoDetections(keys, *[t[:n] for t in full], class_num=self.class_num, settings=self.settings, store=store)
+        vd = VideoDetections(keys, *[t[:n] for t in full], class_num=self.class_num, settings=self.settings, store=store, nms_iou=self.nms["iou"])
         if full_a is not None:
-            vd.actors = VideoActors(keys, *[t[:n] for t in full_a], settings=self.actor_settings, store=store)
+            vd.actors = VideoActors(keys, *[t[:n] for t in full_a], settings=self.actor_settings, store=store, nms_iou=self.nms["actors_iou"])
         return vd
 
 
@@ -548,12 +596,19 @@ class VideoStream:
     ``VideoDetections`` without keys when only smoothed rows were left) -- one ``tuber_track_actions_stream`` call per push.  ``tracks()``
     returns the actor tracks that closed since the last call.  The stream then also holds the actors' link state (2560 bytes) and the track
     ring (``tuber_track_stream_state_bytes``); beyond the kernel's bounds ``evaluation.ActorTracker`` answers on the host, one line says so,
-    and ``tracks_path`` is "host" instead of "device"."""
+    and ``tracks_path`` is "host" instead of "device".
+
+    Tube NMS (``CONFIG.VAL.TUBE_NMS``) is not part of the stream: when a tube closes, a tube that would suppress it may
+    still be open with its final score unknown, so no streaming rule equals the whole-video one.  A config that sets it is ignored here, with
+    one line on stderr at construction; ``tubes()`` / ``tracks()`` return every closed tube."""
 
     def __init__(self, cfg, model, batch=2, stride=None, rule=None, max_chunk=64, score_thr=None, topk=None, actor_thr=None, graphed=True,
                  link=True, actors=None):
-        from .config import actor_settings, detect_settings, video_map_settings
+        from .config import actor_settings, detect_settings, tube_nms_settings, video_map_settings
         self.cfg, self.model = cfg, model
+        if any(v is not None for v in tube_nms_settings(cfg).values()):
+            print("[tuber] VideoStream: CONFIG.VAL.TUBE_NMS is ignored: a closed tube's suppressor may still be open, so tube NMS is defined over "
+                  "whole videos only (VideoDetector)", file=sys.stderr, flush=True)
         self.batch, self.max_chunk, self.link = int(batch), int(max_chunk), bool(link)
         if self.batch < 1 or self.max_chunk < 1:
             raise ValueError("VideoStream: batch = %r and max_chunk = %r must be >= 1" % (batch, max_chunk))
