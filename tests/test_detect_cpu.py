@@ -10,7 +10,7 @@ import torch
 
 from tubelet_transformer_amd import lib
 from tubelet_transformer_amd.config import detect_settings, get_cfg_defaults
-from tubelet_transformer_amd.detect import FIELDS, Detections, decode_topk_host, graph_key
+from tubelet_transformer_amd.detect import FIELDS, Detections, decode_topk_host, graph_key, host_parts
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -164,6 +164,34 @@ def test_detections_to_host_trims_to_count():
     assert np.array_equal(host[0]["scores"], np.float32([.9, .5])) and np.array_equal(host[0]["aux"], np.float32([.95, .85]))
     for k in ("boxes", "scores", "labels", "queries", "aux"):
         assert len(host[1][k]) == 0
+
+
+def mixed_parts(device="cpu"):
+    """[(numpy array, the tensor on ``device`` that holds it)]: fp32 [2, 3, 4] with a NaN and a negative zero, fp64 [5], int32 [2, 3], uint8 [7], a
+    tensor of no elements and a non-contiguous view"""
+    rng = np.random.default_rng(3)
+    f32 = rng.standard_normal((2, 3, 4)).astype(np.float32)
+    f32[0, 1, 2], f32[1, 0, 0] = np.nan, -0.0
+    wide = rng.integers(-9, 9, (4, 6)).astype(np.int32)
+    arrays = [f32, rng.standard_normal(5), rng.integers(-2 ** 31, 2 ** 31 - 1, (2, 3)).astype(np.int32), rng.integers(0, 256, 7).astype(np.uint8),
+              np.zeros((0, 4), dtype=np.float32)]
+    parts = [(a, torch.from_numpy(a.copy()).to(device)) for a in arrays]
+    return parts + [(np.ascontiguousarray(wide.T[1:5:2]), torch.from_numpy(wide.copy()).to(device).t()[1:5:2])]
+
+
+def assert_same_arrays(got, want):
+    assert len(got) == len(want)
+    for g, w in zip(got, want):
+        assert isinstance(g, np.ndarray) and g.dtype == w.dtype and g.shape == w.shape
+        assert np.ascontiguousarray(g).tobytes() == np.ascontiguousarray(w).tobytes()
+
+
+def test_host_parts_keeps_dtype_shape_and_bits():
+    parts = mixed_parts()
+    assert [str(a.dtype) for a, _ in parts] == ["float32", "float64", "int32", "uint8", "float32", "int32"]
+    assert parts[4][1].numel() == 0 and not parts[5][1].is_contiguous() and parts[5][1].shape == (2, 4)
+    assert_same_arrays(host_parts([t for _, t in parts]), [a for a, _ in parts])
+    assert host_parts([]) == []
 
 
 def test_header_declares_and_library_exports_the_detect_entries():

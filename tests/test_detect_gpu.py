@@ -19,10 +19,12 @@ import numpy as np
 import pytest
 import torch
 
+from test_detect_cpu import assert_same_arrays, mixed_parts
+from test_video_gpu import _count_syncs
 from tubelet_transformer_amd import ab, lib, synth
 from tubelet_transformer_amd.config import load_cfg
 from tubelet_transformer_amd.criterion import PostProcess, PostProcessAVA
-from tubelet_transformer_amd.detect import FIELDS, Detector, GraphedEval, decode_topk_host, empty_detections
+from tubelet_transformer_amd.detect import FIELDS, Detector, GraphedEval, decode_topk_host, empty_detections, host_parts
 from tubelet_transformer_amd.misc import NestedTensor
 from tubelet_transformer_amd.tuber import build_model
 
@@ -286,6 +288,17 @@ def test_exact_ties_keep_query_then_class_order_and_k_cuts_by_it(dev):
     for K in (4, 1):
         want = _check_kernel(fx, K, dev, "top1 ties")
         assert want["queries"][0].tolist()[:2] == [4, 5][:K]
+
+
+def test_host_parts_is_one_copy_of_device_tensors(dev, monkeypatch):
+    """the mixed list of tests/test_detect_cpu.py on the device: every array as the tensor's own ``.cpu().numpy()``, one ``.cpu()`` in all"""
+    parts = [t for _, t in mixed_parts(dev)]
+    assert all(t.is_cuda for t in parts) and not parts[5].is_contiguous()
+    want = [t.cpu().numpy() for t in parts]
+    got, syncs = _count_syncs(monkeypatch, lambda: host_parts(parts))
+    assert syncs.count("cpu") == 1 and not {"item", "tolist", "synchronize"} & set(syncs), syncs
+    assert_same_arrays(got, want)
+    assert_same_arrays(got, [a for a, _ in mixed_parts()])
 
 
 def test_beyond_the_bounds_nothing_is_launched_and_the_detector_answers_by_the_fallback(dev):

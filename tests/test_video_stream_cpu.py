@@ -7,8 +7,8 @@ import itertools
 import numpy as np
 import pytest
 
-from tubelet_transformer_amd.evaluation import TubeLinker, link_rows
-from tubelet_transformer_amd.video import RULES, StreamSchedule, clip_indices, clip_span, frames_needed, ring_frames
+from tubelet_transformer_amd.evaluation import TubeLinker, link_rows, tubes_from_link
+from tubelet_transformer_amd.video import RULES, StreamSchedule, TubeAssembler, clip_indices, clip_span, frames_needed, ring_frames
 
 LINK_IOU = 0.25
 A = (0, 0, 10, 10)
@@ -142,6 +142,87 @@ def test_tube_linker_split_at_every_cut_and_pair_of_cuts_gives_the_same_records(
         assert same_records(pushed(linker, fx, 0, cut), whole), cut
     with pytest.raises(ValueError):
         linker.push(fx["box"][:K + 1], fx["label"][:K + 1], fx["score"][:K + 1], K + 1)      # another K inside a video
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# TubeAssembler: the host side of VideoStream.tubes()
+# ------------------------------------------------------------------------------------------------------------------------------
+STRIDE = 30                                                             # key frame number = key ordinal * STRIDE
+
+
+def wanted_tubes(fx, v, min_len):
+    """the tubes of one video by the one-shot definition, as ``VideoStream.tubes()`` gives them: ``tubes_from_link`` of ``link_rows``, frames as
+    key frame numbers, tubes shorter than ``min_len`` dropped"""
+    box, label, score, S = video_rows(fx, v)
+    got = one_shot(fx, v)
+    link = dict(layout=dict(videos=["video"], video_off=np.asarray([0, S]), first_frame=np.asarray([0])), row_head=got["row_head"],
+                row_slot=np.repeat(np.arange(S), fx["K"]), row_cls=label, tube_score=got["tube_score"], det_box=box)
+    return [dict(cls=t["cls"], score=t["score"], frames=[STRIDE * s for s in t["frames"]], boxes=t["boxes"], length=len(t["frames"]), head=t["head"])
+            for t in tubes_from_link(link) if len(t["frames"]) >= min_len]
+
+
+def assert_same_tube(got, want):
+    assert sorted(got) == sorted(want) == ["boxes", "cls", "frames", "head", "length", "score"]
+    assert (got["cls"], got["frames"], got["length"], got["head"]) == (want["cls"], want["frames"], want["length"], want["head"])
+    assert isinstance(got["score"], float) and np.float64(got["score"]).tobytes() == np.float64(want["score"]).tobytes()
+    assert got["boxes"].dtype == np.float32 and got["boxes"].shape == want["boxes"].shape and got["boxes"].tobytes() == want["boxes"].tobytes()
+
+
+def assembled(asm, linker, fx, v, cuts=()):
+    """one video through ``TubeLinker.push`` and ``TubeAssembler.add`` piece by piece, a ``take()`` after every piece, ``end()`` and a ``take()``
+    at the end -> [(next key ordinal, the tubes that take() returned, whether the video had ended)]"""
+    box, label, score, S = video_rows(fx, v)
+    K = fx["K"]
+    edges = [0] + sorted(cuts) + [S]
+    seen = []
+    for a, b in zip(edges[:-1], edges[1:]):
+        rec = linker.push(box[a * K:b * K], label[a * K:b * K], score[a * K:b * K], K)
+        n = b - a
+        asm.add(a, [STRIDE * s for s in range(a, b)], box[a * K:b * K].reshape(n, K, 4), label[a * K:b * K].reshape(n, K), rec["row_head"].reshape(n, K),
+                rec["row_score"].reshape(n, K), rec["row_len"].reshape(n, K))
+        seen.append((b, asm.take(), False))
+    asm.end()
+    seen.append((S, asm.take(), True))
+    assert asm.take() == []
+    return seen
+
+
+@pytest.mark.parametrize("name,min_len", [("lattice", 1), ("lattice", 2), ("ranked", 1), ("ranked", 2)])
+def test_the_tube_assembler_returns_the_one_shot_tubes_and_no_tube_before_it_is_closed(name, min_len):
+    fx = FIXTURES[name]()
+    S, gap = fx["videos"][0][1], fx["max_gap"]
+    want = wanted_tubes(fx, 0, min_len)
+    by_head = {t["head"]: t for t in want}
+    last = {h: t["frames"][-1] // STRIDE for h, t in by_head.items()}    # the key ordinal of a tube's last row
+    assert len(want) >= 2 and all(t["cls"] >= 1 for t in want) and max(t["length"] for t in want) >= 2
+    if min_len == 2:
+        assert len(want) < len(wanted_tubes(fx, 0, 1))                   # the filter drops something
+    linker, asm = TubeLinker(fx["C"], fx["link_iou"], gap), TubeAssembler(gap, min_len)
+    early = 0
+    for cut in [()] + [(c,) for c in range(1, S)] + list(itertools.combinations(range(1, S), 2)):
+        linker.reset()
+        done = set()
+        for next_ord, tubes, ended in assembled(asm, linker, fx, 0, cut):
+            assert [t["head"] for t in tubes] == sorted(t["head"] for t in tubes)          # head order within a call
+            assert not done & {t["head"] for t in tubes}                # a tube comes out once
+            for t in tubes:                                             # and whole: as the one-shot definition has it, no later slot extends it
+                assert_same_tube(t, by_head[t["head"]])
+            done |= {t["head"] for t in tubes}
+            if not ended:                                               # closed, no sooner and no later: no key frame to come can extend it
+                early += len(tubes)
+                assert done == {h for h in by_head if next_ord - last[h] > gap + 1}, (cut, next_ord)
+        assert done == set(by_head), cut
+    # some cut closes a tube while the video runs (the last cut point is key S - 1); the tube the fixtures guarantee may be a single detection
+    assert (early > 0) == any(S - 1 - o > gap + 1 for o in last.values())
+    assert early > 0 or min_len > 1
+    # the next video starts from head 0 again
+    linker.reset()
+    v = len(fx["videos"]) - 1
+    got = [t for _, tubes, _ in assembled(asm, linker, fx, v, (1,)) for t in tubes]
+    want = wanted_tubes(fx, v, min_len)
+    assert len(got) == len(want) >= 1 and min(t["head"] for t in got) == 0
+    for g, w in zip(sorted(got, key=lambda t: t["head"]), want):
+        assert_same_tube(g, w)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -321,49 +321,12 @@ class GraphedEval:
 # ---------------------------------------------------------------------------------------------------------------------
 # detections
 # ---------------------------------------------------------------------------------------------------------------------
-class Detections:
-    """Ranked detections of a batch as device tensors: boxes [B, K, 4] f32 xyxy pixels, scores / aux [B, K] f32, labels / queries [B, K]
-    i32 (-1 in empty rows), count [B] = min(total, K), total [B].  A detector's result is a view of its buffers: valid until its next call."""
-    __slots__ = FIELDS + ("_retry", "actors")
-
-    def __init__(self, boxes, scores, labels, queries, aux, count, total):
-        self.boxes, self.scores, self.labels, self.queries, self.aux, self.count, self.total = boxes, scores, labels, queries, aux, count, total
-        self._retry = None           # (ParamStore, callable -> Detections of the same batch): set by Detector, consumed by to_host
-        self.actors = None           # the ``Actors`` of the same batch: ``Detector(..., actors=A)``
-
-    def tensors(self):
-        return tuple(getattr(self, k) for k in FIELDS)
-
-    def _fetch(self, store):
-        """every field, and the cooperative decoder's error word when there is a store, in ONE device-to-host copy"""
-        parts = list(self.tensors()) + ([store.coop_sync] if store is not None else [])
-        blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()       # synchronises with the producing stream
-        host, o = [], 0
-        for t in parts:
-            n = t.numel() * t.element_size()
-            host.append(blob[o:o + n].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape)))
-            o += n
-        return dict(zip(FIELDS, host)), (host[-1] if store is not None else None)
-
-    def to_host(self):
-        """a list, per clip, of dicts of numpy arrays trimmed to ``count``.  The only place that synchronises; it reads the cooperative
-        decoder's error word there and, on a failure, runs the batch once more on the launch chain (a new key, hence a new capture)."""
-        retry, self._retry = self._retry, None
-        store, again = retry if retry is not None else (None, None)
-        host, word = self._fetch(store)
-        if word is not None and word[2] and not store.coop_off and store.coop_failed():
-            host, _ = again()._fetch(None)
-        out = []
-        for b in range(len(host["count"])):
-            n = int(host["count"][b])
-            d = {k: host[k][b, :n].copy() for k in ("boxes", "scores", "labels", "queries", "aux")}
-            d["count"], d["total"] = n, int(host["total"][b])
-            out.append(d)
-        return out
-
-
-def _host_parts(parts):
-    """the tensors ``parts`` as numpy arrays, in ONE device-to-host copy (it synchronises with the producing stream)"""
+def host_parts(parts):
+    """the tensors ``parts`` as typed, shaped numpy arrays, in ONE device-to-host copy (it synchronises with the producing stream); tensors that
+    are on the CPU already pass through without the concatenation.  All of ``parts`` are on one device.  The one packed copy of the package."""
+    parts = [t.contiguous() for t in parts]
+    if not any(t.is_cuda for t in parts):
+        return [t.numpy() for t in parts]
     blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
     host, o = [], 0
     for t in parts:
@@ -373,46 +336,97 @@ def _host_parts(parts):
     return host
 
 
-class Actors:
-    """The actors of a batch as device tensors (``decode_actors_host``): boxes [B, A, 4] f32 xyxy pixels, actor [B, A] f32 (the actor probability),
-    queries [B, A] i32 (-1 in empty rows), actions [B, A, C] f32 (every class's score ``sigmoid(logit) * actor``), count [B] = min(total, A),
-    total [B].  A detector's result is a view of its buffers: valid until its next call."""
-    __slots__ = ACTOR_FIELDS + ("_retry",)
+# dtype, shape behind the leading [clips] (n: the rows per clip, K or A; C: the classes) and the value in an empty result, per field name
+FIELD_SPEC = {"boxes": (torch.float32, ("n", 4), 0), "scores": (torch.float32, ("n",), 0), "labels": (torch.int32, ("n",), -1),
+              "queries": (torch.int32, ("n",), -1), "aux": (torch.float32, ("n",), 0), "actor": (torch.float32, ("n",), 0),
+              "actions": (torch.float32, ("n", "C"), 0), "count": (torch.int32, (), 0), "total": (torch.int32, (), 0)}
 
-    def __init__(self, boxes, actor, queries, actions, count, total):
-        self.boxes, self.actor, self.queries, self.actions, self.count, self.total = boxes, actor, queries, actions, count, total
-        self._retry = None           # (ParamStore, callable -> Actors of the same batch): set by Detector, consumed by to_host
+
+def field_tensors(fields, B, n, device, C=None, filled=True):
+    """the tensors of ``fields`` for B clips of n rows each: an empty result (zero, -1 in labels / queries), or uninitialised (``filled=False``)"""
+    out = []
+    for k in fields:
+        dtype, tail, fill = FIELD_SPEC[k]
+        shape = (B,) + tuple({"n": n, "C": C}.get(d, d) for d in tail)
+        out.append(torch.full(shape, fill, dtype=dtype, device=device) if filled else torch.empty(shape, dtype=dtype, device=device))
+    return out
+
+
+class Record:
+    """What the four result classes share.  ``FIELDS`` names the tensors of a result, ``ROW_FIELDS`` those with a row per detection, which
+    ``to_host`` trims to ``count``.  What a failed cooperative decoder launch means differs -- a detector's result runs its batch again, a
+    video's raises -- and stays in the ``to_host`` of either family."""
+    __slots__ = ()
+    FIELDS = ROW_FIELDS = ()
+
+    def __init__(self, *tensors):
+        for k, t in zip(self.FIELDS, tensors):
+            setattr(self, k, t)
 
     def tensors(self):
-        return tuple(getattr(self, k) for k in ACTOR_FIELDS)
+        return tuple(getattr(self, k) for k in self.FIELDS)
 
-    def _fetch(self, store):
-        host = _host_parts(list(self.tensors()) + ([store.coop_sync] if store is not None else []))
-        return dict(zip(ACTOR_FIELDS, host)), (host[-1] if store is not None else None)
+    def _fetch(self, extra=()):
+        """(every field as a dict of numpy arrays, the ``extra`` tensors -- the cooperative decoder's error word, link records -- as a list), in
+        ONE device-to-host copy"""
+        host = host_parts(list(self.tensors()) + list(extra))
+        return dict(zip(self.FIELDS, host)), host[len(self.FIELDS):]
+
+    def _trimmed(self, host, i, **first):
+        """row ``i`` of the fetched fields as a dict trimmed to its ``count``"""
+        n = int(host["count"][i])
+        return dict({k: host[k][i, :n].copy() for k in self.ROW_FIELDS}, **first, count=n, total=int(host["total"][i]))
+
+
+class _BatchRecord(Record):
+    """a ``Detector``'s result: the view of its buffers and the way to run the batch again"""
+    __slots__ = ("_retry",)
+
+    def __init__(self, *tensors):
+        super().__init__(*tensors)
+        self._retry = None           # (ParamStore, callable -> the same record of the same batch): set by Detector, consumed by to_host
 
     def to_host(self):
-        """a list, per clip, of dicts of numpy arrays trimmed to ``count`` (``boxes``, ``actor``, ``queries``, ``actions`` [count, C], ``count``,
-        ``total``): one copy, the only place that synchronises.  The fail-safe of ``Detections.to_host``: a poisoned forward has NaN actor
-        probabilities, hence no actor; the error word travels in the same copy and the batch runs once more on the launch chain."""
+        """a list, per clip, of dicts of numpy arrays trimmed to ``count``: one copy.  The only place that synchronises; it reads the cooperative
+        decoder's error word there and, on a failure, runs the batch once more on the launch chain (a new key, hence a new capture).  A
+        poisoned forward has NaN scores and NaN actor probabilities, hence neither a detection nor an actor."""
         retry, self._retry = self._retry, None
         store, again = retry if retry is not None else (None, None)
-        host, word = self._fetch(store)
-        if word is not None and word[2] and not store.coop_off and store.coop_failed():
-            host, _ = again()._fetch(None)
-        out = []
-        for b in range(len(host["count"])):
-            n = int(host["count"][b])
-            d = {k: host[k][b, :n].copy() for k in ("boxes", "actor", "queries", "actions")}
-            d["count"], d["total"] = n, int(host["total"][b])
-            out.append(d)
-        return out
+        host, word = self._fetch([store.coop_sync] if store is not None else [])
+        if word and word[0][2] and not store.coop_off and store.coop_failed():
+            host, _ = again()._fetch()
+        return [self._trimmed(host, b) for b in range(len(host["count"]))]
+
+
+class Detections(_BatchRecord):
+    """Ranked detections of a batch as device tensors: boxes [B, K, 4] f32 xyxy pixels, scores / aux [B, K] f32, labels / queries [B, K]
+    i32 (-1 in empty rows), count [B] = min(total, K), total [B].  A detector's result is a view of its buffers: valid until its next call."""
+    __slots__ = FIELDS + ("actors",)
+    FIELDS, ROW_FIELDS = FIELDS, FIELDS[:5]
+
+    def __init__(self, boxes, scores, labels, queries, aux, count, total):
+        super().__init__(boxes, scores, labels, queries, aux, count, total)
+        self.actors = None           # the ``Actors`` of the same batch: ``Detector(..., actors=A)``
+
+
+class Actors(_BatchRecord):
+    """The actors of a batch as device tensors (``decode_actors_host``): boxes [B, A, 4] f32 xyxy pixels, actor [B, A] f32 (the actor probability),
+    queries [B, A] i32 (-1 in empty rows), actions [B, A, C] f32 (every class's score ``sigmoid(logit) * actor``), count [B] = min(total, A),
+    total [B].  A detector's result is a view of its buffers: valid until its next call.  ``to_host()``: ``boxes``, ``actor``, ``queries``,
+    ``actions`` [count, C], ``count``, ``total`` per clip."""
+    __slots__ = ACTOR_FIELDS
+    FIELDS, ROW_FIELDS = ACTOR_FIELDS, ACTOR_FIELDS[:4]
+
+    def __init__(self, boxes, actor, queries, actions, count, total):
+        super().__init__(boxes, actor, queries, actions, count, total)
+
+
+def empty_detections(B, K, device):
+    return Detections(*field_tensors(FIELDS, B, K, device))
 
 
 def empty_actors(B, A, C, device):
-    f32, i32 = torch.float32, torch.int32
-    return Actors(torch.zeros(B, A, 4, dtype=f32, device=device), torch.zeros(B, A, dtype=f32, device=device),
-                  torch.full((B, A), -1, dtype=i32, device=device), torch.zeros(B, A, C, dtype=f32, device=device),
-                  torch.zeros(B, dtype=i32, device=device), torch.zeros(B, dtype=i32, device=device))
+    return Actors(*field_tensors(ACTOR_FIELDS, B, A, device, C))
 
 
 def actors_launch(logits, logits_b, boxes, sizes, q_begin, Qs, actor_thr, A, out=None):
@@ -475,14 +489,6 @@ def detect_launch(mode, logits, logits_b, boxes, sizes, q_begin, Qs, actor_thr, 
     lib.call("tuber_detect_ava" if mode == "ava" else "tuber_detect_top1", logits, logits_b, boxes, sizes, q_begin, B, Qtot, Qs, C, NB, lb_rows,
              dtypes, float(actor_thr), float(score_thr), int(K), *out.tensors())
     return out
-
-
-def empty_detections(B, K, device):
-    f32, i32 = torch.float32, torch.int32
-    return Detections(torch.zeros(B, K, 4, dtype=f32, device=device), torch.zeros(B, K, dtype=f32, device=device),
-                      torch.full((B, K), -1, dtype=i32, device=device), torch.full((B, K), -1, dtype=i32, device=device),
-                      torch.zeros(B, K, dtype=f32, device=device), torch.zeros(B, dtype=i32, device=device),
-                      torch.zeros(B, dtype=i32, device=device))
 
 
 class Detector:

@@ -34,6 +34,54 @@ from . import evaluation as _ev
 log = logging.getLogger(__name__)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# the host side of the tube kernels (csrc/tube_map.hip), shared with video.py
+# ---------------------------------------------------------------------------------------------------------------------------------------
+LINK_NAMES = ("row_cls", "row_head", "tube_score", "tube_len", "tube_last")
+
+
+def link_records(N, dev):
+    """the five link-record tensors of N rows as the linkers want them: ``row_cls`` / ``row_head`` are written for every row, ``tube_score`` /
+    ``tube_len`` / ``tube_last`` at head rows only, hence their fill"""
+    i32 = torch.int32
+    return dict(row_cls=torch.empty(N, dtype=i32, device=dev), row_head=torch.empty(N, dtype=i32, device=dev),
+                tube_score=torch.zeros(N, dtype=torch.float64, device=dev), tube_len=torch.zeros(N, dtype=i32, device=dev),
+                tube_last=torch.full((N,), -1, dtype=i32, device=dev))
+
+
+def link_limits():
+    """(the most rows per slot, the most active tubes) the linkers take"""
+    return lib.query("tuber_frame_match_max_dets"), lib.query("tuber_tube_link_max_active")
+
+
+def link_beyond(what, rows, max_gap):
+    """why the linker cannot take ``rows`` rows per slot with ``max_gap`` (``what`` names them), or None"""
+    most, active = link_limits()
+    return "%s: beyond %d rows or %d active tubes" % (what, most, active) if rows > most or rows * (max_gap + 1) > active else None
+
+
+def link_ranked(boxes, labels, scores, C, link_iou, max_gap):
+    """``tuber_tube_link_ranked`` over the padded store [S][K] of one video as it is -> (link records, slot_off, video_off) on the device"""
+    S, K = scores.shape
+    dev = boxes.device
+    slot_off = torch.arange(S + 1, dtype=torch.int32, device=dev) * K                   # rows behind a key's count carry label -1: not counted
+    video_off = torch.tensor([0, S], dtype=torch.int32).to(dev)
+    link = link_records(S * K, dev)
+    lib.call("tuber_tube_link_ranked", boxes.contiguous(), labels.contiguous(), scores.contiguous(), slot_off, video_off, 1, S, S * K, int(C), K,
+             float(link_iou), int(max_gap), *(link[k] for k in LINK_NAMES))
+    return link, slot_off, video_off
+
+
+def tube_nms_launch(boxes, slot_off, video_off, link, V, S, N, C, max_rows, min_len, iou):
+    """``tuber_tube_nms`` over a device link record -> tube_keep [N] uint8 on the device (1 kept head, 0 suppressed head, 2 not a head or
+    shorter than ``min_len``, 3 a (video, class) beyond the kernel's bound)"""
+    keep = torch.full((N,), 2, dtype=torch.uint8, device=boxes.device)
+    work = torch.empty(max(lib.query("tuber_tube_nms_work_bytes", N), 16), dtype=torch.uint8, device=boxes.device)
+    lib.call("tuber_tube_nms", boxes, slot_off, video_off, *(link[k] for k in LINK_NAMES), int(V), int(S), N, int(C), int(max_rows), int(min_len),
+             float(iou), work, keep)
+    return keep
+
+
 class DeviceFrameMAP:
     """Arguments as ``evaluation.FrameMAP``; ``device``: where the detection buffers live (a CPU store runs the host evaluator)."""
 
@@ -540,9 +588,9 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
     def _video_beyond(self, a):
         if not a["layout"]["parsed"]:
             return "a key is not of the form <video>-<frame number>"
-        if a["max_rows"] > lib.query("tuber_frame_match_max_dets") or a["max_rows"] * (self.max_gap + 1) > lib.query("tuber_tube_link_max_active"):
-            return "%d rows in a frame with MAX_GAP %d: beyond %d rows or %d active tubes" % (
-                a["max_rows"], self.max_gap, lib.query("tuber_frame_match_max_dets"), lib.query("tuber_tube_link_max_active"))
+        why = link_beyond("%d rows in a frame with MAX_GAP %d" % (a["max_rows"], self.max_gap), a["max_rows"], self.max_gap)
+        if why:
+            return why
         if a["max_gt_rows"] > lib.query("tuber_frame_match_max_gt") or a["max_gt_tubes"] > lib.query("tuber_tube_match_max_gt"):
             return "%d ground-truth boxes in a frame / %d ground-truth tubes in a (video, class): beyond %d / %d" % (
                 a["max_gt_rows"], a["max_gt_tubes"], lib.query("tuber_frame_match_max_gt"), lib.query("tuber_tube_match_max_gt"))
@@ -562,23 +610,14 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
             host = self.to_video_host_evaluator().link()
             return {k: (torch.from_numpy(np.ascontiguousarray(v)) if isinstance(v, np.ndarray) else v) for k, v in host.items() if k != "tubes"}
         N, dev = a["N"], self.device
-        out = dict(order=a["order"], det_box=a["det_box"], det_prob=a["det_prob"], row_slot=a["row_slot"], layout=a["layout"],
-                   row_cls=torch.empty(N, dtype=torch.int32, device=dev), row_head=torch.empty(N, dtype=torch.int32, device=dev),
-                   tube_score=torch.zeros(N, dtype=torch.float64, device=dev), tube_len=torch.zeros(N, dtype=torch.int32, device=dev),
-                   tube_last=torch.full((N,), -1, dtype=torch.int32, device=dev))
+        out = dict(link_records(N, dev), order=a["order"], det_box=a["det_box"], det_prob=a["det_prob"], row_slot=a["row_slot"], layout=a["layout"])
         lib.call("tuber_tube_link", a["det_box"], a["det_prob"], a["slot_off"], a["video_off"], a["V"], a["S"], N, a["C"], a["max_rows"],
-                 self.link_iou, self.max_gap, out["row_cls"], out["row_head"], out["tube_score"], out["tube_len"], out["tube_last"])
+                 self.link_iou, self.max_gap, *(out[k] for k in LINK_NAMES))
         return out
 
     def nms(self, a, link):
-        """``tuber_tube_nms`` over a device link record -> tube_keep [N] uint8 on the device (1 kept head, 0 suppressed head, 2 not a head or
-        shorter than ``min_len``, 3 a (video, class) beyond the kernel's bound)"""
-        N, dev = a["N"], self.device
-        keep = torch.full((N,), 2, dtype=torch.uint8, device=dev)
-        work = torch.empty(max(lib.query("tuber_tube_nms_work_bytes", N), 16), dtype=torch.uint8, device=dev)
-        lib.call("tuber_tube_nms", a["det_box"], a["slot_off"], a["video_off"], link["row_cls"], link["row_head"], link["tube_score"],
-                 link["tube_len"], link["tube_last"], a["V"], a["S"], N, a["C"], a["max_rows"], self.min_len, self.tube_nms, work, keep)
-        return keep
+        """``tube_nms_launch`` over the store's device link record -> tube_keep [N] uint8 on the device"""
+        return tube_nms_launch(a["det_box"], a["slot_off"], a["video_off"], link, a["V"], a["S"], a["N"], a["C"], a["max_rows"], self.min_len, self.tube_nms)
 
     def tubes(self):
         """the linked tubes read back: a list of dict(video, cls (1-based), score, frames, boxes, head, rows) in head order; with ``tube_nms``

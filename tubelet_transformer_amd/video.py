@@ -22,7 +22,8 @@ import torch
 
 from . import input_pipeline as ip
 from . import lib
-from .detect import ACTOR_FIELDS, FIELDS, Detector
+from .detect import ACTOR_FIELDS, FIELDS, Detector, Record, field_tensors, host_parts
+from .device_map import link_beyond, link_limits, link_ranked, tube_nms_launch
 from .misc import NestedTensor
 
 RULES = ("ava", "jhmdb", "edge")
@@ -91,91 +92,80 @@ def _nms_value(who, nms):
     return nms
 
 
-def _nms_device(boxes, slot_off, video_off, link, S, N, C, K, min_len, nms):
-    """``tuber_tube_nms`` behind ``tuber_tube_link_ranked`` over a padded [S][K] store -> tube_keep [N] uint8 on the device"""
-    keep = torch.full((N,), 2, dtype=torch.uint8, device=boxes.device)
-    work = torch.empty(max(lib.query("tuber_tube_nms_work_bytes", N), 16), dtype=torch.uint8, device=boxes.device)
-    lib.call("tuber_tube_nms", boxes, slot_off, video_off, link["row_cls"], link["row_head"], link["tube_score"], link["tube_len"], link["tube_last"], 1,
-             S, N, int(C), K, max(int(min_len), 1), float(nms), work, keep)
-    return keep
+def _track_labels(mean, label_thr):
+    """the 0-based classes with ``mean >= label_thr`` by mean descending, then class"""
+    with np.errstate(invalid="ignore"):
+        return sorted(np.nonzero(mean >= label_thr)[0].tolist(), key=lambda c: (-mean[c], c))
 
 
-class VideoDetections:
+class _VideoRecord(Record):
+    """What ``VideoDetections`` and ``VideoActors`` share: a row per key frame, the defaults of ``tubes()`` / ``tracks()``, and ``to_host``."""
+
+    def __init__(self, keys, tensors, settings, store, nms_iou):
+        super().__init__(*tensors)
+        self.keys = [int(k) for k in keys]
+        self.nms_iou = None if nms_iou is None else float(nms_iou)                      # the default of tubes(nms=) / tracks(nms=): CONFIG.VAL.TUBE_NMS
+        self.settings = dict(settings)
+        self._store = store                                                            # the engine's ParamStore: to_host reads its error word
+        self.row_head = self.row_score = self.row_len = None                           # the link records of a VideoStream push
+        if not all(len(self.keys) == t.shape[0] for t in tensors):
+            raise ValueError("%s: %d keys, %d rows" % (type(self).__name__, len(self.keys), self.boxes.shape[0]))
+
+    def to_host(self):
+        """a list, per key frame, of dicts of numpy arrays trimmed to ``count`` (``key``, the per-row fields, ``count``, ``total``): one copy, the
+        place that synchronises.  A cooperative decoder launch that timed out during the video leaves empty key frames (detect.py,
+        "Fail-safe"); its error word travels in the same copy and raises here, the engine having switched to the launch chain: run the video
+        again."""
+        word = [self._store.coop_sync] if self._store is not None and self.boxes.device.type == "cuda" else []
+        host, word = self._fetch(word)
+        if word and word[0][2] and not self._store.coop_off:
+            self._store.check_coop()
+        return [self._trimmed(host, i, key=key) for i, key in enumerate(self.keys)]
+
+    def _keep(self, host, link, nms, min_len):
+        """None without ``nms``; else the kernel's ``tube_keep``, or ``evaluation.tube_nms`` over the host record ``link`` on the host path and at
+        the kernel's escape"""
+        from .evaluation import tube_nms
+        if nms is None:
+            return None
+        keep = host.get("tube_keep")
+        return tube_nms(link, nms, max(min_len, 1)) if keep is None or (keep == 3).any() else keep      # the host path, or the kernel's escape
+
+    def _linked(self, link, slot_off, video_off, names, C, nms, min_len):
+        """the fields and the link records ``names`` (with ``nms``, ``tube_keep`` of ``tuber_tube_nms`` as well) as one dict, in one copy"""
+        S, n = self.boxes.shape[:2]
+        if nms is not None:
+            link["tube_keep"] = tube_nms_launch(self.boxes.contiguous(), slot_off, video_off, link, 1, S, S * n, C, n, max(int(min_len), 1), nms)
+            names += ("tube_keep",)
+        host, records = self._fetch([link[k] for k in names])
+        return dict(host, **dict(zip(names, records)))
+
+
+class VideoDetections(_VideoRecord):
     """The ranked detections of a video's key frames: ``keys`` (frame numbers) and, as tensors on one device, ``boxes`` [n, K, 4] fp32 xyxy in
     source-video pixels, ``scores`` / ``aux`` [n, K] fp32, ``labels`` / ``queries`` [n, K] int32 (-1 in the rows behind ``count``), ``count`` /
     ``total`` [n] int32 -- the fields of ``detect.Detections``, a row per key frame."""
+    FIELDS, ROW_FIELDS = FIELDS, FIELDS[:5]
 
     def __init__(self, keys, boxes, scores, labels, queries, aux, count, total, class_num, settings=None, store=None, nms_iou=None):
-        self.keys = [int(k) for k in keys]
-        self.nms_iou = None if nms_iou is None else float(nms_iou)                      # the default of tubes(nms=): CONFIG.VAL.TUBE_NMS.IOU
-        self.boxes, self.scores, self.labels, self.queries, self.aux, self.count, self.total = boxes, scores, labels, queries, aux, count, total
+        # the defaults of tubes(): CONFIG.VAL.VIDEO_MAP, CONFIG.VAL.TUBE_NMS.IOU
+        super().__init__(keys, (boxes, scores, labels, queries, aux, count, total), settings or dict(link_iou=0.2, max_gap=2, min_len=1), store, nms_iou)
         self.class_num = int(class_num)
-        self.settings = dict(settings or dict(link_iou=0.2, max_gap=2, min_len=1))      # the defaults of tubes(): CONFIG.VAL.VIDEO_MAP
         self.tubes_path = None                                                         # "device" or "host" after tubes()
-        self._store = store                                                            # the engine's ParamStore: to_host reads its error word
-        self.row_head = self.row_score = self.row_len = None                           # the link records of a VideoStream push (link=True)
         self.actors = None                                                             # the ``VideoActors`` of ``VideoDetector(..., actors=A)``
-        if not (len(self.keys) == boxes.shape[0] == scores.shape[0] == count.shape[0]):
-            raise ValueError("VideoDetections: %d keys, %d rows" % (len(self.keys), boxes.shape[0]))
-
-    def tensors(self):
-        return tuple(getattr(self, k) for k in FIELDS)
-
-    def _fetch(self, extra=()):
-        """every field (and ``extra`` tensors) as numpy arrays, in ONE device-to-host copy"""
-        parts = [t.contiguous() for t in list(self.tensors()) + list(extra)]
-        if self.boxes.device.type != "cuda":
-            return [t.numpy() for t in parts]
-        blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
-        host, o = [], 0
-        for t in parts:
-            n = t.numel() * t.element_size()
-            host.append(blob[o:o + n].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape)))
-            o += n
-        return host
-
-    def to_host(self):
-        """a list, per key frame, of dicts of numpy arrays trimmed to ``count`` (``key``, ``boxes``, ``scores``, ``labels``, ``queries``, ``aux``,
-        ``count``, ``total``): one copy, the place that synchronises.  A cooperative decoder launch that timed out during the video leaves empty
-        key frames (detect.py, "Fail-safe"); its error word travels in the same copy and raises here, the engine having switched to the launch
-        chain: run the video again."""
-        word = [self._store.coop_sync] if self._store is not None and self.boxes.device.type == "cuda" else []
-        host = self._fetch(word)
-        if word and host[-1][2] and not self._store.coop_off:
-            self._store.check_coop()
-        host = dict(zip(FIELDS, host))
-        out = []
-        for i, key in enumerate(self.keys):
-            n = int(host["count"][i])
-            d = {k: host[k][i, :n].copy() for k in ("boxes", "scores", "labels", "queries", "aux")}
-            d["key"], d["count"], d["total"] = key, n, int(host["total"][i])
-            out.append(d)
-        return out
 
     # -- tubes ------------------------------------------------------------------------------------------------------------
     def _link_device(self, link_iou, max_gap, nms=None, min_len=1):
         """``tuber_tube_link_ranked`` (and, with ``nms``, ``tuber_tube_nms`` behind it) over the padded store as it is, or None where the
         linker's bounds refuse it"""
-        S, K = self.scores.shape
+        K = self.scores.shape[1]
         if self.boxes.device.type != "cuda":
             return None, "the store is on the CPU"
-        if K > lib.query("tuber_frame_match_max_dets") or K * (max_gap + 1) > lib.query("tuber_tube_link_max_active"):
-            return None, "%d rows per key frame with max_gap %d: beyond %d rows or %d active tubes" % (
-                K, max_gap, lib.query("tuber_frame_match_max_dets"), lib.query("tuber_tube_link_max_active"))
-        dev, N = self.boxes.device, S * K
-        slot_off = torch.arange(S + 1, dtype=torch.int32, device=dev) * K               # rows behind a key's count carry label -1: not counted
-        video_off = torch.tensor([0, S], dtype=torch.int32).to(dev)
-        out = dict(row_cls=torch.empty(N, dtype=torch.int32, device=dev), row_head=torch.empty(N, dtype=torch.int32, device=dev),
-                   tube_score=torch.zeros(N, dtype=torch.float64, device=dev), tube_len=torch.zeros(N, dtype=torch.int32, device=dev),
-                   tube_last=torch.full((N,), -1, dtype=torch.int32, device=dev))
-        lib.call("tuber_tube_link_ranked", self.boxes.contiguous(), self.labels.contiguous(), self.scores.contiguous(), slot_off, video_off, 1, S, N,
-                 self.class_num, K, float(link_iou), int(max_gap), out["row_cls"], out["row_head"], out["tube_score"], out["tube_len"], out["tube_last"])
-        names = ("row_head", "tube_score", "tube_len", "tube_last")
-        if nms is not None:
-            out["tube_keep"] = _nms_device(self.boxes.contiguous(), slot_off, video_off, out, S, N, self.class_num, K, min_len, nms)
-            names += ("tube_keep",)
-        host = self._fetch([out[k] for k in names])
-        return dict(zip(FIELDS + names, host)), None
+        why = link_beyond("%d rows per key frame with max_gap %d" % (K, max_gap), K, max_gap)
+        if why:
+            return None, why
+        link, slot_off, video_off = link_ranked(self.boxes, self.labels, self.scores, self.class_num, link_iou, max_gap)
+        return self._linked(link, slot_off, video_off, ("row_head", "tube_score", "tube_len", "tube_last"), self.class_num, nms, min_len), None
 
     def tubes(self, link_iou=None, max_gap=None, min_len=None, nms=None):
         """The action tubes of the video: a list of ``dict(cls, score, frames, boxes, length)`` in head order (the order of the tubes' first
@@ -188,7 +178,7 @@ class VideoDetections:
         ``CONFIG.VAL.TUBE_NMS.IOU``; None: off): per class a tube whose spatio-temporal IoU with a higher-scored kept tube exceeds it is
         dropped -- one more launch, ``tuber_tube_nms``, whose bytes travel in the same copy; on the host path
         ``evaluation.tube_nms``."""
-        from .evaluation import link_rows, tube_nms, tubes_from_link
+        from .evaluation import link_rows, tubes_from_link
         nms = _nms_value("VideoDetections.tubes", self.nms_iou if nms is None else nms)
         link_iou = float(self.settings["link_iou"] if link_iou is None else link_iou)
         max_gap = int(self.settings["max_gap"] if max_gap is None else max_gap)
@@ -198,18 +188,14 @@ class VideoDetections:
         host, why = self._link_device(link_iou, max_gap, nms, min_len)
         if host is None:
             print("[tuber] VideoDetections.tubes: %s; linking on the host" % why, file=sys.stderr, flush=True)
-            host = dict(zip(FIELDS, self._fetch()))
+            host = self._fetch()[0]
             host.update(link_rows(host["boxes"].reshape(-1, 4), host["labels"].reshape(-1), host["scores"].reshape(-1), slot, [0, S], self.class_num,
                                   link_iou, max_gap))
         self.tubes_path = "host" if why else "device"
         layout = dict(videos=["video"], video_off=np.asarray([0, S]), first_frame=np.asarray([0]))
         link = dict(layout=layout, row_head=host["row_head"], row_slot=slot, row_cls=host["labels"].reshape(-1), tube_score=host["tube_score"],
                     det_box=host["boxes"].reshape(-1, 4))
-        keep = None
-        if nms is not None:
-            keep = host.get("tube_keep")
-            if keep is None or (keep == 3).any():                                      # the host path, or the kernel's escape
-                keep = tube_nms(link, nms, max(min_len, 1))
+        keep = self._keep(host, link, nms, min_len)
         out = []
         for t in tubes_from_link(link):
             if len(t["frames"]) >= min_len and (keep is None or keep[t["head"]] != 0):
@@ -217,59 +203,22 @@ class VideoDetections:
         return out
 
 
-class VideoActors:
+class VideoActors(_VideoRecord):
     """The actors of a video's key frames (``VideoDetector(..., actors=A)``): ``keys`` (frame numbers) and, as tensors on one
     device, ``boxes`` [n, A, 4] fp32 xyxy in source-video pixels, ``actor`` [n, A] fp32 (the actor probability), ``queries`` [n, A] int32 (-1 in
     the rows behind ``count``), ``actions`` [n, A, C] fp32 (every class's score), ``count`` / ``total`` [n] int32 -- the fields of
     ``detect.Actors``, a row per key frame."""
+    FIELDS, ROW_FIELDS = ACTOR_FIELDS, ACTOR_FIELDS[:4]
 
     def __init__(self, keys, boxes, actor, queries, actions, count, total, settings=None, store=None, nms_iou=None):
-        self.keys = [int(k) for k in keys]
-        self.nms_iou = None if nms_iou is None else float(nms_iou)                      # the default of tracks(nms=): CONFIG.VAL.TUBE_NMS.ACTORS_IOU
-        self.boxes, self.actor, self.queries, self.actions, self.count, self.total = boxes, actor, queries, actions, count, total
+        # the defaults of tracks(): CONFIG.VAL.ACTORS, CONFIG.VAL.TUBE_NMS.ACTORS_IOU
+        super().__init__(keys, (boxes, actor, queries, actions, count, total),
+                         settings or dict(link_iou=0.2, max_gap=2, min_len=1, window=1, label_thr=0.05), store, nms_iou)
         self.class_num = int(actions.shape[2])
-        # the defaults of tracks(): CONFIG.VAL.ACTORS
-        self.settings = dict(settings or dict(link_iou=0.2, max_gap=2, min_len=1, window=1, label_thr=0.05))
         self.tracks_path = None                                                        # "device" or "host" after tracks()
-        self._store = store
         # the track records of a VideoStream(actors=A) push: row_head / row_score / row_len [n, A], row_mean / row_peak [n, A, C], smooth [m, A, C]
-        self.row_head = self.row_score = self.row_len = self.row_mean = self.row_peak = self.smooth = None
+        self.row_mean = self.row_peak = self.smooth = None
         self.smooth_first = None                                                       # the key ordinal of smooth's first slot (a host int)
-        if not (len(self.keys) == boxes.shape[0] == actor.shape[0] == actions.shape[0] == count.shape[0]):
-            raise ValueError("VideoActors: %d keys, %d rows" % (len(self.keys), boxes.shape[0]))
-
-    def tensors(self):
-        return tuple(getattr(self, k) for k in ACTOR_FIELDS)
-
-    def _fetch(self, extra=()):
-        """every field (and ``extra`` tensors) as numpy arrays, in ONE device-to-host copy"""
-        parts = [t.contiguous() for t in list(self.tensors()) + list(extra)]
-        if self.boxes.device.type != "cuda":
-            return [t.numpy() for t in parts]
-        blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
-        host, o = [], 0
-        for t in parts:
-            n = t.numel() * t.element_size()
-            host.append(blob[o:o + n].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape)))
-            o += n
-        return host
-
-    def to_host(self):
-        """a list, per key frame, of dicts of numpy arrays trimmed to ``count`` (``key``, ``boxes``, ``actor``, ``queries``, ``actions``,
-        ``count``, ``total``): one copy, the place that synchronises; the cooperative decoder's error word travels in it and raises here, as in
-        ``VideoDetections.to_host``."""
-        word = [self._store.coop_sync] if self._store is not None and self.boxes.device.type == "cuda" else []
-        host = self._fetch(word)
-        if word and host[-1][2] and not self._store.coop_off:
-            self._store.check_coop()
-        host = dict(zip(ACTOR_FIELDS, host))
-        out = []
-        for i, key in enumerate(self.keys):
-            n = int(host["count"][i])
-            d = {k: host[k][i, :n].copy() for k in ("boxes", "actor", "queries", "actions")}
-            d["key"], d["count"], d["total"] = key, n, int(host["total"][i])
-            out.append(d)
-        return out
 
     # -- tracks -----------------------------------------------------------------------------------------------------------
     NAMES = ("row_head", "tube_score", "tube_len", "tube_last", "row_smooth", "track_mean", "track_peak")
@@ -280,30 +229,18 @@ class VideoActors:
         S, A, C = self.actions.shape
         if self.boxes.device.type != "cuda":
             return None, "the store is on the CPU"
-        rows, active = lib.query("tuber_frame_match_max_dets"), lib.query("tuber_tube_link_max_active")
-        max_a, max_c = lib.query("tuber_track_actions_limits", 0), lib.query("tuber_track_actions_limits", 1)
+        (rows, active), max_a, max_c = link_limits(), lib.query("tuber_track_actions_limits", 0), lib.query("tuber_track_actions_limits", 1)
         if A > min(rows, max_a) or A * (max_gap + 1) > active or C > max_c:
             return None, "%d actors per key frame with max_gap %d and %d classes: beyond %d rows, %d active tracks or %d classes" % (
                 A, max_gap, C, min(rows, max_a), active, max_c)
-        dev, N = self.boxes.device, S * A
-        f64, i32 = torch.float64, torch.int32
-        slot_off = torch.arange(S + 1, dtype=i32, device=dev) * A
-        video_off = torch.tensor([0, S], dtype=i32).to(dev)
-        label = torch.where(self.queries >= 0, 0, -1).to(i32).contiguous()               # one class; a row behind its key's count is not counted
-        out = dict(row_cls=torch.empty(N, dtype=i32, device=dev), row_head=torch.empty(N, dtype=i32, device=dev),
-                   tube_score=torch.zeros(N, dtype=f64, device=dev), tube_len=torch.zeros(N, dtype=i32, device=dev),
-                   tube_last=torch.full((N,), -1, dtype=i32, device=dev), row_smooth=torch.empty(N, C, dtype=f64, device=dev),
-                   track_mean=torch.empty(N, C, dtype=f64, device=dev), track_peak=torch.empty(N, C, dtype=torch.float32, device=dev))
-        lib.call("tuber_tube_link_ranked", self.boxes.contiguous(), label, self.actor.contiguous(), slot_off, video_off, 1, S, N, 1, A, float(link_iou),
-                 int(max_gap), out["row_cls"], out["row_head"], out["tube_score"], out["tube_len"], out["tube_last"])
-        lib.call("tuber_track_actions", self.actions.contiguous(), out["row_head"], out["tube_last"], S, A, C, int(window), out["row_smooth"],
-                 out["track_mean"], out["track_peak"])
-        names = self.NAMES
-        if nms is not None:
-            out["tube_keep"] = _nms_device(self.boxes.contiguous(), slot_off, video_off, out, S, N, 1, A, min_len, nms)
-            names += ("tube_keep",)
-        host = self._fetch([out[k] for k in names])
-        return dict(zip(ACTOR_FIELDS + names, host)), None
+        label = torch.where(self.queries >= 0, 0, -1).to(torch.int32)                   # one class; a row behind its key's count is not counted
+        link, slot_off, video_off = link_ranked(self.boxes, label, self.actor, 1, link_iou, max_gap)
+        f64 = torch.float64
+        link.update(row_smooth=torch.empty(S * A, C, dtype=f64, device=label.device), track_mean=torch.empty(S * A, C, dtype=f64, device=label.device),
+                    track_peak=torch.empty(S * A, C, dtype=torch.float32, device=label.device))
+        lib.call("tuber_track_actions", self.actions.contiguous(), link["row_head"], link["tube_last"], S, A, C, int(window), link["row_smooth"],
+                 link["track_mean"], link["track_peak"])
+        return self._linked(link, slot_off, video_off, self.NAMES, 1, nms, min_len), None
 
     def tracks(self, link_iou=None, max_gap=None, min_len=None, window=None, label_thr=None, nms=None):
         """The actor tracks of the video -- who is there, from when to when, doing what: a list, in head order (the order of the tracks' first
@@ -317,7 +254,7 @@ class VideoActors:
         instead of "device".  ``nms`` (default: ``CONFIG.VAL.TUBE_NMS.ACTORS_IOU``; None: off): a track whose spatio-temporal IoU with a
         kept track of higher mean actor probability exceeds it is dropped, class-agnostically: ``tuber_tube_nms`` on
         the device, ``evaluation.tube_nms`` on the host path.  The aggregates of the kept tracks are unchanged."""
-        from .evaluation import actor_tracks, tube_nms
+        from .evaluation import actor_tracks
         nms = _nms_value("VideoActors.tracks", self.nms_iou if nms is None else nms)
         st = self.settings
         link_iou = float(st["link_iou"] if link_iou is None else link_iou)
@@ -331,7 +268,7 @@ class VideoActors:
         host, why = self._tracks_device(link_iou, max_gap, window, nms, min_len)
         if host is None:
             print("[tuber] VideoActors.tracks: %s; tracks on the host" % why, file=sys.stderr, flush=True)
-            host = dict(zip(ACTOR_FIELDS, self._fetch()))
+            host = self._fetch()[0]
             host.update(actor_tracks(host["boxes"], host["actor"], host["queries"], host["actions"], S, A, link_iou, max_gap, window))
         self.tracks_path = "host" if why else "device"
         head = np.asarray(host["row_head"]).reshape(-1)
@@ -339,27 +276,113 @@ class VideoActors:
         members = {}
         for r in np.nonzero(head >= 0)[0].tolist():
             members.setdefault(int(head[r]), []).append(r)
-        keep = None
-        if nms is not None:
-            keep = host.get("tube_keep")
-            if keep is None or (keep == 3).any():                                      # the host path, or the kernel's escape
-                keep = tube_nms(dict(layout=dict(video_off=np.asarray([0, S])), row_head=head, row_slot=np.repeat(np.arange(S, dtype=np.int64), A),
-                                     row_cls=np.where(query >= 0, 0, -1), tube_score=host["tube_score"], det_box=box), nms, max(min_len, 1))
+        keep = self._keep(host, dict(layout=dict(video_off=np.asarray([0, S])), row_head=head, row_slot=np.repeat(np.arange(S, dtype=np.int64), A),
+                                     row_cls=np.where(query >= 0, 0, -1), tube_score=host["tube_score"], det_box=box), nms, min_len)
         out = []
         for h in sorted(members):
             rows = members[h]
             if len(rows) < min_len or (keep is not None and keep[h] == 0):
                 continue
             mean = np.array(host["track_mean"][h], dtype=np.float64)
-            with np.errstate(invalid="ignore"):
-                labels = sorted(np.nonzero(mean >= label_thr)[0].tolist(), key=lambda c: (-mean[c], c))
             out.append(dict(score=float(host["tube_score"][h]), frames=[self.keys[r // A] for r in rows], boxes=box[rows].copy(), actor=actor[rows].copy(),
                             queries=query[rows].copy(), actions=act[rows].copy(), smooth=np.array(host["row_smooth"][rows], dtype=np.float64), mean=mean,
-                            peak=np.array(host["track_peak"][h], dtype=np.float32), labels=labels, length=len(rows)))
+                            peak=np.array(host["track_peak"][h], dtype=np.float32), labels=_track_labels(mean, label_thr), length=len(rows)))
         return out
 
 
-class VideoDetector:
+class _VideoRunner:
+    """What ``VideoDetector`` and ``VideoStream`` share: the settings, the checks of a call, the buffers of a video size, the resize launch and the
+    ``Detector`` run over the clip buffer.  Where the frames come from (the resident video and its index table, or the ring and its rule) and
+    what becomes of the rows is the subclass's."""
+
+    def __init__(self, cfg, model, batch, score_thr, topk, actor_thr, graphed, rule, actors):
+        from .config import actor_settings, detect_settings, video_map_settings
+        self.cfg, self.model, self.batch = cfg, model, int(batch)
+        vm = video_map_settings(cfg)
+        self.settings = dict(link_iou=float(vm["link_iou"]), max_gap=int(vm["max_gap"]), min_len=int(vm["min_len"]))
+        if topk is None:
+            topk = max(1, min(detect_settings(cfg)["topk"], lib.query("tuber_tube_link_max_active") // (self.settings["max_gap"] + 1)))
+        self.detector = Detector(cfg, model, score_thr=score_thr, topk=topk, actor_thr=actor_thr, graphed=graphed, actors=actors)
+        self.actor_settings = None
+        if actors is not None:
+            st = actor_settings(cfg)
+            self.actor_settings = {k: st[k] for k in ("link_iou", "max_gap", "min_len", "window", "label_thr")}
+        self.mode = model.dataset_mode
+        self.rule = rule if rule is not None else ("ava" if self.mode == "ava" else "jhmdb")
+        if self.rule not in RULES:
+            raise ValueError("%s: rule %r is not one of %s" % (type(self).__name__, rule, ", ".join(RULES)))
+        D = cfg.CONFIG.DATA
+        self.T, self.rate, self.size, self.class_num = int(D.TEMP_LEN), int(D.FRAME_RATE), int(D.IMG_SIZE), int(D.NUM_CLASSES)
+        self._bufs = {}                    # (device, H0, W0) -> the buffers of a video size
+
+    def _stride(self, stride):
+        """one second's worth for AVA (30 frames: the reference's ``timef * 30``, datasets/ava_frame.py:43) and 1 for JHMDB / UCF101-24"""
+        stride = int(stride) if stride is not None else (30 if self.mode == "ava" else 1)
+        if stride < 1:
+            raise ValueError("%s: stride = %r must be >= 1" % (type(self).__name__, stride))
+        return stride
+
+    def _check_eval(self):
+        if self.model.training:
+            raise RuntimeError("%s runs an eval forward: call model.eval() first" % type(self).__name__)
+
+    def _frames(self, frames, n, least):
+        """the frames of a call as a uint8 tensor [n, H, W, 3] of at least ``least`` frames (``n``: the letter the message calls their number)"""
+        self._check_eval()
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < least:
+            raise ValueError("%s wants uint8 frames [%s, H, W, 3], got %s %s" % (type(self).__name__, n, frames.dtype, tuple(frames.shape)))
+        return frames
+
+    def _buffers(self, dev, H0, W0):
+        """the buffers of a video size: one clip buffer, one zero mask (every frame of a video has one size), the per-batch constants and the
+        resize coefficients"""
+        key = (str(dev), H0, W0)
+        b = self._bufs.get(key)
+        if b is None:
+            nh, nw, y1, x1, h, w = working_geometry(H0, W0, self.size)
+            B, T = self.batch, self.T
+            b = self._bufs[key] = dict(H0=H0, W0=W0, nh=nh, nw=nw, window=(y1, x1, h, w), same=(nh, nw) == (H0, W0),
+                                       clips=torch.empty(B, 3, T, h, w, dtype=torch.float32, device=dev),
+                                       mask=torch.zeros(B, h, w, dtype=torch.bool, device=dev),
+                                       key_pos=torch.full((B,), T // 2, dtype=torch.int64, device=dev),
+                                       sizes=torch.tensor([[H0, W0]] * B, dtype=torch.float32).to(dev, non_blocking=True),
+                                       lut=ip._device_tables(dev, (ip.MEAN, ip.STD))[0])
+            if not b["same"]:
+                b["coeffs"] = ip._device_coeffs(dev, H0, W0, nh, nw)
+        return b
+
+    @staticmethod
+    def _scratch(b, chunk, dev):
+        """the scratch ``tuber_frames_resize`` wants for up to ``chunk`` frames: only a resize in both directions runs in two passes"""
+        two_pass = not b["same"] and b["nw"] != b["W0"] and b["nh"] != b["H0"]
+        return torch.empty(chunk * b["coeffs"][4] * b["nw"] * 3, dtype=torch.uint8, device=dev) if two_pass else None
+
+    def _resize(self, b, src, dst, tmp):
+        """the frames ``src`` [m, H0, W0, 3] at working resolution into ``dst[:m]``: ``tuber_frames_resize``, or a copy where the sizes agree"""
+        if b["same"]:
+            dst[:src.shape[0]].copy_(src)
+        else:
+            (bh, kh, bv, kv), ksh, ksv, y0, rows = b["coeffs"]
+            lib.call("tuber_frames_resize", src, tmp, dst, src.shape[0], b["H0"], b["W0"], b["nh"], b["nw"], bh, kh, ksh, bv, kv, ksv, y0, rows)
+
+    def _stores(self, rows, dev):
+        """the uninitialised stores of ``rows`` key frames: the seven detection fields and, with ``actors``, the six actor fields (else None)"""
+        A = self.detector.actors
+        return (field_tensors(FIELDS, rows, self.detector.topk, dev, filled=False),
+                None if A is None else field_tensors(ACTOR_FIELDS, rows, A, dev, self.class_num, filled=False))
+
+    def _detect(self, b, stores, row):
+        """the ``Detector`` over the clip buffer, its fields copied device-to-device into the rows ``row .. row + batch - 1`` of the stores"""
+        det = self.detector(NestedTensor(b["clips"], b["mask"]), b["sizes"], b["key_pos"])
+        for full, rec in zip(stores, (det, det.actors)):
+            if full is not None:
+                for dst, src in zip(full, rec.tensors()):
+                    dst[row:row + self.batch].copy_(src)
+
+
+class VideoDetector(_VideoRunner):
     """``VideoDetector(cfg, model)(frames)`` -> ``VideoDetections``: every key frame of a video through the captured ``detect.Detector``.
 
     ``frames``: uint8 [N, H0, W0, 3] (numpy, a host tensor or a device tensor).  They are uploaded ``chunk`` frames at a time and each frame is
@@ -378,104 +401,41 @@ class VideoDetector:
     when to when, doing what" (DESIGN.md section 6i)."""
 
     def __init__(self, cfg, model, batch=2, score_thr=None, topk=None, actor_thr=None, graphed=True, rule=None, actors=None):
-        from .config import actor_settings, detect_settings, tube_nms_settings, video_map_settings
-        self.cfg, self.model = cfg, model
+        from .config import tube_nms_settings
         self.nms = tube_nms_settings(cfg)                  # the defaults of tubes(nms=) / tracks(nms=): kept out of ``settings``
-        self.batch = int(batch)
-        if self.batch < 1:
+        if int(batch) < 1:
             raise ValueError("VideoDetector: batch = %r must be >= 1" % (batch,))
-        vm = video_map_settings(cfg)
-        self.settings = dict(link_iou=float(vm["link_iou"]), max_gap=int(vm["max_gap"]), min_len=int(vm["min_len"]))
-        if topk is None:
-            topk = max(1, min(detect_settings(cfg)["topk"], lib.query("tuber_tube_link_max_active") // (self.settings["max_gap"] + 1)))
-        self.detector = Detector(cfg, model, score_thr=score_thr, topk=topk, actor_thr=actor_thr, graphed=graphed, actors=actors)
-        self.actor_settings = None
-        if actors is not None:
-            st = actor_settings(cfg)
-            self.actor_settings = {k: st[k] for k in ("link_iou", "max_gap", "min_len", "window", "label_thr")}
-        self.mode = model.dataset_mode
-        self.rule = rule if rule is not None else ("ava" if self.mode == "ava" else "jhmdb")
-        if self.rule not in RULES:
-            raise ValueError("VideoDetector: rule %r is not one of %s" % (rule, ", ".join(RULES)))
-        D = cfg.CONFIG.DATA
-        self.T, self.rate, self.size, self.class_num = int(D.TEMP_LEN), int(D.FRAME_RATE), int(D.IMG_SIZE), int(D.NUM_CLASSES)
-        self._bufs = {}
-
-    def _resident(self, frames, dev, chunk):
-        """the video at working resolution on the device, uint8 [N, nh, nw, 3]: uploaded and resized ``chunk`` frames at a time"""
-        N, H0, W0 = (int(v) for v in frames.shape[:3])
-        nh, nw = working_geometry(H0, W0, self.size)[:2]
-        out = torch.empty(N, nh, nw, 3, dtype=torch.uint8, device=dev)
-        same = (nh, nw) == (H0, W0)
-        if not same:
-            (bh, kh, bv, kv), ksh, ksv, y0, rows = ip._device_coeffs(dev, H0, W0, nh, nw)
-            tmp = torch.empty(chunk * rows * nw * 3, dtype=torch.uint8, device=dev) if (nw != W0 and nh != H0) else None
-        for i in range(0, N, chunk):
-            src = frames[i:i + chunk].to(dev, non_blocking=True).contiguous()
-            if same:
-                out[i:i + chunk].copy_(src)
-            else:
-                lib.call("tuber_frames_resize", src, tmp, out[i:], src.shape[0], H0, W0, nh, nw, bh, kh, ksh, bv, kv, ksv, y0, rows)
-        return out
+        super().__init__(cfg, model, batch, score_thr, topk, actor_thr, graphed, rule, actors)
 
     @torch.no_grad()
     def __call__(self, frames, keys=None, stride=None, chunk=256):
-        if self.model.training:
-            raise RuntimeError("VideoDetector runs an eval forward: call model.eval() first")
-        if isinstance(frames, np.ndarray):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3 or frames.shape[0] < 1:
-            raise ValueError("VideoDetector wants uint8 frames [N, H, W, 3], got %s %s" % (frames.dtype, tuple(frames.shape)))
+        frames = self._frames(frames, "N", 1)
         chunk = int(chunk)
         if chunk < 1:
             raise ValueError("VideoDetector: chunk = %r must be >= 1" % (chunk,))
         store, _ = self.model.engine()
         dev = store.device
         N, H0, W0 = (int(v) for v in frames.shape[:3])
-        if keys is None:
-            stride = int(stride) if stride is not None else (30 if self.mode == "ava" else 1)
-            if stride < 1:
-                raise ValueError("VideoDetector: stride = %r must be >= 1" % (stride,))
-            keys = range(0, N, stride)
-        keys = [int(k) for k in keys]
+        keys = [int(k) for k in (range(0, N, self._stride(stride)) if keys is None else keys)]
         if not keys:
             raise ValueError("VideoDetector: no key frames")
         n, B, T = len(keys), self.batch, self.T
         nb = (n + B - 1) // B
         table = clip_indices(N, keys + [keys[-1]] * (nb * B - n), T, self.rate, self.rule)      # the padded last batch repeats its last key
         table = torch.from_numpy(table).to(dev, non_blocking=True)
-        resident = self._resident(frames, dev, chunk)
-        nh, nw, y1, x1, h, w = working_geometry(H0, W0, self.size)
-        lut = ip._device_tables(dev, (ip.MEAN, ip.STD))[0]
-        bufs = self._bufs.get((str(dev), h, w))
-        if bufs is None:                       # one clip buffer, one zero mask (every frame of a video has one size), the per-batch constants
-            bufs = self._bufs[str(dev), h, w] = (torch.empty(B, 3, T, h, w, dtype=torch.float32, device=dev),
-                                                 torch.zeros(B, h, w, dtype=torch.bool, device=dev),
-                                                 torch.full((B,), T // 2, dtype=torch.int64, device=dev))
-        clips, mask, key_pos = bufs
-        sizes = torch.tensor([[H0, W0]] * B, dtype=torch.float32).to(dev, non_blocking=True)
-        K = self.detector.topk
-        f32, i32 = torch.float32, torch.int32
-        full = [torch.empty(nb * B, K, 4, dtype=f32, device=dev), torch.empty(nb * B, K, dtype=f32, device=dev), torch.empty(nb * B, K, dtype=i32, device=dev),
-                torch.empty(nb * B, K, dtype=i32, device=dev), torch.empty(nb * B, K, dtype=f32, device=dev), torch.empty(nb * B, dtype=i32, device=dev),
-                torch.empty(nb * B, dtype=i32, device=dev)]
-        A, full_a = self.detector.actors, None
-        if A is not None:
-            full_a = [torch.empty(nb * B, A, 4, dtype=f32, device=dev), torch.empty(nb * B, A, dtype=f32, device=dev),
-                      torch.empty(nb * B, A, dtype=i32, device=dev), torch.empty(nb * B, A, self.class_num, dtype=f32, device=dev),
-                      torch.empty(nb * B, dtype=i32, device=dev), torch.empty(nb * B, dtype=i32, device=dev)]
-        samples = NestedTensor(clips, mask)
-        for b in range(nb):
-            lib.call("tuber_video_clips", resident, N, nh, nw, table[b * B:], B, T, y1, x1, h, w, lut, clips)
-            det = self.detector(samples, sizes, key_pos)
-            for dst, src in zip(full, det.tensors()):
-                dst[b * B:(b + 1) * B].copy_(src)
-            if full_a is not None:
-                for dst, src in zip(full_a, det.actors.tensors()):
-                    dst[b * B:(b + 1) * B].copy_(src)
-        vd = VideoDetections(keys, *[t[:n] for t in full], class_num=self.class_num, settings=self.settings, store=store, nms_iou=self.nms["iou"])
-        if full_a is not None:
-            vd.actors = VideoActors(keys, *[t[:n] for t in full_a], settings=self.actor_settings, store=store, nms_iou=self.nms["actors_iou"])
+        b = self._buffers(dev, H0, W0)
+        tmp = self._scratch(b, chunk, dev)
+        # the video at working resolution on the device, uploaded and resized ``chunk`` frames at a time
+        resident = torch.empty(N, b["nh"], b["nw"], 3, dtype=torch.uint8, device=dev)
+        for i in range(0, N, chunk):
+            self._resize(b, frames[i:i + chunk].to(dev, non_blocking=True).contiguous(), resident[i:], tmp)
+        stores = self._stores(nb * B, dev)
+        for i in range(nb):
+            lib.call("tuber_video_clips", resident, N, b["nh"], b["nw"], table[i * B:], B, T, *b["window"], b["lut"], b["clips"])
+            self._detect(b, stores, i * B)
+        vd = VideoDetections(keys, *[t[:n] for t in stores[0]], class_num=self.class_num, settings=self.settings, store=store, nms_iou=self.nms["iou"])
+        if stores[1] is not None:
+            vd.actors = VideoActors(keys, *[t[:n] for t in stores[1]], settings=self.actor_settings, store=store, nms_iou=self.nms["actors_iou"])
         return vd
 
 
@@ -558,7 +518,7 @@ class StreamSchedule:
         return n_total, batches
 
 
-class VideoStream:
+class VideoStream(_VideoRunner):
     """``VideoDetector`` for a video that arrives in pieces: ``push(frames)`` as they come, ``finish()`` at the end, ``tubes()`` whenever wanted.
     The rows of every ``push`` and of ``finish``, concatenated, are ``VideoDetector(cfg, model, batch, ...)(video, stride=stride)``'s, bit for
     bit, and so are the tubes.
@@ -604,54 +564,35 @@ class VideoStream:
 
     def __init__(self, cfg, model, batch=2, stride=None, rule=None, max_chunk=64, score_thr=None, topk=None, actor_thr=None, graphed=True,
                  link=True, actors=None):
-        from .config import actor_settings, detect_settings, tube_nms_settings, video_map_settings
-        self.cfg, self.model = cfg, model
+        from .config import tube_nms_settings
+        from .evaluation import ActorTracker, TubeLinker
         if any(v is not None for v in tube_nms_settings(cfg).values()):
             print("[tuber] VideoStream: CONFIG.VAL.TUBE_NMS is ignored: a closed tube's suppressor may still be open, so tube NMS is defined over "
                   "whole videos only (VideoDetector)", file=sys.stderr, flush=True)
-        self.batch, self.max_chunk, self.link = int(batch), int(max_chunk), bool(link)
-        if self.batch < 1 or self.max_chunk < 1:
+        self.max_chunk, self.link = int(max_chunk), bool(link)
+        if int(batch) < 1 or self.max_chunk < 1:
             raise ValueError("VideoStream: batch = %r and max_chunk = %r must be >= 1" % (batch, max_chunk))
         if actors is not None and not self.link:
             raise ValueError("VideoStream: actors = %r needs link=True: the actor tracks are link records" % (actors,))
-        vm = video_map_settings(cfg)
-        self.settings = dict(link_iou=float(vm["link_iou"]), max_gap=int(vm["max_gap"]), min_len=int(vm["min_len"]))
-        if topk is None:
-            topk = max(1, min(detect_settings(cfg)["topk"], lib.query("tuber_tube_link_max_active") // (self.settings["max_gap"] + 1)))
-        self.detector = Detector(cfg, model, score_thr=score_thr, topk=topk, actor_thr=actor_thr, graphed=graphed, actors=actors)
-        self.actor_settings = None
-        if actors is not None:
-            st = actor_settings(cfg)
-            self.actor_settings = {k: st[k] for k in ("link_iou", "max_gap", "min_len", "window", "label_thr")}
-        self.mode = model.dataset_mode
-        self.rule = rule if rule is not None else ("ava" if self.mode == "ava" else "jhmdb")
-        if self.rule not in RULES:
-            raise ValueError("VideoStream: rule %r is not one of %s" % (rule, ", ".join(RULES)))
-        self.stride = int(stride) if stride is not None else (30 if self.mode == "ava" else 1)
-        if self.stride < 1:
-            raise ValueError("VideoStream: stride = %r must be >= 1" % (stride,))
-        D = cfg.CONFIG.DATA
-        self.T, self.rate, self.size, self.class_num = int(D.TEMP_LEN), int(D.FRAME_RATE), int(D.IMG_SIZE), int(D.NUM_CLASSES)
+        super().__init__(cfg, model, batch, score_thr, topk, actor_thr, graphed, rule, actors)
+        self.stride = self._stride(stride)
         self.schedule = StreamSchedule(self.T, self.rate, self.rule, self.batch, self.stride, self.max_chunk)
         self.R = self.schedule.R
         K, gap = self.detector.topk, self.settings["max_gap"]
-        self._why_host = None
-        if K > lib.query("tuber_frame_match_max_dets") or K * (gap + 1) > lib.query("tuber_tube_link_max_active"):
-            self._why_host = "%d rows per key frame with max_gap %d: beyond %d rows or %d active tubes" % (
-                K, gap, lib.query("tuber_frame_match_max_dets"), lib.query("tuber_tube_link_max_active"))
-        self._host_linker, self._said = None, False
-        self._bufs = {}                    # (device, H0, W0) -> the buffers of a video size
+        self._why_host = link_beyond("%d rows per key frame with max_gap %d" % (K, gap), K, gap)
+        self._host_linker = _HostDefinition(lambda: TubeLinker(self.class_num, self.settings["link_iou"], gap))
         self._cur = None                   # the current video's buffers
         self.wrapped = False               # whether a ring slot has been overwritten in the current video
         self._pending = []                 # link records since the last tubes() call; None marks the end of a video
-        self._open = {}                    # head -> the rows of an open tube, on the host
+        self._tubes = TubeAssembler(gap, self.settings["min_len"])                      # the rows of open tubes, on the host
         # actor tracks (actors=A): their own pending list and their own open rows; tubes() and tracks() consume neither the other's
         self.tracks_path = None            # "device" or "host" once a push has decided keys
-        self._why_host_tracks, self._host_tracker, self._said_tracks = None, None, False
+        self._why_host_tracks, self._host_tracker = None, None
         self._pending_tracks, self._assembler = [], None
         self._video_keys = 0               # keys decided in the current video
         if actors is not None:
             A, st = self.detector.actors, self.actor_settings
+            self._host_tracker = _HostDefinition(lambda: ActorTracker(st["link_iou"], st["max_gap"], st["window"]))
             self._assembler = TrackAssembler(A, st["max_gap"], st["window"], st["min_len"], st["label_thr"])
             self._track_bytes = lib.query("tuber_track_stream_state_bytes", A, self.class_num, st["max_gap"], st["window"])
             if A > lib.query("tuber_frame_match_max_dets") or not self._track_bytes:
@@ -661,26 +602,15 @@ class VideoStream:
 
     # -- buffers ----------------------------------------------------------------------------------------------------------
     def _buffers(self, dev, H0, W0):
-        key = (str(dev), H0, W0)
-        b = self._bufs.get(key)
-        if b is None:
-            nh, nw, y1, x1, h, w = working_geometry(H0, W0, self.size)
-            B, T, R = self.batch, self.T, self.R
-            b = dict(H0=H0, W0=W0, nh=nh, nw=nw, window=(y1, x1, h, w), same=(nh, nw) == (H0, W0),
-                     ring=torch.empty(R + 1, nh, nw, 3, dtype=torch.uint8, device=dev),
-                     clips=torch.empty(B, 3, T, h, w, dtype=torch.float32, device=dev), mask=torch.zeros(B, h, w, dtype=torch.bool, device=dev),
-                     key_pos=torch.full((B,), T // 2, dtype=torch.int64, device=dev),
-                     sizes=torch.tensor([[H0, W0]] * B, dtype=torch.float32).to(dev, non_blocking=True),
-                     lut=ip._device_tables(dev, (ip.MEAN, ip.STD))[0],
-                     state=torch.zeros(lib.query("tuber_tube_link_state_bytes", self.class_num), dtype=torch.uint8, device=dev))
-            if not b["same"]:
-                b["coeffs"] = ip._device_coeffs(dev, H0, W0, nh, nw)
-                rows = b["coeffs"][4]
-                b["tmp"] = torch.empty(self.max_chunk * rows * nw * 3, dtype=torch.uint8, device=dev) if (nw != W0 and nh != H0) else None
+        """the shared buffers of a video size plus the stream's own: the ring, the resize scratch, the link state and, with actors, theirs"""
+        b = super()._buffers(dev, H0, W0)
+        if "ring" not in b:
+            b["tmp"] = self._scratch(b, self.max_chunk, dev)
+            b["ring"] = torch.empty(self.R + 1, b["nh"], b["nw"], 3, dtype=torch.uint8, device=dev)
+            b["state"] = torch.zeros(lib.query("tuber_tube_link_state_bytes", self.class_num), dtype=torch.uint8, device=dev)
             if self.detector.actors is not None and self._why_host_tracks is None:      # the actors' own link state (one class) and the track ring
                 b["actor_state"] = torch.zeros(lib.query("tuber_tube_link_state_bytes", 1), dtype=torch.uint8, device=dev)
                 b["track_state"] = torch.zeros(self._track_bytes, dtype=torch.uint8, device=dev)
-            self._bufs[key] = b
         return b
 
     def device_bytes(self):
@@ -694,35 +624,23 @@ class VideoStream:
         R, m = self.R, int(src.shape[0])
         s0 = first % R
         for lo, hi, slot in ((0, min(m, R - s0), s0), (min(m, R - s0), m, 0)):
-            if hi <= lo:
-                continue
-            if b["same"]:
-                b["ring"][slot:slot + hi - lo].copy_(src[lo:hi])
-            else:
-                (bh, kh, bv, kv), ksh, ksv, y0, rows = b["coeffs"]
-                lib.call("tuber_frames_resize", src[lo:hi], b["tmp"], b["ring"][slot:], hi - lo, b["H0"], b["W0"], b["nh"], b["nw"], bh, kh, ksh, bv, kv,
-                         ksv, y0, rows)
+            if hi > lo:
+                self._resize(b, src[lo:hi], b["ring"][slot:], b["tmp"])
         if first == 0:
             b["ring"][R].copy_(b["ring"][0])                   # frame 0 in its fixed slot as well
         self.wrapped = self.wrapped or first + m > R
 
     # -- key frames -------------------------------------------------------------------------------------------------------
-    def _run(self, b, full, row, first_ord, n_keys, n_total, full_a=None):
-        """one batch: the keys ``first_ord .. first_ord + n_keys - 1`` (the last one repeated up to ``batch``) into rows ``row ..`` of ``full``
-        (and of ``full_a``: the six actor fields)"""
-        B = self.batch
-        lib.call("tuber_video_clips_ring", b["ring"], self.R, b["nh"], b["nw"], first_ord * self.stride, self.stride, n_keys, B, self.T, self.rate,
-                 RULES.index(self.rule), n_total, *b["window"], b["lut"], b["clips"])
-        det = self.detector(NestedTensor(b["clips"], b["mask"]), b["sizes"], b["key_pos"])
-        for dst, src in zip(full, det.tensors()):
-            dst[row:row + B].copy_(src)
-        if full_a is not None:
-            for dst, src in zip(full_a, det.actors.tensors()):
-                dst[row:row + B].copy_(src)
+    def _run(self, b, stores, row, first_ord, n_keys, n_total):
+        """one batch: the keys ``first_ord .. first_ord + n_keys - 1`` (the last one repeated up to ``batch``) into rows ``row ..`` of the stores"""
+        lib.call("tuber_video_clips_ring", b["ring"], self.R, b["nh"], b["nw"], first_ord * self.stride, self.stride, n_keys, self.batch, self.T,
+                 self.rate, RULES.index(self.rule), n_total, *b["window"], b["lut"], b["clips"])
+        self._detect(b, stores, row)
 
-    def _result(self, b, full, first_ord, n, store, full_a=None, flush=False):
-        """the ``VideoDetections`` of the keys ``first_ord .. first_ord + n - 1`` in the first n rows of ``full``, linked; with ``full_a`` its
+    def _result(self, b, stores, first_ord, n, store, flush=False):
+        """the ``VideoDetections`` of the keys ``first_ord .. first_ord + n - 1`` in the first n rows of the stores, linked; with actors its
         ``.actors`` as well, tracked (``flush``: these are the video's last keys)"""
+        full, full_a = stores
         if n == 0 and not (full_a is not None and flush and self._video_keys and self.actor_settings["window"]):
             return None                    # (with actors, a finish() that runs no key still emits the smoothed rows that waited for it)
         vd = VideoDetections([(first_ord + i) * self.stride for i in range(n)], *[t[:n] for t in full], class_num=self.class_num,
@@ -740,7 +658,7 @@ class VideoStream:
     def _track(self, b, va, first_ord, flush):
         """the track records of the keys ``first_ord ..`` onto ``va``: ``tuber_tube_link_stream`` with one class, the label derived from
         ``queries`` on the device, then ``tuber_track_actions_stream``; ``evaluation.ActorTracker`` on the host beyond their bounds"""
-        from .evaluation import ActorTracker, smooth_range
+        from .evaluation import smooth_range
         n, A, C = va.actions.shape
         st, dev = self.actor_settings, va.actions.device
         if (first_ord + n) * A > 0x7FFFFFFF:
@@ -760,15 +678,11 @@ class VideoStream:
             lib.call("tuber_track_actions_stream", va.actions.contiguous(), va.row_head, n, A, C, first_ord, st["max_gap"], st["window"], 1 if flush else 0,
                      b["track_state"], va.row_mean, va.row_peak, va.smooth)
             return
-        if not self._said_tracks:
-            print("[tuber] VideoStream: %s; tracks on the host" % self._why_host_tracks, file=sys.stderr, flush=True)
-            self._said_tracks = True
+        tracker = self._host_tracker("[tuber] VideoStream: %s; tracks on the host" % self._why_host_tracks)
         self.tracks_path = "host"
-        if self._host_tracker is None:
-            self._host_tracker = ActorTracker(st["link_iou"], st["max_gap"], st["window"])
-        host = dict(zip(ACTOR_FIELDS, va._fetch()))
-        got = self._host_tracker.push(host["boxes"].reshape(-1, 4), host["actor"].reshape(-1), host["queries"].reshape(-1), host["actions"].reshape(n * A, C), A,
-                                      flush=flush)
+        host = va._fetch()[0]
+        got = tracker.push(host["boxes"].reshape(-1, 4), host["actor"].reshape(-1), host["queries"].reshape(-1), host["actions"].reshape(n * A, C), A,
+                           flush=flush)
         up = lambda a, dtype, *shape: torch.from_numpy(np.ascontiguousarray(a.astype(dtype))).reshape(*shape).to(dev)
         va.row_head, va.row_score, va.row_len = up(got["row_head"], np.int32, n, A), up(got["row_score"], np.float64, n, A), up(got["row_len"], np.int32, n, A)
         va.row_mean, va.row_peak = up(got["row_mean"], np.float64, n, A, C), up(got["row_peak"], np.float32, n, A, C)
@@ -787,40 +701,16 @@ class VideoStream:
             lib.call("tuber_tube_link_stream", vd.boxes.contiguous(), vd.labels.contiguous(), vd.scores.contiguous(), n, K, first_ord, self.class_num,
                      self.settings["link_iou"], self.settings["max_gap"], b["state"], vd.row_head, vd.row_score, vd.row_len)
             return
-        from .evaluation import TubeLinker
-        if not self._said:
-            print("[tuber] VideoStream: %s; linking on the host" % why, file=sys.stderr, flush=True)
-            self._said = True
-        if self._host_linker is None:
-            self._host_linker = TubeLinker(self.class_num, self.settings["link_iou"], self.settings["max_gap"])
-        host = dict(zip(FIELDS, vd._fetch()))
-        got = self._host_linker.push(host["boxes"].reshape(-1, 4), host["labels"].reshape(-1), host["scores"].reshape(-1), K)
+        linker = self._host_linker("[tuber] VideoStream: %s; linking on the host" % why)
+        host = vd._fetch()[0]
+        got = linker.push(host["boxes"].reshape(-1, 4), host["labels"].reshape(-1), host["scores"].reshape(-1), K)
         vd.row_head = torch.from_numpy(got["row_head"].reshape(n, K).astype(np.int32)).to(dev)
         vd.row_score = torch.from_numpy(got["row_score"].reshape(n, K)).to(dev)
         vd.row_len = torch.from_numpy(got["row_len"].reshape(n, K).astype(np.int32)).to(dev)
 
-    def _empty(self, rows, dev):
-        K, f32, i32 = self.detector.topk, torch.float32, torch.int32
-        return [torch.empty(rows, K, 4, dtype=f32, device=dev), torch.empty(rows, K, dtype=f32, device=dev), torch.empty(rows, K, dtype=i32, device=dev),
-                torch.empty(rows, K, dtype=i32, device=dev), torch.empty(rows, K, dtype=f32, device=dev), torch.empty(rows, dtype=i32, device=dev),
-                torch.empty(rows, dtype=i32, device=dev)]
-
-    def _empty_actors(self, rows, dev):
-        A = self.detector.actors
-        if A is None:
-            return None
-        f32, i32 = torch.float32, torch.int32
-        return [torch.empty(rows, A, 4, dtype=f32, device=dev), torch.empty(rows, A, dtype=f32, device=dev), torch.empty(rows, A, dtype=i32, device=dev),
-                torch.empty(rows, A, self.class_num, dtype=f32, device=dev), torch.empty(rows, dtype=i32, device=dev), torch.empty(rows, dtype=i32, device=dev)]
-
     @torch.no_grad()
     def push(self, frames):
-        if self.model.training:
-            raise RuntimeError("VideoStream runs an eval forward: call model.eval() first")
-        if isinstance(frames, np.ndarray):
-            frames = torch.from_numpy(np.ascontiguousarray(frames))
-        if frames.dtype != torch.uint8 or frames.dim() != 4 or frames.shape[3] != 3:
-            raise ValueError("VideoStream wants uint8 frames [n, H, W, 3], got %s %s" % (frames.dtype, tuple(frames.shape)))
+        frames = self._frames(frames, "n", 0)
         m, H0, W0 = (int(v) for v in frames.shape[:3])
         sch = self.schedule
         if sch.frames and (H0, W0) != (self._cur["H0"], self._cur["W0"]):
@@ -835,21 +725,19 @@ class VideoStream:
         first_frame, first_ord = sch.frames, sch.decided
         plan = sch.push(m)                                      # host integers first: the pieces, and the batches ready after each
         total = sum(len(batches) for _, _, batches in plan)
-        full = self._empty(total * B, dev) if total else None
-        full_a = self._empty_actors(total * B, dev) if total else None
+        stores = self._stores(total * B, dev) if total else None
         row = 0
         for i, length, batches in plan:
             src = frames[i:i + length].to(dev, non_blocking=True).contiguous()
             self._store_frames(b, src, first_frame + i)
             for k in batches:
-                self._run(b, full, row, k, B, -1, full_a)
+                self._run(b, stores, row, k, B, -1)
                 row += B
-        return self._result(b, full, first_ord, row, store, full_a) if row else None
+        return self._result(b, stores, first_ord, row, store) if row else None
 
     @torch.no_grad()
     def finish(self):
-        if self.model.training:
-            raise RuntimeError("VideoStream runs an eval forward: call model.eval() first")
+        self._check_eval()
         decided = self.schedule.decided
         n_total, batches = self.schedule.finish()
         self.wrapped = False
@@ -859,107 +747,143 @@ class VideoStream:
         store, _ = self.model.engine()
         out = None
         if batches:
-            full, full_a = self._empty(len(batches) * B, store.device), self._empty_actors(len(batches) * B, store.device)
+            stores = self._stores(len(batches) * B, store.device)
             for i, (k, n_keys) in enumerate(batches):
-                self._run(b, full, i * B, k, n_keys, n_total, full_a)
-            out = self._result(b, full, batches[0][0], batches[-1][0] + batches[-1][1] - batches[0][0], store, full_a, flush=True)
+                self._run(b, stores, i * B, k, n_keys, n_total)
+            out = self._result(b, stores, batches[0][0], batches[-1][0] + batches[-1][1] - batches[0][0], store, flush=True)
         elif self.detector.actors is not None:                  # no key left to run: the smoothed rows that waited for the end (S = 0, flush)
-            out = self._result(b, self._empty(0, store.device), decided, 0, store, self._empty_actors(0, store.device), flush=True)
+            out = self._result(b, self._stores(0, store.device), decided, 0, store, flush=True)
         b["state"].zero_()
         for k in ("actor_state", "track_state"):
             if k in b:
                 b[k].zero_()
-        if self._host_linker is not None:
-            self._host_linker.reset()
-        if self._host_tracker is not None:
-            self._host_tracker.reset()
+        self._host_linker.reset()
         if self.link:
             self._pending.append(None)
         if self.detector.actors is not None:
+            self._host_tracker.reset()
             self._pending_tracks.append(None)
             self._video_keys = 0
         return out
 
-    # -- tubes ------------------------------------------------------------------------------------------------------------
+    # -- tubes and actor tracks -------------------------------------------------------------------------------------------
+    TUBE_NAMES = ("boxes", "labels", "row_head", "row_score", "row_len")
+    TRACK_NAMES = ("boxes", "actor", "queries", "actions", "row_head", "row_score", "row_len", "row_mean", "row_peak", "smooth")
+
+    @staticmethod
+    def _drain(pending, assembler, names, last=()):
+        """the records of ``pending`` through ``assembler`` -> what closed: ONE device-to-host copy for every record, ``end()`` at the markers of a
+        video's end"""
+        host = host_parts([getattr(p[1], k) for p in pending if p is not None for k in names])
+        out, i, m = [], 0, len(names)
+        for p in pending:
+            if p is None:                                       # the end of a video: whatever is open closes
+                assembler.end()
+                out += assembler.take()
+                continue
+            first_ord, rec = p
+            assembler.add(first_ord, rec.keys, *host[m * i:m * i + m], *(getattr(rec, k) for k in last))
+            i += 1
+        return out + assembler.take()
+
     def tubes(self):
         if not self.link:
             raise RuntimeError("VideoStream(link=False) keeps no link records: no tubes")
         pending, self._pending = self._pending, []
-        recs = [p for p in pending if p is not None]
-        names = ("boxes", "labels", "row_head", "row_score", "row_len")
-        parts = [getattr(vd, k).contiguous() for _, vd in recs for k in names]
-        host, o = [], 0
-        if parts:                                               # one copy for every record
-            blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
-            for t in parts:
-                nbytes = t.numel() * t.element_size()
-                host.append(blob[o:o + nbytes].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape)))
-                o += nbytes
-        gap, min_len, out, i = self.settings["max_gap"], self.settings["min_len"], [], 0
-        next_ord = None
-
-        def close(everything):
-            for h in sorted(self._open):
-                t = self._open[h]
-                if everything or next_ord - t["last"] > gap + 1:
-                    del self._open[h]
-                    if t["length"] >= min_len:
-                        out.append(dict(cls=t["cls"], score=t["score"], frames=t["frames"], boxes=np.stack(t["boxes"]), length=t["length"], head=h))
-        for p in pending:
-            if p is None:                                       # the end of a video: whatever is open closes
-                close(True)
-                next_ord = None
-                continue
-            first_ord, vd = p
-            boxes, labels, head, score, length = host[5 * i:5 * i + 5]
-            i += 1
-            for s, q in zip(*np.nonzero(head >= 0)):
-                h = int(head[s, q])
-                t = self._open.get(h)
-                if t is None:
-                    t = self._open[h] = dict(cls=int(labels[s, q]) + 1, frames=[], boxes=[])
-                t["frames"].append(vd.keys[s])
-                t["boxes"].append(boxes[s, q].copy())
-                t["score"], t["length"], t["last"] = float(score[s, q]), int(length[s, q]), first_ord + int(s)
-            next_ord = first_ord + len(vd.keys)
-        if next_ord is not None:
-            close(False)
-        return out
-
-    # -- actor tracks -----------------------------------------------------------------------------------------------------
-    TRACK_NAMES = ("boxes", "actor", "queries", "actions", "row_head", "row_score", "row_len", "row_mean", "row_peak", "smooth")
+        return self._drain(pending, self._tubes, self.TUBE_NAMES)
 
     def tracks(self):
         """The actor tracks (``actors=A``) that CLOSED since the last call: the next key ordinal is more than ``max(max_gap + 1, window)`` past
         their last one -- no key frame still to come can extend them, and the smoothed row of their last key has been emitted -- and after
         ``finish()`` all that remain.  ``VideoActors.tracks``' dicts plus ``head`` (key ordinal * A + position of the first row), in head
         order; ``score`` / ``mean`` / ``peak`` are the records of the track's last row.  One device-to-host copy per call; the rows of open
-        tracks are kept on the host in between (``TrackAssembler``).  ``tubes()`` keeps its own records: neither consumes the other's."""
+        tracks are kept on the host in between (``TrackAssembler``; ``TubeAssembler`` for ``tubes()``).  ``tubes()`` keeps its own records:
+        neither consumes the other's."""
         if self._assembler is None:
             raise RuntimeError("VideoStream without actors=A keeps no actor records: no tracks")
         pending, self._pending_tracks = self._pending_tracks, []
-        recs = [p for p in pending if p is not None]
-        parts = [getattr(va, k).contiguous() for _, va in recs for k in self.TRACK_NAMES]
-        host, o = [], 0
-        if parts:                                               # one copy for every record
-            blob = torch.cat([t.reshape(-1).view(torch.uint8) for t in parts]).cpu().numpy()
-            for t in parts:
-                nbytes = t.numel() * t.element_size()
-                host.append(blob[o:o + nbytes].view(np.dtype(str(t.dtype).replace("torch.", ""))).reshape(tuple(t.shape)))
-                o += nbytes
-        out, i, m = [], 0, len(self.TRACK_NAMES)
-        for p in pending:
-            if p is None:                                       # the end of a video: whatever is open closes
-                self._assembler.end()
-                out += self._assembler.take()
-                continue
-            first_ord, va = p
-            self._assembler.add(first_ord, va.keys, *host[m * i:m * i + m], va.smooth_first)
-            i += 1
-        return out + self._assembler.take()
+        return self._drain(pending, self._assembler, self.TRACK_NAMES, ("smooth_first",))
 
 
-class TrackAssembler:
+class _HostDefinition:
+    """Say it once, then use the host definition: ``self(line)`` prints ``line`` on stderr the first time only and returns the object ``make()``
+    built on first use; ``reset()`` resets it for the next video if it was ever built."""
+
+    def __init__(self, make):
+        self.make, self.made = make, None
+
+    def __call__(self, line):
+        if self.made is None:
+            print(line, file=sys.stderr, flush=True)
+            self.made = self.make()
+        return self.made
+
+    def reset(self):
+        if self.made is not None:
+            self.made.reset()
+
+
+class _Assembler:
+    """What ``TubeAssembler`` and ``TrackAssembler`` share: open records by head, a record closing once the next key ordinal is more than
+    ``stale`` past its last one or the video ends, closed records shorter than ``min_len`` dropped, ``take()`` in head order."""
+
+    def __init__(self, stale, min_len):
+        self.stale, self.min_len = int(stale), int(min_len)
+        self._open, self._closed, self._next = {}, [], 0
+
+    def _rows(self, first_ord, keys, row_head, row_score, row_len):
+        """every counted row (s, q) of a push with the open record it extends -- a new one for a new head -- its frame, score, length and last
+        ordinal already noted"""
+        head = np.asarray(row_head)
+        for s, q in zip(*np.nonzero(head >= 0)):
+            h = int(head[s, q])
+            t = self._open.setdefault(h, dict(head=h, frames=[]))
+            t["frames"].append(int(keys[s]))
+            t["score"], t["length"], t["last"] = float(row_score[s, q]), int(row_len[s, q]), int(first_ord) + int(s)
+            yield s, q, t
+
+    def _advance(self, next_ord):
+        self._next = int(next_ord)
+        self._close(False)
+
+    def end(self):
+        self._close(True)
+        self._next = 0
+
+    def _close(self, everything):
+        for h in sorted(self._open):
+            t = self._open[h]
+            if everything or self._next - t["last"] > self.stale:
+                del self._open[h]
+                if t["length"] >= self.min_len:
+                    self._closed.append(self._finished(t))
+
+    def take(self):
+        out, self._closed = sorted(self._closed, key=lambda t: t["head"]), []
+        return out
+
+
+class TubeAssembler(_Assembler):
+    """The host side of ``VideoStream.tubes()``: the per-push link records of a stream (host arrays) in, closed tubes out.
+    ``add(first_ord, keys, boxes, labels, row_head, row_score, row_len)`` takes the records of the keys ``first_ord ..`` ([n, K, ...] arrays);
+    ``end()`` marks the end of the video; ``take()`` returns the tubes closed since the last call, in head order: after ``end()`` all of them,
+    before it those whose last key lies more than ``max_gap + 1`` ordinals behind the next one.  A tube is ``VideoDetections.tubes``' dict plus
+    ``head``; tubes shorter than ``min_len`` are dropped."""
+
+    def __init__(self, max_gap, min_len=1):
+        super().__init__(int(max_gap) + 1, min_len)
+
+    def add(self, first_ord, keys, boxes, labels, row_head, row_score, row_len):
+        for s, q, t in self._rows(first_ord, keys, row_head, row_score, row_len):
+            t.setdefault("cls", int(labels[s, q]) + 1)
+            t.setdefault("boxes", []).append(boxes[s, q].copy())
+        self._advance(first_ord + len(keys))
+
+    def _finished(self, t):
+        return dict(cls=t["cls"], score=t["score"], frames=t["frames"], boxes=np.stack(t["boxes"]), length=t["length"], head=t["head"])
+
+
+class TrackAssembler(_Assembler):
     """The host side of ``VideoStream.tracks()``: the per-push records of a stream's actors (host arrays) in, closed actor tracks out.
     ``add(first_ord, keys, boxes, actor, queries, actions, row_head, row_score, row_len, row_mean, row_peak, smooth, smooth_first)`` takes the
     records of the keys ``first_ord ..`` ([n, A, ...] arrays; ``smooth`` [m, A, C] belongs to the slots ``smooth_first ..``, which lag
@@ -968,49 +892,29 @@ class TrackAssembler:
     is ``VideoActors.tracks``' dict plus ``head``; tracks shorter than ``min_len`` are dropped."""
 
     def __init__(self, A, max_gap, window, min_len=1, label_thr=0.05):
-        self.A, self.max_gap, self.window, self.min_len, self.label_thr = int(A), int(max_gap), int(window), int(min_len), float(label_thr)
-        self._open, self._waiting, self._closed, self._next = {}, {}, [], 0
+        super().__init__(max(int(max_gap) + 1, int(window)), min_len)
+        self.A, self.max_gap, self.window, self.label_thr = int(A), int(max_gap), int(window), float(label_thr)
+        self._waiting = {}
 
     def add(self, first_ord, keys, boxes, actor, queries, actions, row_head, row_score, row_len, row_mean, row_peak, smooth, smooth_first):
-        head = np.asarray(row_head)
-        for s, a in zip(*np.nonzero(head >= 0)):
-            h, o = int(head[s, a]), int(first_ord) + int(s)
-            t = self._open.get(h)
-            if t is None:
-                t = self._open[h] = dict(frames=[], boxes=[], actor=[], queries=[], actions=[], smooth=[])
-            t["frames"].append(int(keys[s]))
+        for s, a, t in self._rows(first_ord, keys, row_head, row_score, row_len):
             for k, src in (("boxes", boxes), ("actor", actor), ("queries", queries), ("actions", actions)):
-                t[k].append(np.array(src[s, a]))
-            t["score"], t["length"], t["last"] = float(row_score[s, a]), int(row_len[s, a]), o
+                t.setdefault(k, []).append(np.array(src[s, a]))
             t["mean"], t["peak"] = np.array(row_mean[s, a], dtype=np.float64), np.array(row_peak[s, a], dtype=np.float32)
-            self._waiting.setdefault(o, []).append((int(a), h))           # the row's smoothed scores come `window` keys later
+            t.setdefault("smooth", [])
+            self._waiting.setdefault(t["last"], []).append((int(a), t["head"]))     # the row's smoothed scores come `window` keys later
         for j in range(len(smooth)):                                      # slots in order: a track's smoothed rows arrive in slot order
             for a, h in self._waiting.pop(int(smooth_first) + j, []):
                 self._open[h]["smooth"].append(np.array(smooth[j, a], dtype=np.float64))
-        self._next = int(first_ord) + len(keys)
-        self._close(False)
+        self._advance(int(first_ord) + len(keys))
 
     def end(self):
-        self._close(True)
-        self._waiting, self._next = {}, 0
+        super().end()
+        self._waiting = {}
 
-    def _close(self, everything):
-        for h in sorted(self._open):
-            t = self._open[h]
-            if not (everything or self._next - t["last"] > max(self.max_gap + 1, self.window)):
-                continue
-            del self._open[h]
-            if t["length"] < self.min_len:
-                continue
-            if len(t["smooth"]) != len(t["frames"]):
-                raise RuntimeError("TrackAssembler: track %d closes with %d of its %d smoothed rows" % (h, len(t["smooth"]), len(t["frames"])))
-            mean = t["mean"]
-            with np.errstate(invalid="ignore"):
-                labels = sorted(np.nonzero(mean >= self.label_thr)[0].tolist(), key=lambda c: (-mean[c], c))
-            self._closed.append(dict(score=t["score"], frames=t["frames"], boxes=np.stack(t["boxes"]), actor=np.stack(t["actor"]),
-                                     queries=np.stack(t["queries"]), actions=np.stack(t["actions"]), smooth=np.stack(t["smooth"]), mean=mean,
-                                     peak=t["peak"], labels=labels, length=t["length"], head=h))
-
-    def take(self):
-        out, self._closed = sorted(self._closed, key=lambda t: t["head"]), []
-        return out
+    def _finished(self, t):
+        if len(t["smooth"]) != len(t["frames"]):
+            raise RuntimeError("TrackAssembler: track %d closes with %d of its %d smoothed rows" % (t["head"], len(t["smooth"]), len(t["frames"])))
+        return dict(score=t["score"], frames=t["frames"], boxes=np.stack(t["boxes"]), actor=np.stack(t["actor"]), queries=np.stack(t["queries"]),
+                    actions=np.stack(t["actions"]), smooth=np.stack(t["smooth"]), mean=t["mean"], peak=t["peak"],
+                    labels=_track_labels(t["mean"], self.label_thr), length=t["length"], head=t["head"])
