@@ -157,8 +157,10 @@ def get_cfg_defaults():
         DEVICE_MAP=dict(ENABLE=False, FILES=True),
         # video-mAP of validate_tuber_ucf_detection over linked action tubes (evaluation.VideoMAP / device_map.DeviceVideoMAP; not reference
         # keys): consecutive detections of a class link when their IoU is at least LINK_IOU, over at most MAX_GAP empty frames; tubes shorter
-        # than MIN_LEN are not counted; THRESHOLDS: spatio-temporal IoU thresholds, "0.5:0.95" the mean over 0.50, 0.55, ..., 0.95
-        VIDEO_MAP=dict(ENABLE=False, LINK_IOU=0.2, MAX_GAP=2, MIN_LEN=1, THRESHOLDS=[0.2, 0.5, 0.75, "0.5:0.95"]),
+        # than MIN_LEN are not counted; THRESHOLDS: spatio-temporal IoU thresholds, "0.5:0.95" the mean over 0.50, 0.55, ..., 0.95; DENSE: the
+        # default of tubes(dense=) / tracks(dense=) of video.py -- a box on every frame of a tube's extent, interpolated between the linked key
+        # detections (evaluation.dense_rows / tuber_tube_dense); no part of video-mAP
+        VIDEO_MAP=dict(ENABLE=False, LINK_IOU=0.2, MAX_GAP=2, MIN_LEN=1, THRESHOLDS=[0.2, 0.5, 0.75, "0.5:0.95"], DENSE=False),
         # ranked detections decoded on the device (detect.Detector; not reference keys): a candidate scores at least SCORE_THR, the best TOPK
         # per clip are kept; ACTOR_THR: the actor-probability gate of the AVA rule (the reference's 0.8)
         DETECT=dict(SCORE_THR=0.05, TOPK=100, ACTOR_THR=0.8),
@@ -202,6 +204,8 @@ def video_map_settings(cfg):
     number = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool) and v == v
     if not isinstance(vm.ENABLE, bool):
         bad("ENABLE", "must be True or False")
+    if not isinstance(vm.DENSE, bool):
+        bad("DENSE", "must be True or False")
     if not number(vm.LINK_IOU) or not 0.0 <= vm.LINK_IOU <= 1.0:
         bad("LINK_IOU", "must be a number in [0, 1]")
     if not isinstance(vm.MAX_GAP, int) or isinstance(vm.MAX_GAP, bool) or vm.MAX_GAP < 0:
@@ -218,6 +222,13 @@ def video_map_settings(cfg):
         bad("THRESHOLDS", "entries must be distinct")
     return dict(link_iou=float(vm.LINK_IOU), max_gap=int(vm.MAX_GAP), min_len=int(vm.MIN_LEN),
                 thresholds=tuple(t if t == "0.5:0.95" else float(t) for t in thr))
+
+
+def dense_setting(cfg):
+    """CONFIG.VAL.VIDEO_MAP.DENSE validated (with the rest of VIDEO_MAP): the default of ``tubes(dense=)`` and, inherited like MAX_GAP, of
+    ``tracks(dense=)``.  Kept out of ``video_map_settings``' dict: that one is the keyword arguments of the evaluators"""
+    video_map_settings(cfg)
+    return cfg.CONFIG.VAL.VIDEO_MAP.DENSE
 
 
 def tube_nms_settings(cfg):

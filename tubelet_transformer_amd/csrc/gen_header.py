@@ -394,6 +394,20 @@ DOC = {
                       "min_len < 1, nms_iou NaN or outside [0, 1], N > S * max_rows, negative sizes, a null pointer or a misaligned work: negative, nothing launched, "
                       "nothing written. N == 0 or V == 0: 0, nothing written.",
     "tuber_tube_nms_work_bytes": "bytes of the scratch of tuber_tube_nms for N rows: 64 partner heads and one status word (int32) per row, rounded up to 16; 0 for N <= 0.",
+    "tuber_tube_dense": "dense action tubes on the device (evaluation.dense_rows: the definition; the per-frame tubes of the UCF101-24 / JHMDB protocol, which the "
+                        "ACT-detector tooling also fills by interpolating between key detections): a box and a score on every frame between two linked key "
+                        "detections of ONE video's padded [S][K] store. det_box [S * K][4] / det_score [S * K] fp32, row_head [S * K] as tuber_tube_link_ranked "
+                        "wrote it, slot_frame [S] the frame number of every key ordinal, strictly ascending; G >= the most frames a row can own, max(1, max over s "
+                        "of slot_frame[min(s + max_gap + 1, S - 1)] - slot_frame[s]), a host integer. Out per row r of slot s: row_next, the first row with r's "
+                        "head in the slots s + 1 .. s + max_gap + 1 (-1: none); row_span g = slot_frame[its slot] - slot_frame[s] (1 without a successor; 0, with "
+                        "row_next -1, for a row with head < 0); dense_box [S * K][G][4] / dense_score [S * K][G] fp32 at j < g, frame slot_frame[s] + j: the row's "
+                        "own bytes at j = 0, float(double(a) + (double(b) - double(a)) * (double(j) / double(g))) per coordinate and for the score behind it (a "
+                        "the row, b its successor; every operation rounded on its own, a NaN result 0x7FC00000): the definition's bits. Nothing is written at j "
+                        ">= g. g < 1 or g > G (unsorted slot_frame, a G too small): row_span -1 and nothing else, the caller answers with the definition. One "
+                        "wave per row: the candidate heads in lanes and one ballot, then lanes j, j + 64, ... write a 16-byte box and a score each; no LDS, no "
+                        "atomics, plain vector stores. K > tuber_frame_match_max_dets(), K * (max_gap + 1) > tuber_tube_link_max_active(), S * K * G beyond an "
+                        "int32, G < 1, K < 1, negative sizes, a null pointer, det_box / dense_box not 16-byte or another pointer not 4-byte aligned: "
+                        "TUBER_EINVAL, nothing launched, nothing written. S == 0: 0, no launch.",
     "tuber_tube_match_max_gt": "ground-truth tubes per (video, class) tuber_tube_match takes (32).",
     "tuber_tube_match_max_thresholds": "thresholds per call tuber_tube_match takes (16).",
     "tuber_detect_ava": "ranked detections of an AVA eval forward in ONE launch (PostProcessAVA, models/criterion.py:447-482, the post-processor models/tuber_ava.py builds; "

@@ -16,6 +16,8 @@
 //   4. tube_nms_kernel      (tuber_tube_nms, evaluation.tube_nms: the definition) between steps 1 and 2, or behind step 1 over a padded store: a wave
 //                           per (video, class) adds the per-slot IoU of every two live tubes into a [64][64] table, records the pairs above the
 //                           threshold when the first of the two ends, and visits the tubes by descending score: suppressed iff a kept one overlaps.
+//   5. tube_dense_kernel    (tuber_tube_dense, evaluation.dense_rows: the definition) behind step 1 (and step 4) over a padded store: a wave per row
+//                           finds the row's successor by one ballot and writes a box and a score for every frame up to it.
 // No floating-point atomics, every sum sequential in slot order: the same input gives the same bits.
 #include "map_common.h"
 
@@ -506,6 +508,83 @@ __global__ __launch_bounds__(64) void tube_nms_kernel(const float* __restrict__ 
     }
 }
 
+// Dense tubes (evaluation.dense_rows: the definition; tuber_tube_dense): a box and a score on every frame between two linked key detections
+// of ONE video's padded [S][K] store.  A wave per row r of slot s.  Phase 1: lane c < K * (max_gap + 1) reads the head of candidate row
+// (s + 1 + c / K) * K + c % K -- the slots the linker may have bridged to, in row order -- and the lowest lane of the ballot "my row's head"
+// is the successor.  Phase 2: the two boxes, the two scores and g = slot_frame[successor's slot] - slot_frame[s] (1 without a successor) are
+// wave-uniform; lane j, j + 64, ... < g writes frame j of the row: the row's own bytes at j = 0, behind that the fp64 interpolation, every
+// operation rounded on its own as numpy rounds it.  No LDS, no atomics, plain vector stores; nothing is written at j >= g.
+#define TDENSE_WAVES 4            // rows per workgroup: a wave each
+
+__device__ __forceinline__ float tdense_lerp(float a, float b, double w) {
+#pragma clang fp contract(off)
+    const double d = (double)b - (double)a;
+    const double p = d * w;
+    const float v = (float)((double)a + p);
+    return v != v ? __int_as_float(0x7FC00000) : v;                               // one NaN: the definition's
+}
+
+__global__ __launch_bounds__(64 * TDENSE_WAVES) void tube_dense_kernel(const float* __restrict__ det_box, const float* __restrict__ det_score,
+                                                                       const int* __restrict__ row_head, const int* __restrict__ slot_frame, int S,
+                                                                       int K, int max_gap, int G, float* __restrict__ dense_box,
+                                                                       float* __restrict__ dense_score, int* __restrict__ row_span,
+                                                                       int* __restrict__ row_next) {
+#pragma clang fp contract(off)
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * TDENSE_WAVES + (threadIdx.x >> 6);          // wave-uniform from here on
+    if (r >= (long)S * K) return;
+    const int s = (int)(r / K);
+    const int h = row_head[r];
+    if (h < 0) {                                                                  // not counted: owns no frame
+        if (lane == 0) {
+            row_span[r] = 0;
+            row_next[r] = -1;
+        }
+        return;
+    }
+    // phase 1: the successor
+    const int cs = s + 1 + lane / K;
+    const bool cand = lane < K * (max_gap + 1) && cs < S;
+    const unsigned long long m = __ballot(cand && row_head[(long)cs * K + lane % K] == h);
+    int nx = -1;
+    long g = 1;
+    if (m) {
+        const int p = __ffsll((long long)m) - 1;
+        const int ns = s + 1 + p / K;
+        nx = ns * K + p % K;
+        g = (long)slot_frame[ns] - (long)slot_frame[s];
+    }
+    if (g < 1 || g > G) {                                                         // unsorted slot_frame or a G too small: the host answers
+        if (lane == 0) row_span[r] = -1;
+        return;
+    }
+    // phase 2: the frames the row owns
+    const float4 a = ((const float4*)det_box)[r];
+    const float4 b = nx >= 0 ? ((const float4*)det_box)[nx] : a;
+    const float sa = det_score[r];
+    const float sb = nx >= 0 ? det_score[nx] : sa;
+    float4* ob = (float4*)dense_box + r * G;
+    float* os = dense_score + r * G;
+    for (int j = lane; j < (int)g; j += 64) {
+        float4 v = a;
+        float sv = sa;
+        if (j > 0) {
+            const double w = (double)j / (double)g;
+            v.x = tdense_lerp(a.x, b.x, w);
+            v.y = tdense_lerp(a.y, b.y, w);
+            v.z = tdense_lerp(a.z, b.z, w);
+            v.w = tdense_lerp(a.w, b.w, w);
+            sv = tdense_lerp(sa, sb, w);
+        }
+        ob[j] = v;
+        os[j] = sv;
+    }
+    if (lane == 0) {
+        row_span[r] = (int)g;
+        row_next[r] = nx;
+    }
+}
+
 // Actor tracks (evaluation.actor_tracks: the definition): per-track and temporally smoothed action scores over ONE video's [S][A] actor store
 // linked class-agnostically by tube_link_kernel.  A workgroup per row r = slot * A + a, a wave per 64 classes; a row's track is the rows with its
 // row_head, at most one per slot, found by comparing the slot's A heads in the lanes of the wave (one ballot).  Every sum is fp64, sequential in
@@ -890,6 +969,32 @@ int tuber_tube_nms(const float* det_box, const int* slot_off, const int* video_o
 }
 // bytes of the scratch of tuber_tube_nms: per row 64 partner heads and one status word (int32), rounded up to 16 bytes; 0 for N <= 0
 long tuber_tube_nms_work_bytes(long N) { return N > 0 ? (N * (TNMS_ROW + 1) * 4 + 15) & ~15l : 0; }
+
+// Dense tubes (evaluation.dense_rows: the definition): per-frame boxes and scores between the linked key detections of ONE video's padded
+// [S][K] store.  det_box [S * K][4] / det_score [S * K] fp32, row_head [S * K] as tuber_tube_link_ranked wrote it, slot_frame [S] the frame
+// number of every key ordinal (strictly ascending), G >= the most frames a row can own (evaluation.dense_extent: a host integer).  Out, per
+// row r: row_next the first row with r's head in the next max_gap + 1 slots (-1: none), row_span g = the frames between the two keys (1
+// without a successor, 0 for a row with head < 0, whose row_next is -1), dense_box [S * K][G][4] / dense_score [S * K][G] at j < g: the
+// row's own bytes at j = 0, float(double(a) + (double(b) - double(a)) * (double(j) / double(g))) behind it; nothing is written at j >= g.
+// g < 1 or g > G (unsorted slot_frame, a G too small): row_span -1 and nothing else -- the caller answers with the definition.  Refused
+// (TUBER_EINVAL, nothing launched, nothing written): K > tuber_frame_match_max_dets(), K * (max_gap + 1) > tuber_tube_link_max_active(),
+// S * K * G beyond an int32, G < 1, K < 1, negative sizes, a null pointer, det_box / dense_box not 16-byte or another pointer not 4-byte
+// aligned.  S == 0: TUBER_OK, no launch.
+int tuber_tube_dense(const float* det_box, const float* det_score, const int* row_head, const int* slot_frame, int S, int K, int max_gap, int G,
+                     float* dense_box, float* dense_score, int* row_span, int* row_next, hipStream_t stream) {
+    if (S < 0 || K < 1 || max_gap < 0 || G < 1) return TUBER_EINVAL;
+    if (K > FMAP_MAX_DETS || (long)K * ((long)max_gap + 1) > TUBE_MAX_ACTIVE) return TUBER_EINVAL;
+    if ((long)S * K > 0x7FFFFFFFl || (long)S * K * G > 0x7FFFFFFFl) return TUBER_EINVAL;
+    if (S == 0) return TUBER_OK;
+    if (!det_box || !det_score || !row_head || !slot_frame || !dense_box || !dense_score || !row_span || !row_next) return TUBER_EINVAL;
+    if (((uintptr_t)det_box & 15) || ((uintptr_t)dense_box & 15)) return TUBER_EINVAL;
+    if (((uintptr_t)det_score | (uintptr_t)row_head | (uintptr_t)slot_frame | (uintptr_t)dense_score | (uintptr_t)row_span | (uintptr_t)row_next) & 3)
+        return TUBER_EINVAL;
+    const long N = (long)S * K;
+    hipLaunchKernelGGL(tube_dense_kernel, dim3((unsigned)((N + TDENSE_WAVES - 1) / TDENSE_WAVES)), dim3(64 * TDENSE_WAVES), 0, stream, det_box, det_score,
+                       row_head, slot_frame, S, K, max_gap, G, dense_box, dense_score, row_span, row_next);
+    TUBER_RETURN_LAUNCH();
+}
 
 int tuber_tube_match_max_gt() { return TUBE_MAX_GT; }
 int tuber_tube_match_max_thresholds() { return TUBE_MAX_THR; }

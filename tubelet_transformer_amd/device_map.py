@@ -82,6 +82,26 @@ def tube_nms_launch(boxes, slot_off, video_off, link, V, S, N, C, max_rows, min_
     return keep
 
 
+DENSE_NAMES = ("dense_box", "dense_score", "row_span", "row_next")
+
+
+def dense_beyond(S, K, G):
+    """why ``tuber_tube_dense`` cannot take a [S][K] store with ``G`` frames per row, or None"""
+    return "%d key frames of %d rows with up to %d frames per row: beyond 32 bits" % (S, K, G) if S * K * G > 0x7FFFFFFF else None
+
+
+def tube_dense_launch(boxes, scores, row_head, keys, max_gap, G):
+    """``tuber_tube_dense`` over the padded store [S][K] of one video behind its link step -> dict(dense_box [S * K, G, 4] fp32, dense_score
+    [S * K, G] fp32, row_span / row_next [S * K] int32) on the device; the entries behind a row's span are not written"""
+    S, K = scores.shape
+    dev, i32 = boxes.device, torch.int32
+    slot_frame = torch.tensor([int(k) for k in keys], dtype=i32).to(dev)
+    out = dict(dense_box=torch.empty(S * K, G, 4, dtype=torch.float32, device=dev), dense_score=torch.empty(S * K, G, dtype=torch.float32, device=dev),
+               row_span=torch.empty(S * K, dtype=i32, device=dev), row_next=torch.empty(S * K, dtype=i32, device=dev))
+    lib.call("tuber_tube_dense", boxes.contiguous(), scores.contiguous(), row_head, slot_frame, S, K, int(max_gap), int(G), *(out[k] for k in DENSE_NAMES))
+    return out
+
+
 class DeviceFrameMAP:
     """Arguments as ``evaluation.FrameMAP``; ``device``: where the detection buffers live (a CPU store runs the host evaluator)."""
 

@@ -586,6 +586,109 @@ def tube_nms(link, nms_iou, min_len=1):
     return keep
 
 
+# ---------------------------------------------------------------------------------------------------------------------------------------
+# dense tubes: a box on every frame of a tube's extent
+# ---------------------------------------------------------------------------------------------------------------------------------------
+def _dense_keys(who, keys):
+    """the frame numbers of the key ordinals as int64; they must ascend strictly"""
+    keys = np.asarray([int(k) for k in keys], dtype=np.int64)
+    if len(keys) > 1 and not (np.diff(keys) > 0).all():
+        raise ValueError("%s: the key frames must be strictly ascending, got %s" % (who, keys.tolist()[:16]))
+    return keys
+
+
+def dense_extent(keys, max_gap):
+    """G, the most frames one row can own: ``max(1, max over s of keys[min(s + max_gap + 1, S - 1)] - keys[s])`` -- a host integer, known from
+    the keys alone"""
+    keys, gap = _dense_keys("dense_extent", keys), int(max_gap)
+    S = len(keys)
+    return max([1] + [int(keys[min(s + gap + 1, S - 1)] - keys[s]) for s in range(S)])
+
+
+def _dense_fill(box_a, score_a, box_b, score_b, g, out_box, out_score):
+    """The arithmetic of ``dense_rows`` / ``dense_tube`` / ``tuber_tube_dense``: the ``g`` frames a key row owns into ``out_box[:g]`` /
+    ``out_score[:g]``.  ``j = 0``: the row's own bytes.  ``j >= 1``: ``float32(float64(a) + (float64(b) - float64(a)) * (float64(j) /
+    float64(g)))`` per coordinate and for the score, every operation rounded on its own; a NaN result is the one quiet NaN 0x7FC00000."""
+    out_box[0], out_score[0] = box_a, score_a
+    if g > 1:
+        a = np.concatenate([box_a, [score_a]]).astype(np.float64)
+        b = np.concatenate([box_b, [score_b]]).astype(np.float64)
+        with np.errstate(all="ignore"):
+            w = np.arange(1, g, dtype=np.float64) / np.float64(g)
+            d = b - a
+            v = (a[None, :] + d[None, :] * w[:, None]).astype(np.float32)
+        v[np.isnan(v)] = np.float32(np.nan)
+        out_box[1:g], out_score[1:g] = v[:, :4], v[:, 4]
+
+
+def dense_rows(box, score, row_head, keys, K, max_gap, G=None, dense_box=None, dense_score=None):
+    """Per-frame boxes between linked key detections: the definition of ``tuber_tube_dense`` and the host path of
+    ``tubes(dense=True)`` / ``tracks(dense=True)``.  A padded [S][K] store of ONE video: ``box`` [S * K, 4] fp32, ``score`` [S * K] fp32,
+    ``row_head`` [S * K] as ``link_rows`` / ``tuber_tube_link_ranked`` wrote it, ``keys`` [S] the frame number of every key ordinal, strictly
+    ascending.  The SUCCESSOR of a counted row r of slot s is the first row with r's head in the slots ``s + 1 .. s + max_gap + 1`` (the
+    linker bridges no more; one row per slot); ``span(r) = keys[s'] - keys[s]`` with a successor, 1 without, 0 for a row with head < 0.  Row
+    r owns the frames ``keys[s] + j``, ``j < span(r)``: at j = 0 its own bytes, behind that the fp64 interpolation towards the successor
+    (``_dense_fill``).  -> ``dense_box`` [S * K, G, 4] fp32, ``dense_score`` [S * K, G] fp32 (given, or zeros; entries at ``j >= span(r)``
+    are left as they were), ``row_span`` [S * K], ``row_next`` [S * K] (the successor row, -1 without one).  ``G``: ``dense_extent`` by
+    default; a row whose span exceeds a smaller one gets ``row_span`` -1 and nothing else, as in the kernel."""
+    keys, K, gap = _dense_keys("dense_rows", keys), int(K), int(max_gap)
+    S = len(keys)
+    N = S * K
+    box = np.asarray(box, dtype=np.float32).reshape(N, 4)
+    score = np.asarray(score, dtype=np.float32).reshape(N)
+    head = np.asarray(row_head).reshape(N)
+    G = dense_extent(keys, gap) if G is None else int(G)
+    if G < 1 or gap < 0 or K < 1:
+        raise ValueError("dense_rows: G = %d and K = %d must be >= 1, max_gap = %d >= 0" % (G, K, gap))
+    dense_box = np.zeros((N, G, 4), dtype=np.float32) if dense_box is None else dense_box
+    dense_score = np.zeros((N, G), dtype=np.float32) if dense_score is None else dense_score
+    span, nxt = np.zeros(N, dtype=np.int64), np.full(N, -1, dtype=np.int64)
+    for r in np.nonzero(head >= 0)[0].tolist():
+        s, n = r // K, -1
+        for t in range(s + 1, min(s + gap + 1, S - 1) + 1):
+            m = np.nonzero(head[t * K:(t + 1) * K] == head[r])[0]
+            if len(m):
+                n = t * K + int(m[0])
+                break
+        g = int(keys[n // K] - keys[s]) if n >= 0 else 1
+        if g > G:
+            span[r] = -1
+            continue
+        span[r], nxt[r] = g, n
+        _dense_fill(box[r], score[r], box[n], score[n], g, dense_box[r], dense_score[r])
+    return dict(dense_box=dense_box, dense_score=dense_score, row_span=span, row_next=nxt)
+
+
+def dense_tube(frames, boxes, scores):
+    """``dense_rows`` for one assembled tube on the host (``video.VideoStream.tubes(dense=True)``): its key frames (strictly ascending), [L, 4]
+    fp32 boxes and [L] fp32 scores -> dict(``frames``: every frame from the first key to the last, ``boxes`` [F, 4] fp32, ``frame_scores``
+    [F] fp32, ``key_index`` [F]: the index of the key that owns the frame).  The arithmetic is ``dense_rows``' (``_dense_fill``)."""
+    keys = _dense_keys("dense_tube", frames)
+    L = len(keys)
+    boxes = np.asarray(boxes, dtype=np.float32).reshape(L, 4)
+    scores = np.asarray(scores, dtype=np.float32).reshape(L)
+    spans = [int(keys[i + 1] - keys[i]) for i in range(L - 1)] + [1] * min(L, 1)
+    F = sum(spans)
+    out_box, out_score, at = np.zeros((F, 4), dtype=np.float32), np.zeros(F, dtype=np.float32), 0
+    for i, g in enumerate(spans):
+        n = min(i + 1, L - 1)
+        _dense_fill(boxes[i], scores[i], boxes[n], scores[n], g, out_box[at:at + g], out_score[at:at + g])
+        at += g
+    return dict(frames=list(range(int(keys[0]), int(keys[0]) + F)) if L else [], boxes=out_box, frame_scores=out_score,
+                key_index=np.repeat(np.arange(L, dtype=np.int64), spans))
+
+
+def dense_from_rows(rows, keys, K, dense):
+    """one tube's dense fields from the per-row record ``dense_rows`` / ``tuber_tube_dense`` leave: ``rows`` the tube's rows in slot order ->
+    ``dense_tube``'s dict"""
+    rows = np.asarray(rows, dtype=np.int64)
+    span = np.asarray(dense["row_span"])[rows].astype(np.int64)
+    first = int(keys[int(rows[0]) // K])
+    owned = np.arange(dense["dense_score"].shape[1])[None, :] < span[:, None]           # row-major: the rows in order, each one's frames in order
+    return dict(frames=list(range(first, first + int(span.sum()))), boxes=dense["dense_box"][rows][owned], frame_scores=dense["dense_score"][rows][owned],
+                key_index=np.repeat(np.arange(len(rows), dtype=np.int64), span))
+
+
 def actor_tracks(box, actor, queries, actions, S, A, link_iou, max_gap, window):
     """Actor tracks of ONE video: the definition of ``tuber_track_actions`` and the fallback of ``video.VideoActors.tracks``.
     The rows are a padded [S][A] actor store (``detect.decode_actors_host`` per key frame): ``box`` [S * A, 4] fp32 xyxy, ``actor`` [S * A] fp32,

@@ -13,6 +13,10 @@ change, and the linker resumed push by push (``tuber_tube_link_stream``; ``evalu
 ``VideoDetector`` is the definition the stream is held to.  With ``actors=A`` the stream carries the actor tracks of section 6i as well
 (DESIGN.md section 6j): per-track action sums resumed push by push (``tuber_track_actions_stream``; ``evaluation.ActorTracker`` is its
 definition and its fallback) and ``VideoStream.tracks()``.
+
+``tubes(dense=True)`` / ``tracks(dense=True)`` put a box on every frame of a tube's extent, interpolated between the linked
+key detections: ``tuber_tube_dense`` behind the link step over a whole video (``evaluation.dense_rows`` is its definition and its fallback),
+``evaluation.dense_tube`` on the host for the closed tubes of a stream.
 """
 import functools
 import sys
@@ -23,7 +27,7 @@ import torch
 from . import input_pipeline as ip
 from . import lib
 from .detect import ACTOR_FIELDS, FIELDS, Detector, Record, field_tensors, host_parts
-from .device_map import link_beyond, link_limits, link_ranked, tube_nms_launch
+from .device_map import DENSE_NAMES, dense_beyond, link_beyond, link_limits, link_ranked, tube_dense_launch, tube_nms_launch
 from .misc import NestedTensor
 
 RULES = ("ava", "jhmdb", "edge")
@@ -98,13 +102,20 @@ def _track_labels(mean, label_thr):
         return sorted(np.nonzero(mean >= label_thr)[0].tolist(), key=lambda c: (-mean[c], c))
 
 
+def _densified(t, dense):
+    """the dict of a tube or track with a box on every frame (``dense``: ``evaluation.dense_tube``'s dict): ``frames`` / ``boxes`` per frame, the
+    key frames and their boxes under ``keys`` / ``key_boxes``, and ``frame_scores`` / ``key_index`` beside them"""
+    return dict(t, keys=t["frames"], key_boxes=t["boxes"], **dense)
+
+
 class _VideoRecord(Record):
     """What ``VideoDetections`` and ``VideoActors`` share: a row per key frame, the defaults of ``tubes()`` / ``tracks()``, and ``to_host``."""
 
-    def __init__(self, keys, tensors, settings, store, nms_iou):
+    def __init__(self, keys, tensors, settings, store, nms_iou, dense=False):
         super().__init__(*tensors)
         self.keys = [int(k) for k in keys]
         self.nms_iou = None if nms_iou is None else float(nms_iou)                      # the default of tubes(nms=) / tracks(nms=): CONFIG.VAL.TUBE_NMS
+        self.dense = bool(dense)                                                       # the default of tubes(dense=) / tracks(dense=): CONFIG.VAL.VIDEO_MAP.DENSE
         self.settings = dict(settings)
         self._store = store                                                            # the engine's ParamStore: to_host reads its error word
         self.row_head = self.row_score = self.row_len = None                           # the link records of a VideoStream push
@@ -131,12 +142,35 @@ class _VideoRecord(Record):
         keep = host.get("tube_keep")
         return tube_nms(link, nms, max(min_len, 1)) if keep is None or (keep == 3).any() else keep      # the host path, or the kernel's escape
 
-    def _linked(self, link, slot_off, video_off, names, C, nms, min_len):
-        """the fields and the link records ``names`` (with ``nms``, ``tube_keep`` of ``tuber_tube_nms`` as well) as one dict, in one copy"""
+    def _extent(self, dense, max_gap):
+        """None without ``dense`` (None: the record's default); else G, the most frames a row can own (``evaluation.dense_extent``) -- host
+        integers only, and keys that do not ascend strictly raise here, before anything is launched"""
+        from .evaluation import dense_extent
+        return dense_extent(self.keys, max_gap) if (self.dense if dense is None else bool(dense)) else None
+
+    def _dense(self, host, score, max_gap, G, linked_on_host):
+        """(None, None) without ``G``; else (the per-row dense record, why it was made on the host behind a device link or None): the
+        kernel's four arrays as they were fetched, or ``evaluation.dense_rows`` on the host path, beyond 32 bits and at the kernel's escape"""
+        from .evaluation import dense_rows
+        if G is None:
+            return None, None
+        S, K = self.boxes.shape[:2]
+        span = host.get("row_span")
+        if span is not None and not (span == -1).any():
+            return host, None
+        why = None if linked_on_host else (dense_beyond(S, K, G) or "tuber_tube_dense left a row to the host (more than %d frames)" % G)
+        return dense_rows(host["boxes"].reshape(-1, 4), score.reshape(-1), host["row_head"], self.keys, K, max_gap), why
+
+    def _linked(self, link, slot_off, video_off, names, C, nms, min_len, dense=None):
+        """the fields and the link records ``names`` (with ``nms``, ``tube_keep`` of ``tuber_tube_nms`` as well; with ``dense`` = (scores,
+        max_gap, G), the four outputs of ``tuber_tube_dense``) as one dict, in one copy"""
         S, n = self.boxes.shape[:2]
         if nms is not None:
             link["tube_keep"] = tube_nms_launch(self.boxes.contiguous(), slot_off, video_off, link, 1, S, S * n, C, n, max(int(min_len), 1), nms)
             names += ("tube_keep",)
+        if dense is not None and dense[2] is not None and not dense_beyond(S, n, dense[2]):
+            link.update(tube_dense_launch(self.boxes, dense[0], link["row_head"], self.keys, dense[1], dense[2]))
+            names += DENSE_NAMES
         host, records = self._fetch([link[k] for k in names])
         return dict(host, **dict(zip(names, records)))
 
@@ -147,17 +181,18 @@ class VideoDetections(_VideoRecord):
     ``total`` [n] int32 -- the fields of ``detect.Detections``, a row per key frame."""
     FIELDS, ROW_FIELDS = FIELDS, FIELDS[:5]
 
-    def __init__(self, keys, boxes, scores, labels, queries, aux, count, total, class_num, settings=None, store=None, nms_iou=None):
+    def __init__(self, keys, boxes, scores, labels, queries, aux, count, total, class_num, settings=None, store=None, nms_iou=None, dense=False):
         # the defaults of tubes(): CONFIG.VAL.VIDEO_MAP, CONFIG.VAL.TUBE_NMS.IOU
-        super().__init__(keys, (boxes, scores, labels, queries, aux, count, total), settings or dict(link_iou=0.2, max_gap=2, min_len=1), store, nms_iou)
+        super().__init__(keys, (boxes, scores, labels, queries, aux, count, total), settings or dict(link_iou=0.2, max_gap=2, min_len=1), store, nms_iou,
+                         dense)
         self.class_num = int(class_num)
         self.tubes_path = None                                                         # "device" or "host" after tubes()
         self.actors = None                                                             # the ``VideoActors`` of ``VideoDetector(..., actors=A)``
 
     # -- tubes ------------------------------------------------------------------------------------------------------------
-    def _link_device(self, link_iou, max_gap, nms=None, min_len=1):
-        """``tuber_tube_link_ranked`` (and, with ``nms``, ``tuber_tube_nms`` behind it) over the padded store as it is, or None where the
-        linker's bounds refuse it"""
+    def _link_device(self, link_iou, max_gap, nms=None, min_len=1, G=None):
+        """``tuber_tube_link_ranked`` (and, with ``nms``, ``tuber_tube_nms``, with ``G``, ``tuber_tube_dense`` behind it) over the padded store
+        as it is, or None where the linker's bounds refuse it"""
         K = self.scores.shape[1]
         if self.boxes.device.type != "cuda":
             return None, "the store is on the CPU"
@@ -165,9 +200,10 @@ class VideoDetections(_VideoRecord):
         if why:
             return None, why
         link, slot_off, video_off = link_ranked(self.boxes, self.labels, self.scores, self.class_num, link_iou, max_gap)
-        return self._linked(link, slot_off, video_off, ("row_head", "tube_score", "tube_len", "tube_last"), self.class_num, nms, min_len), None
+        return self._linked(link, slot_off, video_off, ("row_head", "tube_score", "tube_len", "tube_last"), self.class_num, nms, min_len,
+                            (self.scores, max_gap, G)), None
 
-    def tubes(self, link_iou=None, max_gap=None, min_len=None, nms=None):
+    def tubes(self, link_iou=None, max_gap=None, min_len=None, nms=None, dense=None):
         """The action tubes of the video: a list of ``dict(cls, score, frames, boxes, length)`` in head order (the order of the tubes' first
         detections) -- ``cls`` 1-based as in ``evaluation.tubes_from_link``, ``score`` the fp64 mean of the linked fp32 scores, ``frames`` the key
         frame numbers, ``boxes`` [length, 4] in source pixels; tubes shorter than ``min_len`` are dropped.  The slots of the linker are key
@@ -177,21 +213,31 @@ class VideoDetections(_VideoRecord):
         ``topk`` is 21 = 64 // (MAX_GAP + 1) with the shipped MAX_GAP of 2, so that the default path is the device's.  ``nms`` (default:
         ``CONFIG.VAL.TUBE_NMS.IOU``; None: off): per class a tube whose spatio-temporal IoU with a higher-scored kept tube exceeds it is
         dropped -- one more launch, ``tuber_tube_nms``, whose bytes travel in the same copy; on the host path
-        ``evaluation.tube_nms``."""
-        from .evaluation import link_rows, tubes_from_link
+        ``evaluation.tube_nms``.  ``dense`` (default: ``CONFIG.VAL.VIDEO_MAP.DENSE``, False): a box on EVERY frame from the tube's first key
+        to its last -- ``frames`` becomes that range and ``boxes`` [F, 4]: a key frame carries its detection's bytes,
+        a frame between two linked keys the fp64 interpolation of the two boxes (``evaluation.dense_rows``: the definition), a key the linker
+        bridged over is filled like any other gap; the key frames and their boxes move to ``keys`` / ``key_boxes``, ``frame_scores`` [F] fp32
+        is the score interpolated alike and ``key_index`` [F] the index into ``keys`` of the key that owns the frame.  One more launch,
+        ``tuber_tube_dense``, behind the link (and the NMS, which decides on the key rows as before), its four outputs in the same copy;
+        on the host path, beyond 32 bits or at the kernel's escape ``evaluation.dense_rows``.  The keys must ascend strictly."""
+        from .evaluation import dense_from_rows, link_rows, tubes_from_link
         nms = _nms_value("VideoDetections.tubes", self.nms_iou if nms is None else nms)
         link_iou = float(self.settings["link_iou"] if link_iou is None else link_iou)
         max_gap = int(self.settings["max_gap"] if max_gap is None else max_gap)
         min_len = int(self.settings["min_len"] if min_len is None else min_len)
         S, K = self.scores.shape
+        G = self._extent(dense, max_gap)
         slot = np.repeat(np.arange(S, dtype=np.int64), K)
-        host, why = self._link_device(link_iou, max_gap, nms, min_len)
+        host, why = self._link_device(link_iou, max_gap, nms, min_len, G)
         if host is None:
             print("[tuber] VideoDetections.tubes: %s; linking on the host" % why, file=sys.stderr, flush=True)
             host = self._fetch()[0]
             host.update(link_rows(host["boxes"].reshape(-1, 4), host["labels"].reshape(-1), host["scores"].reshape(-1), slot, [0, S], self.class_num,
                                   link_iou, max_gap))
-        self.tubes_path = "host" if why else "device"
+        rows, dense_why = self._dense(host, host["scores"], max_gap, G, why is not None)
+        if dense_why:
+            print("[tuber] VideoDetections.tubes: %s; per-frame boxes on the host" % dense_why, file=sys.stderr, flush=True)
+        self.tubes_path = "host" if why or dense_why else "device"
         layout = dict(videos=["video"], video_off=np.asarray([0, S]), first_frame=np.asarray([0]))
         link = dict(layout=layout, row_head=host["row_head"], row_slot=slot, row_cls=host["labels"].reshape(-1), tube_score=host["tube_score"],
                     det_box=host["boxes"].reshape(-1, 4))
@@ -199,7 +245,8 @@ class VideoDetections(_VideoRecord):
         out = []
         for t in tubes_from_link(link):
             if len(t["frames"]) >= min_len and (keep is None or keep[t["head"]] != 0):
-                out.append(dict(cls=t["cls"], score=t["score"], frames=[self.keys[s] for s in t["frames"]], boxes=t["boxes"], length=len(t["frames"])))
+                d = dict(cls=t["cls"], score=t["score"], frames=[self.keys[s] for s in t["frames"]], boxes=t["boxes"], length=len(t["frames"]))
+                out.append(d if rows is None else _densified(d, dense_from_rows(t["rows"], self.keys, K, rows)))
         return out
 
 
@@ -210,10 +257,10 @@ class VideoActors(_VideoRecord):
     ``detect.Actors``, a row per key frame."""
     FIELDS, ROW_FIELDS = ACTOR_FIELDS, ACTOR_FIELDS[:4]
 
-    def __init__(self, keys, boxes, actor, queries, actions, count, total, settings=None, store=None, nms_iou=None):
+    def __init__(self, keys, boxes, actor, queries, actions, count, total, settings=None, store=None, nms_iou=None, dense=False):
         # the defaults of tracks(): CONFIG.VAL.ACTORS, CONFIG.VAL.TUBE_NMS.ACTORS_IOU
         super().__init__(keys, (boxes, actor, queries, actions, count, total),
-                         settings or dict(link_iou=0.2, max_gap=2, min_len=1, window=1, label_thr=0.05), store, nms_iou)
+                         settings or dict(link_iou=0.2, max_gap=2, min_len=1, window=1, label_thr=0.05), store, nms_iou, dense)
         self.class_num = int(actions.shape[2])
         self.tracks_path = None                                                        # "device" or "host" after tracks()
         # the track records of a VideoStream(actors=A) push: row_head / row_score / row_len [n, A], row_mean / row_peak [n, A, C], smooth [m, A, C]
@@ -223,9 +270,9 @@ class VideoActors(_VideoRecord):
     # -- tracks -----------------------------------------------------------------------------------------------------------
     NAMES = ("row_head", "tube_score", "tube_len", "tube_last", "row_smooth", "track_mean", "track_peak")
 
-    def _tracks_device(self, link_iou, max_gap, window, nms=None, min_len=1):
-        """``tuber_tube_link_ranked`` with one class and ``tuber_track_actions`` (and, with ``nms``, ``tuber_tube_nms``) over the padded store as
-        it is, everything read back in one copy; or None where the kernels' bounds refuse it"""
+    def _tracks_device(self, link_iou, max_gap, window, nms=None, min_len=1, G=None):
+        """``tuber_tube_link_ranked`` with one class and ``tuber_track_actions`` (and, with ``nms``, ``tuber_tube_nms``, with ``G``,
+        ``tuber_tube_dense``) over the padded store as it is, everything read back in one copy; or None where the kernels' bounds refuse it"""
         S, A, C = self.actions.shape
         if self.boxes.device.type != "cuda":
             return None, "the store is on the CPU"
@@ -240,9 +287,9 @@ class VideoActors(_VideoRecord):
                     track_peak=torch.empty(S * A, C, dtype=torch.float32, device=label.device))
         lib.call("tuber_track_actions", self.actions.contiguous(), link["row_head"], link["tube_last"], S, A, C, int(window), link["row_smooth"],
                  link["track_mean"], link["track_peak"])
-        return self._linked(link, slot_off, video_off, self.NAMES, 1, nms, min_len), None
+        return self._linked(link, slot_off, video_off, self.NAMES, 1, nms, min_len, (self.actor, max_gap, G)), None
 
-    def tracks(self, link_iou=None, max_gap=None, min_len=None, window=None, label_thr=None, nms=None):
+    def tracks(self, link_iou=None, max_gap=None, min_len=None, window=None, label_thr=None, nms=None, dense=None):
         """The actor tracks of the video -- who is there, from when to when, doing what: a list, in head order (the order of the tracks' first
         rows), of ``dict(score, frames, boxes, actor, queries, actions, smooth, mean, peak, labels, length)``: ``score`` the fp64 mean actor
         probability, ``frames`` the key frame numbers, ``boxes`` [L, 4] in source pixels, ``actor`` / ``queries`` [L], ``actions`` [L, C] fp32 the
@@ -253,8 +300,11 @@ class VideoActors(_VideoRecord):
         A * (max_gap + 1) > 64, C > 4096) or on a CPU store the definition answers on the host, one line says so, and ``tracks_path`` is "host"
         instead of "device".  ``nms`` (default: ``CONFIG.VAL.TUBE_NMS.ACTORS_IOU``; None: off): a track whose spatio-temporal IoU with a
         kept track of higher mean actor probability exceeds it is dropped, class-agnostically: ``tuber_tube_nms`` on
-        the device, ``evaluation.tube_nms`` on the host path.  The aggregates of the kept tracks are unchanged."""
-        from .evaluation import actor_tracks
+        the device, ``evaluation.tube_nms`` on the host path.  The aggregates of the kept tracks are unchanged.  ``dense`` (default:
+        ``CONFIG.VAL.VIDEO_MAP.DENSE``): as in ``VideoDetections.tubes`` -- ``frames`` / ``boxes`` per frame, ``keys`` / ``key_boxes`` /
+        ``frame_scores`` (the interpolated actor probability) / ``key_index`` added; the per-key fields (``actor``, ``actions``, ``smooth``,
+        ...) stay per key and are addressed per frame through ``key_index``."""
+        from .evaluation import actor_tracks, dense_from_rows
         nms = _nms_value("VideoActors.tracks", self.nms_iou if nms is None else nms)
         st = self.settings
         link_iou = float(st["link_iou"] if link_iou is None else link_iou)
@@ -265,12 +315,16 @@ class VideoActors(_VideoRecord):
         if max_gap < 0 or window < 0:
             raise ValueError("VideoActors.tracks: max_gap = %d and window = %d must be >= 0" % (max_gap, window))
         S, A, C = self.actions.shape
-        host, why = self._tracks_device(link_iou, max_gap, window, nms, min_len)
+        G = self._extent(dense, max_gap)
+        host, why = self._tracks_device(link_iou, max_gap, window, nms, min_len, G)
         if host is None:
             print("[tuber] VideoActors.tracks: %s; tracks on the host" % why, file=sys.stderr, flush=True)
             host = self._fetch()[0]
             host.update(actor_tracks(host["boxes"], host["actor"], host["queries"], host["actions"], S, A, link_iou, max_gap, window))
-        self.tracks_path = "host" if why else "device"
+        dense_rec, dense_why = self._dense(host, host["actor"], max_gap, G, why is not None)
+        if dense_why:
+            print("[tuber] VideoActors.tracks: %s; per-frame boxes on the host" % dense_why, file=sys.stderr, flush=True)
+        self.tracks_path = "host" if why or dense_why else "device"
         head = np.asarray(host["row_head"]).reshape(-1)
         box, actor, query, act = host["boxes"].reshape(-1, 4), host["actor"].reshape(-1), host["queries"].reshape(-1), host["actions"].reshape(-1, C)
         members = {}
@@ -284,9 +338,10 @@ class VideoActors(_VideoRecord):
             if len(rows) < min_len or (keep is not None and keep[h] == 0):
                 continue
             mean = np.array(host["track_mean"][h], dtype=np.float64)
-            out.append(dict(score=float(host["tube_score"][h]), frames=[self.keys[r // A] for r in rows], boxes=box[rows].copy(), actor=actor[rows].copy(),
-                            queries=query[rows].copy(), actions=act[rows].copy(), smooth=np.array(host["row_smooth"][rows], dtype=np.float64), mean=mean,
-                            peak=np.array(host["track_peak"][h], dtype=np.float32), labels=_track_labels(mean, label_thr), length=len(rows)))
+            d = dict(score=float(host["tube_score"][h]), frames=[self.keys[r // A] for r in rows], boxes=box[rows].copy(), actor=actor[rows].copy(),
+                     queries=query[rows].copy(), actions=act[rows].copy(), smooth=np.array(host["row_smooth"][rows], dtype=np.float64), mean=mean,
+                     peak=np.array(host["track_peak"][h], dtype=np.float32), labels=_track_labels(mean, label_thr), length=len(rows))
+            out.append(d if dense_rec is None else _densified(d, dense_from_rows(rows, self.keys, A, dense_rec)))
         return out
 
 
@@ -296,9 +351,10 @@ class _VideoRunner:
     what becomes of the rows is the subclass's."""
 
     def __init__(self, cfg, model, batch, score_thr, topk, actor_thr, graphed, rule, actors):
-        from .config import actor_settings, detect_settings, video_map_settings
+        from .config import actor_settings, dense_setting, detect_settings, video_map_settings
         self.cfg, self.model, self.batch = cfg, model, int(batch)
         vm = video_map_settings(cfg)
+        self.dense = dense_setting(cfg)    # the default of tubes(dense=) / tracks(dense=): kept out of ``settings``
         self.settings = dict(link_iou=float(vm["link_iou"]), max_gap=int(vm["max_gap"]), min_len=int(vm["min_len"]))
         if topk is None:
             topk = max(1, min(detect_settings(cfg)["topk"], lib.query("tuber_tube_link_max_active") // (self.settings["max_gap"] + 1)))
@@ -433,9 +489,11 @@ class VideoDetector(_VideoRunner):
         for i in range(nb):
             lib.call("tuber_video_clips", resident, N, b["nh"], b["nw"], table[i * B:], B, T, *b["window"], b["lut"], b["clips"])
             self._detect(b, stores, i * B)
-        vd = VideoDetections(keys, *[t[:n] for t in stores[0]], class_num=self.class_num, settings=self.settings, store=store, nms_iou=self.nms["iou"])
+        vd = VideoDetections(keys, *[t[:n] for t in stores[0]], class_num=self.class_num, settings=self.settings, store=store, nms_iou=self.nms["iou"],
+                             dense=self.dense)
         if stores[1] is not None:
-            vd.actors = VideoActors(keys, *[t[:n] for t in stores[1]], settings=self.actor_settings, store=store, nms_iou=self.nms["actors_iou"])
+            vd.actors = VideoActors(keys, *[t[:n] for t in stores[1]], settings=self.actor_settings, store=store, nms_iou=self.nms["actors_iou"],
+                                    dense=self.dense)
         return vd
 
 
@@ -560,7 +618,11 @@ class VideoStream(_VideoRunner):
 
     Tube NMS (``CONFIG.VAL.TUBE_NMS``) is not part of the stream: when a tube closes, a tube that would suppress it may
     still be open with its final score unknown, so no streaming rule equals the whole-video one.  A config that sets it is ignored here, with
-    one line on stderr at construction; ``tubes()`` / ``tracks()`` return every closed tube."""
+    one line on stderr at construction; ``tubes()`` / ``tracks()`` return every closed tube.
+
+    Dense tubes (``tubes(dense=True)`` / ``tracks(dense=True)``, default ``CONFIG.VAL.VIDEO_MAP.DENSE``) ARE part of the
+    stream: a closed tube never changes, so a box on every frame of its extent is filled in on the host where the tube is assembled
+    (``evaluation.dense_tube``) and equals ``VideoDetector``'s, bit for bit."""
 
     def __init__(self, cfg, model, batch=2, stride=None, rule=None, max_chunk=64, score_thr=None, topk=None, actor_thr=None, graphed=True,
                  link=True, actors=None):
@@ -767,42 +829,46 @@ class VideoStream(_VideoRunner):
         return out
 
     # -- tubes and actor tracks -------------------------------------------------------------------------------------------
-    TUBE_NAMES = ("boxes", "labels", "row_head", "row_score", "row_len")
+    TUBE_NAMES = ("boxes", "labels", "row_head", "row_score", "row_len", "scores")
     TRACK_NAMES = ("boxes", "actor", "queries", "actions", "row_head", "row_score", "row_len", "row_mean", "row_peak", "smooth")
 
     @staticmethod
-    def _drain(pending, assembler, names, last=()):
-        """the records of ``pending`` through ``assembler`` -> what closed: ONE device-to-host copy for every record, ``end()`` at the markers of a
-        video's end"""
+    def _drain(pending, assembler, names, last=(), dense=False):
+        """the records of ``pending`` through ``assembler`` -> what closed (``dense``: with a box on every frame): ONE device-to-host copy for
+        every record, ``end()`` at the markers of a video's end"""
         host = host_parts([getattr(p[1], k) for p in pending if p is not None for k in names])
         out, i, m = [], 0, len(names)
         for p in pending:
             if p is None:                                       # the end of a video: whatever is open closes
                 assembler.end()
-                out += assembler.take()
+                out += assembler.take(dense)
                 continue
             first_ord, rec = p
             assembler.add(first_ord, rec.keys, *host[m * i:m * i + m], *(getattr(rec, k) for k in last))
             i += 1
-        return out + assembler.take()
+        return out + assembler.take(dense)
 
-    def tubes(self):
+    def tubes(self, dense=None):
+        """The tubes that closed since the last call (the class docstring).  ``dense`` (default: ``CONFIG.VAL.VIDEO_MAP.DENSE``): every closed
+        tube through ``evaluation.dense_tube`` on the host, where it was assembled anyway -- ``VideoDetections.tubes(dense=True)``'s dicts
+        (plus ``head``), bit for bit; no device state is added and ``push`` is as it was."""
         if not self.link:
             raise RuntimeError("VideoStream(link=False) keeps no link records: no tubes")
         pending, self._pending = self._pending, []
-        return self._drain(pending, self._tubes, self.TUBE_NAMES)
+        return self._drain(pending, self._tubes, self.TUBE_NAMES, dense=self.dense if dense is None else bool(dense))
 
-    def tracks(self):
+    def tracks(self, dense=None):
         """The actor tracks (``actors=A``) that CLOSED since the last call: the next key ordinal is more than ``max(max_gap + 1, window)`` past
         their last one -- no key frame still to come can extend them, and the smoothed row of their last key has been emitted -- and after
         ``finish()`` all that remain.  ``VideoActors.tracks``' dicts plus ``head`` (key ordinal * A + position of the first row), in head
         order; ``score`` / ``mean`` / ``peak`` are the records of the track's last row.  One device-to-host copy per call; the rows of open
         tracks are kept on the host in between (``TrackAssembler``; ``TubeAssembler`` for ``tubes()``).  ``tubes()`` keeps its own records:
-        neither consumes the other's."""
+        neither consumes the other's.  ``dense`` (default: ``CONFIG.VAL.VIDEO_MAP.DENSE``): as in ``tubes``, the interpolated score being
+        the actor probability -- ``VideoActors.tracks(dense=True)``'s dicts."""
         if self._assembler is None:
             raise RuntimeError("VideoStream without actors=A keeps no actor records: no tracks")
         pending, self._pending_tracks = self._pending_tracks, []
-        return self._drain(pending, self._assembler, self.TRACK_NAMES, ("smooth_first",))
+        return self._drain(pending, self._assembler, self.TRACK_NAMES, ("smooth_first",), dense=self.dense if dense is None else bool(dense))
 
 
 class _HostDefinition:
@@ -826,6 +892,8 @@ class _HostDefinition:
 class _Assembler:
     """What ``TubeAssembler`` and ``TrackAssembler`` share: open records by head, a record closing once the next key ordinal is more than
     ``stale`` past its last one or the video ends, closed records shorter than ``min_len`` dropped, ``take()`` in head order."""
+
+    SCORE, SCORE_IS_PUBLIC = None, True                # the per-key field ``take(dense=True)`` interpolates, and whether the plain dict shows it
 
     def __init__(self, stale, min_len):
         self.stale, self.min_len = int(stale), int(min_len)
@@ -858,9 +926,21 @@ class _Assembler:
                 if t["length"] >= self.min_len:
                     self._closed.append(self._finished(t))
 
-    def take(self):
+    def take(self, dense=False):
         out, self._closed = sorted(self._closed, key=lambda t: t["head"]), []
-        return out
+        return [self._emit(t, dense) for t in out]
+
+    def _emit(self, t, dense):
+        """a closed record as its public dict: without ``dense`` as ``_finished`` left it; with it through ``evaluation.dense_tube``, the
+        interpolated score being the record's ``SCORE`` field (per key)"""
+        from .evaluation import dense_tube
+        t = dict(t)
+        score = t.get(self.SCORE) if self.SCORE_IS_PUBLIC else t.pop(self.SCORE, None)
+        if not dense:
+            return t
+        if score is None:
+            raise RuntimeError("%s: dense tubes need the per-key %s, which add() was not given" % (type(self).__name__, self.SCORE))
+        return _densified(t, dense_tube(t["frames"], t["boxes"], score))
 
 
 class TubeAssembler(_Assembler):
@@ -868,19 +948,26 @@ class TubeAssembler(_Assembler):
     ``add(first_ord, keys, boxes, labels, row_head, row_score, row_len)`` takes the records of the keys ``first_ord ..`` ([n, K, ...] arrays);
     ``end()`` marks the end of the video; ``take()`` returns the tubes closed since the last call, in head order: after ``end()`` all of them,
     before it those whose last key lies more than ``max_gap + 1`` ordinals behind the next one.  A tube is ``VideoDetections.tubes``' dict plus
-    ``head``; tubes shorter than ``min_len`` are dropped."""
+    ``head``; tubes shorter than ``min_len`` are dropped.  ``take(dense=True)``: ``VideoDetections.tubes(dense=True)``'s dicts instead
+    (``evaluation.dense_tube`` per closed tube); it needs ``add(..., scores)``, the [n, K] fp32 scores of the rows."""
+    SCORE, SCORE_IS_PUBLIC = "scores", False
 
     def __init__(self, max_gap, min_len=1):
         super().__init__(int(max_gap) + 1, min_len)
 
-    def add(self, first_ord, keys, boxes, labels, row_head, row_score, row_len):
+    def add(self, first_ord, keys, boxes, labels, row_head, row_score, row_len, scores=None):
         for s, q, t in self._rows(first_ord, keys, row_head, row_score, row_len):
             t.setdefault("cls", int(labels[s, q]) + 1)
             t.setdefault("boxes", []).append(boxes[s, q].copy())
+            if scores is not None:
+                t.setdefault("scores", []).append(np.float32(scores[s, q]))
         self._advance(first_ord + len(keys))
 
     def _finished(self, t):
-        return dict(cls=t["cls"], score=t["score"], frames=t["frames"], boxes=np.stack(t["boxes"]), length=t["length"], head=t["head"])
+        out = dict(cls=t["cls"], score=t["score"], frames=t["frames"], boxes=np.stack(t["boxes"]), length=t["length"], head=t["head"])
+        if len(t.get("scores", ())) == len(t["frames"]):
+            out["scores"] = np.asarray(t["scores"], dtype=np.float32)
+        return out
 
 
 class TrackAssembler(_Assembler):
@@ -889,7 +976,9 @@ class TrackAssembler(_Assembler):
     records of the keys ``first_ord ..`` ([n, A, ...] arrays; ``smooth`` [m, A, C] belongs to the slots ``smooth_first ..``, which lag
     ``window`` keys behind); ``end()`` marks the end of the video; ``take()`` returns the tracks closed since the last call, in head order: after
     ``end()`` all of them, before it those whose last key lies more than ``max(max_gap + 1, window)`` ordinals behind the next one.  A track
-    is ``VideoActors.tracks``' dict plus ``head``; tracks shorter than ``min_len`` are dropped."""
+    is ``VideoActors.tracks``' dict plus ``head``; tracks shorter than ``min_len`` are dropped.  ``take(dense=True)``:
+    ``VideoActors.tracks(dense=True)``'s dicts instead (``evaluation.dense_tube`` per closed track over its ``actor`` probabilities)."""
+    SCORE, SCORE_IS_PUBLIC = "actor", True
 
     def __init__(self, A, max_gap, window, min_len=1, label_thr=0.05):
         super().__init__(max(int(max_gap) + 1, int(window)), min_len)
