@@ -3,8 +3,6 @@ same bf16-rounded inputs.  Tolerances: bf16 outputs are compared at 2^-7 relativ
 (one bf16 rounding + fp32 accumulation-order noise); fp32 outputs / statistics at 1e-3 relative."""
 import math
 
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -87,12 +85,11 @@ def test_gemm_nt_bn_prologue_stats(dev, M, N, K):
     close("gemm_nt stats sumsq", st1.sum(0), (ref * ref).sum(0), rel=2e-3)
 
 
-@pytest.mark.parametrize("cfg", [7, 13, 0] + ([2, 12, 17] if os.environ.get("TUBER_AB_VARIANTS") else []))
+@pytest.mark.parametrize("cfg", [7, 13, 0])
 @pytest.mark.parametrize("M,N,K", [(5632, 256, 1024), (5632, 1024, 256), (700, 128, 192), (130, 64, 64)])
 def test_gemm_nt_forced_tile_configs(dev, cfg, M, N, K):
     """every tile configuration of the product library (13: 64x64, 7: 64x128, 0: 128x128 -- forced here also for the shapes that would
-    not pick them; the rejected A/B variants 2 / 12 / 17 join when library and test run are built / started with TUBER_AB_VARIANTS=1)
-    through all prologue / epilogue variants, incl. an odd number of k-tiles and a single tile"""
+    not pick them) through all prologue / epilogue variants, incl. an odd number of k-tiles and a single tile"""
     assert lib.query("tuber_gemm_nt_has_cfg", cfg), "tile variant %d is not in this build of libtuber_hip.so" % cfg
     A = rnd(M, K, dev=dev, seed=1).to(BF)
     B = rnd(N, K, dev=dev, seed=2, scale=K ** -0.5).to(BF)
@@ -178,6 +175,33 @@ def test_gemm_nt_wave_split_k(dev, M, N, K):
     close("wsk join dz", got["join"][0], refj)
     close("wsk join vs shared tile", got["join"][0], base["join"][0], rel=2 ** -8)
     close("wsk join sum dz*c", got["join"][2].sum(0), (refj * Cm.float()).sum(0), abs_=2e-3 * float((refj * Cm.float()).abs().sum(0).max()))
+
+
+@pytest.mark.parametrize("M,N,K,form", [(130, 64, 64, (0, 64, 64)), (2048, 256, 256, (0, 64, 128)), (1100, 1024, 1024, (1, 96, 64)), (8192, 64, 64, (2, 96, 64))])
+def test_gemm_nt_launches_what_the_plan_says(dev, M, N, K, form):
+    """tuber_gemm_nt_plan is the decision the launcher takes: the statistics epilogue writes one partial row per tile row, so the rows of the
+    [ceil(M / 64)][N] buffers that hold anything are ceil(M / plan rows) -- the shared-tile 64 x 64 and 64 x 128 configurations, wave split-K
+    on 96-row tiles (1100 x 1024: 288 tiles of 64 rows, 192 of 96) and the regular 96 x 64 form; the 96-row forms write the rest as zero
+    (the buffers start as NaN).  Column sums against fp32 at the tolerance of test_gemm_nt_bn_prologue_stats."""
+    v = lib.query("tuber_gemm_nt_plan", M, N, K, 0, 1, 0, 0, 1)
+    assert (v // 1000000, v // 1000 % 1000, v % 1000) == form, v
+    bm = form[1]
+    A = rnd(M, K, dev=dev, seed=1).to(BF)
+    B = rnd(N, K, dev=dev, seed=2, scale=K ** -0.5).to(BF)
+    ref = A.float() @ B.float().t()
+    rows = lib.query("tuber_gemm_nt_stat_rows", M, N)
+    assert rows == (M + 63) // 64
+    C = torch.empty(M, N, device=dev, dtype=BF)
+    st0, st1 = torch.full((rows, N), float("nan"), device=dev), torch.full((rows, N), float("nan"), device=dev)
+    lib.call("tuber_gemm_nt", A, K, B, K, C, N, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, None, None, N, 0,
+             0, st0, st1, None, N, None, None, 1.0, 0.0, None, 0, None, 0, None)
+    for st in (st0, st1):
+        assert bool(torch.isfinite(st).all())
+        used = (st != 0).any(1)
+        assert int(used.sum()) == (M + bm - 1) // bm and bool(used[:(M + bm - 1) // bm].all()), (int(used.sum()), bm)
+    close("plan %s out" % (form,), C, ref)
+    close("plan %s stats sum" % (form,), st0.sum(0), ref.sum(0), rel=2e-3, abs_=2e-3 * float(ref.abs().sum(0).max()))
+    close("plan %s stats sumsq" % (form,), st1.sum(0), (ref * ref).sum(0), rel=2e-3)
 
 
 def test_gemm_nt_gather(dev):

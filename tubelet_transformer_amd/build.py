@@ -16,8 +16,6 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=f
 # -ffp-contract=fast the backend fuses across statements whatever `#pragma clang fp contract(off)` says; under "on" the pragma holds.
 # detect.hip evaluates decode()'s box expressions without contraction for the same reason.
 SOURCE_FLAGS = {"frame_map.hip": ["-ffp-contract=on"], "tube_map.hip": ["-ffp-contract=on"], "detect.hip": ["-ffp-contract=on"]}
-if os.environ.get("TUBER_AB_VARIANTS"):      # also build the measured-and-rejected GEMM tile variants (tuning runs only; not the product library)
-    FLAGS.append("-DTUBER_AB_VARIANTS")
 
 
 def sources():

@@ -606,174 +606,215 @@ static bool nt_full(const GemmNT& p, int bn) {
     return p.N % bn == 0 && !(p.ldc & 7) && !p.out_f32 && (!p.Cm || !(p.ldcm & 7)) && (!p.Ym || !(p.ldym & 7)) && (!p.R || !(p.ldr & 7));
 }
 
-template <int BM, int BN, int WM, int WN, int G, int OCC>
-static int launch_nt_cfg(const GemmNT& p, int amode, int epi, hipStream_t s) {
-    const int tiles = ceil_div(p.M, BM) * ceil_div(p.N, BN);
-    const bool full = nt_full(p, BN);
-    const size_t lds = 2 * (BM + BN) * 128 + (amode == A_BN_RELU ? (size_t)p.K * 8 : (amode == A_BN_BWD ? (size_t)p.K * 12 : 0));
-    dim3 grid(tiles), block(256);
-#define LNT(AM, EP)                                                                                                   \
-    do {                                                                                                              \
-        if (lds > 65536) { /* more than 64 KB of dynamic LDS needs a one-time opt-in per kernel */                    \
-            static LdsOptIn opt[2];                                                                                   \
-            TUBER_LDS_OPT_IN(opt[0], (gemm_nt_kernel<BM, BN, WM, WN, G, AM, EP, OCC>), 160 * 1024);                   \
-            TUBER_LDS_OPT_IN(opt[1], (gemm_nt_kernel<BM, BN, WM, WN, G, AM, EP, OCC, 0, true>), 160 * 1024);          \
-        }                                                                                                             \
-        if (full) hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, G, AM, EP, OCC, 0, true>), grid, block, lds, s, p);         \
-        else hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, G, AM, EP, OCC>), grid, block, lds, s, p);                \
-    } while (0)
-    if (amode == A_PLAIN) {
-        if (epi == EPI_EVAL) return TUBER_EINVAL;        // the eval output epilogue comes with the BatchNorm + ReLU operand prologue only (conv4)
-        if (epi == EPI_PLAIN) LNT(A_PLAIN, EPI_PLAIN);
-        else if (epi == EPI_STATS) LNT(A_PLAIN, EPI_STATS);
-        else if (epi == EPI_JOIN) LNT(A_PLAIN, EPI_JOIN);
-        else if (epi == EPI_JOIN_SR) LNT(A_PLAIN, EPI_JOIN_SR);
-        else if (epi == EPI_JOIN_DS) LNT(A_PLAIN, EPI_JOIN_DS);
-        else if (IS_JOIN_M(epi)) {                      // the bit-field forms: full tiles only
-            if (!full) return TUBER_EINVAL;
-            if (epi == EPI_JOIN_M) hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, G, A_PLAIN, EPI_JOIN_M, OCC, 0, true>), grid, block, lds, s, p);
-            else if (epi == EPI_JOIN_SR_M) hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, G, A_PLAIN, EPI_JOIN_SR_M, OCC, 0, true>), grid, block, lds, s, p);
-            else hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, G, A_PLAIN, EPI_JOIN_DS_M, OCC, 0, true>), grid, block, lds, s, p);
-        }
-        else LNT(A_PLAIN, EPI_BWD);
-    } else {
-        if (amode == A_BN_RELU) {
-            if (epi == EPI_PLAIN) LNT(A_BN_RELU, EPI_PLAIN);
-            else if (epi == EPI_STATS) LNT(A_BN_RELU, EPI_STATS);
-            else if (IS_JOIN(epi) || IS_JOIN_M(epi)) return TUBER_EINVAL;
-            else if (epi == EPI_EVAL) {
-                if (!full) return TUBER_EINVAL;
-                hipLaunchKernelGGL((gemm_nt_kernel<BM, BN, WM, WN, G, A_BN_RELU, EPI_EVAL, OCC, 0, true>), grid, block, lds, s, p);
-            }
-            else LNT(A_BN_RELU, EPI_BWD);
-        } else if (amode == A_ADD) {
-            if (epi != EPI_PLAIN) return TUBER_EINVAL;
-            LNT(A_ADD, EPI_PLAIN);
-        } else {
-            return TUBER_EINVAL;                          // A_BN_BWD prologue: measured slower than the separate apply kernel, not built
-        }
-    }
-#undef LNT
-    TUBER_RETURN_LAUNCH();
-}
-
-static int g_nt_wsk96 = 1;        // EXPERIMENT hook (round 5): 0 = 64-row tiles everywhere (tuber_gemm_nt_wsk96_set)
-// wave split-K launch (64x64 tiles, plain A): 64 KB of LDS (four private 16 KB images), two workgroups per CU
-static bool nt_wsk_96(const GemmNT& p, int epi) {
-    // 96-row tiles where the 64-row tiling needs more workgroups than there are CUs and the 96-row one does not (layer3: 352 -> 236,
-    // layer4: 352 -> 240); full tiles only, the three epilogues those convs use
-    const long t64 = (long)ceil_div(p.M, 64) * ceil_div(p.N, 64), t96 = (long)ceil_div(p.M, 96) * ceil_div(p.N, 64);
-    return g_nt_wsk96 && t64 > 256 && t96 <= 256 && nt_full(p, 64) && (epi == EPI_PLAIN || epi == EPI_STATS || epi == EPI_BWD);
-}
-static int launch_nt_wsk(const GemmNT& p, int epi, hipStream_t s) {
-    if (nt_wsk_96(p, epi)) {
-        dim3 grid96(ceil_div(p.M, 96) * ceil_div(p.N, 64)), block96(256);
-        constexpr size_t lds96 = 4 * (size_t)wsk_image_bytes(96);
-#define LWSK96(EP)                                                                                                            \
-    do {                                                                                                                      \
-        static LdsOptIn opt;                                                                                                  \
-        TUBER_LDS_OPT_IN(opt, (gemm_nt_kernel<96, 64, 2, 2, 2, A_PLAIN, EP, 1, 1, true>), lds96);                              \
-        hipLaunchKernelGGL((gemm_nt_kernel<96, 64, 2, 2, 2, A_PLAIN, EP, 1, 1, true>), grid96, block96, lds96, s, p);          \
-    } while (0)
-        if (epi == EPI_PLAIN) LWSK96(EPI_PLAIN);
-        else if (epi == EPI_STATS) LWSK96(EPI_STATS);
-        else LWSK96(EPI_BWD);
-#undef LWSK96
-        TUBER_RETURN_LAUNCH();
-    }
-    const int tiles = ceil_div(p.M, 64) * ceil_div(p.N, 64);
-    dim3 grid(tiles), block(256);
-    const size_t lds = 4 * 16384;
-    const bool full = nt_full(p, 64);
-#define LWSK(EP)                                                                                                               \
-    do {                                                                                                                       \
-        if (full) hipLaunchKernelGGL((gemm_nt_kernel<64, 64, 2, 2, 2, A_PLAIN, EP, 2, 1, true>), grid, block, lds, s, p);       \
-        else hipLaunchKernelGGL((gemm_nt_kernel<64, 64, 2, 2, 2, A_PLAIN, EP, 2, 1>), grid, block, lds, s, p);                  \
-    } while (0)
-    if (epi == EPI_PLAIN) LWSK(EPI_PLAIN);
-    else if (epi == EPI_STATS) LWSK(EPI_STATS);
-    else if (epi == EPI_JOIN) LWSK(EPI_JOIN);
-    else if (epi == EPI_JOIN_SR) LWSK(EPI_JOIN_SR);
-    else if (epi == EPI_JOIN_DS) LWSK(EPI_JOIN_DS);
-    else LWSK(EPI_BWD);
-#undef LWSK
-    TUBER_RETURN_LAUNCH();
-}
-// 96-row tiles on the REGULAR pipeline (round 6): every plain-A shape with many rows.  `scripts/gemm_bench.py nt 0,7,13,23` on the model's shapes with
-// M >= 16 896 (profiles/r06_gemm_nt_96_row_tiles.txt): 96 x 64 is at or ahead of the 64 x 64 / 64 x 128 / 128 x 128 choice on every one -- the class branch's
-// 16 896-row GEMMs by 5 - 18 % (2048 x 512: 60.2 -> 57.4 us against 128 x 128, 256 x 2048: 35.8 -> 29.2 against 64 x 64, 2048 x 256: 35.7 -> 31.7 against 64 x 128),
-// layer2's conv1 forward / conv4 data gradient (44 032 x 128 x 512: 1 376 tiles of 64 rows = a full round of the chip at four per CU and a third of one; 918 at 96 rows)
-// by 1 - 5 %.  40 KB of LDS per workgroup: four per CU fill the 160 KB exactly; 115 - 128 VGPRs, no scratch.  Outputs bit-identical (same k order), statistics rows per
-// 96 rows (the unused rows of the 64-row layout are written as zero, as the wave-split-K form does).  The layer3 / layer4 long-K shapes (M = 5 632 / 2 816) stay on the
-// wave-split-K 96-row form: the regular 96 x 64 kernel wins their isolated microbenchmark (9.1 vs 10.2 us) and LOSES in the step (13.80 vs 13.62 ms, three pairs).
+// ---- the tile decision: nt_plan is the one place that reads the hooks and the shape thresholds ----
+static int g_nt_force = -1;       // tuber_gemm_nt_set_cfg (tuning runs / kernel tests only)
+static int g_nt_wsk96 = 1;        // EXPERIMENT hook (round 5): 0 = 64-row wave-split-K tiles everywhere (tuber_gemm_nt_wsk96_set)
 static int g_nt_96 = 1;           // EXPERIMENT hook: 0 = the round-5 tile choice (tuber_gemm_nt_96_set)
-static bool nt_use_96(const GemmNT& p, int amode, int epi) {
-    return g_nt_96 && amode == A_PLAIN && !p.gather && p.M >= 8192 && nt_full(p, 64) && (epi == EPI_PLAIN || epi == EPI_STATS || epi == EPI_BWD);
-}
-static int launch_nt_96(const GemmNT& p, int epi, hipStream_t s) {
-    dim3 grid(ceil_div(p.M, 96) * ceil_div(p.N, 64)), block(256);
-    constexpr size_t lds = 2 * (96 + 64) * 128;
-#define L96(EP) hipLaunchKernelGGL((gemm_nt_kernel<96, 64, 2, 2, 2, A_PLAIN, EP, 4, 0, true>), grid, block, lds, s, p)
-    if (epi == EPI_PLAIN) L96(EPI_PLAIN);
-    else if (epi == EPI_STATS) L96(EPI_STATS);
-    else L96(EPI_BWD);
-#undef L96
-    TUBER_RETURN_LAUNCH();
-}
-// shapes that take it: plain A, no row gather, at least `min_kt` k-tiles, and few enough 64x64 tiles that they are all resident at once
-static bool nt_use_wsk(const GemmNT& p, int amode) {
-    constexpr int min_kt = 16;
-    if (min_kt <= 0 || amode != A_PLAIN || p.gather || p.out_f32) return false;
-    const long tiles = (long)ceil_div(p.M, 64) * ceil_div(p.N, 64);
-    return p.K / 64 >= min_kt && tiles <= 512;
+
+enum { NT_TILE = 0, NT_WSK = 1, NT_R96 = 2 };
+struct NtPlan {
+    int form;      // NT_TILE: the shared-tile pipeline at `cfg`;  NT_WSK: wave split-K, 64 x 64 or 96 x 64;  NT_R96: 96 x 64 tiles on the regular pipeline
+    int cfg;       // NT_TILE: 0 = 128x128, 7 = 64x128, 13 = 64x64 with a two-tile prefetch
+    int pick;      // what tuber_gemm_nt_cfg reports: the forced cfg, else the shape's choice before the form and epilogue rules below
+    int bm, bn;    // tile rows x columns
+    bool full;     // nt_full(p, bn): the launch takes the FULL instantiation
+};
+
+// (prologue, epilogue, full) combinations the shared-tile configurations are built with (launch_nt_tile below)
+static bool nt_tile_built(int amode, int epi, bool full) {
+    // the eval output epilogue comes with the BatchNorm + ReLU operand prologue only (conv4); it and the bit-field joins: full tiles only
+    if (amode == A_PLAIN) return epi != EPI_EVAL && (full || !IS_JOIN_M(epi));
+    if (amode == A_BN_RELU) return !IS_JOIN(epi) && !IS_JOIN_M(epi) && (full || epi != EPI_EVAL);
+    return amode == A_ADD && epi == EPI_PLAIN;            // A_BN_BWD prologue: measured slower than the separate apply kernel, not built
 }
 
-// tile choice: (cfg 0) 128x128, (1) 128x64, (2) 64x64
-static int g_nt_force = -1;      // tuber_gemm_nt_set_cfg (tuning runs / kernel tests only)
-static int nt_force_cfg() {
-    return g_nt_force;
-}
-static int nt_pick_cfg(int M, int N, int K) {
-    if (nt_force_cfg() >= 0) return nt_force_cfg();       // tuning / experiments only
+static int nt_plan(const GemmNT& p, int amode, int epi, NtPlan* out) {
+    const int M = p.M, N = p.N, K = p.K, force = g_nt_force;
     // measured on MI355X in isolation (scripts/gemm_bench.py, profiles/r02_gemm_nt_tile_ab.txt): 64-row tiles everywhere except the two
     // FLOP-dense class-branch FFN GEMMs.  64x128 (3 workgroups per CU by LDS, registers budgeted for exactly that) wins the wide
     // short-K shapes (conv4 / dgrad1 of layer1-3, class-branch projections) where re-reading A per 64 columns is what costs;
     // 64x64 with a TWO-tile prefetch (cfg 13: 93-109 VGPRs, no spills at 4 workgroups per CU) the small-N and long-K ones -- the
-    // four-tile prefetch of round 1 (cfg 2) spilled in the BN-prologue / masked-epilogue variants and is 5-15 % slower everywhere;
+    // four-tile prefetch of round 1 spilled in the BN-prologue / masked-epilogue variants and is 5-15 % slower everywhere;
     // 128x128 only where M*N is large enough to fill the chip with 2 workgroups per CU.
-    if ((long)M * N >= (1L << 25) && N >= 1024 && K >= 256) return 0;
-    return (N >= 256 && K <= 512 && M >= 2048) ? 7 : 13;
+    int cfg = ((long)M * N >= (1L << 25) && N >= 1024 && K >= 256) ? 0 : (N >= 256 && K <= 512 && M >= 2048) ? 7 : 13;
+    if (force >= 0) cfg = force;                           // tuning / experiments only
+    out->pick = cfg;
+
+    const long t64 = (long)ceil_div(M, 64) * ceil_div(N, 64), t96 = (long)ceil_div(M, 96) * ceil_div(N, 64);
+    // what the 96-row kernels (both forms) are built for: plain A, full tiles, the three epilogues the convs that take them use
+    const bool can96 = amode == A_PLAIN && nt_full(p, 64) && (epi == EPI_PLAIN || epi == EPI_STATS || epi == EPI_BWD);
+
+    // wave split-K (64 KB of LDS: four private 16 KB images, two workgroups per CU): plain A, no row gather, at least 16 k-tiles, and few
+    // enough 64x64 tiles that they are all resident at once
+    if (force < 0 && cfg == 13 && !IS_JOIN_M(epi) && amode == A_PLAIN && !p.gather && !p.out_f32 && K / 64 >= 16 && t64 <= 512) {
+        // 96-row tiles where the 64-row tiling needs more workgroups than there are CUs and the 96-row one does not (layer3: 352 -> 236,
+        // layer4: 352 -> 240)
+        const bool rows96 = g_nt_wsk96 && t64 > 256 && t96 <= 256 && can96;
+        out->form = NT_WSK; out->cfg = 13; out->bm = rows96 ? 96 : 64; out->bn = 64; out->full = nt_full(p, 64);
+        return TUBER_OK;
+    }
+    // 96-row tiles on the REGULAR pipeline (round 6): every plain-A shape with many rows.  `scripts/gemm_bench.py nt 0,7,13,23` on the model's shapes with
+    // M >= 16 896 (profiles/r06_gemm_nt_96_row_tiles.txt): 96 x 64 is at or ahead of the 64 x 64 / 64 x 128 / 128 x 128 choice on every one -- the class branch's
+    // 16 896-row GEMMs by 5 - 18 % (2048 x 512: 60.2 -> 57.4 us against 128 x 128, 256 x 2048: 35.8 -> 29.2 against 64 x 64, 2048 x 256: 35.7 -> 31.7 against 64 x 128),
+    // layer2's conv1 forward / conv4 data gradient (44 032 x 128 x 512: 1 376 tiles of 64 rows = a full round of the chip at four per CU and a third of one; 918 at 96 rows)
+    // by 1 - 5 %.  40 KB of LDS per workgroup: four per CU fill the 160 KB exactly; 115 - 128 VGPRs, no scratch.  Outputs bit-identical (same k order), statistics rows per
+    // 96 rows (the unused rows of the 64-row layout are written as zero, as the wave-split-K form does).  The layer3 / layer4 long-K shapes (M = 5 632 / 2 816) stay on the
+    // wave-split-K 96-row form: the regular 96 x 64 kernel wins their isolated microbenchmark (9.1 vs 10.2 us) and LOSES in the step (13.80 vs 13.62 ms, three pairs).
+    // A forced cfg 23 names this form for every shape it is built for and is cfg 13 for the rest.
+    if (force == 23 ? can96 : (force < 0 && g_nt_96 && can96 && !p.gather && M >= 8192)) {
+        out->form = NT_R96; out->cfg = 23; out->bm = 96; out->bn = 64; out->full = true;
+        return TUBER_OK;
+    }
+    if (force == 23) cfg = 13;
+    if (force < 0) {
+        if (cfg == 0 && epi != EPI_PLAIN) cfg = 7;         // statistics rows are per 64 output rows (tuber_gemm_nt_stat_rows)
+        if (cfg == 7 && (epi == EPI_JOIN_DS || epi == EPI_JOIN_DS_M)) cfg = 13;     // three side operands spill the 64x128 tile (21 registers at 3 workgroups / CU)
+    }
+    if (cfg != 0 && cfg != 7 && cfg != 13) return TUBER_EINVAL;
+    out->form = NT_TILE; out->cfg = cfg; out->bm = cfg == 0 ? 128 : 64; out->bn = cfg == 13 ? 64 : 128; out->full = nt_full(p, out->bn);
+    return nt_tile_built(amode, epi, out->full) ? TUBER_OK : TUBER_EINVAL;
 }
-static int nt_dispatch(const GemmNT& p, int amode, int epi, hipStream_t stream);
-static void nt_cfg_dims(int cfg, int* bm, int* wm) {
-    if (cfg == 0 || cfg == 21) { *bm = 128; *wm = 2; }
-    else if (cfg == 22) { *bm = 128; *wm = 4; }
-    else if (cfg == 7 || cfg == 17) { *bm = 64; *wm = 1; }
-    else { *bm = 64; *wm = 2; }
+
+// ---- launch: one instantiation, then per form the table of the instantiations it is built with ----
+template <int BM, int BN, int WM, int WN, int G, int OCC, int WSK, int AM, int EP, bool FULL>
+static int nt_launch(const GemmNT& p, hipStream_t s) {
+    const auto kernel = gemm_nt_kernel<BM, BN, WM, WN, G, AM, EP, OCC, WSK, FULL>;
+    // wave split-K: four wave-private images;  shared tiles: two stages of (BM + BN) 128-byte rows and the prologue's (scale, shift) per k
+    const size_t lds = WSK ? 4 * (size_t)wsk_image_bytes(BM) : 2 * (BM + BN) * 128 + (AM == A_BN_RELU ? (size_t)p.K * 8 : 0);
+    if (lds > 65536) {            // more than 64 KB of dynamic LDS needs a one-time opt-in per kernel
+        static LdsOptIn opt;
+        TUBER_LDS_OPT_IN(opt, kernel, WSK ? lds : 160 * 1024);
+    }
+    hipLaunchKernelGGL(kernel, dim3(ceil_div(p.M, BM) * ceil_div(p.N, BN)), dim3(256), lds, s, p);
+    TUBER_RETURN_LAUNCH();
+}
+// (prologue, epilogue) as the FULL / bounds-checked pair, or FULL alone; the tile geometry is the caller's BM .. WSK
+#define NT_PAIR(AM, EP) return full ? nt_launch<BM, BN, WM, WN, G, OCC, WSK, AM, EP, true>(p, s) : nt_launch<BM, BN, WM, WN, G, OCC, WSK, AM, EP, false>(p, s)
+#define NT_FULL(AM, EP) return nt_launch<BM, BN, WM, WN, G, OCC, WSK, AM, EP, true>(p, s)
+
+// shared-tile pipeline; nt_plan has refused what nt_tile_built does not list
+template <int BM, int BN, int WM, int WN, int G, int OCC>
+static int launch_nt_tile(const GemmNT& p, int amode, int epi, bool full, hipStream_t s) {
+    constexpr int WSK = 0;
+    if (amode == A_ADD) NT_PAIR(A_ADD, EPI_PLAIN);
+    if (amode == A_BN_RELU) switch (epi) {
+        case EPI_PLAIN: NT_PAIR(A_BN_RELU, EPI_PLAIN);
+        case EPI_STATS: NT_PAIR(A_BN_RELU, EPI_STATS);
+        case EPI_EVAL: NT_FULL(A_BN_RELU, EPI_EVAL);
+        default: NT_PAIR(A_BN_RELU, EPI_BWD);
+    }
+    switch (epi) {
+        case EPI_PLAIN: NT_PAIR(A_PLAIN, EPI_PLAIN);
+        case EPI_STATS: NT_PAIR(A_PLAIN, EPI_STATS);
+        case EPI_JOIN: NT_PAIR(A_PLAIN, EPI_JOIN);
+        case EPI_JOIN_SR: NT_PAIR(A_PLAIN, EPI_JOIN_SR);
+        case EPI_JOIN_DS: NT_PAIR(A_PLAIN, EPI_JOIN_DS);
+        case EPI_JOIN_M: NT_FULL(A_PLAIN, EPI_JOIN_M);
+        case EPI_JOIN_SR_M: NT_FULL(A_PLAIN, EPI_JOIN_SR_M);
+        case EPI_JOIN_DS_M: NT_FULL(A_PLAIN, EPI_JOIN_DS_M);
+        default: NT_PAIR(A_PLAIN, EPI_BWD);
+    }
+}
+// wave split-K on 64 x 64 tiles: plain A, two workgroups per CU
+static int launch_nt_wsk64(const GemmNT& p, int epi, bool full, hipStream_t s) {
+    constexpr int BM = 64, BN = 64, WM = 2, WN = 2, G = 2, OCC = 2, WSK = 1;
+    switch (epi) {
+        case EPI_PLAIN: NT_PAIR(A_PLAIN, EPI_PLAIN);
+        case EPI_STATS: NT_PAIR(A_PLAIN, EPI_STATS);
+        case EPI_JOIN: NT_PAIR(A_PLAIN, EPI_JOIN);
+        case EPI_JOIN_SR: NT_PAIR(A_PLAIN, EPI_JOIN_SR);
+        case EPI_JOIN_DS: NT_PAIR(A_PLAIN, EPI_JOIN_DS);
+        default: NT_PAIR(A_PLAIN, EPI_BWD);
+    }
+}
+// 96 x 64 tiles, plain A, full tiles, three epilogues: wave split-K (one workgroup per CU) or the regular pipeline (four)
+template <int OCC, int WSK>
+static int launch_nt_96(const GemmNT& p, int epi, hipStream_t s) {
+    constexpr int BM = 96, BN = 64, WM = 2, WN = 2, G = 2;
+    switch (epi) {
+        case EPI_PLAIN: NT_FULL(A_PLAIN, EPI_PLAIN);
+        case EPI_STATS: NT_FULL(A_PLAIN, EPI_STATS);
+        default: NT_FULL(A_PLAIN, EPI_BWD);
+    }
+}
+#undef NT_PAIR
+#undef NT_FULL
+
+// plan, then launch the plan
+static int nt_dispatch(const GemmNT& p, int amode, int epi, hipStream_t stream) {
+    NtPlan pl;
+    if (nt_plan(p, amode, epi, &pl) != TUBER_OK) return TUBER_EINVAL;
+    if (pl.form == NT_WSK) return pl.bm == 96 ? launch_nt_96<1, 1>(p, epi, stream) : launch_nt_wsk64(p, epi, pl.full, stream);
+    if (pl.form == NT_R96) return launch_nt_96<4, 0>(p, epi, stream);
+    switch (pl.cfg) {
+        case 0: return launch_nt_tile<128, 128, 2, 2, 2, 2>(p, amode, epi, pl.full, stream);     // class-branch FFN (plain epilogue)
+        case 7: return launch_nt_tile<64, 128, 1, 4, 2, 3>(p, amode, epi, pl.full, stream);
+        default: return launch_nt_tile<64, 64, 2, 2, 2, 4>(p, amode, epi, pl.full, stream);      // cfg 13
+    }
+}
+
+// the argument block every entry point starts from: the common size / leading-dimension check, everything zero, no scaling, no dropout,
+// and the GEMM itself; each entry point adds only what is its own
+static int nt_problem(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K, GemmNT* p) {
+    if (M <= 0 || N <= 0 || K <= 0 || (K & 63) || (lda & 7) || (ldb & 7)) return TUBER_EINVAL;
+    memset(p, 0, sizeof *p);
+    p->alpha = 1.f; p->drop_inv_keep = 1.f;
+    p->A = (const bf16*)A; p->lda = lda; p->B = (const bf16*)B; p->ldb = ldb; p->C = C; p->ldc = ldc;
+    p->M = M; p->N = N; p->K = K;
+    return TUBER_OK;
+}
+// the statistics side of the join epilogues: residual R, statistics operand Cm and the two partial-row buffers
+static void nt_join_operands(GemmNT* p, const void* R, long ldr, const void* Cm, long ldcm, float* stat0, float* stat1) {
+    p->R = (const bf16*)R; p->ldr = ldr; p->Cm = (const bf16*)Cm; p->ldcm = ldcm; p->stat0 = stat0; p->stat1 = stat1;
+}
+// the strided-shortcut row map of the *_strided joins: false where it does not describe M output rows
+static bool nt_strided_rows(GemmNT* p, int M, int To, int Ho, int Wo, int Ti, int Hi, int Wi, int st, int ss) {
+    if (st < 1 || ss < 1 || To != (Ti - 1) / st + 1 || Ho != (Hi - 1) / ss + 1 || Wo != (Wi - 1) / ss + 1 || M % (Ti * Hi * Wi)) return false;
+    p->To = To; p->Ho = Ho; p->Wo = Wo; p->Ti = Ti; p->Hi = Hi; p->Wi = Wi; p->st = st; p->ss = ss;
+    return true;
+}
+// the shape-only problem of the host queries: ldc = N, or a leading dimension no 16-byte access can use
+static GemmNT nt_query_problem(int M, int N, int K, int gather = 0, int out_f32 = 0, int aligned = 1) {
+    GemmNT p{};
+    p.M = M; p.N = N; p.K = K; p.ldc = aligned ? N : (N | 7); p.gather = gather; p.out_f32 = out_f32;
+    return p;
 }
 
 extern "C" {
 
-// number of partial-statistics rows gemm_nt writes for (M, N): the caller sizes stat0/stat1 as
-// [rows][N] floats and hands the same row count to the finalize kernels.
-// tile configuration tuber_gemm_nt picks for (M, N): 0 = 128x128, 1 = 128x64, 2 = 64x64 (profiling / tests)
-int tuber_gemm_nt_cfg(int M, int N, int K) { return nt_pick_cfg(M, N, K); }
+// tile configuration tuber_gemm_nt picks for (M, N, K) before the form and epilogue rules of nt_plan: 13 = 64x64 (two-tile prefetch), 7 = 64x128,
+// 0 = 128x128; the forced one while tuber_gemm_nt_set_cfg holds (profiling / tests)
+int tuber_gemm_nt_cfg(int M, int N, int K) {
+    NtPlan pl;
+    (void)nt_plan(nt_query_problem(M, N, K), A_PLAIN, EPI_PLAIN, &pl);
+    return pl.pick;
+}
 
 int tuber_gemm_nt_wsk96_set(int on) { g_nt_wsk96 = on; return 0; }
 int tuber_gemm_nt_96_set(int on) { g_nt_96 = on; return 0; }
 // rows per tile of the wave-split-K form tuber_gemm_nt takes for a plain-A (M, N, K) with a 16-byte addressable output: 0 = not taken, 64 or 96
 int tuber_gemm_nt_wsk_tile_rows(int M, int N, int K) {
-    GemmNT p{};
-    p.M = M; p.N = N; p.K = K; p.ldc = N;
-    if (nt_force_cfg() >= 0 || nt_pick_cfg(M, N, K) != 13 || !nt_use_wsk(p, A_PLAIN)) return 0;
-    return nt_wsk_96(p, EPI_STATS) ? 96 : 64;
+    NtPlan pl;
+    return nt_plan(nt_query_problem(M, N, K), A_PLAIN, EPI_STATS, &pl) == TUBER_OK && pl.form == NT_WSK ? pl.bm : 0;
 }
 int tuber_gemm_nt_set_cfg(int cfg) { g_nt_force = cfg < 0 ? -1 : cfg; return 0; }
 
+// number of partial-statistics rows gemm_nt writes for (M, N): the caller sizes stat0/stat1 as [rows][N] floats and hands the same row
+// count to the finalize kernels.  One row per 64 output rows -- no automatic choice gives a statistics epilogue taller tiles, and the
+// 96-row forms write the 64-row layout (rows they do not produce are zero) --, per 128 only while cfg 0 is forced.
 int tuber_gemm_nt_stat_rows(int M, int N) {
-    int bm, wm;
-    nt_cfg_dims(nt_pick_cfg(M, N, 64), &bm, &wm);     // every automatic choice has 64-row tiles
-    return ceil_div(M, bm);
+    NtPlan pl;
+    const bool rows128 = nt_plan(nt_query_problem(M, N, 64), A_PLAIN, EPI_STATS, &pl) == TUBER_OK && pl.bm == 128;
+    return ceil_div(M, rows128 ? 128 : 64);
+}
+
+// what tuber_gemm_nt and its siblings launch for a problem, packed as form * 1000000 + tile rows * 1000 + tile columns (form 0: shared-tile
+// pipeline, 1: wave split-K, 2: 96-row tiles on the regular pipeline), or TUBER_EINVAL where the (amode, epi) combination is not built for
+// the shape.  aligned: every leading dimension of the epilogue's tensors is a multiple of 8 (ldc = N).  Host only.
+int tuber_gemm_nt_plan(int M, int N, int K, int amode, int epi, int gather, int out_f32, int aligned) {
+    NtPlan pl;
+    if (nt_plan(nt_query_problem(M, N, K, gather, out_f32, aligned), amode, epi, &pl) != TUBER_OK) return TUBER_EINVAL;
+    return pl.form * 1000000 + pl.bm * 1000 + pl.bn;
 }
 
 int tuber_gemm_nt(const void* A, long lda, const void* B, long ldb, void* C, long ldc, int M, int N, int K,
@@ -785,25 +826,21 @@ int tuber_gemm_nt(const void* A, long lda, const void* B, long ldb, void* C, lon
                   float alpha, float drop_p, const void* seed_ptr, unsigned long long salt,
                   const void* A2, long lda2, const float* a_coef2,
                   hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || (K & 63) || (lda & 7) || (ldb & 7)) return TUBER_EINVAL;
+    GemmNT p;
+    if (nt_problem(A, lda, B, ldb, C, ldc, M, N, K, &p) != TUBER_OK) return TUBER_EINVAL;
     if (amode != A_PLAIN && (!a_scale || !a_shift)) return TUBER_EINVAL;
     if (amode == A_BN_BWD && (!A2 || !a_coef2 || (lda2 & 7) || gather || epi == EPI_STATS)) return TUBER_EINVAL;
     if (amode < 0 || amode > 2) return TUBER_EINVAL;                  // (A_ADD has its own entry point: tuber_gemm_nt_addproj)
     if (epi == EPI_BWD && !Cm) return TUBER_EINVAL;
     if (epi != EPI_PLAIN && out_f32) return TUBER_EINVAL;
     if (drop_p < 0.f || drop_p >= 1.f || (drop_p > 0.f && epi != EPI_PLAIN)) return TUBER_EINVAL;
-    GemmNT p;
     p.alpha = alpha;
-    p.A2 = (const bf16*)A2; p.lda2 = lda2; p.a_coef2 = a_coef2;
-    p.drop_thresh = (uint32_t)((double)drop_p * 4294967296.0); p.drop_inv_keep = dropout_inv_keep(drop_p);
-    p.seed_ptr = (const uint64_t*)seed_ptr; p.salt = (uint64_t)salt;
-    p.A = (const bf16*)A; p.lda = lda; p.B = (const bf16*)B; p.ldb = ldb; p.C = C; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K; p.a_scale = a_scale; p.a_shift = a_shift;
+    p.a_scale = a_scale; p.a_shift = a_shift; p.A2 = (const bf16*)A2; p.lda2 = lda2; p.a_coef2 = a_coef2;
     p.gather = gather; p.To = To; p.Ho = Ho; p.Wo = Wo; p.Ti = Ti; p.Hi = Hi; p.Wi = Wi; p.st = st; p.ss = ss;
     p.bias = bias; p.R = (const bf16*)R; p.ldr = ldr; p.relu = relu; p.out_f32 = out_f32;
     p.stat0 = stat0; p.stat1 = stat1; p.Cm = (const bf16*)Cm; p.ldcm = ldcm; p.m_scale = m_scale; p.m_shift = m_shift;
-    p.Ym = nullptr; p.ldym = 0; p.add_ncols = 0;
-    p.Dm = nullptr; p.lddm = 0; p.stat2 = nullptr; p.R32 = nullptr; p.ldr32 = 0; p.C32 = nullptr; p.ldc32 = 0;
+    p.drop_thresh = (uint32_t)((double)drop_p * 4294967296.0); p.drop_inv_keep = dropout_inv_keep(drop_p);
+    p.seed_ptr = (const uint64_t*)seed_ptr; p.salt = (uint64_t)salt;
     return nt_dispatch(p, amode, epi, stream);
 }
 
@@ -816,14 +853,11 @@ int tuber_gemm_nt(const void* A, long lda, const void* B, long ldb, void* C, lon
 int tuber_gemm_nt_bn_out(const void* A, long lda, const float* a_scale, const float* a_shift, const void* B, long ldb,
                          const float* out_scale, const float* out_shift, const float* R32, long ldr32, void* y, long ldy, float* y32, long ldy32,
                          int M, int N, int K, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || (K & 63) || (lda & 7) || (ldb & 7) || (ldy & 7) || (ldr32 & 3) || (ldy32 & 3) || (N & 63) ||
+    GemmNT p;
+    if (nt_problem(A, lda, B, ldb, y, ldy, M, N, K, &p) != TUBER_OK || (ldy & 7) || (ldr32 & 3) || (ldy32 & 3) || (N & 63) ||
         !a_scale || !a_shift || !out_scale || !out_shift || !R32 || !y || !y32)
         return TUBER_EINVAL;
-    GemmNT p;
-    memset(&p, 0, sizeof p);
-    p.alpha = 1.f; p.drop_inv_keep = 1.f;
-    p.A = (const bf16*)A; p.lda = lda; p.B = (const bf16*)B; p.ldb = ldb; p.C = y; p.ldc = ldy;
-    p.M = M; p.N = N; p.K = K; p.a_scale = a_scale; p.a_shift = a_shift;
+    p.a_scale = a_scale; p.a_shift = a_shift;
     p.m_scale = out_scale; p.m_shift = out_shift; p.R32 = R32; p.ldr32 = ldr32; p.C32 = y32; p.ldc32 = ldy32;
     return nt_dispatch(p, A_BN_RELU, EPI_EVAL, stream);
 }
@@ -834,12 +868,9 @@ int tuber_gemm_nt_bn_out(const void* A, long lda, const float* a_scale, const fl
 // kernel and two GEMM launches; the bf16 sum A + A2 is exactly what the add kernel would have stored.
 int tuber_gemm_nt_addproj(const void* A, long lda, const void* A2, long lda2, int add_ncols, const void* B, long ldb, void* C, long ldc,
                           int M, int N, int K, const float* bias, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || (K & 63) || (lda & 7) || (lda2 & 7) || (ldb & 7) || !A2 || add_ncols < 0 || (add_ncols & 127)) return TUBER_EINVAL;   // any tile width (64 / 128) divides it
     GemmNT p;
-    memset(&p, 0, sizeof p);
-    p.alpha = 1.f; p.drop_inv_keep = 1.f;
-    p.A = (const bf16*)A; p.lda = lda; p.B = (const bf16*)B; p.ldb = ldb; p.C = C; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K; p.bias = bias;
+    if (nt_problem(A, lda, B, ldb, C, ldc, M, N, K, &p) != TUBER_OK || (lda2 & 7) || !A2 || add_ncols < 0 || (add_ncols & 127)) return TUBER_EINVAL;   // any tile width (64 / 128) divides add_ncols
+    p.bias = bias;
     p.A2 = (const bf16*)A2; p.lda2 = lda2; p.add_ncols = add_ncols;
     return nt_dispatch(p, A_ADD, EPI_PLAIN, stream);
 }
@@ -851,14 +882,9 @@ int tuber_gemm_nt_addproj(const void* A, long lda, const void* A2, long lda2, in
 int tuber_gemm_nt_join(const void* A, long lda, const void* B, long ldb, void* dz, long ldc, int M, int N, int K,
                        const void* R, long ldr, const void* Y, long ldy, const void* Cm, long ldcm, float* stat0, float* stat1,
                        hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || (K & 63) || (lda & 7) || (ldb & 7) || !Y || !Cm || !stat0 || !stat1) return TUBER_EINVAL;
     GemmNT p;
-    memset(&p, 0, sizeof p);
-    p.alpha = 1.f; p.drop_inv_keep = 1.f;
-    p.A = (const bf16*)A; p.lda = lda; p.B = (const bf16*)B; p.ldb = ldb; p.C = dz; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K;
-    p.R = (const bf16*)R; p.ldr = ldr;
-    p.stat0 = stat0; p.stat1 = stat1; p.Cm = (const bf16*)Cm; p.ldcm = ldcm;
+    if (nt_problem(A, lda, B, ldb, dz, ldc, M, N, K, &p) != TUBER_OK || !Y || !Cm || !stat0 || !stat1) return TUBER_EINVAL;
+    nt_join_operands(&p, R, ldr, Cm, ldcm, stat0, stat1);
     p.Ym = (const bf16*)Y; p.ldym = ldy;
     return nt_dispatch(p, A_PLAIN, EPI_JOIN, stream);
 }
@@ -869,14 +895,9 @@ int tuber_gemm_nt_join(const void* A, long lda, const void* B, long ldb, void* d
 int tuber_gemm_nt_join_mask(const void* A, long lda, const void* B, long ldb, void* dz, long ldc, int M, int N, int K,
                             const void* R, long ldr, const void* Ymask, const void* Cm, long ldcm, float* stat0, float* stat1,
                             hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || (K & 63) || (lda & 7) || (ldb & 7) || (N & 63) || !Ymask || !Cm || !stat0 || !stat1) return TUBER_EINVAL;
     GemmNT p;
-    memset(&p, 0, sizeof p);
-    p.alpha = 1.f; p.drop_inv_keep = 1.f;
-    p.A = (const bf16*)A; p.lda = lda; p.B = (const bf16*)B; p.ldb = ldb; p.C = dz; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K;
-    p.R = (const bf16*)R; p.ldr = ldr;
-    p.stat0 = stat0; p.stat1 = stat1; p.Cm = (const bf16*)Cm; p.ldcm = ldcm;
+    if (nt_problem(A, lda, B, ldb, dz, ldc, M, N, K, &p) != TUBER_OK || (N & 63) || !Ymask || !Cm || !stat0 || !stat1) return TUBER_EINVAL;
+    nt_join_operands(&p, R, ldr, Cm, ldcm, stat0, stat1);
     p.Ymask = (const uint8_t*)Ymask;
     return nt_dispatch(p, A_PLAIN, EPI_JOIN_M, stream);
 }
@@ -886,14 +907,10 @@ int tuber_gemm_nt_join_mask(const void* A, long lda, const void* B, long ldb, vo
 int tuber_gemm_nt_join_ds(const void* A, long lda, const void* B, long ldb, void* dz, long ldc, int M, int N, int K,
                           const void* R, long ldr, const void* Y, long ldy, const void* Cm, long ldcm, const void* Cd, long ldcd,
                           float* stat0, float* stat1, float* stat2, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || (K & 63) || (lda & 7) || (ldb & 7) || !Y || !Cm || !Cd || !stat0 || !stat1 || !stat2) return TUBER_EINVAL;
     GemmNT p;
-    memset(&p, 0, sizeof p);
-    p.alpha = 1.f; p.drop_inv_keep = 1.f;
-    p.A = (const bf16*)A; p.lda = lda; p.B = (const bf16*)B; p.ldb = ldb; p.C = dz; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K;
-    p.R = (const bf16*)R; p.ldr = ldr;
-    p.stat0 = stat0; p.stat1 = stat1; p.stat2 = stat2; p.Cm = (const bf16*)Cm; p.ldcm = ldcm; p.Dm = (const bf16*)Cd; p.lddm = ldcd;
+    if (nt_problem(A, lda, B, ldb, dz, ldc, M, N, K, &p) != TUBER_OK || !Y || !Cm || !Cd || !stat0 || !stat1 || !stat2) return TUBER_EINVAL;
+    nt_join_operands(&p, R, ldr, Cm, ldcm, stat0, stat1);
+    p.Dm = (const bf16*)Cd; p.lddm = ldcd; p.stat2 = stat2;
     p.Ym = (const bf16*)Y; p.ldym = ldy;
     return nt_dispatch(p, A_PLAIN, EPI_JOIN_DS, stream);
 }
@@ -905,16 +922,10 @@ int tuber_gemm_nt_join_ds(const void* A, long lda, const void* B, long ldb, void
 int tuber_gemm_nt_join_strided(const void* A, long lda, const void* B, long ldb, void* dz, long ldc, int M, int N, int K,
                                const void* R, long ldr, int To, int Ho, int Wo, int Ti, int Hi, int Wi, int st, int ss,
                                const void* Y, long ldy, const void* Cm, long ldcm, float* stat0, float* stat1, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || (K & 63) || (lda & 7) || (ldb & 7) || !Y || !Cm || !stat0 || !stat1 || !R || st < 1 || ss < 1
-        || To != (Ti - 1) / st + 1 || Ho != (Hi - 1) / ss + 1 || Wo != (Wi - 1) / ss + 1 || M % (Ti * Hi * Wi)) return TUBER_EINVAL;
     GemmNT p;
-    memset(&p, 0, sizeof p);
-    p.alpha = 1.f; p.drop_inv_keep = 1.f;
-    p.A = (const bf16*)A; p.lda = lda; p.B = (const bf16*)B; p.ldb = ldb; p.C = dz; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K;
-    p.R = (const bf16*)R; p.ldr = ldr;
-    p.To = To; p.Ho = Ho; p.Wo = Wo; p.Ti = Ti; p.Hi = Hi; p.Wi = Wi; p.st = st; p.ss = ss;
-    p.stat0 = stat0; p.stat1 = stat1; p.Cm = (const bf16*)Cm; p.ldcm = ldcm;
+    if (nt_problem(A, lda, B, ldb, dz, ldc, M, N, K, &p) != TUBER_OK || !Y || !Cm || !stat0 || !stat1 || !R ||
+        !nt_strided_rows(&p, M, To, Ho, Wo, Ti, Hi, Wi, st, ss)) return TUBER_EINVAL;
+    nt_join_operands(&p, R, ldr, Cm, ldcm, stat0, stat1);
     p.Ym = (const bf16*)Y; p.ldym = ldy;
     return nt_dispatch(p, A_PLAIN, EPI_JOIN_SR, stream);
 }
@@ -924,67 +935,26 @@ int tuber_gemm_nt_join_strided(const void* A, long lda, const void* B, long ldb,
 int tuber_gemm_nt_join_ds_mask(const void* A, long lda, const void* B, long ldb, void* dz, long ldc, int M, int N, int K,
                                const void* R, long ldr, const void* Ymask, const void* Cm, long ldcm, const void* Cd, long ldcd,
                                float* stat0, float* stat1, float* stat2, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || (K & 63) || (lda & 7) || (ldb & 7) || (N & 63) || !Ymask || !Cm || !Cd || !stat0 || !stat1 || !stat2) return TUBER_EINVAL;
     GemmNT p;
-    memset(&p, 0, sizeof p);
-    p.alpha = 1.f; p.drop_inv_keep = 1.f;
-    p.A = (const bf16*)A; p.lda = lda; p.B = (const bf16*)B; p.ldb = ldb; p.C = dz; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K;
-    p.R = (const bf16*)R; p.ldr = ldr;
-    p.stat0 = stat0; p.stat1 = stat1; p.stat2 = stat2; p.Cm = (const bf16*)Cm; p.ldcm = ldcm; p.Dm = (const bf16*)Cd; p.lddm = ldcd;
+    if (nt_problem(A, lda, B, ldb, dz, ldc, M, N, K, &p) != TUBER_OK || (N & 63) || !Ymask || !Cm || !Cd || !stat0 || !stat1 || !stat2) return TUBER_EINVAL;
+    nt_join_operands(&p, R, ldr, Cm, ldcm, stat0, stat1);
+    p.Dm = (const bf16*)Cd; p.lddm = ldcd; p.stat2 = stat2;
     p.Ymask = (const uint8_t*)Ymask;
     return nt_dispatch(p, A_PLAIN, EPI_JOIN_DS_M, stream);
 }
 int tuber_gemm_nt_join_strided_mask(const void* A, long lda, const void* B, long ldb, void* dz, long ldc, int M, int N, int K,
                                     const void* R, long ldr, int To, int Ho, int Wo, int Ti, int Hi, int Wi, int st, int ss,
                                     const void* Ymask, const void* Cm, long ldcm, float* stat0, float* stat1, hipStream_t stream) {
-    if (M <= 0 || N <= 0 || K <= 0 || (K & 63) || (lda & 7) || (ldb & 7) || (N & 63) || !Ymask || !Cm || !stat0 || !stat1 || !R || st < 1 || ss < 1
-        || To != (Ti - 1) / st + 1 || Ho != (Hi - 1) / ss + 1 || Wo != (Wi - 1) / ss + 1 || M % (Ti * Hi * Wi)) return TUBER_EINVAL;
     GemmNT p;
-    memset(&p, 0, sizeof p);
-    p.alpha = 1.f; p.drop_inv_keep = 1.f;
-    p.A = (const bf16*)A; p.lda = lda; p.B = (const bf16*)B; p.ldb = ldb; p.C = dz; p.ldc = ldc;
-    p.M = M; p.N = N; p.K = K;
-    p.R = (const bf16*)R; p.ldr = ldr;
-    p.To = To; p.Ho = Ho; p.Wo = Wo; p.Ti = Ti; p.Hi = Hi; p.Wi = Wi; p.st = st; p.ss = ss;
-    p.stat0 = stat0; p.stat1 = stat1; p.Cm = (const bf16*)Cm; p.ldcm = ldcm;
+    if (nt_problem(A, lda, B, ldb, dz, ldc, M, N, K, &p) != TUBER_OK || (N & 63) || !Ymask || !Cm || !stat0 || !stat1 || !R ||
+        !nt_strided_rows(&p, M, To, Ho, Wo, Ti, Hi, Wi, st, ss)) return TUBER_EINVAL;
+    nt_join_operands(&p, R, ldr, Cm, ldcm, stat0, stat1);
     p.Ymask = (const uint8_t*)Ymask;
     return nt_dispatch(p, A_PLAIN, EPI_JOIN_SR_M, stream);
 }
 
-static int nt_dispatch(const GemmNT& p, int amode, int epi, hipStream_t stream) {
-    const int M = p.M, N = p.N, K = p.K;
-    int cfg = nt_pick_cfg(M, N, K);
-    if (nt_force_cfg() < 0 && cfg == 13 && !IS_JOIN_M(epi) && nt_use_wsk(p, amode)) return launch_nt_wsk(p, epi, stream);
-    if ((nt_force_cfg() < 0 && nt_use_96(p, amode, epi)) || (nt_force_cfg() == 23 && amode == A_PLAIN && nt_full(p, 64) && (epi == EPI_PLAIN || epi == EPI_STATS || epi == EPI_BWD))) return launch_nt_96(p, epi, stream);
-    if (nt_force_cfg() == 23) cfg = 13;
-    if (cfg == 0 && epi != EPI_PLAIN && nt_force_cfg() < 0) cfg = 7;     // statistics rows are per 64 output rows (tuber_gemm_nt_stat_rows)
-    if ((epi == EPI_JOIN_DS || epi == EPI_JOIN_DS_M) && cfg == 7 && nt_force_cfg() < 0) cfg = 13;   // three side operands spill the 64x128 tile (21 registers at 3 workgroups / CU)
-    switch (cfg) {
-        case 0: return launch_nt_cfg<128, 128, 2, 2, 2, 2>(p, amode, epi, stream);    // class-branch FFN (plain epilogue)
-        case 7: return launch_nt_cfg<64, 128, 1, 4, 2, 3>(p, amode, epi, stream);
-        case 13: return launch_nt_cfg<64, 64, 2, 2, 2, 4>(p, amode, epi, stream);
-#ifdef TUBER_AB_VARIANTS
-        // the measured-and-rejected tile variants of profiles/r02_gemm_nt_tile_ab.txt (deeper prefetch, round-1 register cap: they
-        // spill to scratch) are built only with -DTUBER_AB_VARIANTS (TUBER_AB_VARIANTS=1 python -m tubelet_transformer_amd.build)
-        case 12: return launch_nt_cfg<64, 64, 2, 2, 4, 3>(p, amode, epi, stream);     // 64x64, four-tile prefetch, 3 workgroups / CU
-        case 17: return launch_nt_cfg<64, 128, 1, 4, 2, 4>(p, amode, epi, stream);    // round-1 register cap (spills)
-        case 2: return launch_nt_cfg<64, 64, 2, 2, 4, 4>(p, amode, epi, stream);      // round-1 default (spills in the fused variants)
-        case 21: return launch_nt_cfg<128, 64, 2, 2, 2, 3>(p, amode, epi, stream);    // round-4 experiment: half the weight re-reads of the long-K layer3 convs
-        case 22: return launch_nt_cfg<128, 64, 4, 1, 2, 3>(p, amode, epi, stream);
-#endif
-        default: return TUBER_EINVAL;
-    }
-}
-
 // 1 when tuber_gemm_nt_set_cfg(cfg) names a tile configuration this library was built with
-int tuber_gemm_nt_has_cfg(int cfg) {
-#ifdef TUBER_AB_VARIANTS
-    return cfg == 23 || cfg == 0 || cfg == 7 || cfg == 13 || cfg == 12 || cfg == 17 || cfg == 2 || cfg == 21 || cfg == 22;
-#else
-    return cfg == 0 || cfg == 7 || cfg == 13 || cfg == 23;
-#endif
-}
+int tuber_gemm_nt_has_cfg(int cfg) { return cfg == 0 || cfg == 7 || cfg == 13 || cfg == 23; }
 
 }  // extern "C"
 
@@ -1672,17 +1642,17 @@ extern "C" {
 // layer4's down-sample weight gradient, 2048 x 1024 over M = 704, took 71.6 us on the in-register-transpose 128-tile kernel against
 // ~14 us for the same work as 512 tiles of gemm_tn2)
 static int tn_tile(int N, int K) { return !((N | K) & 7) ? 64 : (long)ceil_div(N, 128) * ceil_div(K, 128) >= 128 ? 128 : 64; }
-// 128 x 128 transpose-read tiles (gemm_tn3): layer3 / layer4 convs, FFN and class-branch linears, packed in-projections
-static const int g_tn_big = 1;
+// the LDS transpose-read kernels (gemm_tn2 / gemm_tn3) take this shape: 16-byte rows of both operands (then tn_tile is 64)
+static bool tn_transpose_read(int N, int K, long ldg, long lda) { return !((N | K | ldg | lda) & 7); }
+// 128 x 128 transpose-read tiles (gemm_tn3): layer3 / layer4 convs, FFN and class-branch linears, packed in-projections.
 // Measured (scripts/gemm_bench.py tngroup, round 3): eight layer3 problems 68.2 -> 50.9 us, six layer4 ones 87.5 -> 82.6 us; but the
 // long-M class-branch pair (M = 16896) 132 -> 224 us WITH THE SLAB COUNT OF THE SMALL TILES (2 and 1: few tiles x few slabs underfill
 // the chip at two workgroups per CU; see below) and the short-M encoder FFNs (M = 704: 11 steps) 13.5 -> 20.8 us.
 static bool tn_big(int M, int N, int K) {
     // long M (the class-branch FFN pair, M = 16896, 256 x 2048 and 2048 x 512): with enough slabs to fill the chip (2112 rows = 33 steps
     // each: 8 slabs) the big tiles win there too -- 130.8 -> 81.8 us for the pair (650 TFLOP/s), 86.8 / 92.6 / 87.4 us with 12 / 6 / 4 slabs
-    constexpr int max_m = 32768;
     if (M > 8192 && (long)N * K < (1L << 19)) return false;
-    return g_tn_big && M >= 2048 && M <= max_m && !((N | K) & 127) && (long)N * K >= (1L << 17) && tn_tile(N, K) == 64;
+    return M >= 2048 && M <= 32768 && !((N | K) & 127) && (long)N * K >= (1L << 17) && tn_tile(N, K) == 64;
 }
 static int tn_slabs_wanted(int M, int N, int K) {
     const int T = tn_big(M, N, K) ? 128 : tn_tile(N, K);
@@ -1725,64 +1695,11 @@ int tuber_gemm_tn_slabs(int M, int N, int K) { return ceil_div(M, tn_rows_per_sl
 //   2: yes, S = tuber_gemm_tn_slabs > 1: bias_grad must point to S*N floats and receives one partial row per slab (reduce them with
 //      tuber_reduce_rows(bias_grad, dbias, S, N, 1) or a tuber_multi_reduce entry).
 int tuber_gemm_tn_fuses_bias(int M, int N, int K, long ldg, long lda) {
-    if (!(tn_tile(N, K) == 64 && !((N | K | ldg | lda) & 7))) return 0;
+    if (!tn_transpose_read(N, K, ldg, lda)) return 0;
     return tuber_gemm_tn_slabs(M, N, K) == 1 ? 1 : 2;
 }
 
-int tuber_gemm_tn(const void* G, long ldg, const void* A, long lda, float* partial, float* out, int accumulate,
-                  int M, int N, int K, int amode, const float* a_scale, const float* a_shift,
-                  int gather, int To, int Ho, int Wo, int Ti, int Hi, int Wi, int st, int ss,
-                  const void* G2, long ldg2, const float* gA, const float* gB, const float* gC,
-                  float* bias_grad, hipStream_t stream) {
-    // N / K need not be multiples of 4, but G / A must be readable up to ceil4(N) / ceil4(K) columns (padded ld)
-    if (M <= 0 || N <= 0 || K <= 0 || (ldg & 3) || (lda & 3) || ldg < ((N + 3) & ~3) || lda < ((K + 3) & ~3)) return TUBER_EINVAL;
-    GemmTN p;
-    p.G = (const bf16*)G; p.ldg = ldg; p.A = (const bf16*)A; p.lda = lda;
-    p.M = M; p.N = N; p.K = K;
-    p.rows_per_slab = tn_rows_per_slab(M, N, K);
-    p.S = tuber_gemm_tn_slabs(M, N, K);
-    p.accumulate = accumulate;
-    p.P = p.S == 1 ? out : partial;            // a single slab writes (or accumulates into) the gradient directly
-    p.a_scale = a_scale; p.a_shift = a_shift;
-    const int gmode = 0;
-    if (G2) return TUBER_EINVAL;               // BatchNorm-backward apply on the G operand (GMODE 1): measured slower than the apply kernel, not built
-    p.G2 = (const bf16*)G2; p.ldg2 = ldg2; p.gA = gA; p.gB = gB; p.gC = gC;
-    p.gather = gather; p.To = To; p.Ho = Ho; p.Wo = Wo; p.Ti = Ti; p.Hi = Hi; p.Wi = Wi; p.st = st; p.ss = ss;
-    p.amode = amode;
-    p.A2 = nullptr; p.lda2 = 0;
-    const int T = tn_tile(N, K);
-    const int tiles = ceil_div(N, T) * ceil_div(K, T);
-    dim3 grid(tiles * p.S), block(256);
-    const size_t lds = 2 * 2 * T * 128;
-#define LTN(AM, TT, GM) hipLaunchKernelGGL((gemm_tn_kernel<AM, TT, GM>), grid, block, lds, stream, p)
-    const int use_tr = 1;
-    p.bias_grad = nullptr;
-    if (bias_grad && !tuber_gemm_tn_fuses_bias(M, N, K, ldg, lda)) return TUBER_EINVAL;
-    if (T == 64 && !gmode && use_tr && !((N | K | ldg | lda) & 7) && tn_big(M, N, K)) {     // ... on 128 x 128 tiles
-        p.bias_grad = bias_grad;
-        const dim3 grid3(ceil_div(N, 128) * ceil_div(K, 128) * p.S);
-        if (amode == A_BN_RELU) hipLaunchKernelGGL(gemm_tn3_kernel<A_BN_RELU>, grid3, block, 0, stream, p);
-        else hipLaunchKernelGGL(gemm_tn3_kernel<A_PLAIN>, grid3, block, 0, stream, p);
-    } else if (T == 64 && !gmode && use_tr && !((N | K | ldg | lda) & 7)) {     // LDS transpose-read kernel
-        p.bias_grad = bias_grad;
-        if (amode == A_BN_RELU) hipLaunchKernelGGL(gemm_tn2_kernel<A_BN_RELU>, grid, block, 0, stream, p);
-        else hipLaunchKernelGGL(gemm_tn2_kernel<A_PLAIN>, grid, block, 0, stream, p);
-    } else if (T == 128) {
-        if (amode == A_BN_RELU) LTN(A_BN_RELU, 128, 0); else LTN(A_PLAIN, 128, 0);
-    } else {
-        if (amode == A_BN_RELU) LTN(A_BN_RELU, 64, 0); else LTN(A_PLAIN, 64, 0);
-    }
-#undef LTN
-    if (p.S > 1 && accumulate != 2) {          // accumulate == 2: the caller reduces the slabs later (tuber_multi_reduce)
-        const long n = (long)N * K;
-        if (p.S <= 16) hipLaunchKernelGGL(reduce_slabs_flat_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, stream, partial, out, n, p.S, accumulate);
-        else hipLaunchKernelGGL(reduce_slabs_kernel, dim3(ceil_div(n, 32)), dim3(1024), 0, stream, partial, out, n, p.S, accumulate);
-    }
-    TUBER_RETURN_LAUNCH();
-}
-
-
-// one entry of tuber_gemm_tn_group (HOST memory): the tuber_gemm_tn arguments of one weight-gradient GEMM
+// one weight-gradient GEMM: the tuber_gemm_tn arguments, and one entry of tuber_gemm_tn_group (HOST memory)
 struct TuberGemmTNArgs {
     const void* G; long ldg; const void* A; long lda; float* partial; float* out;
     int accumulate, M, N, K, amode, gather, To, Ho, Wo, Ti, Hi, Wi, st, ss;
@@ -1790,12 +1707,66 @@ struct TuberGemmTNArgs {
     float* bias_grad;            // optional, as in tuber_gemm_tn: dbias[N] (single slab, accumulated) or [slabs][N] partial rows
     const void* A2; long lda2;   // optional: A := A + A2 (no gather then)
 };
+// its kernel argument block: slab rows and count, where the slabs go, the operands and the row gather
+static void tn_problem(const TuberGemmTNArgs& x, GemmTN* p) {
+    memset(p, 0, sizeof *p);
+    p->G = (const bf16*)x.G; p->ldg = x.ldg; p->A = (const bf16*)x.A; p->lda = x.lda;
+    p->M = x.M; p->N = x.N; p->K = x.K;
+    p->rows_per_slab = tn_rows_per_slab(x.M, x.N, x.K);
+    p->S = tuber_gemm_tn_slabs(x.M, x.N, x.K);
+    p->accumulate = x.accumulate;
+    p->P = p->S == 1 ? x.out : x.partial;      // a single slab writes (or accumulates into) the gradient directly
+    p->a_scale = x.a_scale; p->a_shift = x.a_shift; p->amode = x.amode;
+    p->bias_grad = x.bias_grad;
+    p->A2 = (const bf16*)x.A2; p->lda2 = x.lda2;
+    p->gather = x.gather; p->To = x.To; p->Ho = x.Ho; p->Wo = x.Wo; p->Ti = x.Ti; p->Hi = x.Hi; p->Wi = x.Wi; p->st = x.st; p->ss = x.ss;
+}
+
+// Accepts: leading dimensions that are multiples of 4 and cover ceil4(N) / ceil4(K) columns (N / K themselves may be odd: G / A must be
+// readable up to the padded width); bias_grad only where tuber_gemm_tn_fuses_bias says so.  Shapes tn_transpose_read takes run gemm_tn2 /
+// gemm_tn3, the rest the in-register-transpose kernel.  With several slabs the second-stage reduce is launched here unless
+// accumulate == 2 (the caller reduces the slabs later: tuber_multi_reduce).  G2 .. gC (BatchNorm-backward apply on the G operand) are
+// kept in the ABI only: measured slower than the apply kernel, not built, so a non-null G2 is refused.
+int tuber_gemm_tn(const void* G, long ldg, const void* A, long lda, float* partial, float* out, int accumulate,
+                  int M, int N, int K, int amode, const float* a_scale, const float* a_shift,
+                  int gather, int To, int Ho, int Wo, int Ti, int Hi, int Wi, int st, int ss,
+                  const void* G2, long ldg2, const float* gA, const float* gB, const float* gC,
+                  float* bias_grad, hipStream_t stream) {
+    if (M <= 0 || N <= 0 || K <= 0 || (ldg & 3) || (lda & 3) || ldg < ((N + 3) & ~3) || lda < ((K + 3) & ~3)) return TUBER_EINVAL;
+    if (G2) return TUBER_EINVAL;
+    const bool tr = tn_transpose_read(N, K, ldg, lda);
+    if (bias_grad && !tr) return TUBER_EINVAL;
+    const TuberGemmTNArgs x = {G, ldg, A, lda, partial, out, accumulate, M, N, K, amode, gather, To, Ho, Wo, Ti, Hi, Wi, st, ss,
+                               a_scale, a_shift, bias_grad, nullptr, 0};
+    GemmTN p;
+    tn_problem(x, &p);
+    const int T = tr && tn_big(M, N, K) ? 128 : tn_tile(N, K);
+    const dim3 grid(ceil_div(N, T) * ceil_div(K, T) * p.S), block(256);
+#define LTN(KERNEL, LDS, ...)                                                                                             \
+    do {                                                                                                                  \
+        if (amode == A_BN_RELU) hipLaunchKernelGGL((KERNEL<A_BN_RELU, ##__VA_ARGS__>), grid, block, LDS, stream, p);      \
+        else hipLaunchKernelGGL((KERNEL<A_PLAIN, ##__VA_ARGS__>), grid, block, LDS, stream, p);                           \
+    } while (0)
+    if (tr && T == 128) LTN(gemm_tn3_kernel, 0);                  // transpose-read kernel on 128 x 128 tiles
+    else if (tr) LTN(gemm_tn2_kernel, 0);                         // ... on 64 x 64 tiles
+    else if (T == 128) LTN(gemm_tn_kernel, 2 * 2 * T * 128, 128, 0);     // in-register transpose: two stages of 2 T 128-byte rows
+    else LTN(gemm_tn_kernel, 2 * 2 * T * 128, 64, 0);
+#undef LTN
+    if (p.S > 1 && accumulate != 2) {
+        const long n = (long)N * K;
+        if (p.S <= 16) hipLaunchKernelGGL(reduce_slabs_flat_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, stream, partial, out, n, p.S, accumulate);
+        else hipLaunchKernelGGL(reduce_slabs_kernel, dim3(ceil_div(n, 32)), dim3(1024), 0, stream, partial, out, n, p.S, accumulate);
+    }
+    TUBER_RETURN_LAUNCH();
+}
+
 int tuber_gemm_tn_args_bytes(void) { return (int)sizeof(TuberGemmTNArgs); }
 int tuber_gemm_tn_group_max(void) { return TN_GROUP_MAX; }
 
-// n <= tuber_gemm_tn_group_max() weight-gradient GEMMs (each exactly what tuber_gemm_tn would compute, transpose-read kernel
-// shapes only: 64 x 64 tiles, N / K / ld multiples of 8) in ONE launch.  Slab partials / accumulate flags per entry as in
-// tuber_gemm_tn; with several slabs the caller reduces them (accumulate must be 2 then: the second stage is not launched here).
+// n <= tuber_gemm_tn_group_max() weight-gradient GEMMs (each exactly what tuber_gemm_tn would compute) in ONE launch.
+// Accepts: transpose-read kernel shapes only (N / K / ld multiples of 8, ld >= the width), plain or BatchNorm + ReLU A, an addend A2 only
+// for plain ungathered A; with several slabs accumulate must be 2 (the second stage is not launched here: the caller reduces them).
+// Slab partials / accumulate flags per entry as in tuber_gemm_tn.
 int tuber_gemm_tn_group(const void* args_host, int n, hipStream_t stream) {
     if (!args_host || n <= 0 || n > TN_GROUP_MAX) return TUBER_EINVAL;
     const TuberGemmTNArgs* a = (const TuberGemmTNArgs*)args_host;
@@ -1805,28 +1776,16 @@ int tuber_gemm_tn_group(const void* args_host, int n, hipStream_t stream) {
     memset(gs, 0, sizeof gs);
     for (int i = 0; i < n; ++i) {
         const TuberGemmTNArgs& x = a[i];
-        if (x.M <= 0 || x.N <= 0 || x.K <= 0 || ((x.N | x.K | x.ldg | x.lda) & 7) || x.ldg < x.N || x.lda < x.K) return TUBER_EINVAL;
-        if (tn_tile(x.N, x.K) != 64 || (x.amode != A_PLAIN && x.amode != A_BN_RELU)) return TUBER_EINVAL;
+        if (x.M <= 0 || x.N <= 0 || x.K <= 0 || !tn_transpose_read(x.N, x.K, x.ldg, x.lda) || x.ldg < x.N || x.lda < x.K) return TUBER_EINVAL;
+        if (x.amode != A_PLAIN && x.amode != A_BN_RELU) return TUBER_EINVAL;
         if (x.amode == A_BN_RELU && (!x.a_scale || !x.a_shift)) return TUBER_EINVAL;
-        const int big = tn_big(x.M, x.N, x.K) ? 1 : 0;
-        GemmTNGroup& g = gs[big];
-        GemmTN& p = g.p[cnt[big]];
-        p.G = (const bf16*)x.G; p.ldg = x.ldg; p.A = (const bf16*)x.A; p.lda = x.lda;
-        p.M = x.M; p.N = x.N; p.K = x.K;
-        p.rows_per_slab = tn_rows_per_slab(x.M, x.N, x.K);
-        p.S = tuber_gemm_tn_slabs(x.M, x.N, x.K);
-        if (p.S > 1 && x.accumulate != 2) return TUBER_EINVAL;
-        p.accumulate = x.accumulate;
-        p.P = p.S == 1 ? x.out : x.partial;
-        if (!p.P) return TUBER_EINVAL;
-        p.a_scale = x.a_scale; p.a_shift = x.a_shift;
-        p.G2 = nullptr; p.ldg2 = 0; p.gA = p.gB = p.gC = nullptr; p.bias_grad = x.bias_grad;
         if (x.A2 && (x.gather || (x.lda2 & 7) || x.lda2 < x.K || x.amode != A_PLAIN)) return TUBER_EINVAL;
-        p.A2 = (const bf16*)x.A2; p.lda2 = x.lda2;
-        p.gather = x.gather; p.To = x.To; p.Ho = x.Ho; p.Wo = x.Wo; p.Ti = x.Ti; p.Hi = x.Hi; p.Wi = x.Wi; p.st = x.st; p.ss = x.ss;
-        p.amode = x.amode;
+        const int big = tn_big(x.M, x.N, x.K) ? 1 : 0;
+        GemmTN& p = gs[big].p[cnt[big]];
+        tn_problem(x, &p);
+        if ((p.S > 1 && x.accumulate != 2) || !p.P) return TUBER_EINVAL;
         const int T = big ? 128 : 64;
-        g.begin[cnt[big]] = total[big];
+        gs[big].begin[cnt[big]] = total[big];
         total[big] += ceil_div(x.N, T) * ceil_div(x.K, T) * p.S;
         ++cnt[big];
     }

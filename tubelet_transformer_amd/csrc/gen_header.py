@@ -211,7 +211,12 @@ DOC = {
                      "+ partial (sum dz, sum dz*Cm) rows for BatchNorm backward (stat rows optional: with m_scale NULL it is the ReLU / ReLU+Dropout "
                      "backward mask from the saved activation). Accumulators are scaled by alpha first; epi 0 can end with Dropout(drop_p) "
                      "keyed by (seed, salt, m*N+n) -- FFN linear1 (transformer.py:160-162). K % 64 == 0.",
-    "tuber_gemm_nt_cfg": "tile configuration tuber_gemm_nt uses for (M,N,K): 13 = 64x64 (two-tile prefetch), 7 = 64x128, 0 = 128x128 (plain epilogue only); 2 / 12 / 17 = rejected A/B variants, built only with -DTUBER_AB_VARIANTS.",
+    "tuber_gemm_nt_cfg": "tile configuration tuber_gemm_nt uses for (M,N,K): 13 = 64x64 (two-tile prefetch), 7 = 64x128, 0 = 128x128 (plain epilogue only); "
+                         "the forced configuration while tuber_gemm_nt_set_cfg holds. What is launched after the form and epilogue rules: tuber_gemm_nt_plan.",
+    "tuber_gemm_nt_plan": "what tuber_gemm_nt and its siblings launch for (M, N, K, amode, epi, gather, out_f32), packed as form * 1000000 + tile rows * 1000 + tile "
+                          "columns: form 0 = the shared-tile pipeline (128x128, 64x128, 64x64), 1 = wave split-K (64x64, 96x64), 2 = 96x64 tiles on the regular "
+                          "pipeline; TUBER_EINVAL where the (amode, epi) combination is not built for the shape. aligned: every leading dimension of the epilogue's "
+                          "tensors is a multiple of 8 (ldc = N). Reads the same decision the launchers take (tile hooks included); host only.",
     "tuber_gemm_tn_tile": "output tile edge of the transpose-read weight-gradient kernel for (M, N, K): 128 (mid-M backbone shapes, N and K multiples of 128) or 64.",
     "tuber_gemm_nt_has_cfg": "1 when tuber_gemm_nt_set_cfg(cfg) names a tile configuration this library was built with.",
     "tuber_gemm_nt_stat_rows": "rows of partial statistics tuber_gemm_nt(epi 1|2) writes for (M,N).",
