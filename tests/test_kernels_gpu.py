@@ -23,6 +23,12 @@ def bfr(x):
     return x.to(BF).float()
 
 
+def nans(*shape, dev, dtype=torch.float32):
+    """a GEMM output before the launch: NaN, not torch.empty -- the caching allocator hands a second launch of the same shape the block the
+    first one filled, and an element the kernel never writes would still hold the earlier, correct value"""
+    return torch.full(shape, float("nan"), device=dev, dtype=dtype)
+
+
 def close(name, got, ref, rel=2 ** -7, abs_=None):
     got, ref = got.float(), ref.float()
     scale = float(ref.abs().max()) + 1e-12
@@ -45,7 +51,7 @@ class rows64:
 def gemm_nt(A, B, M, N, K, amode=0, sc=None, sh=None, gather=None, epi=0, bias=None, R=None, relu=0, out_f32=0,
             Cm=None, msc=None, msh=None, lda=None):
     dev = A.device
-    C = torch.empty(M, N, device=dev, dtype=torch.float32 if out_f32 else BF)
+    C = nans(M, N, dev=dev, dtype=torch.float32 if out_f32 else BF)
     rows = lib.query("tuber_gemm_nt_stat_rows", M, N)
     st0 = torch.zeros(rows, N, device=dev) if epi else None
     st1 = torch.zeros(rows, N, device=dev) if epi else None
@@ -137,7 +143,7 @@ def test_gemm_nt_wave_split_k(dev, M, N, K):
         out["stats"] = gemm_nt(A, B, M, N, K, epi=1)
         out["bwd"] = gemm_nt(A, B, M, N, K, epi=2, Cm=Cm)
         rows = lib.query("tuber_gemm_nt_stat_rows", M, N)
-        dz, b0, b1 = torch.empty(M, N, device=dev, dtype=BF), torch.zeros(rows, N, device=dev), torch.zeros(rows, N, device=dev)
+        dz, b0, b1 = nans(M, N, dev=dev, dtype=BF), torch.zeros(rows, N, device=dev), torch.zeros(rows, N, device=dev)
         lib.call("tuber_gemm_nt_join", A, K, B, K, dz, N, M, N, K, R, N, Y, N, Cm, N, b0, b1)
         out["join"] = (dz, b0, b1)
         return out
@@ -191,7 +197,7 @@ def test_gemm_nt_launches_what_the_plan_says(dev, M, N, K, form):
     ref = A.float() @ B.float().t()
     rows = lib.query("tuber_gemm_nt_stat_rows", M, N)
     assert rows == (M + 63) // 64
-    C = torch.empty(M, N, device=dev, dtype=BF)
+    C = nans(M, N, dev=dev, dtype=BF)
     st0, st1 = torch.full((rows, N), float("nan"), device=dev), torch.full((rows, N), float("nan"), device=dev)
     lib.call("tuber_gemm_nt", A, K, B, K, C, N, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0, 1, None, None, N, 0,
              0, st0, st1, None, N, None, None, 1.0, 0.0, None, 0, None, 0, None)
@@ -245,7 +251,7 @@ def test_gemm_tn(dev, M, N, K, amode):
     a = bfr((A.float() * sc + sh).relu()) if amode else A.float()
     ref = G.float().t() @ a
     S = lib.query("tuber_gemm_tn_slabs", M, N, K)
-    part = torch.empty(S, N, K, device=dev)
+    part = nans(S, N, K, dev=dev)
     out = torch.zeros(N, K, device=dev)
     lib.call("tuber_gemm_tn", G, N, A, K, part, out, 0, M, N, K, amode, sc if amode else None, sh if amode else None,
              0, 0, 0, 0, 0, 0, 0, 0, 0, None, 0, None, None, None, None)
@@ -264,7 +270,7 @@ def test_gemm_tn_gather(dev):
     M = Xs.shape[0]
     G = rnd(M, N, dev=dev, seed=3).to(BF)
     S = lib.query("tuber_gemm_tn_slabs", M, N, K)
-    part = torch.empty(S, N, K, device=dev)
+    part = nans(S, N, K, dev=dev)
     out = torch.zeros(N, K, device=dev)
     lib.call("tuber_gemm_tn", G, N, X, K, part, out, 0, M, N, K, 0, None, None, 1, To, Ho, Wo, Ti, Hi, Wi, st, ss, None, 0, None, None, None, None)
     close("gemm_tn gather", out, G.float().t() @ Xs.float(), rel=2e-3)
@@ -627,7 +633,7 @@ def test_in_projection_data_gradients_in_one_launch(dev, M, N, Nq, Kin, with_res
     g = rnd(M, N, dev=dev, seed=1).to(BF)
     wt = (rnd(Kin, N, dev=dev, seed=2) / 16).to(BF)            # W^T rows [Kin][N]
     res = rnd(M, Kin, dev=dev, seed=3).to(BF) if with_res else None
-    dx0, da0 = torch.empty(M, Kin, device=dev, dtype=BF), torch.empty(M, Kin, device=dev, dtype=BF)
+    dx0, da0 = nans(M, Kin, dev=dev, dtype=BF), nans(M, Kin, dev=dev, dtype=BF)
     for ncols, r, out in ((N, res, dx0), (Nq, None, da0)):
         lib.call("tuber_gemm_nt", g, N, wt, N, out, Kin, M, Kin, ncols, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
                  0, None, r, Kin, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)
@@ -641,7 +647,7 @@ def test_in_projection_data_gradients_in_one_launch(dev, M, N, Nq, Kin, with_res
     ref = g.float() @ wt.float().t() + (res.float() if with_res else 0)
     close("rows_dx2 dx vs fp32", dx1, ref, rel=2 ** -6)
     close("rows_dx2 dpos vs fp32", da1, g.float()[:, :Nq] @ wt.float()[:, :Nq].t(), rel=2 ** -6)
-    dx2 = torch.empty(M, Kin, device=dev, dtype=BF)
+    dx2 = nans(M, Kin, dev=dev, dtype=BF)
     lib.call("tuber_rows_dx2", g, N, M, N, Nq, wt, N, Kin, dx2, res, None)                # the prefix result not wanted
     assert torch.equal(dx2, dx1)
 
@@ -653,7 +659,7 @@ def test_gemm_epilogue_dropout_and_masked_dgrad(dev):
     x = rnd(M, K, dev=dev, seed=1).to(BF)
     w = (rnd(N, K, dev=dev, seed=2) / 16).to(BF)
     bias = 0.1 * rnd(N, dev=dev, seed=3)
-    h = torch.empty(M, N, device=dev, dtype=BF)
+    h = nans(M, N, dev=dev, dtype=BF)
     lib.call("tuber_gemm_nt", x, K, w, K, h, N, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
              0, bias, None, 0, 1, 0, None, None, None, 0, None, None, 1.0, p, seed, salt, None, 0, None)
     ones = torch.ones(M, N, device=dev, dtype=BF)
@@ -665,7 +671,7 @@ def test_gemm_epilogue_dropout_and_masked_dgrad(dev):
     K2 = 256
     g = rnd(M, K2, dev=dev, seed=4).to(BF)
     w2t = (rnd(N, K2, dev=dev, seed=5) / 16).to(BF)            # W2^T rows = N (output features of the dgrad GEMM)
-    dpre = torch.empty(M, N, device=dev, dtype=BF)
+    dpre = nans(M, N, dev=dev, dtype=BF)
     alpha = 1.0 / (1.0 - p)
     lib.call("tuber_gemm_nt", g, K2, w2t, K2, dpre, N, M, N, K2, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
              2, None, None, 0, 0, 0, None, None, h, N, None, None, alpha, 0.0, None, 0, None, 0, None)
@@ -684,7 +690,7 @@ def test_gemm_tn_fused_bias_gradient(dev, M, N, K):
     A = rnd(M, K, dev=dev, seed=2).to(BF)
     out = torch.ones(N, K, device=dev)
     db = torch.ones(N, device=dev)
-    part = torch.empty(N * K, device=dev)
+    part = nans(N * K, dev=dev)
     lib.call("tuber_gemm_tn", G, N, A, K, part, out, 1, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0, None, 0, None, None, None, db)
     close("gemm_tn (+bias) dW", out - 1, G.float().t() @ A.float(), rel=4e-3)
     close("gemm_tn fused dbias", db - 1, G.float().sum(0), abs_=2e-3 * float(G.float().abs().sum(0).max()))
@@ -1031,7 +1037,7 @@ def test_gemm_nt_join_equals_dgrad_then_block_out_bwd(dev, M, N, K, res):
     Rr = rnd(M, N, dev=dev, seed=3).to(BF) if res else None
     Y = rnd(M, N, dev=dev, seed=4).to(BF).relu()
     C4 = rnd(M, N, dev=dev, seed=5).to(BF)
-    dx = torch.empty(M, N, device=dev, dtype=BF)
+    dx = nans(M, N, dev=dev, dtype=BF)
     lib.call("tuber_gemm_nt", A, K, B, K, dx, N, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
              0, None, Rr, N, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)
     R0 = lib.query("tuber_rowblock_count", M, N)
@@ -1075,7 +1081,7 @@ def test_gemm_nt_join_strided_residual(dev, n, Ti, Hi, Wi, st, ss, N, K):
     Rs = rnd(Mo, N, dev=dev, seed=3).to(BF)                      # the projection shortcut's data gradient, one row per sampled position
     Y = rnd(M, N, dev=dev, seed=4).to(BF).relu()
     C4 = rnd(M, N, dev=dev, seed=5).to(BF)
-    dx = torch.empty(M, N, device=dev, dtype=BF)
+    dx = nans(M, N, dev=dev, dtype=BF)
     lib.call("tuber_gemm_nt", A, K, B, K, dx, N, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0,
              0, None, None, N, 0, 0, None, None, None, 0, None, None, 1.0, 0.0, None, 0, None, 0, None)
     lib.call("tuber_rows_scatter_add", dx, Rs, Mo, To, Ho, Wo, Ti, Hi, Wi, st, ss, N)
@@ -1569,7 +1575,7 @@ def test_gemm_nt_bn_out_eval_tail(dev, M, N, K):
     sc, sh = rnd(K, dev=dev, seed=3).abs() + 0.5, rnd(K, dev=dev, seed=4) * 0.3
     s4, h4 = rnd(N, dev=dev, seed=5).abs() + 0.5, rnd(N, dev=dev, seed=6) * 0.3
     R32 = rnd(M, N, dev=dev, seed=7).abs()
-    y, y32 = torch.empty(M, N, device=dev, dtype=BF), torch.empty(M, N, device=dev)
+    y, y32 = nans(M, N, dev=dev, dtype=BF), nans(M, N, dev=dev)
     lib.call("tuber_gemm_nt_bn_out", A, K, sc, sh, W, K, s4, h4, R32, N, y, N, y32, N, M, N, K)
     a = bfr((A.float() * sc + sh).relu())
     ref = (bfr(a @ W.float().t()) * s4 + h4 + R32).relu()            # c4 passes through bf16 (in registers) like in the two-launch path
@@ -1601,7 +1607,7 @@ def test_gemm_nt_96_row_tiles(dev, M, N, K):
     def run_all():
         out = {"plain": gemm_nt(A, B, M, N, K, bias=bias, R=R, relu=1)[0]}
         for name, kw in (("stats", dict(epi=1)), ("bwd", dict(epi=2, Cm=Cm, msc=msc, msh=msh))):
-            C = torch.empty(M, N, device=dev, dtype=BF)
+            C = nans(M, N, dev=dev, dtype=BF)
             st0, st1 = torch.full((rows, N), 7.0, device=dev), torch.full((rows, N), 7.0, device=dev)      # poisoned: every row must be written
             lib.call("tuber_gemm_nt", A, K, B, K, C, N, M, N, K, 0, None, None, 0, 0, 0, 0, 0, 0, 0, 0, 0, kw["epi"], None, None, N, 0, 0, st0, st1,
                      kw.get("Cm"), N, kw.get("msc"), kw.get("msh"), 1.0, 0.0, None, 0, None, 0, None)
@@ -1649,7 +1655,7 @@ def test_join_backward_reads_the_relu_mask_as_a_bit_field(dev, M, N, K):
     rows = lib.query("tuber_gemm_nt_stat_rows", M, N)
     outs = []
     for masked in (False, True):
-        dz = torch.empty(M, N, device=dev, dtype=BF)
+        dz = nans(M, N, dev=dev, dtype=BF)
         b0, b1 = torch.full((rows, N), 7.0, device=dev), torch.full((rows, N), 7.0, device=dev)
         if masked:
             lib.call("tuber_gemm_nt_join_mask", A, K, W, K, dz, N, M, N, K, R, N, ymask, c4, N, b0, b1)
@@ -1686,7 +1692,7 @@ def test_strided_and_first_block_joins_with_the_bit_field_mask(dev):
     R1 = lib.query("tuber_gemm_nt_stat_rows", M, N)
     res = []
     for masked in (False, True):
-        dz = torch.empty(M, N, device=dev, dtype=BF)
+        dz = nans(M, N, dev=dev, dtype=BF)
         b0, b1 = torch.full((R1, N), 7.0, device=dev), torch.full((R1, N), 7.0, device=dev)
         if masked:
             lib.call("tuber_gemm_nt_join_strided_mask", A, K, B, K, dz, N, M, N, K, Rs, N, To, Ho, Wo, Ti, Hi, Wi, st, ss, ym, C4, N, b0, b1)
@@ -1697,7 +1703,7 @@ def test_strided_and_first_block_joins_with_the_bit_field_mask(dev):
         assert torch.equal(a, b)
     res = []
     for masked in (False, True):
-        dz = torch.empty(M, N, device=dev, dtype=BF)
+        dz = nans(M, N, dev=dev, dtype=BF)
         d0, d1, d2 = (torch.full((R1, N), 7.0, device=dev) for _ in range(3))
         if masked:
             lib.call("tuber_gemm_nt_join_ds_mask", A, K, B, K, dz, N, M, N, K, Rr, N, ym, C4, N, Cd, N, d0, d1, d2)

@@ -603,7 +603,8 @@ __global__ __launch_bounds__(256, OCC) void gemm_nt_kernel(GemmNT p) {
 
 // every output column of every tile exists and every epilogue tensor can be read / written in 16-byte pieces
 static bool nt_full(const GemmNT& p, int bn) {
-    return p.N % bn == 0 && !(p.ldc & 7) && !p.out_f32 && (!p.Cm || !(p.ldcm & 7)) && (!p.Ym || !(p.ldym & 7)) && (!p.R || !(p.ldr & 7));
+    return p.N % bn == 0 && !(p.ldc & 7) && !p.out_f32 && (!p.Cm || !(p.ldcm & 7)) && (!p.Ym || !(p.ldym & 7)) && (!p.R || !(p.ldr & 7)) &&
+           (!p.Dm || !(p.lddm & 7));
 }
 
 // ---- the tile decision: nt_plan is the one place that reads the hooks and the shape thresholds ----

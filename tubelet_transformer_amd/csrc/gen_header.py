@@ -117,7 +117,8 @@ DOC = {
                                   "position, n*To*Ho*Wo rows) and is added to the output rows (n, t, h, w) with t % st == h % ss == w % ss == 0 inside the epilogue -- replaces "
                                   "tuber_gemm_nt + tuber_rows_scatter_add + tuber_block_out_bwd (autograd of models/backbones/ir_CSN_152.py:72,86-89,155-161).",
     "tuber_gemm_nt_join_ds": "tuber_gemm_nt_join below a stage's FIRST block: Cd = the raw output of that block's projection shortcut, stat2 = the rows sum dz*cd of the "
-                             "shortcut BatchNorm's backward (tuber_block_out_bwd's third statistics buffer). autograd of models/backbones/ir_CSN_152.py:86-89,155-161.",
+                             "shortcut BatchNorm's backward (tuber_block_out_bwd's third statistics buffer). autograd of models/backbones/ir_CSN_152.py:86-89,155-161. "
+                             "ldcd counts like the other epilogue leading dimensions: an odd one selects the bounds-checked instantiation (tuber_gemm_nt_join_ds_mask: TUBER_EINVAL).",
     "tuber_gemm_tn_group": "n <= tuber_gemm_tn_group_max() weight-gradient GEMMs (each exactly one tuber_gemm_tn: dW = G^T f(A) of a 1x1x1 conv, "
                            "autograd of models/backbones/ir_CSN_152.py:41,58,155-161) in ONE launch; args_host = HOST array of struct TuberGemmTNArgs "
                            "{const void* G; long ldg; const void* A; long lda; float* partial; float* out; int accumulate, M, N, K, amode, gather, "
@@ -210,7 +211,13 @@ DOC = {
                      "epi 1: bf16 out + per-column partial (sum, sum^2) rows for training-mode BatchNorm; epi 2: out = acc*[Cm*m_scale+m_shift>0] "
                      "+ partial (sum dz, sum dz*Cm) rows for BatchNorm backward (stat rows optional: with m_scale NULL it is the ReLU / ReLU+Dropout "
                      "backward mask from the saved activation). Accumulators are scaled by alpha first; epi 0 can end with Dropout(drop_p) "
-                     "keyed by (seed, salt, m*N+n) -- FFN linear1 (transformer.py:160-162). K % 64 == 0.",
+                     "keyed by (seed, salt, m*N+n) -- FFN linear1 (transformer.py:160-162). K % 64 == 0. "
+                     "LAYOUT CONTRACT of this entry point and its siblings (tuber_gemm_nt_addproj, _join*, _bn_out): lda / ldb / lda2 are multiples of 8 (else TUBER_EINVAL) "
+                     "and A / B / A2 start on a 16-byte boundary -- the main loop loads 16 bytes; the base pointers are the caller's responsibility and are NOT checked. "
+                     "The epilogue's tensors (C, R, Cm, Y, Cd) take any leading dimension >= N: with N a multiple of the tile width and every one of those leading dimensions "
+                     "a multiple of 8 the FULL instantiation (16-byte accesses) runs, otherwise the bounds-checked one (element accesses), with bit-identical results; "
+                     "a tensor whose leading dimension is a multiple of 8 must start on a 16-byte boundary. Nothing outside rows [0, M) x columns [0, N) of an output "
+                     "and nothing outside rows x [0, K) / [0, N) of an operand is touched. The bit-field joins and tuber_gemm_nt_bn_out are built FULL only (TUBER_EINVAL otherwise).",
     "tuber_gemm_nt_cfg": "tile configuration tuber_gemm_nt uses for (M,N,K): 13 = 64x64 (two-tile prefetch), 7 = 64x128, 0 = 128x128 (plain epilogue only); "
                          "the forced configuration while tuber_gemm_nt_set_cfg holds. What is launched after the form and epilogue rules: tuber_gemm_nt_plan.",
     "tuber_gemm_nt_plan": "what tuber_gemm_nt and its siblings launch for (M, N, K, amode, epi, gather, out_f32), packed as form * 1000000 + tile rows * 1000 + tile "
@@ -221,7 +228,11 @@ DOC = {
     "tuber_gemm_nt_has_cfg": "1 when tuber_gemm_nt_set_cfg(cfg) names a tile configuration this library was built with.",
     "tuber_gemm_nt_stat_rows": "rows of partial statistics tuber_gemm_nt(epi 1|2) writes for (M,N).",
     "tuber_gemm_tn": "dW[N,K] (+)= sum_m G[m,N]^T . f(A)[m,K]: weight gradient of the same convs / linears (autograd of the ops above); "
-                     "split over M into fp32 slabs `partial` [tuber_gemm_tn_slabs][N][K], then reduced deterministically.",
+                     "split over M into fp32 slabs `partial` [tuber_gemm_tn_slabs][N][K], then reduced deterministically. "
+                     "LAYOUT CONTRACT: ldg / lda are multiples of 4 and >= ceil4(N) / ceil4(K) (else TUBER_EINVAL). N, K, ldg, lda all multiples of 8: the transpose-read kernels, "
+                     "16-byte loads, G / A (and partial / out) on 16-byte boundaries. Otherwise the in-register-transpose kernel: 8-byte loads, G / A on 8-byte boundaries; it reads "
+                     "whole 4-column groups, i.e. up to ceil4(N) / ceil4(K) columns of a row, and the values in those pad columns (anything, NaN included) only reach output "
+                     "rows / columns that are never stored. Base pointers are NOT checked. partial / out / bias_grad are dense.",
     "tuber_gemm_tn_fuses_bias": "can tuber_gemm_tn also produce the bias gradient for this shape: 0 no; 1 yes, accumulated into bias_grad[N] directly (single slab); 2 yes, bias_grad receives one partial row per slab ([tuber_gemm_tn_slabs][N], reduced by the caller).",
     "tuber_gemm_tn_slabs": "number of slabs (size of `partial` / (N*K)) tuber_gemm_tn uses.",
     "tuber_dwconv_fwd": "depthwise Conv3d(C,C,3,groups=C,stride=(st,ss,ss),padding=1) on NDHWC bf16, ResNeXtBottleneck.conv3 "
