@@ -14,8 +14,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=fast", "-Wno-unused-result"]
 # per-source flags, appended (the last -ffp-contract wins).  frame_map.hip and tube_map.hip decide "IoU >= threshold" exactly as the host evaluator does: under
 # -ffp-contract=fast the backend fuses across statements whatever `#pragma clang fp contract(off)` says; under "on" the pragma holds.
-# detect.hip evaluates decode()'s box expressions without contraction for the same reason.
-SOURCE_FLAGS = {"frame_map.hip": ["-ffp-contract=on"], "tube_map.hip": ["-ffp-contract=on"], "detect.hip": ["-ffp-contract=on"]}
+# detect.hip evaluates decode()'s box expressions without contraction for the same reason, tube_crops.hip the fp64 resampling of crops.crop_rows.
+SOURCE_FLAGS = {"frame_map.hip": ["-ffp-contract=on"], "tube_map.hip": ["-ffp-contract=on"], "detect.hip": ["-ffp-contract=on"],
+                "tube_crops.hip": ["-ffp-contract=on"]}
 
 
 def sources():

@@ -173,6 +173,10 @@ def get_cfg_defaults():
         # spatio-temporal IoU with a higher-scored kept tube exceeds IOU is dropped -- before video-mAP in validate_tuber_ucf_detection and in
         # video.VideoDetections.tubes(); ACTORS_IOU: the same, class-agnostic, for video.VideoActors.tracks().  None: off.  0.3 is customary
         TUBE_NMS=dict(IOU=None, ACTORS_IOU=None),
+        # crops of tubes and actor tracks out of the resident video (crops.py / tuber_tube_crops; not reference keys): the defaults of
+        # video.VideoDetections.crops() -- SIZE (h, w) of a crop, SCALE enlarges a box about its centre, SAMPLES: every output pixel is the mean
+        # of SAMPLES x SAMPLES bilinear samples (RoIAlign's sampling_ratio)
+        CROPS=dict(SIZE=[112, 112], SCALE=1.0, SAMPLES=1),
         # both validation loops run the eval forward as a captured hipGraph per input shape (detect.GraphedEval; not a reference key)
         GRAPHED=False), new_allowed=True)
     cfg.DATA = CfgNode(dict(
@@ -241,6 +245,22 @@ def tube_nms_settings(cfg):
             raise ValueError("CONFIG.VAL.TUBE_NMS.%s = %r: must be None or a number in [0, 1]" % (key, v))
         out[key.lower()] = None if v is None else float(v)
     return out
+
+
+def crop_settings(cfg):
+    """CONFIG.VAL.CROPS validated -> dict(size, scale, samples), the defaults of ``VideoDetections.crops``; a bad value raises ValueError naming its key"""
+    c = cfg.CONFIG.VAL.CROPS
+
+    def bad(key, why):
+        raise ValueError("CONFIG.VAL.CROPS.%s = %r: %s" % (key, c[key], why))
+    integer = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    if not isinstance(c.SIZE, (list, tuple)) or len(c.SIZE) != 2 or not all(integer(v) and v >= 1 for v in c.SIZE):
+        bad("SIZE", "must be two integers >= 1 (h, w)")
+    if not isinstance(c.SCALE, (int, float)) or isinstance(c.SCALE, bool) or not 0.0 < c.SCALE < float("inf"):
+        bad("SCALE", "must be a finite number > 0")
+    if not integer(c.SAMPLES) or not 1 <= c.SAMPLES <= 4:
+        bad("SAMPLES", "must be an integer in 1 .. 4")
+    return dict(size=(int(c.SIZE[0]), int(c.SIZE[1])), scale=float(c.SCALE), samples=int(c.SAMPLES))
 
 
 def detect_settings(cfg):

@@ -424,6 +424,28 @@ DOC = {
                         "atomics, plain vector stores. K > tuber_frame_match_max_dets(), K * (max_gap + 1) > tuber_tube_link_max_active(), S * K * G beyond an "
                         "int32, G < 1, K < 1, negative sizes, a null pointer, det_box / dense_box not 16-byte or another pointer not 4-byte aligned: "
                         "TUBER_EINVAL, nothing launched, nothing written. S == 0: 0, no launch.",
+    "tuber_tube_crops": "crops of action tubes and actor tracks out of the resident video (crops.crop_rows: the definition; what RoIAlign with a sampling_ratio does "
+                        "to an image, and torch's grid_sample(mode=bilinear, padding_mode=border, align_corners=False) to within fp64 rounding): row r of a crop "
+                        "table -- frame_index int32 [R], boxes fp32 [R][4] xyxy in source-video pixels, pixel j covering [j, j + 1) -- resampled to h x w out of "
+                        "frames uint8 [N][H][W][3] (packed, at any byte alignment). fx = W / W0, fy = H / H0: the host's fp64 quotients of the frame size by the "
+                        "size the boxes refer to; scale > 0 enlarges a box about its centre; samples = s: an output pixel is the mean of an s x s regular grid of "
+                        "bilinear samples. Per axis, in fp64, every operation rounded on its own: cx = (x1 + x2) * 0.5; bw = (x2 - x1) * scale; X1 = (cx - bw * "
+                        "0.5) * fx; sx = (bw * fx) / double(w * s); sample column c: u = X1 + (c + 0.5) * sx - 0.5 clamped to [0, W - 1] (edge replication; a "
+                        "NaN, which only an overflowing scale gives, to 0), j0 = floor(u), j1 = min(j0 + 1, W - 1), a = u - j0; per channel top = p[i0][j0] + "
+                        "(p[i0][j1] - p[i0][j0]) * a, bot likewise on line i1, val = top + (bot - top) * b; pixel (i, j): acc = 0, then acc = acc + val(i * s + "
+                        "dy, j * s + dx) for dy, for dx; byte = floor(acc / double(s * s) + 0.5): the definition's bytes. lut == NULL: out is uint8 [R][h][w][3] "
+                        "at any byte alignment. lut != NULL: the fp32 [3][256] mean/std table tuber_video_clips reads, and out is fp32 [R][3][h][w] with "
+                        "out[r][ch][i][j] = lut[ch][byte] -- a crop pixel is what a clip pixel of the same byte would be. valid uint8 [R]: 0 at a row whose "
+                        "frame_index lies outside [0, N) or whose box has a coordinate that is not finite; its bytes are 0. x2 < x1 mirrors, a box of no area gives "
+                        "a constant. A workgroup per row and band of output lines (at most 2040 output bytes); the coordinates and weights of the sample columns "
+                        "and lines once in LDS tables; per pass over the sample lines the span of the two source lines each one needs staged into LDS with "
+                        "aligned dword loads; aligned dword stores over the flat output with a byte head and tail per band (16-byte stores in the table form); "
+                        "no atomics, plain vector stores, nothing written outside the R rows and valid. W > tuber_tube_crops_limits(0), h or w > limits(1), "
+                        "samples > limits(2); h, w, samples, H or W below 1; negative N or R; R * bands beyond an int32; fx, fy or scale not finite or not "
+                        "positive; a null pointer; boxes not 16-byte, frame_index, lut or an fp32 out not 4-byte aligned: TUBER_EINVAL, nothing launched, "
+                        "nothing written. R == 0: 0, no launch, the pointers are not inspected.",
+    "tuber_tube_crops_limits": "bounds of tuber_tube_crops: which = 0 the largest frame width W (4096: two staged lines of 3 * W bytes and the column table fit a "
+                               "workgroup's LDS), 1 the largest h or w of a crop (512), 2 the largest samples (4); anything else -1.",
     "tuber_tube_match_max_gt": "ground-truth tubes per (video, class) tuber_tube_match takes (32).",
     "tuber_tube_match_max_thresholds": "thresholds per call tuber_tube_match takes (16).",
     "tuber_detect_ava": "ranked detections of an AVA eval forward in ONE launch (PostProcessAVA, models/criterion.py:447-482, the post-processor models/tuber_ava.py builds; "

@@ -17,6 +17,9 @@ definition and its fallback) and ``VideoStream.tracks()``.
 ``tubes(dense=True)`` / ``tracks(dense=True)`` put a box on every frame of a tube's extent, interpolated between the linked
 key detections: ``tuber_tube_dense`` behind the link step over a whole video (``evaluation.dense_rows`` is its definition and its fallback),
 ``evaluation.dense_tube`` on the host for the closed tubes of a stream.
+
+``VideoDetector(..., keep_video=True)`` leaves the resident video with its result, whose ``crops(tubes)`` cuts the boxes
+of tubes and tracks out of it on the device (``crops.tube_crops`` / ``tuber_tube_crops``; ``crops.crop_rows`` is its definition and its fallback).
 """
 import functools
 import sys
@@ -188,6 +191,8 @@ class VideoDetections(_VideoRecord):
         self.class_num = int(class_num)
         self.tubes_path = None                                                         # "device" or "host" after tubes()
         self.actors = None                                                             # the ``VideoActors`` of ``VideoDetector(..., actors=A)``
+        # ``VideoDetector(..., keep_video=True)``: the resident video uint8 [N, nh, nw, 3], the size (H0, W0) the boxes refer to, CONFIG.VAL.CROPS
+        self.video, self.source_size, self.crop_settings = None, None, None
 
     # -- tubes ------------------------------------------------------------------------------------------------------------
     def _link_device(self, link_iou, max_gap, nms=None, min_len=1, G=None):
@@ -248,6 +253,21 @@ class VideoDetections(_VideoRecord):
                 d = dict(cls=t["cls"], score=t["score"], frames=[self.keys[s] for s in t["frames"]], boxes=t["boxes"], length=len(t["frames"]))
                 out.append(d if rows is None else _densified(d, dense_from_rows(t["rows"], self.keys, K, rows)))
         return out
+
+    # -- crops ------------------------------------------------------------------------------------------------------------
+    def crops(self, tubes, size=None, scale=None, samples=None, normalize=False):
+        """The pixels of ``tubes`` -- the dicts of ``tubes()`` or of ``actors.tracks()``, dense or not -- cut out of the resident video and
+        resampled to ``size``: ``crops.tube_crops(self.video, tubes, ..., source_size=self.source_size)``, a
+        ``crops.TubeCrops`` whose ``[i]`` is tube i's rows, uint8 [F, h, w, 3] on the device (``normalize=True``: fp32 [F, 3, h, w] through the
+        clips' mean/std table).  One upload of the crop table, one ``tuber_tube_crops`` launch, no synchronisation.  The boxes are in
+        source-video pixels and the video is held at working resolution: ``source_size`` carries the ratio.  Defaults: ``CONFIG.VAL.CROPS``
+        (SIZE 112 x 112, SCALE 1.0, SAMPLES 1).  Needs ``VideoDetector(..., keep_video=True)``."""
+        from .crops import tube_crops
+        if self.video is None:
+            raise RuntimeError("VideoDetections.crops: the video was not kept: construct VideoDetector(..., keep_video=True)")
+        st = self.crop_settings or dict(size=(112, 112), scale=1.0, samples=1)
+        return tube_crops(self.video, tubes, st["size"] if size is None else size, source_size=self.source_size,
+                          scale=st["scale"] if scale is None else scale, samples=st["samples"] if samples is None else samples, normalize=normalize)
 
 
 class VideoActors(_VideoRecord):
@@ -454,11 +474,16 @@ class VideoDetector(_VideoRunner):
     64 active tubes, MAX_GAP 2) -- so that ``tubes()`` with its defaults links on the device.  ``score_thr`` / ``actor_thr`` / ``graphed``: as
     ``Detector``.  ``actors=A`` (AVA models; default None: off): the ``Detector``'s actor decode as well, its six tensors copied device-to-device
     into the video's store beside the seven; the result carries ``.actors``, a ``VideoActors``, whose ``tracks()`` answers "who is there, from
-    when to when, doing what" (DESIGN.md section 6i)."""
+    when to when, doing what" (DESIGN.md section 6i).  ``keep_video=True`` (default False: off, nothing about a call changes): the result
+    carries ``video``, the resident uint8 [N, nh, nw, 3] tensor the call builds anyway, and ``source_size = (H0, W0)``, and its
+    ``crops(tubes)`` cuts tubes and actor tracks out of it on the device.  The cost: the resident video -- 134 MB for
+    512 frames of 256 x 340 -- stays allocated for as long as the result is alive instead of being freed when the call returns."""
 
-    def __init__(self, cfg, model, batch=2, score_thr=None, topk=None, actor_thr=None, graphed=True, rule=None, actors=None):
-        from .config import tube_nms_settings
+    def __init__(self, cfg, model, batch=2, score_thr=None, topk=None, actor_thr=None, graphed=True, rule=None, actors=None, keep_video=False):
+        from .config import crop_settings, tube_nms_settings
         self.nms = tube_nms_settings(cfg)                  # the defaults of tubes(nms=) / tracks(nms=): kept out of ``settings``
+        self.keep_video = bool(keep_video)
+        self.crop_settings = crop_settings(cfg)            # the defaults of VideoDetections.crops()
         if int(batch) < 1:
             raise ValueError("VideoDetector: batch = %r must be >= 1" % (batch,))
         super().__init__(cfg, model, batch, score_thr, topk, actor_thr, graphed, rule, actors)
@@ -494,6 +519,8 @@ class VideoDetector(_VideoRunner):
         if stores[1] is not None:
             vd.actors = VideoActors(keys, *[t[:n] for t in stores[1]], settings=self.actor_settings, store=store, nms_iou=self.nms["actors_iou"],
                                     dense=self.dense)
+        if self.keep_video:
+            vd.video, vd.source_size, vd.crop_settings = resident, (H0, W0), self.crop_settings
         return vd
 
 
@@ -622,7 +649,11 @@ class VideoStream(_VideoRunner):
 
     Dense tubes (``tubes(dense=True)`` / ``tracks(dense=True)``, default ``CONFIG.VAL.VIDEO_MAP.DENSE``) ARE part of the
     stream: a closed tube never changes, so a box on every frame of its extent is filled in on the host where the tube is assembled
-    (``evaluation.dense_tube``) and equals ``VideoDetector``'s, bit for bit."""
+    (``evaluation.dense_tube``) and equals ``VideoDetector``'s, bit for bit.
+
+    Crops (``VideoDetector(..., keep_video=True)``) are not part of the stream and it takes no ``keep_video``: the ring
+    holds only the recent frames, so the pixels of a tube are gone by the time it closes.  ``crops.tube_crops`` over frames the caller kept
+    does the same work."""
 
     def __init__(self, cfg, model, batch=2, stride=None, rule=None, max_chunk=64, score_thr=None, topk=None, actor_thr=None, graphed=True,
                  link=True, actors=None):
