@@ -179,3 +179,65 @@ def test_postprocess_forward_is_decode_copied_to_numpy():
         assert np.array_equal(np.ascontiguousarray(d.numpy()).view(np.int32), np.ascontiguousarray(f).view(np.int32))
     want = torch.softmax(out["pred_logits"], -1).numpy()
     assert np.array_equal(fwd[0].view(np.int32), want.view(np.int32))
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# the ranking step both device evaluators share (device_map.rank_by_class), on CPU tensors against the rule stated in numpy
+# ------------------------------------------------------------------------------------------------------------------------------
+def _rank_rule(score, cls, counted, C):
+    """per bucket the rows by descending score, NaN last, equal scores in input order; rows that are not counted: bucket C"""
+    bucket = np.where(counted, np.clip(cls, 0, C), C)
+    perm, pos = [], []
+    for b in range(C + 1):
+        rows = np.nonzero(bucket == b)[0]
+        key = np.where(np.isnan(score[rows]), -np.inf, score[rows])
+        rows = rows[np.argsort(-key, kind="stable")]
+        perm.extend(rows.tolist())
+        pos.extend(range(len(rows)))
+    perm = np.asarray(perm, dtype=np.int64)
+    return np.where(np.isnan(score[perm]), -np.inf, score[perm]), bucket[perm], perm, np.asarray(pos, dtype=np.int64)
+
+
+def _rank_case(N, C=3):
+    """N rows over C classes with class 1 empty: scores in tenths (ties inside a class and across classes), two NaNs, some rows not counted"""
+    rng = np.random.default_rng(40 + N)
+    score = (rng.integers(1, 8, N) / 10.0).astype(np.float64)
+    cls = rng.choice([0, 2], N).astype(np.int64)
+    counted = rng.random(N) < 0.8
+    if N >= 40:
+        score[[3, 17]] = np.nan
+        cls[3] = cls[17] = 2
+        score[[30, 5, 9]], cls[[30, 5, 9]] = 0.75, 0                   # three equal scores no other row has: input order 5, 9, 30
+        counted[[3, 5, 9, 17, 30]] = True
+        counted[11] = False
+    return score, cls, counted
+
+
+@pytest.mark.parametrize("N", [0, 1, 40])
+@pytest.mark.parametrize("dtype", [torch.float32, torch.float64])
+def test_rank_by_class_is_the_stated_rule_on_cpu_tensors(N, dtype):
+    from tubelet_transformer_amd.device_map import bucket_tie_counts, rank_by_class
+    C = 3
+    score, cls, counted = _rank_case(N)
+    score = score.astype(np.float32 if dtype == torch.float32 else np.float64)
+    t_score = torch.from_numpy(score.copy())
+    ranked, bucket, perm, pos = rank_by_class(t_score, torch.from_numpy(cls), torch.from_numpy(counted), C)
+    assert np.array_equal(t_score.numpy(), score, equal_nan=True)            # the caller's scores are left alone
+    want = _rank_rule(score, cls, counted, C)
+    for got, w in zip((ranked, bucket, perm, pos), want):
+        assert got.shape == (N,) and np.array_equal(got.numpy(), w), (got, w)
+    assert perm.dtype == pos.dtype == bucket.dtype == torch.int64
+    if N == 40:
+        b, p = bucket.numpy(), perm.numpy()
+        assert (b == 1).sum() == 0 and (b == C).sum() == (~counted).sum() >= 2
+        assert p[b == 2][-2:].tolist() == [3, 17]                            # the NaNs close their class, in input order
+        at = {int(r): int(x) for r, x in zip(p, pos.numpy())}
+        assert (at[5], at[9], at[30]) == (0, 1, 2)                           # equal scores keep input order
+        for c in range(C + 1):
+            assert pos.numpy()[b == c].tolist() == list(range(int((b == c).sum())))
+    # the tie count beside it: rows that share their score with a neighbour of their bucket
+    ties = bucket_tie_counts(ranked, bucket, C).numpy()
+    r, b = ranked.numpy(), bucket.numpy()
+    for c in range(C + 1):
+        _, counts = np.unique(r[b == c], return_counts=True)
+        assert ties[c] == counts[counts > 1].sum(), c

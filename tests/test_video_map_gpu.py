@@ -13,11 +13,12 @@ import numpy as np
 import pytest
 import torch
 
+from test_tube_nms_cpu import BOX, FAR, planted, record, shifted, span
 from test_video_map_cpu import _bits, _case_evaluator, _same_results, _store
 from tubelet_transformer_amd import device_map, lib, synth
 from tubelet_transformer_amd.config import load_cfg, video_map_settings
 from tubelet_transformer_amd.device_map import DeviceFrameMAPUCF, DeviceVideoMAP
-from tubelet_transformer_amd.evaluation import VIDEO_MAP_RANGE, VideoMAP, validate_tuber_ucf_detection
+from tubelet_transformer_amd.evaluation import VIDEO_MAP_RANGE, VideoMAP, tubes_from_link, validate_tuber_ucf_detection
 from tubelet_transformer_amd.tuber import build_model
 
 pytestmark = pytest.mark.gpu
@@ -268,6 +269,94 @@ def test_tube_link_and_match_at_the_active_tube_bound(dev):
     assert per_slot.tolist() == [64, 64, 5] and (got["row_cls"] == 1).all() and (got["row_head"] >= 0).all()
     lens = got["tube_len"][got["row_head"] == np.arange(len(got["row_head"]))]
     assert (lens >= 2).sum() >= 32 and (lens == 1).sum() >= 1 and (flags[0.2] == 1).sum() >= 1
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# link records made by hand (tests/test_tube_nms_cpu.py ``record``): what no linker writes
+# ------------------------------------------------------------------------------------------------------------------------------
+def _with_ground_truth(rec, gts, C, slots, thresholds):
+    """``rec`` completed to what ``VideoMAP.match`` and ``_operands`` read, with the ground-truth tubes ``gts`` = [(video, class, id, {slot in
+    the video: box})] -> the evaluator that holds them"""
+    ev = VideoMAP(class_num=C, min_len=1, thresholds=thresholds)
+    rows = [(v, s, c, i, b) for v, c, i, boxes in gts for s, b in boxes.items()]
+    ev.add_ground_truth(["v%d-%d" % (v, s) for v, s, _, _, _ in rows], [r[4] for r in rows], [r[2] for r in rows], [r[3] for r in rows])
+    rec["layout"]["gt_slot"] = np.asarray([v * slots + s for v, s, _, _, _ in rows], dtype=np.int64)
+    rec["det_prob"] = np.zeros((len(rec["row_head"]), C + 1), np.float32)
+    rec["tubes"] = tubes_from_link(rec)
+    return ev
+
+
+def _match_record(o, rec, C, thresholds, dev, max_rows=None):
+    """``tuber_tube_match`` over the host record ``rec`` with the operands ``o`` -> (tube_flag [T, N], work) read back; both start from a pattern"""
+    T, N, i32 = len(thresholds), o["N"], np.int32
+    up = lambda a, dt: torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=dt))).to(dev)
+    flags = torch.full((T, N), 77, dtype=torch.uint8, device=dev)
+    work = torch.full((N * max(o["max_gt_tubes"], 1),), 12345.0, dtype=torch.float64, device=dev)
+    lib.call("tuber_tube_match", o["det_box"], o["slot_off"], o["video_off"], up(rec["row_cls"], i32), up(rec["row_head"], i32),
+             up(rec["tube_score"], np.float64), up(rec["tube_len"], i32), up(rec["tube_last"], i32), o["gt_box"], o["gt_cls"], o["gt_tube"], o["gt_off"],
+             torch.tensor(thresholds, dtype=torch.float64, device=dev), o["V"], o["S"], N, o["G"], C, T, o["max_rows"] if max_rows is None else max_rows,
+             o["max_gt_rows"], o["max_gt_tubes"], 1, work, flags)
+    return flags.cpu().numpy(), work.cpu().numpy().reshape(N, -1)
+
+
+def test_more_live_tubes_than_lanes_are_flagged_not_decided(dev):
+    """tests/test_tube_nms_gpu.py's record of the same name, matched: 33 one-row heads in slot 0 and 33 in slot 1 of class 0, every one with
+    tube_last = 5, are 66 tubes live at slot 1 with max_rows = 33.  No link inside the linker's bounds looks like this; the kernel answers with
+    byte 3 in every threshold plane and decides the video's other class as usual."""
+    thresholds = (0.2, 0.5)
+    grid = lambda i: (50.0 * (i % 8), 80.0 * (i // 8), 50.0 * (i % 8) + 40, 80.0 * (i // 8) + 60)
+    tubes = [(0, 0, 0.5, {s: grid(i)}) for s in (0, 1) for i in range(33)]
+    tubes += [(0, 1, 0.9, span(BOX, 2, 5)), (0, 1, 0.8, span(shifted(BOX, 2.0), 2, 5)), (0, 1, 0.7, span(FAR, 2, 5))]
+    rec, heads = record(tubes, 1, 6)
+    rec["tube_last"][heads[:66]] = 5
+    ev = _with_ground_truth(rec, [(0, 0, 0, span(grid(0), 0, 1)), (0, 1, 0, span(BOX, 2, 5))], 2, 6, thresholds)
+    _, want, _ = ev.match(rec)
+    o = _operands(ev, rec, dev)
+    assert o["max_rows"] == 33 and o["N"] == 78
+    got, _ = _match_record(o, rec, 2, thresholds, dev, max_rows=33)
+    rest = np.setdiff1d(np.arange(o["N"]), heads)
+    for i, thr in enumerate(thresholds):
+        assert (got[i][heads[:66]] == 3).all() and (want[thr][heads[:66]] != 2).all()
+        assert got[i][heads[66:]].tolist() == want[thr][heads[66:]].tolist() == [1, 0, 0]
+        assert (got[i][rest] == 2).all()
+
+
+def test_malformed_heads_are_not_counted(dev):
+    """tests/test_tube_nms_gpu.py's plants (a head beyond the record, a head that points forward), and a row of class 1 whose head is the
+    head row of a class-0 tube of its video: the flags are those of the record with these rows and their followers at head -1, and no
+    `work` row is written that the cleaned record leaves alone -- a head of another class is another wave's row."""
+    rec, where = planted()
+    N = len(rec["row_head"])
+    beyond, forward, other = where["vid_a"], where["cls_b"], where["cls_a"]
+    crossed = int(np.nonzero(rec["row_head"] == forward)[0][-1])            # the last row of cls_b: class 1, video 2
+    assert rec["row_cls"][crossed] == 1 and rec["row_cls"][other] == 0 and other < crossed and rec["row_head"][beyond + 1] == beyond
+    bad = dict(rec, row_head=rec["row_head"].copy(), layout=dict(rec["layout"]))
+    bad["row_head"][beyond] = N + 5
+    bad["row_head"][forward] = forward + 1
+    bad["row_head"][crossed] = other
+    clean = dict(rec, row_head=rec["row_head"].copy(), layout=dict(rec["layout"]))
+    for h in (beyond, forward):
+        clean["row_head"][rec["row_head"] == h] = -1
+    near = shifted(BOX, 2.0)
+    gts = [(0, 1, 0, span(BOX, 0, 3)), (2, 0, 0, span(BOX, 0, 3)), (2, 1, 0, span(near, 0, 3)), (3, 0, 0, span(BOX, 0, 3)), (5, 0, 4, span(BOX, 0, 5)),
+           (6, 2, 0, span(BOX, 0, 3)), (6, 2, 1, span(shifted(BOX, 24.0), 0, 3)), (7, 1, 0, span(BOX, 0, 5))]
+    ev = _with_ground_truth(clean, gts, 3, 8, THRESHOLDS)
+    _, want, _ = ev.match(clean)
+    assert min(abs(x - t) for row in ev.st_iou(clean)[1].values() for x in row.values() for t in THRESHOLDS) > 1e-9    # no decision on an edge
+    assert all(want[t][beyond] == want[t][forward] == 2 for t in THRESHOLDS) and (want[0.5] == 1).sum() >= 5 and (want[0.5] == 0).sum() >= 3
+    o = _operands(ev, clean, dev)
+    assert o["max_gt_tubes"] == 2
+    clean_flags, clean_work = _match_record(o, clean, 3, THRESHOLDS, dev)
+    for i, thr in enumerate(THRESHOLDS):
+        assert np.array_equal(clean_flags[i], want[thr]), thr
+    bad_flags, bad_work = _match_record(o, bad, 3, THRESHOLDS, dev)
+    assert np.array_equal(bad_flags, clean_flags), np.argwhere(bad_flags != clean_flags)[:10]
+    heads = np.nonzero(clean["row_head"] == np.arange(N))[0]
+    assert (clean_work[other] != 12345.0).all() and (clean_work[np.setdiff1d(np.arange(N), heads)] == 12345.0).all()
+    for c in range(3):                                                       # the rows of the heads of every class, the other classes' among them
+        rows = heads[clean["row_cls"][heads] == c]
+        assert np.array_equal(bad_work[rows].view(np.int64), clean_work[rows].view(np.int64)), c
+    assert np.array_equal(bad_work.view(np.int64), clean_work.view(np.int64))
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -6,16 +6,16 @@
 //                           (mean score, head), the pick of a tube a wave arg-max over the order keys of the rows it may take.
 //                           Its STREAM form (tuber_tube_link_stream, video.VideoStream) links one video whose slots arrive in pieces: the
 //                           lanes are loaded from and stored to a caller-owned state around the walk.
-//   2. tube_match_kernel    a wave per (video, class): walks the slots again with the live tubes in lanes and adds the per-slot IoU against the
-//                           ground-truth boxes of the class into a [64][32] table (tube lane x ground-truth tube), writes a tube's spatio-temporal
-//                           IoU row when the tube ends, then visits the counted tubes by descending score and matches them greedily, a lane per
-//                           threshold with its taken set in one 32-bit mask.
+//   2. tube_match_kernel    a wave per (video, class) on the slot walk it shares with step 4 (tube_span .. tube_next_head: the live tubes in
+//                           lanes, then the counted heads by descending score): adds the per-slot IoU against the ground-truth boxes of the class
+//                           into a [64][32] table (tube lane x ground-truth tube), writes a tube's spatio-temporal IoU row when the tube ends, and
+//                           matches the visited tubes greedily, a lane per threshold with its taken set in one 32-bit mask.
 //   3. track_actions_kernel (tuber_track_actions, actor tracks of an AVA video): behind tube_link_kernel run with one class over a [S][A] actor store, a
 //                           workgroup per row averages the action rows of the row's track -- over the whole track at its head, over a window of slots
 //                           at every row -- in fp64, sequentially in slot order.
-//   4. tube_nms_kernel      (tuber_tube_nms, evaluation.tube_nms: the definition) between steps 1 and 2, or behind step 1 over a padded store: a wave
-//                           per (video, class) adds the per-slot IoU of every two live tubes into a [64][64] table, records the pairs above the
-//                           threshold when the first of the two ends, and visits the tubes by descending score: suppressed iff a kept one overlaps.
+//   4. tube_nms_kernel      (tuber_tube_nms, evaluation.tube_nms: the definition) between steps 1 and 2, or behind step 1 over a padded store: step
+//                           2's walk with a [64][64] table of the per-slot IoU of every two live tubes; the pairs above the threshold are recorded
+//                           when the first of the two ends, and a visited tube is suppressed iff a kept one overlaps.
 //   5. tube_dense_kernel    (tuber_tube_dense, evaluation.dense_rows: the definition) behind step 1 (and step 4) over a padded store: a wave per row
 //                           finds the row's successor by one ballot and writes a box and a score for every frame up to it.
 // No floating-point atomics, every sum sequential in slot order: the same input gives the same bits.
@@ -212,6 +212,77 @@ __global__ __launch_bounds__(256) void tube_rows_stream_kernel(int N, int* __res
     row_len[r] = 0;
 }
 
+// The slot walk of tube_match_kernel and tube_nms_kernel, a workgroup of ONE wave per (video, class).  Phase 1 walks the video's slots in order:
+// a lane holds one row of the current slot AND one live tube (head, tube_last, tube_len), whose sums sit in the LDS table row of the lane.
+// Phase 2 visits the class's counted heads by descending score.  The helpers with a ballot or a shuffle are reached by all 64 lanes.
+
+// the slots [s0, s1) and the rows [R0, R1) of video v; false: not a CSR row of these arrays, touch nothing
+__device__ __forceinline__ bool tube_span(const int* __restrict__ video_off, const int* __restrict__ slot_off, int v, int S, int N, int& s0, int& s1,
+                                          int& R0, int& R1) {
+    s0 = video_off[v]; s1 = video_off[v + 1];
+    if (s0 < 0 || s1 < s0 || s1 > S) return false;
+    R0 = slot_off[s0]; R1 = slot_off[s1];
+    return !(R0 < 0 || R1 < R0 || R1 > N);
+}
+
+// the row r of a slot of n rows that this lane holds: its head and box, -1 without a row of class c.  A head is a head row of class c in
+// [R0, r] (the linkers write no other), so the `work` row of a head is this wave's whatever the record holds.
+__device__ __forceinline__ int tube_slot_row(const float* __restrict__ det_box, const int* __restrict__ row_cls, const int* __restrict__ row_head,
+                                             int r, int lane, int n, int c, int R0, float& b0, float& b1, float& b2, float& b3) {
+    int rh = -1;
+    b0 = b1 = b2 = b3 = 0.f;
+    if (lane < n && row_cls[r] == c) {                                            // behind the class two memory round trips: head and box, then the
+        const float* d = det_box + (long)r * 4;                                   // head's row; no branch in between that would chain the loads
+        const int h = row_head[r];
+        const float d0 = d[0], d1 = d[1], d2 = d[2], d3 = d[3];
+        const int hr = h >= R0 && h <= r ? h : r;                                 // a row in bounds whatever h is
+        const bool ok = (hr == h) & (row_cls[hr] == c) & (row_head[hr] == hr);
+        rh = ok ? h : -1;
+        b0 = ok ? d0 : 0.f; b1 = ok ? d1 : 0.f; b2 = ok ? d2 : 0.f; b3 = ok ? d3 : 0.f;
+    }
+    return rh;
+}
+
+// the lane that holds the live tube of head h (wave-uniform); without one the first free lane, `begins` set: the kernel fills the lane and
+// zeroes its tables; -1 when every lane is taken: the (video, class) is beyond the bounds
+__device__ __forceinline__ int tube_lane_of(bool valid, int head, int h, bool& begins) {
+    const unsigned long long tm = __ballot(valid && head == h);
+    begins = !tm;
+    if (tm) return __ffsll((long long)tm) - 1;
+    const unsigned long long fm = ~__ballot(valid);
+    return fm ? __ffsll((long long)fm) - 1 : -1;
+}
+
+// nothing is decided for a (video, class) beyond the bounds: byte 3 at its heads, in each of the `planes` N-strided planes of `flag`
+__device__ __forceinline__ void tube_mark_beyond(const int* __restrict__ row_cls, const int* __restrict__ row_head, int R0, int R1, int c, int lane,
+                                                 unsigned char* __restrict__ flag, int planes, int N) {
+    for (int r = R0 + lane; r < R1; r += 64)
+        if (row_cls[r] == c && row_head[r] == r)
+            for (int i = 0; i < planes; ++i) flag[(long)i * N + r] = TUBE_BEYOND_BOUNDS;
+}
+
+// phase 2's visiting order: the heads of class c in [R0, R1) with tube_len >= min_len by descending tube_ord(score), equal scores by ascending
+// head.  (last_hi, last_lo) is the key of the head visited last, (~0, ~0) before the first one; -> the next head (wave-uniform), -1: done
+__device__ __forceinline__ int tube_next_head(const int* __restrict__ row_cls, const int* __restrict__ row_head, const double* __restrict__ tube_score,
+                                              const int* __restrict__ tube_len, int R0, int R1, int c, int min_len, int lane,
+                                              unsigned long long& last_hi, unsigned long long& last_lo) {
+    unsigned long long best_hi = 0ull, best_lo = 0ull;                            // a real key has lo > 0
+    for (int r = R0 + lane; r < R1; r += 64) {
+        if (row_cls[r] != c || row_head[r] != r || tube_len[r] < min_len) continue;
+        const unsigned long long hi = tube_ord(tube_score[r]), lo = 0xFFFFFFFFull - (unsigned long long)(r - R0);
+        if (!(hi < last_hi || (hi == last_hi && lo < last_lo))) continue;
+        if (hi > best_hi || (hi == best_hi && lo > best_lo)) { best_hi = hi; best_lo = lo; }
+    }
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long oh = __shfl_xor(best_hi, o, 64), ol = __shfl_xor(best_lo, o, 64);
+        if (oh > best_hi || (oh == best_hi && ol > best_lo)) { best_hi = oh; best_lo = ol; }
+    }
+    if (!best_lo) return -1;
+    last_hi = best_hi; last_lo = best_lo;
+    return R0 + (int)(0xFFFFFFFFull - best_lo);
+}
+
 __global__ __launch_bounds__(64) void tube_match_kernel(const float* __restrict__ det_box, const int* __restrict__ slot_off,
                                                         const int* __restrict__ video_off, const int* __restrict__ row_cls,
                                                         const int* __restrict__ row_head, const double* __restrict__ tube_score,
@@ -225,10 +296,10 @@ __global__ __launch_bounds__(64) void tube_match_kernel(const float* __restrict_
     __shared__ int s_glen[TUBE_MAX_GT];                                           // slots of a ground-truth tube; 0: no such tube
     const int lane = threadIdx.x;
     const int v = blockIdx.x / C, c = blockIdx.x % C;
-    const int s0 = video_off[v], s1 = video_off[v + 1];
-    if (s0 < 0 || s1 < s0 || s1 > S) return;
-    const int R0 = slot_off[s0], R1 = slot_off[s1], G0 = gt_off[s0], G1 = gt_off[s1];
-    if (R0 < 0 || R1 < R0 || R1 > N || G0 < 0 || G1 < G0 || G1 > G) return;
+    int s0, s1, R0, R1;
+    if (!tube_span(video_off, slot_off, v, S, N, s0, s1, R0, R1)) return;
+    const int G0 = gt_off[s0], G1 = gt_off[s1];
+    if (G0 < 0 || G1 < G0 || G1 > G) return;
     const int KS = K > 0 ? K : 1;
     if (lane < TUBE_MAX_GT) s_glen[lane] = 0;
     __syncthreads();
@@ -246,17 +317,8 @@ __global__ __launch_bounds__(64) void tube_match_kernel(const float* __restrict_
         if (r0 < R0 || r1 < r0 || r1 > R1 || g0 < G0 || g1 < g0 || g1 > G1) return;
         const int n = r1 - r0, g = g1 - g0;
         if (n > FMAP_MAX_DETS || g > FMAP_MAX_GT) { beyond = true; break; }
-        const int r = r0 + lane;
-        int rh = -1;
-        float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
-        if (lane < n && row_cls[r] == c) {
-            rh = row_head[r];
-            if (rh < R0 || rh > r) rh = -1;
-            if (rh >= 0) {
-                const float* d = det_box + (long)r * 4;
-                b0 = d[0]; b1 = d[1]; b2 = d[2]; b3 = d[3];
-            }
-        }
+        float b0, b1, b2, b3;
+        const int rh = tube_slot_row(det_box, row_cls, row_head, r0 + lane, lane, n, c, R0, b0, b1, b2, b3);
         int gk = -1;
         double q0 = 0.0, q1 = 0.0, q2 = 0.0, q3 = 0.0;
         if (lane < g && gt_cls[g0 + lane] == c) {
@@ -269,14 +331,10 @@ __global__ __launch_bounds__(64) void tube_match_kernel(const float* __restrict_
         for (unsigned long long m = __ballot(rh >= 0); m; m &= m - 1) {
             const int p = __ffsll((long long)m) - 1;
             const int h = __shfl(rh, p, 64);
-            const unsigned long long tm = __ballot(valid && head == h);
-            int t;
-            if (tm) {
-                t = __ffsll((long long)tm) - 1;
-            } else {                                                              // a tube begins: a free lane, its table row zeroed
-                const unsigned long long fm = ~__ballot(valid);
-                if (!fm) { beyond = true; break; }
-                t = __ffsll((long long)fm) - 1;
+            bool begins;
+            const int t = tube_lane_of(valid, head, h, begins);
+            if (t < 0) { beyond = true; break; }
+            if (begins) {                                                         // its table row zeroed
                 if (lane == t) {
                     valid = true;
                     head = h;
@@ -306,36 +364,15 @@ __global__ __launch_bounds__(64) void tube_match_kernel(const float* __restrict_
         }
         __syncthreads();
     }
-    if (beyond) {                                                                 // nothing decided for this (video, class)
-        for (int r = R0 + lane; r < R1; r += 64)
-            if (row_cls[r] == c && row_head[r] == r)
-                for (int i = 0; i < T; ++i) tube_flag[(long)i * N + r] = TUBE_BEYOND_BOUNDS;
-        return;
-    }
+    if (beyond) return tube_mark_beyond(row_cls, row_head, R0, R1, c, lane, tube_flag, T, N);
     __threadfence();
     __syncthreads();
 
-    // phase 2: the counted tubes by descending score (equal scores by ascending head), a lane per threshold
+    // phase 2: a lane per threshold
     const double thr = lane < T ? thresholds[lane] : 0.0;
     unsigned taken = 0u;
     unsigned long long last_hi = ~0ull, last_lo = ~0ull;
-    for (;;) {
-        unsigned long long best_hi = 0ull, best_lo = 0ull;                        // a real key has lo > 0
-        for (int r = R0 + lane; r < R1; r += 64) {
-            if (row_cls[r] != c || row_head[r] != r || tube_len[r] < min_len) continue;
-            const unsigned long long hi = tube_ord(tube_score[r]), lo = 0xFFFFFFFFull - (unsigned long long)(r - R0);
-            if (!(hi < last_hi || (hi == last_hi && lo < last_lo))) continue;
-            if (hi > best_hi || (hi == best_hi && lo > best_lo)) { best_hi = hi; best_lo = lo; }
-        }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long oh = __shfl_xor(best_hi, o, 64), ol = __shfl_xor(best_lo, o, 64);
-            if (oh > best_hi || (oh == best_hi && ol > best_lo)) { best_hi = oh; best_lo = ol; }
-        }
-        if (!best_lo) break;
-        last_hi = best_hi;
-        last_lo = best_lo;
-        const int h = R0 + (int)(0xFFFFFFFFull - best_lo);
+    for (int h; (h = tube_next_head(row_cls, row_head, tube_score, tube_len, R0, R1, c, min_len, lane, last_hi, last_lo)) >= 0;) {
         if (lane < T) {
             int bk = -1;                                                          // the largest overlap among the tubes not taken, the first one
             double bv = 0.0;
@@ -354,14 +391,12 @@ __global__ __launch_bounds__(64) void tube_match_kernel(const float* __restrict_
     }
 }
 
-// Spatio-temporal NMS over the linked tubes (evaluation.tube_nms: the definition; tuber_tube_nms).  A wave per (video, class), tube_match_kernel's
-// tube-against-tube twin.  Phase 1 walks the slots with the live tubes in lanes and adds, per slot, the fp64 IoU of every two rows of the class
-// into a [64][64] table (tube lane x tube lane; a row's lane writes only its own table row); when a tube ends, every pair it forms with a
-// tube that is still live is final, and its lane writes the heads of the partners whose stIoU is above nms_iou into its 64-entry row of
-// `work`.  A pair is thus recorded in the row of the tube that ends first, or in both rows.  Phase 2 visits the tubes of at least min_len
-// detections by descending score (equal scores by ascending head): a tube is suppressed iff a kept tube marked it or a partner in its own
-// row is kept; a kept tube marks the partners in its row.  The status words (2 not visited, 1 kept, 0 suppressed or marked) follow the
-// partner rows in `work`.
+// Spatio-temporal NMS over the linked tubes (evaluation.tube_nms: the definition; tuber_tube_nms): the slot walk above, tube against tube.
+// Phase 1 adds, per slot, the fp64 IoU of every two rows of the class into a [64][64] table (tube lane x tube lane; a row's lane writes only
+// its own table row); when a tube ends, every pair it forms with a tube that is still live is final, and its lane writes the heads of the
+// partners whose stIoU is above nms_iou into its 64-entry row of `work`.  A pair is thus recorded in the row of the tube that ends first, or
+// in both rows.  Phase 2: a visited tube is suppressed iff a kept tube marked it or a partner in its own row is kept; a kept tube marks the
+// partners in its row.  The status words (2 not visited, 1 kept, 0 suppressed or marked) follow the partner rows in `work`.
 #define TNMS_LD 65                // leading dimension of the LDS tables: a lane reads its own row without bank conflicts
 #define TNMS_ROW 64               // partner entries per tube in `work`
 
@@ -378,10 +413,8 @@ __global__ __launch_bounds__(64) void tube_nms_kernel(const float* __restrict__ 
     __shared__ int s_head[TUBE_MAX_ACTIVE], s_len[TUBE_MAX_ACTIVE];               // the tube a lane holds
     const int lane = threadIdx.x;
     const int v = blockIdx.x / C, c = blockIdx.x % C;
-    const int s0 = video_off[v], s1 = video_off[v + 1];
-    if (s0 < 0 || s1 < s0 || s1 > S) return;
-    const int R0 = slot_off[s0], R1 = slot_off[s1];
-    if (R0 < 0 || R1 < R0 || R1 > N) return;
+    int s0, s1, R0, R1;
+    if (!tube_span(video_off, slot_off, v, S, N, s0, s1, R0, R1)) return;
     int* status = work + (long)N * TNMS_ROW;
 
     // phase 1: the partners of every tube of the class
@@ -392,33 +425,17 @@ __global__ __launch_bounds__(64) void tube_nms_kernel(const float* __restrict__ 
         if (r0 < R0 || r1 < r0 || r1 > R1) return;
         const int n = r1 - r0;
         if (n > FMAP_MAX_DETS) { beyond = true; break; }
-        const int r = r0 + lane;
-        int rh = -1, mine = -1;                                                   // the row's head, and the lane that holds its tube
-        float b0 = 0.f, b1 = 0.f, b2 = 0.f, b3 = 0.f;
-        if (lane < n && row_cls[r] == c) {
-            rh = row_head[r];
-            if (rh < R0 || rh > r) rh = -1;
-            if (rh >= 0 && (row_cls[rh] != c || row_head[rh] != rh)) rh = -1;     // a head is a head row of this class: its work row is this wave's
-            if (rh >= 0) {
-                const float* d = det_box + (long)r * 4;
-                b0 = d[0]; b1 = d[1]; b2 = d[2]; b3 = d[3];
-            }
-        }
+        float b0, b1, b2, b3;
+        const int rh = tube_slot_row(det_box, row_cls, row_head, r0 + lane, lane, n, c, R0, b0, b1, b2, b3);
+        int mine = -1;                                                            // the lane that holds the row's tube
         for (unsigned long long m = __ballot(rh >= 0); m; m &= m - 1) {
             const int p = __ffsll((long long)m) - 1;
             const int h = __shfl(rh, p, 64);
-            const unsigned long long tm = __ballot(valid && head == h);
-            int t;
-            if (tm) {
-                t = __ffsll((long long)tm) - 1;
-                if (__shfl(seen, t, 64) == s) {                                   // a second row of one tube in one slot: the first one counts
-                    if (lane == p) rh = -1;
-                    continue;
-                }
-            } else {                                                              // a tube begins: a free lane, its table row and column zeroed
-                const unsigned long long fm = ~__ballot(valid);
-                if (!fm) { beyond = true; break; }
-                t = __ffsll((long long)fm) - 1;
+            bool begins;
+            const int t = tube_lane_of(valid, head, h, begins);
+            if (t < 0) { beyond = true; break; }
+            if (!begins && __shfl(seen, t, 64) == s) continue;                    // a second row of one tube in one slot: the first one counts
+            if (begins) {                                                         // its table row and column zeroed
                 if (lane == t) {
                     valid = true;
                     head = h;
@@ -465,33 +482,13 @@ __global__ __launch_bounds__(64) void tube_nms_kernel(const float* __restrict__ 
         }
         __syncthreads();
     }
-    if (beyond) {                                                                 // nothing decided for this (video, class)
-        for (int r = R0 + lane; r < R1; r += 64)
-            if (row_cls[r] == c && row_head[r] == r) tube_keep[r] = TUBE_BEYOND_BOUNDS;
-        return;
-    }
+    if (beyond) return tube_mark_beyond(row_cls, row_head, R0, R1, c, lane, tube_keep, 1, N);
     __threadfence();
     __syncthreads();
 
-    // phase 2: the counted tubes by descending score (equal scores by ascending head)
+    // phase 2
     unsigned long long last_hi = ~0ull, last_lo = ~0ull;
-    for (;;) {
-        unsigned long long best_hi = 0ull, best_lo = 0ull;                        // a real key has lo > 0
-        for (int r = R0 + lane; r < R1; r += 64) {
-            if (row_cls[r] != c || row_head[r] != r || tube_len[r] < min_len) continue;
-            const unsigned long long hi = tube_ord(tube_score[r]), lo = 0xFFFFFFFFull - (unsigned long long)(r - R0);
-            if (!(hi < last_hi || (hi == last_hi && lo < last_lo))) continue;
-            if (hi > best_hi || (hi == best_hi && lo > best_lo)) { best_hi = hi; best_lo = lo; }
-        }
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const unsigned long long oh = __shfl_xor(best_hi, o, 64), ol = __shfl_xor(best_lo, o, 64);
-            if (oh > best_hi || (oh == best_hi && ol > best_lo)) { best_hi = oh; best_lo = ol; }
-        }
-        if (!best_lo) break;
-        last_hi = best_hi;
-        last_lo = best_lo;
-        const int h = R0 + (int)(0xFFFFFFFFull - best_lo);
+    for (int h; (h = tube_next_head(row_cls, row_head, tube_score, tube_len, R0, R1, c, min_len, lane, last_hi, last_lo)) >= 0;) {
         // read at device scope: the words were written by other lanes of this wave, and a neighbouring workgroup on this CU may have pulled
         // their cache lines into the vector L1 before that (tube_match_kernel's work rows)
         const int p = tnms_get(work + (long)h * TNMS_ROW + lane);
@@ -592,9 +589,9 @@ __global__ __launch_bounds__(64 * TDENSE_WAVES) void tube_dense_kernel(const flo
 #define TRACK_THREADS 256
 #define TRACK_MAX_C 4096          // classes of an action row
 
-// the position in slot t of the row whose head is h, -1 when the slot has none (wave-uniform)
-__device__ __forceinline__ int track_member(const int* __restrict__ row_head, int t, int A, int h, int lane) {
-    const unsigned long long m = __ballot(lane < A && row_head[t * A + lane] == h);
+// the position, in the slot whose A heads are `heads`, of the row whose head is h; -1 when the slot has none (wave-uniform; both track kernels)
+__device__ __forceinline__ int tube_member(const int* heads, int A, int h, int lane) {
+    const unsigned long long m = __ballot(lane < A && heads[lane] == h);
     return m ? __ffsll((long long)m) - 1 : -1;
 }
 
@@ -623,7 +620,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_actions_kernel(const floa
             double sum = 0.0;
             int n = 0;
             for (int t = lo; t <= hi; ++t) {
-                const int a = track_member(row_head, t, A, h, lane);
+                const int a = tube_member(row_head + t * A, A, h, lane);
                 if (a < 0) continue;
                 ++n;
                 if (live) sum += (double)actions[((long)t * A + a) * C + c];
@@ -633,7 +630,7 @@ __global__ __launch_bounds__(TRACK_THREADS) void track_actions_kernel(const floa
                 double tot = 0.0;
                 int len = 0;
                 for (int t = s; t <= last; ++t) {
-                    const int a = track_member(row_head, t, A, h, lane);
+                    const int a = tube_member(row_head + t * A, A, h, lane);
                     if (a < 0) continue;
                     ++len;
                     if (live) {
@@ -676,12 +673,6 @@ __host__ __device__ inline long tstream_wave_bytes(int entries) {
     return tstream_record_bytes(entries) + (long)entries * TSTREAM_COLS * 16;
 }
 
-// the position in ring entry e of the row whose head is h, -1 when the slot has none (wave-uniform)
-__device__ __forceinline__ int tstream_member(const int* s_head, int e, int A, int h, int lane) {
-    const unsigned long long m = __ballot(lane < A && s_head[e * A + lane] == h);
-    return m ? __ffsll((long long)m) - 1 : -1;
-}
-
 __global__ __launch_bounds__(64) void track_actions_stream_kernel(const float* __restrict__ actions, const int* __restrict__ row_head, int S,
                                                                   int A, int C, int slot_base, int max_gap, int window, int flush, int H,
                                                                   unsigned char* __restrict__ state, double* __restrict__ row_mean,
@@ -717,7 +708,7 @@ __global__ __launch_bounds__(64) void track_actions_stream_kernel(const float* _
                 n = 0;
                 for (int u = first; u <= last; ++u) {
                     const int e = u % H;
-                    const int j = tstream_member(s_head, e, A, h, lane);
+                    const int j = tube_member(s_head + e * A, A, h, lane);
                     if (j < 0) continue;
                     ++n;
                     if (live) sum += (double)g_act[(long)(e * A + j) * TSTREAM_COLS + lane];
@@ -750,7 +741,7 @@ __global__ __launch_bounds__(64) void track_actions_stream_kernel(const float* _
             }
             int pe = -1, pa = -1;                                                 // the predecessor: the same head at most max_gap + 1 slots back
             for (int t = s - 1; t >= 0 && t >= s - max_gap - 1; --t) {
-                pa = tstream_member(s_head, t % H, A, h, lane);
+                pa = tube_member(s_head + (t % H) * A, A, h, lane);
                 if (pa >= 0) { pe = t % H; break; }
             }
             int len = 1;
@@ -788,6 +779,18 @@ __global__ __launch_bounds__(64) void track_actions_stream_kernel(const float* _
     }
 }
 
+// `rows` rows per slot with max_gap: every tube that can be active at one slot finds a lane
+static bool tube_active_fit(long rows, long max_gap) { return rows * (max_gap + 1) <= TUBE_MAX_ACTIVE; }
+
+// the size and bound arguments of tuber_tube_link and tuber_tube_link_ranked: TUBER_EINVAL, TUBER_OK for nothing to link, 1 to go on (with the pointers)
+static int tube_link_sizes(int V, int S, int N, int C, int max_rows, double link_iou, int max_gap) {
+    if (V < 0 || S < 0 || N < 0 || C <= 0 || max_rows < 0 || max_gap < 0 || !(link_iou == link_iou)) return TUBER_EINVAL;
+    if (max_rows > FMAP_MAX_DETS || !tube_active_fit(max_rows, max_gap)) return TUBER_EINVAL;
+    if ((long)N > (long)S * max_rows || S < V) return TUBER_EINVAL;
+    if (N == 0) return TUBER_OK;
+    return (long)V * C > 0x7FFFFFFFl ? TUBER_EINVAL : 1;
+}
+
 extern "C" {
 
 // tuber_track_actions for ONE video whose key frames arrive in pieces (evaluation.ActorTracker: the definition; video.VideoStream(actors=A)).
@@ -804,7 +807,7 @@ int tuber_track_actions_stream(const float* actions, const int* row_head, int S,
                                void* state, double* row_mean, float* row_peak, double* smooth, hipStream_t stream) {
     if (S < 0 || A < 1 || C < 1 || slot_base < 0 || max_gap < 0 || window < 0 || flush < 0) return TUBER_EINVAL;
     if (A > TUBE_MAX_ACTIVE || C > TRACK_MAX_C || window > TSTREAM_MAX_WINDOW) return TUBER_EINVAL;
-    if ((long)A * ((long)max_gap + 1) > TUBE_MAX_ACTIVE || ((long)slot_base + S) * A > 0x7FFFFFFFl) return TUBER_EINVAL;
+    if (!tube_active_fit(A, max_gap) || ((long)slot_base + S) * A > 0x7FFFFFFFl) return TUBER_EINVAL;
     const int H = tstream_slots(max_gap, window);
     if ((long)H * A > TSTREAM_MAX_ENTRIES) return TUBER_EINVAL;                   // cannot happen within the bounds above
     if (!state || ((uintptr_t)state & 15)) return TUBER_EINVAL;
@@ -822,7 +825,7 @@ int tuber_track_actions_stream(const float* actions, const int* row_head, int S,
 // action) columns, H = max(2 * window, max_gap + 1) + 1; 0 for arguments outside the bounds
 long tuber_track_stream_state_bytes(int A, int C, int max_gap, int window) {
     if (A < 1 || C < 1 || max_gap < 0 || window < 0 || A > TUBE_MAX_ACTIVE || C > TRACK_MAX_C || window > TSTREAM_MAX_WINDOW) return 0;
-    if ((long)A * ((long)max_gap + 1) > TUBE_MAX_ACTIVE) return 0;
+    if (!tube_active_fit(A, max_gap)) return 0;
     const long entries = (long)tstream_slots(max_gap, window) * A;
     if (entries > TSTREAM_MAX_ENTRIES) return 0;
     return (long)((C + TSTREAM_COLS - 1) / TSTREAM_COLS) * tstream_wave_bytes((int)entries);
@@ -858,11 +861,8 @@ int tuber_track_actions_limits(int which) { return which == 0 ? TUBE_MAX_ACTIVE 
 int tuber_tube_link(const float* det_box, const float* det_prob, const int* slot_off, const int* video_off, int V, int S, int N, int C, int max_rows,
                     double link_iou, int max_gap, int* row_cls, int* row_head, double* tube_score, int* tube_len, int* tube_last,
                     hipStream_t stream) {
-    if (V < 0 || S < 0 || N < 0 || C <= 0 || max_rows < 0 || max_gap < 0 || !(link_iou == link_iou)) return TUBER_EINVAL;
-    if (max_rows > FMAP_MAX_DETS || (long)max_rows * ((long)max_gap + 1) > TUBE_MAX_ACTIVE) return TUBER_EINVAL;
-    if ((long)N > (long)S * max_rows || S < V) return TUBER_EINVAL;
-    if (N == 0) return TUBER_OK;
-    if ((long)V * C > 0x7FFFFFFFl) return TUBER_EINVAL;
+    const int rc = tube_link_sizes(V, S, N, C, max_rows, link_iou, max_gap);
+    if (rc != 1) return rc;
     if (!det_box || !det_prob || !slot_off || !video_off || !row_cls || !row_head || !tube_score || !tube_len || !tube_last) return TUBER_EINVAL;
     hipLaunchKernelGGL(tube_rows_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, det_prob, N, C, row_cls, row_head);
     const long waves = (long)V * C;
@@ -878,11 +878,8 @@ int tuber_tube_link(const float* det_box, const float* det_prob, const int* slot
 int tuber_tube_link_ranked(const float* det_box, const int* det_label, const float* det_score, const int* slot_off, const int* video_off, int V, int S,
                            int N, int C, int max_rows, double link_iou, int max_gap, int* row_cls, int* row_head, double* tube_score, int* tube_len,
                            int* tube_last, hipStream_t stream) {
-    if (V < 0 || S < 0 || N < 0 || C <= 0 || max_rows < 0 || max_gap < 0 || !(link_iou == link_iou)) return TUBER_EINVAL;
-    if (max_rows > FMAP_MAX_DETS || (long)max_rows * ((long)max_gap + 1) > TUBE_MAX_ACTIVE) return TUBER_EINVAL;
-    if ((long)N > (long)S * max_rows || S < V) return TUBER_EINVAL;
-    if (N == 0) return TUBER_OK;
-    if ((long)V * C > 0x7FFFFFFFl) return TUBER_EINVAL;
+    const int rc = tube_link_sizes(V, S, N, C, max_rows, link_iou, max_gap);
+    if (rc != 1) return rc;
     if (!det_box || !det_label || !det_score || !slot_off || !video_off || !row_cls || !row_head || !tube_score || !tube_len || !tube_last)
         return TUBER_EINVAL;
     hipLaunchKernelGGL(tube_rows_ranked_kernel, dim3((N + 255) / 256), dim3(256), 0, stream, det_label, N, C, row_cls, row_head);
@@ -904,7 +901,7 @@ int tuber_tube_link_max_active() { return TUBE_MAX_ACTIVE; }
 int tuber_tube_link_stream(const float* det_box, const int* det_label, const float* det_score, int S, int K, int slot_base, int C, double link_iou,
                            int max_gap, void* state, int* row_head, double* row_score, int* row_len, hipStream_t stream) {
     if (S < 0 || K <= 0 || slot_base < 0 || C <= 0 || max_gap < 0 || !(link_iou == link_iou)) return TUBER_EINVAL;
-    if (K > FMAP_MAX_DETS || (long)K * ((long)max_gap + 1) > TUBE_MAX_ACTIVE) return TUBER_EINVAL;
+    if (K > FMAP_MAX_DETS || !tube_active_fit(K, max_gap)) return TUBER_EINVAL;
     if (((long)slot_base + S) * K > 0x7FFFFFFFl || (long)C * 64 * TUBE_STATE_LANE_BYTES > 0x7FFFFFFFl) return TUBER_EINVAL;
     if (!state || ((uintptr_t)state & 15)) return TUBER_EINVAL;
     if (S == 0) return TUBER_OK;
@@ -983,7 +980,7 @@ long tuber_tube_nms_work_bytes(long N) { return N > 0 ? (N * (TNMS_ROW + 1) * 4 
 int tuber_tube_dense(const float* det_box, const float* det_score, const int* row_head, const int* slot_frame, int S, int K, int max_gap, int G,
                      float* dense_box, float* dense_score, int* row_span, int* row_next, hipStream_t stream) {
     if (S < 0 || K < 1 || max_gap < 0 || G < 1) return TUBER_EINVAL;
-    if (K > FMAP_MAX_DETS || (long)K * ((long)max_gap + 1) > TUBE_MAX_ACTIVE) return TUBER_EINVAL;
+    if (K > FMAP_MAX_DETS || !tube_active_fit(K, max_gap)) return TUBER_EINVAL;
     if ((long)S * K > 0x7FFFFFFFl || (long)S * K * G > 0x7FFFFFFFl) return TUBER_EINVAL;
     if (S == 0) return TUBER_OK;
     if (!det_box || !det_score || !row_head || !slot_frame || !dense_box || !dense_score || !row_span || !row_next) return TUBER_EINVAL;

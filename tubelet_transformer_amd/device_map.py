@@ -23,6 +23,7 @@ video-mAP at several thresholds -- ``evaluation.VideoMAP`` on the device.  With 
 steps (``tuber_tube_nms``; ``evaluation.tube_nms`` is the definition).
 """
 import logging
+import time
 
 import numpy as np
 import torch
@@ -102,16 +103,74 @@ def tube_dense_launch(boxes, scores, row_head, keys, max_gap, G):
     return out
 
 
+# the ranking step of the UCF and the video evaluators (plain torch: CPU tensors as well) and the stage timer of every evaluate*()
+def _nan_last(s):
+    """torch.sort ranks NaN first, np.argsort(-score) last: a NaN score (a broken model) ranks below every number"""
+    return s.masked_fill(s != s, float("-inf"))
+
+
+def rank_by_class(score, cls, counted, C):
+    """Every class's ranking over its counted rows: one stable sort by score (descending, NaN last, equal scores in input order), one by class
+    bucket; a row that is not counted goes to bucket ``C`` (row C of a [C + 1][N] layout, which ``tuber_ranked_ap`` does not read or reads
+    with n_gt 0).  ``score`` [N] float, ``cls`` [N] long, ``counted`` [N] bool -> (ranked scores [N] with -inf for NaN, bucket [N] ascending,
+    perm [N]: the input row at every rank, pos [N]: the rank inside its bucket, from 0)."""
+    bucket = torch.where(counted, cls.clamp(0, C), torch.full_like(cls, C))
+    ranked, by_score = torch.sort(_nan_last(score), descending=True, stable=True)
+    bucket, by_class = torch.sort(bucket[by_score], stable=True)
+    count = torch.zeros(C + 1, dtype=torch.long, device=score.device).scatter_add_(0, bucket, torch.ones_like(bucket))
+    pos = torch.arange(score.shape[0], device=score.device) - (count.cumsum(0) - count)[bucket]
+    return ranked[by_class], bucket, by_score[by_class], pos
+
+
+def bucket_tie_counts(ranked, bucket, C):
+    """rows per bucket [C + 1] that share their score with a neighbour of their bucket in the ranking of ``rank_by_class``"""
+    ties = torch.zeros(C + 1, dtype=torch.long, device=ranked.device)
+    if ranked.shape[0] > 1:
+        eq = (ranked[1:] == ranked[:-1]) & (bucket[1:] == bucket[:-1])
+        member = torch.zeros(ranked.shape[0], dtype=torch.bool, device=ranked.device)
+        member[1:] |= eq
+        member[:-1] |= eq
+        ties.scatter_add_(0, bucket, member.long())
+    return ties
+
+
+class _Stages:
+    """the stage timer of an ``evaluate*(timings=)``: with a dict, ``mark(name)`` records a HIP event at the end of stage ``name`` and
+    ``read_back`` leaves ``<name>_ms`` per stage (device time) and ``read_back_ms`` (host time) in it; with None both only do the work"""
+
+    def __init__(self, timings):
+        self.timings, self.marks = timings, []
+        self.mark("start")
+
+    def mark(self, name):
+        if self.timings is not None:
+            e = torch.cuda.Event(enable_timing=True)
+            e.record()
+            self.marks.append((name, e))
+
+    def read_back(self, *tensors):
+        """the tensors as numpy arrays"""
+        if self.timings is not None:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+        out = [t.cpu().numpy() for t in tensors]
+        if self.timings is not None:
+            self.timings["read_back_ms"] = (time.perf_counter() - t0) * 1e3
+            for (_, e0), (name, e1) in zip(self.marks[:-1], self.marks[1:]):
+                self.timings[name + "_ms"] = e0.elapsed_time(e1)
+        return out
+
+
 class DeviceFrameMAP:
     """Arguments as ``evaluation.FrameMAP``; ``device``: where the detection buffers live (a CPU store runs the host evaluator)."""
 
-    def __init__(self, class_num, class_whitelist=None, exclude_keys=(), iou_threshold=0.5, gt_min_score=1e-2, device="cuda"):
+    def __init__(self, class_num, class_whitelist=None, exclude_keys=(), iou_threshold=0.5, gt_min_score=1e-2, device="cuda", widths=None):
         self.class_num, self.iou = int(class_num), float(iou_threshold)
         self.whitelist = set(class_whitelist) if class_whitelist is not None else None
         self.exclude = set(exclude_keys)
         self.gt_min_score = gt_min_score
         self.device = torch.device(device)
-        self._init_store(self.class_num, self.class_num)
+        self._init_store(*(widths or (self.class_num, self.class_num)))
 
     def _init_store(self, score_width, label_width):
         """the empty store: ``score_width`` columns per detection row, ``label_width`` per ground-truth line"""
@@ -263,11 +322,6 @@ class DeviceFrameMAP:
         return ev
 
     @staticmethod
-    def _nan_last(s):
-        """torch.sort ranks NaN first, np.argsort(-score) last: a NaN score (a broken model) ranks below every number"""
-        return s.masked_fill_(s != s, float("-inf"))
-
-    @staticmethod
     def _tie_counts(ranked):
         """rows per class that share their score with a neighbour of the descending ranking [C, N]"""
         if ranked.shape[1] < 2:
@@ -289,7 +343,7 @@ class DeviceFrameMAP:
         ev = self.to_host_evaluator(stable=True)
         mAP, per_class = ev.evaluate()
         s = self.scores.cpu().t().contiguous()
-        ranked = torch.sort(self._nan_last(s), dim=1, descending=True, stable=True).values if s.numel() else s
+        ranked = torch.sort(_nan_last(s), dim=1, descending=True, stable=True).values if s.numel() else s
         ties = self._tie_counts(ranked).numpy()
         self.ties = {c + 1: int(ties[c]) for c in range(self.class_num) if self._wanted(c + 1)}
         return mAP, per_class
@@ -340,19 +394,13 @@ class DeviceFrameMAP:
         the device time of every stage in ms (HIP events) and the host time of the read-back (scripts/device_map_bench.py)."""
         if self.device.type != "cuda":
             return self._evaluate_host()
-        marks = []
-
-        def mark(name):
-            if timings is not None:
-                e = torch.cuda.Event(enable_timing=True)
-                e.record()
-                marks.append((name, e))
-        mark("start")
+        stages = _Stages(timings)
         a = self.device_arrays()
         if self._beyond_bounds(a):
             return self._evaluate_host()
         self.path = "device"
-        return self._evaluate_device(a, mark, marks, timings)
+        stages.mark("frame_sort_and_uploads")
+        return self._finish(*stages.read_back(*self._evaluate_device(a, stages.mark)))
 
     def _beyond_bounds(self, a):
         """a frame the matching kernels do not take: logged once, the store is evaluated on the host"""
@@ -362,13 +410,13 @@ class DeviceFrameMAP:
             return True
         return False
 
-    def _evaluate_device(self, a, mark, marks, timings):
+    def _evaluate_device(self, a, mark):
+        """the device stages behind the layout -> (ap [C] fp64, ties [C]) on the device"""
         C, N = a["C"], a["N"]
-        mark("frame_sort_and_uploads")
         flags = self.match_flags(a)
         mark("tuber_frame_match")
         # every class's ranking: scores descending over all rows, equal scores in store order (NaN last, as np.argsort(-score) has it)
-        ranked, idx = torch.sort(self._nan_last(a["det_score"].t().contiguous()), dim=1, descending=True, stable=True)
+        ranked, idx = torch.sort(_nan_last(a["det_score"].t().contiguous()), dim=1, descending=True, stable=True)
         flags_ranked = flags.t().contiguous().gather(1, idx) if N else torch.empty((C, 0), dtype=torch.uint8, device=self.device)
         mark("rank_sort_and_gather")
         ap = torch.empty(C, dtype=torch.float64, device=self.device)
@@ -377,19 +425,7 @@ class DeviceFrameMAP:
         mark("tuber_ranked_ap")
         ties = self._tie_counts(ranked)
         mark("tie_count")
-        return self._read_back(ap, ties, marks, timings)
-
-    def _read_back(self, ap, ties, marks, timings):
-        if timings is not None:
-            import time
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-        ap, ties = ap.cpu().numpy(), ties.cpu().numpy()
-        if timings is not None:
-            timings["read_back_ms"] = (time.perf_counter() - t0) * 1e3
-            for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
-                timings[name + "_ms"] = e0.elapsed_time(e1)
-        return self._finish(ap, ties)
+        return ap, ties
 
 
 class DeviceFrameMAPUCF(DeviceFrameMAP):
@@ -406,11 +442,9 @@ class DeviceFrameMAPUCF(DeviceFrameMAP):
     TINY = 10                                             # evaluate_ucf.py:60-62
 
     def __init__(self, class_num=24, iou_threshold=0.5, label_width=None, device="cuda"):
-        self.class_num, self.iou = int(class_num), float(iou_threshold)
-        self.whitelist, self.exclude, self.gt_min_score = None, set(), 1e-2
+        super().__init__(class_num, iou_threshold=iou_threshold, device=device,
+                         widths=(int(class_num) + 1, int(label_width) if label_width else max(21, int(class_num))))
         self.num_categories = 24                          # evaluate_ucf.py:15-20
-        self.device = torch.device(device)
-        self._init_store(self.class_num + 1, int(label_width) if label_width else max(21, self.class_num))
 
     def _settings(self):
         return dict(class_num=self.class_num, iou_threshold=self.iou, label_width=self.label_width)
@@ -480,37 +514,23 @@ class DeviceFrameMAPUCF(DeviceFrameMAP):
                  a["F"], a["N"], a["G"], a["C"], self.iou, cls, flag)
         return cls, flag
 
-    def _evaluate_device(self, a, mark, marks, timings):
+    def _evaluate_device(self, a, mark):
         C, N, dev = a["C"], a["N"], self.device
-        mark("frame_sort_and_uploads")
         cls, flag = self.match_flags(a)
         mark("tuber_frame_match_top1")
-        # every class's ranking over its counted rows: one stable sort by score (descending, NaN last), one by class; the rows that are not
-        # counted go to a bucket of their own (row C of the [C + 1][N] layout, which tuber_ranked_ap does not read)
         cls = cls.long()
-        score = self._nan_last(a["det_prob"].gather(1, cls.clamp(0, C)[:, None])[:, 0]) if N else torch.zeros(0, device=dev)
-        bucket = torch.where(flag == 2, torch.full_like(cls, C), cls)
-        ranked, by_score = torch.sort(score, descending=True, stable=True)
-        bucket, by_class = torch.sort(bucket[by_score], stable=True)
-        ranked, flag = ranked[by_class], flag[by_score][by_class]
-        count = torch.zeros(C + 1, dtype=torch.long, device=dev).scatter_add_(0, bucket, torch.ones_like(bucket))
-        pos = torch.arange(N, device=dev) - (count.cumsum(0) - count)[bucket]
+        score = a["det_prob"].gather(1, cls.clamp(0, C)[:, None])[:, 0] if N else torch.zeros(0, device=dev)
+        ranked, bucket, perm, pos = rank_by_class(score, cls, flag != 2, C)
         flags_ranked = torch.full((C + 1, N), 2, dtype=torch.uint8, device=dev)
-        flags_ranked[bucket, pos] = flag
+        flags_ranked[bucket, pos] = flag[perm]
         mark("rank_sort_and_scatter")
         ap = torch.empty(C, dtype=torch.float64, device=dev)
         n_tp = torch.empty(C, dtype=torch.int32, device=dev)
         lib.call("tuber_ranked_ap", flags_ranked, a["n_gt"], C, N, ap, n_tp)
         mark("tuber_ranked_ap")
-        ties = torch.zeros(C + 1, dtype=torch.long, device=dev)
-        if N > 1:
-            eq = (ranked[1:] == ranked[:-1]) & (bucket[1:] == bucket[:-1])
-            member = torch.zeros(N, dtype=torch.bool, device=dev)
-            member[1:] |= eq
-            member[:-1] |= eq
-            ties.scatter_add_(0, bucket, member.long())
+        ties = bucket_tie_counts(ranked, bucket, C)
         mark("tie_count")
-        return self._read_back(ap, ties[:C], marks, timings)
+        return ap, ties[:C]
 
 
 class DeviceVideoMAP(DeviceFrameMAPUCF):
@@ -642,17 +662,15 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
     def tubes(self):
         """the linked tubes read back: a list of dict(video, cls (1-based), score, frames, boxes, head, rows) in head order; with ``tube_nms``
         set, without the suppressed ones"""
-        if self.tube_nms is None:
-            link = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in self.link().items()}
-            return _ev.tubes_from_link(link)
         a = self.video_arrays() if self.device.type == "cuda" else None
         link = self.link(a)
-        on_device = link["row_head"].device.type == "cuda"
-        keep = self.nms(a, link).cpu().numpy() if on_device else None
+        keep = None
+        if self.tube_nms is not None and link["row_head"].device.type == "cuda":
+            keep = self.nms(a, link).cpu().numpy()
         link = {k: (v.cpu().numpy() if torch.is_tensor(v) else v) for k, v in link.items()}
-        if keep is None or (keep == 3).any():
+        if self.tube_nms is not None and (keep is None or (keep == 3).any()):
             keep = _ev.tube_nms(link, self.tube_nms, self.min_len)
-        return [t for t in _ev.tubes_from_link(link) if keep[t["head"]] != 0]
+        return [t for t in _ev.tubes_from_link(link) if keep is None or keep[t["head"]] != 0]
 
     def match_video(self, a, link):
         """``tuber_tube_match`` -> tube_flag [T, N] uint8 on the device (1 true positive, 0 false positive, 2 not counted)"""
@@ -669,14 +687,8 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
         ``timings``: a dict that receives the device time of every stage in ms (HIP events) and the host time of the read-back."""
         if self.device.type != "cuda":
             return self._evaluate_video_host("the store is on the CPU")
-        marks = []
-
-        def mark(name):
-            if timings is not None:
-                e = torch.cuda.Event(enable_timing=True)
-                e.record()
-                marks.append((name, e))
-        mark("start")
+        stages = _Stages(timings)
+        mark = stages.mark
         a = self.video_arrays()
         if a["beyond"]:
             return self._evaluate_video_host(a["beyond"])
@@ -694,16 +706,8 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
             mark("tuber_tube_nms")
         flags = self.match_video(a, link)
         mark("tuber_tube_match")
-        # every class's ranking over its counted tubes, the same for every threshold: one stable sort by score (descending, NaN last), one by
-        # class; rows that are no counted head go to a bucket of their own (row C of every [C + 1][N] slab, with n_gt 0)
-        cls = link["row_cls"].long()
-        score = self._nan_last(link["tube_score"].clone())
-        bucket = torch.where(flags[0] == 2, torch.full_like(cls, C), cls.clamp(0, C)) if N else cls
-        ranked, by_score = torch.sort(score, descending=True, stable=True)
-        bucket, by_class = torch.sort(bucket[by_score], stable=True)
-        perm = by_score[by_class]
-        count = torch.zeros(C + 1, dtype=torch.long, device=dev).scatter_add_(0, bucket, torch.ones_like(bucket))
-        pos = torch.arange(N, device=dev) - (count.cumsum(0) - count)[bucket]
+        # every class's ranking over its counted tubes (rows that are no counted head: bucket C), the same for every threshold
+        _, bucket, perm, pos = rank_by_class(link["tube_score"], link["row_cls"].long(), flags[0] != 2, C)
         flags_ranked = torch.full((T, C + 1, N), 2, dtype=torch.uint8, device=dev)
         if N:
             flags_ranked[:, bucket, pos] = flags[:, perm]
@@ -714,20 +718,12 @@ class DeviceVideoMAP(DeviceFrameMAPUCF):
         if keep is not None:
             ap[-1] = (keep == 3).any()                    # the kernel's escape travels with the APs: no read-back of its own
         mark("tuber_ranked_ap")
-        if timings is not None:
-            import time
-            torch.cuda.synchronize()
-            t0 = time.perf_counter()
-        ap = ap.cpu().numpy()
+        ap, = stages.read_back(ap)
         if keep is not None:
             if ap[-1] != 0.0:
                 return self._evaluate_video_host("more than %d tubes of a (video, class) live at one frame" % lib.query("tuber_tube_link_max_active"))
             ap = ap[:-1]
         ap = ap.reshape(T, C + 1)
-        if timings is not None:
-            timings["read_back_ms"] = (time.perf_counter() - t0) * 1e3
-            for (_, e0), (name, e1) in zip(marks[:-1], marks[1:]):
-                timings[name + "_ms"] = e0.elapsed_time(e1)
         at = {}
         for i, thr in enumerate(a["thr"]):
             per_class = {c + 1: float(ap[i, c]) for c in range(C) if not np.isnan(ap[i, c])}

@@ -482,60 +482,70 @@ def tubes_from_link(link):
     return out
 
 
+def link_slot(tubes, s, cur, score, box64, link_iou, max_gap, base=0):
+    """One slot of the greedy linking of ONE (video, class): the step ``link_rows`` and ``TubeLinker.push`` share, ``tube_link_kernel`` on the
+    host.  ``tubes``: [[head, fp64 score sum, count, last slot, last box fp64], ...]; ``s``: the slot's ordinal; ``cur``: its counted rows of the
+    class, indices into ``score`` (fp32) and ``box64``, ascending.  The tubes whose last detection is at most ``max_gap`` + 1 slots back are
+    visited by descending mean score (fp64 sum of the fp32 scores / count), equal means by ascending head; each takes, among the slot's
+    unclaimed rows whose fp64 IoU with its last box is >= ``link_iou``, the highest score (equal scores: the first row); rows left over start
+    tubes with the head ``base`` + row.  -> (the tubes that survive the slot, {row: the tube that took or began with it}); the records of
+    ``tubes`` are updated in place."""
+    active = [t for t in tubes if s - t[3] <= max_gap + 1]
+    active.sort(key=lambda t: (-(t[1] / t[2]), t[0]))
+    takes = {}
+    for t in active:
+        cand = [r for r in cur if r not in takes]
+        if not cand:
+            break
+        with np.errstate(all="ignore"):
+            iou = _iou_one_to_many(t[4], box64[cand])
+        best = None
+        for r, u in zip(cand, iou):
+            if u >= link_iou and (best is None or score[r] > score[best]):
+                best = r
+        if best is not None:
+            takes[best] = t
+            t[1] += float(score[best]); t[2] += 1; t[3] = s; t[4] = box64[best].copy()
+    for r in cur:
+        if r not in takes:
+            takes[r] = [base + r, float(score[r]), 1, s, box64[r].copy()]
+            active.append(takes[r])
+    return active, takes
+
+
+def _counted_rows(box, cls, score, class_num):
+    """the rows the linkers count: a class inside [0, class_num), a box with x1 < x2 and y1 < y2, a score that is no NaN"""
+    return (cls >= 0) & (cls < class_num) & (box[:, 0] < box[:, 2]) & (box[:, 1] < box[:, 3]) & ~np.isnan(score)
+
+
 def link_rows(box, cls, score, slot, video_off, class_num, link_iou, max_gap):
     """The greedy linking of per-frame detections into tubes, over rows in layout order (video, slot, store order): ``box`` [N, 4] fp32 xyxy,
     ``cls`` [N] the 0-based class of a row, ``score`` [N] fp32, ``slot`` [N] the global slot, ``video_off`` [V + 1] the slots of every video.  A
     row is counted unless its class is outside [0, class_num), its box has x1 >= x2 or y1 >= y2, or its score is NaN.  Per (video, class), slots
-    ascending: the tubes whose last detection is at most ``max_gap`` + 1 slots back are visited by descending mean score (fp64 sum of the fp32
-    scores / count), equal means by ascending head; each takes, among the slot's unclaimed rows whose fp64 IoU with its last box is >=
-    ``link_iou``, the highest score (equal scores: the first row); rows left over start tubes.  -> dict: ``row_head`` (layout row of the tube's
-    first detection, -1 for a row that is not counted) and, at head rows, ``tube_score`` (fp64 mean), ``tube_len``, ``tube_last`` (last slot).
+    ascending, ``link_slot`` links the slot's rows.  -> dict: ``row_head`` (layout row of the tube's first detection, -1 for a row that is not
+    counted) and, at head rows, ``tube_score`` (fp64 mean), ``tube_len``, ``tube_last`` (last slot).
     The body of ``VideoMAP.link``, the definition of ``tuber_tube_link_ranked`` and the fallback of ``video.VideoDetections.tubes``."""
     box = np.asarray(box, dtype=np.float32).reshape(-1, 4)
     cls, score, slot = np.asarray(cls).reshape(-1), np.asarray(score).reshape(-1), np.asarray(slot).reshape(-1)
-    N, C = len(box), int(class_num)
-    counted = (cls >= 0) & (cls < C) & (box[:, 0] < box[:, 2]) & (box[:, 1] < box[:, 3]) & ~np.isnan(score)
+    N = len(box)
     box64 = box.astype(np.float64)
     video = np.searchsorted(np.asarray(video_off), slot, side="right") - 1
     head = np.full(N, -1, dtype=np.int64)
     tscore, tlen, tlast = np.zeros(N), np.zeros(N, dtype=np.int64), np.full(N, -1, dtype=np.int64)
     groups = {}
-    for r in np.nonzero(counted)[0].tolist():
+    for r in np.nonzero(_counted_rows(box, cls, score, int(class_num)))[0].tolist():
         groups.setdefault((int(video[r]), int(cls[r])), []).append(r)
     for rows in groups.values():
-        tubes, i = [], 0                              # a tube: [head, fp64 score sum, count, last slot, last row]
+        tubes, i = [], 0
         while i < len(rows):
             s, j = slot[rows[i]], i
             while j < len(rows) and slot[rows[j]] == s:
                 j += 1
-            cur, i = rows[i:j], j
-            active = [t for t in tubes if s - t[3] <= max_gap + 1]
-            for t in tubes:
-                if s - t[3] > max_gap + 1:
-                    tscore[t[0]], tlen[t[0]], tlast[t[0]] = t[1] / t[2], t[2], t[3]
-            active.sort(key=lambda t: (-(t[1] / t[2]), t[0]))
-            claimed = set()
-            for t in active:
-                cand = [r for r in cur if r not in claimed]
-                if not cand:
-                    break
-                with np.errstate(all="ignore"):
-                    iou = _iou_one_to_many(box64[t[4]], box64[cand])
-                best = None
-                for r, u in zip(cand, iou):
-                    if u >= link_iou and (best is None or score[r] > score[best]):
-                        best = r
-                if best is not None:
-                    claimed.add(best)
-                    head[best] = t[0]
-                    t[1] += float(score[best]); t[2] += 1; t[3] = s; t[4] = best
-            tubes = active
-            for r in cur:
-                if r not in claimed:
-                    head[r] = r
-                    tubes.append([r, float(score[r]), 1, s, r])
-        for t in tubes:
-            tscore[t[0]], tlen[t[0]], tlast[t[0]] = t[1] / t[2], t[2], t[3]
+            tubes, takes = link_slot(tubes, s, rows[i:j], score, box64, link_iou, max_gap)
+            i = j
+            for r, t in takes.items():                # a tube's record at its head is that of its last take
+                head[r] = t[0]
+                tscore[t[0]], tlen[t[0]], tlast[t[0]] = t[1] / t[2], t[2], t[3]
     return dict(row_head=head, tube_score=tscore, tube_len=tlen, tube_last=tlast)
 
 
@@ -758,12 +768,11 @@ class TubeLinker:
             raise ValueError("TubeLinker.push: %d rows per slot after %d" % (K, self.K))
         self.K = K
         base = self.slots * K                         # the global row of this push's row 0
-        counted = (cls >= 0) & (cls < C) & (box[:, 0] < box[:, 2]) & (box[:, 1] < box[:, 3]) & ~np.isnan(score)
         box64 = box.astype(np.float64)
         head = np.full(N, -1, dtype=np.int64)
         rscore, rlen = np.zeros(N), np.zeros(N, dtype=np.int64)
         groups = {}
-        for r in np.nonzero(counted)[0].tolist():
+        for r in np.nonzero(_counted_rows(box, cls, score, C))[0].tolist():
             groups.setdefault(int(cls[r]), []).append(r)
         for c, rows in groups.items():
             tubes, i = self._tubes.get(c, []), 0
@@ -771,31 +780,10 @@ class TubeLinker:
                 s, j = self.slots + rows[i] // K, i
                 while j < len(rows) and self.slots + rows[j] // K == s:
                     j += 1
-                cur, i = rows[i:j], j
-                active = [t for t in tubes if s - t[3] <= self.max_gap + 1]
-                active.sort(key=lambda t: (-(t[1] / t[2]), t[0]))
-                claimed = set()
-                for t in active:
-                    cand = [r for r in cur if r not in claimed]
-                    if not cand:
-                        break
-                    with np.errstate(all="ignore"):
-                        iou = _iou_one_to_many(t[4], box64[cand])
-                    best = None
-                    for r, u in zip(cand, iou):
-                        if u >= self.link_iou and (best is None or score[r] > score[best]):
-                            best = r
-                    if best is not None:
-                        claimed.add(best)
-                        head[best] = t[0]
-                        t[1] += float(score[best]); t[2] += 1; t[3] = s; t[4] = box64[best].copy()
-                        rscore[best], rlen[best] = t[1] / t[2], t[2]
-                tubes = active
-                for r in cur:
-                    if r not in claimed:
-                        head[r] = base + r
-                        tubes.append([base + r, float(score[r]), 1, s, box64[r].copy()])
-                        rscore[r], rlen[r] = float(score[r]), 1
+                tubes, takes = link_slot(tubes, s, rows[i:j], score, box64, self.link_iou, self.max_gap, base)
+                i = j
+                for r, t in takes.items():
+                    head[r], rscore[r], rlen[r] = t[0], t[1] / t[2], t[2]
             self._tubes[c] = tubes
         self.slots += N // K
         return dict(row_head=head, row_score=rscore, row_len=rlen)
