@@ -451,6 +451,92 @@ def test_bn_finalize_and_bwd(dev):
     close("bn eval affine", x * sc2 + sh2, F.batch_norm(x, rm, rv, gamma, beta, False, 0.1, 1e-3), rel=1e-5)
 
 
+@pytest.mark.parametrize("R", [1, 3, 97, 128, 129, 300, 517])
+def test_finalize_kernels_at_every_tail_length(dev, R):
+    """tuber_bn_finalize, tuber_bn_bwd_finalize and tuber_bn_frozen_param_grads over R partial rows, against fp64 torch on the same rows.
+    R = 1, 3: the masked tail alone; 97, 128: main loop + tail of the 256-thread form; 129, 300: the 1024-thread form's tail alone; 517: its
+    main loop + tail.  C = 100 (C % 4 == 0, a partial 32-channel block): the 28 words behind every output keep their sentinel.
+    Tolerances of test_bn_finalize_and_bwd: 1e-5 of the output scale on statistics, 1e-3 on coefficients and gradients."""
+    C, G, eps, mom = 100, 28, 1e-3, 0.1
+    count = 16.0 * R
+    x = rnd(16 * R, C, dev=dev, seed=1, scale=2.0) + 0.5
+    dz = rnd(16 * R, C, dev=dev, seed=2)
+    rows = lambda t: t.view(R, 16, C).sum(1).contiguous()
+    st0, st1, b0, b1 = rows(x), rows(x * x), rows(dz), rows(dz * x)
+    gamma, beta = 1 + 0.1 * rnd(C, dev=dev, seed=3), 0.1 * rnd(C, dev=dev, seed=4)
+    rm0, rv0 = 0.1 * rnd(C, dev=dev, seed=5), 1 + 0.1 * rnd(C, dev=dev, seed=6).abs()
+    dg0, db0 = rnd(C, dev=dev, seed=7), rnd(C, dev=dev, seed=8)
+
+    def guarded(init=None):
+        t = torch.full((C + G,), 7.0, device=dev)
+        t[:C] = float("nan") if init is None else init
+        return t
+
+    def check(name, t, ref, rel):
+        close("%s R=%d" % (name, R), t[:C], ref, rel=rel)
+        assert bool((t[C:] == 7.0).all()), "%s: words behind channel %d written" % (name, C)
+
+    rm, rv = guarded(rm0), guarded(rv0)
+    nbt = torch.full((1,), 41, dtype=torch.int64, device=dev)
+    scale, shift, mean, invstd = (guarded() for _ in range(4))
+    lib.call("tuber_bn_finalize", st0, st1, R, C, count, gamma, beta, rm, rv, nbt, mom, eps, scale, shift, mean, invstd)
+    a, b = st0.double().sum(0), st1.double().sum(0)
+    mu = a / count
+    var = (b / count - mu * mu).clamp_min(0)
+    inv = 1 / torch.sqrt(var + eps)
+    unbiased = var * count / (count - 1)
+    for name, t, ref in (("scale", scale, gamma.double() * inv), ("shift", shift, beta.double() - mu * gamma.double() * inv), ("mean", mean, mu),
+                         ("invstd", invstd, inv), ("running_mean", rm, (1 - mom) * rm0.double() + mom * mu),
+                         ("running_var", rv, (1 - mom) * rv0.double() + mom * unbiased)):
+        check("bn_finalize " + name, t, ref, 1e-5)
+    assert int(nbt) == 42
+    # backward: mean / invstd as the forward published them
+    mu32, r32 = mean[:C].contiguous(), invstd[:C].contiguous()
+    a, b = b0.double().sum(0), b1.double().sum(0)
+    g, mu, r = gamma.double(), mu32.double(), r32.double()
+    xhat = (b - mu * a) * r
+    m1, m2 = a / count, xhat / count
+    cA, cB, cC, dg, db = guarded(), guarded(), guarded(), guarded(dg0), guarded(db0)
+    lib.call("tuber_bn_bwd_finalize", b0, b1, R, C, count, gamma, mu32, r32, cA, cB, cC, dg, db, 1)
+    for name, t, ref in (("cA", cA, g * r), ("cB", cB, -g * r * r * m2), ("cC", cC, g * r * r * m2 * mu - g * r * m1),
+                         ("dgamma", dg, dg0.double() + xhat), ("dbeta", db, db0.double() + a)):
+        check("bn_bwd_finalize " + name, t, ref, 1e-3)
+    nA, nB, nC = guarded(), guarded(), guarded()
+    lib.call("tuber_bn_bwd_finalize", b0, b1, R, C, count, gamma, mu32, r32, nA, nB, nC, None, None, 0)
+    assert torch.equal(nA, cA) and torch.equal(nB, cB) and torch.equal(nC, cC), "coefficients differ without dgamma / dbeta"
+    fg, fb = guarded(dg0), guarded(db0)
+    lib.call("tuber_bn_frozen_param_grads", b0, b1, R, C, mu32, r32, fg, fb)
+    check("bn_frozen_param_grads dgamma", fg, dg0.double() + xhat, 1e-3)
+    check("bn_frozen_param_grads dbeta", fb, db0.double() + a, 1e-3)
+
+
+@pytest.mark.parametrize("M,C", [(37, 64), (5, 2048)])
+@pytest.mark.parametrize("form", ["res", "res_bn", "res32"])
+def test_block_out_fwd_f32_forms(dev, M, C, form):
+    """tuber_block_out_fwd_f32 with the bf16 shortcut alone, with its BatchNorm (rs / rh), and with the fp32 stream (res32), against fp32 torch
+    on the bf16 operands; y is the rounded y32.  (37, 64): 8 threads per row, a ragged last row group; (5, 2048): 256 threads, one row per
+    pass.  y32 is three fp32 roundings of terms no larger than the output scale away from the reference (~2e-7 of it): bound 1e-5.
+    The `res` form also runs tuber_block_out_fwd_mask: y bit-equal to tuber_block_out_fwd's, mask = (y > 0) packed by eight."""
+    c4, res = rnd(M, C, dev=dev, seed=1).to(BF), rnd(M, C, dev=dev, seed=2).to(BF)
+    s4, h4 = 1 + 0.1 * rnd(C, dev=dev, seed=3), 0.1 * rnd(C, dev=dev, seed=4)
+    rs, rh = (1 + 0.1 * rnd(C, dev=dev, seed=5), 0.1 * rnd(C, dev=dev, seed=6)) if form == "res_bn" else (None, None)
+    res32 = rnd(M, C, dev=dev, seed=7) if form == "res32" else None
+    y, y32 = nans(M, C, dev=dev, dtype=BF), nans(M, C, dev=dev)
+    lib.call("tuber_block_out_fwd_f32", c4, s4, h4, res, rs, rh, res32, y, y32, M, C)
+    r = res32 if form == "res32" else (res.float() * rs + rh if form == "res_bn" else res.float())
+    ref = (c4.float() * s4 + h4 + r).relu()
+    close("block_out_fwd_f32 %s y32" % form, y32, ref, rel=1e-5)
+    close("block_out_fwd_f32 %s y" % form, y, ref)
+    assert torch.equal(y, y32.to(BF)), "bf16 output is not the rounded fp32 output"
+    if form == "res":
+        y0, ym = nans(M, C, dev=dev, dtype=BF), nans(M, C, dev=dev, dtype=BF)
+        mk = torch.full((M, C // 8), 0xAA, dtype=torch.uint8, device=dev)
+        lib.call("tuber_block_out_fwd", c4, s4, h4, res, None, None, y0, M, C)
+        lib.call("tuber_block_out_fwd_mask", c4, s4, h4, res, None, None, ym, mk, M, C)
+        close("block_out_fwd y", y0, ref)
+        assert torch.equal(ym, y0) and torch.equal(mk, _bits_of(ym))
+
+
 @pytest.mark.parametrize("M,C,ds", [(3000, 256, False), (700, 2048, True), (5000, 64, True)])
 def test_block_out(dev, M, C, ds):
     c4 = rnd(M, C, dev=dev, seed=1).to(BF)

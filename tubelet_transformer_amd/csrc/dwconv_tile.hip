@@ -14,7 +14,7 @@
 // bn1's partial statistics), weight gradient (27 x 4 accumulators per thread, one partial [27][64] per workgroup).
 #include <cstdlib>
 
-#include "common.h"
+#include "bn_math.h"
 
 typedef float f32x2 __attribute__((ext_vector_type(2)));
 
@@ -58,6 +58,37 @@ struct TileArgs {
     float* fscale; float* fshift; float* fmean; float* finvstd;
     TileGeom g;
 };
+
+// Column sums of a 64-channel strip's partial-statistics rows, after the row fetches: every thread (channel quad tid & 15, row group tid >> 4)
+// hands in its fp64 sums ua / ub of two lists; red [2][32][64] -> red2 [2][4][64] -> threads 0 .. 63 receive the two sums of channel c0 + tid.
+// Two levels (all 512 threads sum 8 row groups each, then 64 threads sum 4): the 32-entry serial fp64 chain of one wave was ~2 us of every
+// workgroup's prologue.  (fp64 sums of fp32 partial rows are exact, so the association does not change the result.)
+// derive (workgroup-uniform): false = nothing is stored or waited for and the sums are 0.  red: 2 * 36 * 64 doubles of LDS.
+__device__ __forceinline__ void strip_reduce(double* red, const double (&ua)[4], const double (&ub)[4], const bool derive, double& sa, double& sb) {
+    const int tid = threadIdx.x;
+    if (derive) {
+        const int q = tid & 15, rg = tid >> 4;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) { red[(0 * 32 + rg) * 64 + q * 4 + e] = ua[e]; red[(1 * 32 + rg) * 64 + q * 4 + e] = ub[e]; }
+    }
+    if (derive) __syncthreads();
+    double* red2 = red + 2 * 32 * 64;                // [2][4][64]
+    if (derive) {
+        const int which = tid >> 8, part = (tid >> 6) & 3, ch = tid & 63;
+        double s = 0.0;
+#pragma unroll
+        for (int k = 0; k < 8; ++k) s += red[(which * 32 + part * 8 + k) * 64 + ch];
+        red2[(which * 4 + part) * 64 + ch] = s;
+    }
+    if (derive) __syncthreads();
+    sa = 0.0; sb = 0.0;
+    if (derive && tid < 64) {
+        sa = (red2[(0 * 4 + 0) * 64 + tid] + red2[(0 * 4 + 1) * 64 + tid]) + (red2[(0 * 4 + 2) * 64 + tid] + red2[(0 * 4 + 3) * 64 + tid]);
+        sb = (red2[(1 * 4 + 0) * 64 + tid] + red2[(1 * 4 + 1) * 64 + tid]) + (red2[(1 * 4 + 2) * 64 + tid] + red2[(1 * 4 + 3) * 64 + tid]);
+    }
+}
+// one fetched partial row into the sums; rows fetched from beyond the list (from its last row) are added as zero
+__device__ __forceinline__ void add4_if(double (&acc)[4], const bool ok, const float4 v) { add4(acc, ok ? v : make_float4(0.f, 0.f, 0.f, 0.f)); }
 
 // (bx, by) = the workgroup's position in ITS problem's grid: the kernels below pass blockIdx, the merged backward launch an offset one
 // FRZ (with BNG): the BatchNorm above is FROZEN (module in eval mode): cA = gamma * invstd, cB = cC = 0 from the per-channel vectors alone;
@@ -177,62 +208,37 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
     fetch(t0 + 1, regs, regx);
 
     if constexpr (FIN) {
-        double* red = (double*)smem;                     // [2][32][64] in the (still empty) ring
         float* coef = smem + 3 * PLANE + 27 * 64;        // [2][64] behind the filter taps
+        double sx, sxx;
         {
             const int q = tid & 15, rg = tid >> 4;
             double ua[4] = {0, 0, 0, 0}, ub[4] = {0, 0, 0, 0};
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {                // rows beyond bR were read from row bR - 1 and are added as zero
-                const bool ok = rg + 32 * k < a.bR;
-                ua[0] += ok ? fu[k].x : 0.f; ua[1] += ok ? fu[k].y : 0.f; ua[2] += ok ? fu[k].z : 0.f; ua[3] += ok ? fu[k].w : 0.f;
-                ub[0] += ok ? fv[k].x : 0.f; ub[1] += ok ? fv[k].y : 0.f; ub[2] += ok ? fv[k].z : 0.f; ub[3] += ok ? fv[k].w : 0.f;
-            }
+            for (int k = 0; k < 4; ++k) { add4_if(ua, rg + 32 * k < a.bR, fu[k]); add4_if(ub, rg + 32 * k < a.bR, fv[k]); }
             const float* p0 = a.bst0 + c0 + q * 4;
             const float* p1 = a.bst1 + c0 + q * 4;
             for (int r = rg + 128; r < a.bR; r += 32) {  // longer lists than the model's shapes produce
-                const float4 u = *(const float4*)(p0 + (long)r * g.C), v = *(const float4*)(p1 + (long)r * g.C);
-                ua[0] += u.x; ua[1] += u.y; ua[2] += u.z; ua[3] += u.w;
-                ub[0] += v.x; ub[1] += v.y; ub[2] += v.z; ub[3] += v.w;
+                add4(ua, *(const float4*)(p0 + (long)r * g.C));
+                add4(ub, *(const float4*)(p1 + (long)r * g.C));
             }
-#pragma unroll
-            for (int e = 0; e < 4; ++e) { red[(0 * 32 + rg) * 64 + q * 4 + e] = ua[e]; red[(1 * 32 + rg) * 64 + q * 4 + e] = ub[e]; }
+            strip_reduce((double*)smem, ua, ub, true, sx, sxx);      // in the (still empty) ring
         }
-        __syncthreads();
-        double* red2 = red + 2 * 32 * 64;                // [2][4][64]
-        {
-            const int which = tid >> 8, part = (tid >> 6) & 3, ch = tid & 63;
-            double s = 0.0;
-#pragma unroll
-            for (int k = 0; k < 8; ++k) s += red[(which * 32 + part * 8 + k) * 64 + ch];
-            red2[(which * 4 + part) * 64 + ch] = s;
-        }
-        __syncthreads();
         if (tid < 64) {
-            // the arithmetic of bn_finalize_kernel (norm.hip), expression for expression: fp64 sums of the fp32 partial rows are exact,
-            // so scale / shift / mean / invstd and the running statistics are the two-launch path's values
-            const double sx = (red2[(0 * 4 + 0) * 64 + tid] + red2[(0 * 4 + 1) * 64 + tid]) + (red2[(0 * 4 + 2) * 64 + tid] + red2[(0 * 4 + 3) * 64 + tid]);
-            const double sxx = (red2[(1 * 4 + 0) * 64 + tid] + red2[(1 * 4 + 1) * 64 + tid]) + (red2[(1 * 4 + 2) * 64 + tid] + red2[(1 * 4 + 3) * 64 + tid]);
+            // fp64 sums of the fp32 partial rows are exact, so scale / shift / mean / invstd and the running statistics are the values of
+            // the two-launch path (tuber_bn_finalize) whatever the order of the sums
             const int cc = c0 + tid;
-            const float count = a.bcount;
-            const double mean = sx / (double)count;
-            double var = sxx / (double)count - mean * mean;
-            if (var < 0.0) var = 0.0;
-            const float invstd = (float)(1.0 / sqrt(var + (double)a.feps));
-            const float scl = f_gam * invstd;
-            const float shf = f_bet - (float)mean * scl;
-            coef[tid] = scl;
-            coef[64 + tid] = shf;
+            const BnStats s = bn_finalize(sx, sxx, a.bcount, a.feps, f_gam, f_bet);
+            coef[tid] = s.scale;
+            coef[64 + tid] = s.shift;
             if (bx == 0) {
-                a.fscale[cc] = scl;
-                a.fshift[cc] = shf;
-                a.fmean[cc] = (float)mean;
-                a.finvstd[cc] = invstd;
+                a.fscale[cc] = s.scale;
+                a.fshift[cc] = s.shift;
+                a.fmean[cc] = (float)s.mean;
+                a.finvstd[cc] = s.invstd;
                 if (a.frmean) {
-                    const double unbiased = count > 1.f ? var * (double)count / ((double)count - 1.0) : var;
-                    const float m = a.fcum ? (float)(1.0 / (double)(*a.fnbt + 1)) : a.fmom;
-                    a.frmean[cc] = (1.f - m) * f_rm + m * (float)mean;
-                    a.frvar[cc] = (1.f - m) * f_rv + m * (float)unbiased;
+                    const BnRunning u = bn_running_update(s.mean, s.var, a.bcount, a.fcum ? bn_cumulative_factor(*a.fnbt) : a.fmom, f_rm, f_rv);
+                    a.frmean[cc] = u.mean;
+                    a.frvar[cc] = u.var;
                 }
                 if (a.fnbt && !a.fcum && by == 0 && tid == 0) *a.fnbt += 1;
             }
@@ -244,6 +250,8 @@ __device__ __forceinline__ void dwconv_tile_body(const TileArgs& a, const int bx
     }
 
     // ---- BNG: coefficients of the BatchNorm backward above, derived under the latency of the fetches just issued ----
+    // (written out, not through strip_reduce / bn_bwd_coefs of bn_math.h: with the helpers these kernels measured 0.05 - 0.15 us slower at the
+    // layer2 - layer4 shapes; the expressions are those of bn_bwd_coefs, and the tests compare the paths bit for bit)
     if constexpr (BNG) {
         double* red = (double*)smem;                     // [2][32][64] in the (still empty) ring
         float* coef = smem + 3 * PLANE + 27 * 64;        // [3][64] behind the filter taps
@@ -659,6 +667,7 @@ __global__ __launch_bounds__(512) void dwconv_tile_bwd_both_kernel(TileArgs a) {
 
     // ---- coefficients of the BatchNorm backward above, derived under the latency of the fetches just issued (identical arithmetic
     // to dwconv_tile_body<., BNG>: dgamma / dbeta and the coefficients are bit-identical) ----
+    // (written out for the reason given there)
     {
         double* red = (double*)smem;                     // [2][32][64] in the (still empty) ring
         float* coef = smem + 3 * PLANE + 27 * 64;        // [3][64] behind the filter taps

@@ -7,20 +7,22 @@
 //   bn_finalize             -> mean / var / running-stat update / scale = g*invstd, shift = b - mean*scale
 //   consumer prologue       -> relu(x*scale + shift)       (gemm.hip A_BN_RELU, dwconv.hip)
 // Backward mirrors it: partial (sum dz, sum dz*x) -> bn_bwd_finalize -> dx = A*dz + B*x + C.
-#include "common.h"
+#include "bn_math.h"
 
 // ---------------------------------------------------------------------------------------------
 // finalize kernels: one block per 32 channels, 1024 threads = 32 row-groups x 32 channels
 // ---------------------------------------------------------------------------------------------
 // column sums of the partial-statistics rows st0/st1 [R][C] for channels c0..c0+31 (NTH threads): thread = (row group
 // of NTH / 8, channel quad); 16-byte loads, 4 row iterations in flight, double accumulation; the result for channel c0+cl is
-// returned in threads 0..31 (cl = threadIdx.x).  NTH = 256 for the short lists (R <= 128: every list of layer3 / layer4 and every
+// returned in threads 0..31 (cl = threadIdx.x); c0 = blockIdx.x * 32.  NTH = 256 for the short lists (R <= 128: every list of layer3 / layer4 and every
 // first-stage-reduced one): device timestamps showed the 1024-thread workgroups of this tiny kernel starting up to 1.0 us apart
 // (16 waves each to dispatch) for a 2.6 us life -- with 4 waves per workgroup the stagger is a quarter of that.
 template <int NTH>
-__device__ __forceinline__ void bn_partial_sums(const float* __restrict__ st0, const float* __restrict__ st1, int R, int C, int c0,
-                                                double (&red)[2][32][33], double& a_out, double& b_out) {
+__device__ __forceinline__ void bn_partial_sums(const float* __restrict__ st0, const float* __restrict__ st1, int R, int C,
+                                                double& a_out, double& b_out) {
+    __shared__ double red[2][32][33];
     constexpr int RG = NTH / 8, NW = NTH / 64;
+    const int c0 = blockIdx.x * 32;
     const int qd = threadIdx.x & 7, rq = threadIdx.x >> 3;       // 8 quads x RG row groups
     const int cq = c0 + qd * 4;
     double a[4] = {0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
@@ -34,10 +36,7 @@ __device__ __forceinline__ void bn_partial_sums(const float* __restrict__ st0, c
                 y[u] = *(const float4*)(st1 + (long)(r + RG * u) * C + cq);
             }
 #pragma unroll
-            for (int u = 0; u < 4; ++u) {
-                a[0] += x[u].x; a[1] += x[u].y; a[2] += x[u].z; a[3] += x[u].w;
-                b[0] += y[u].x; b[1] += y[u].y; b[2] += y[u].z; b[3] += y[u].w;
-            }
+            for (int u = 0; u < 4; ++u) { add4(a, x[u]); add4(b, y[u]); }
         }
         {   // tail: up to three more rows, issued together
             float4 x[3], y[3];
@@ -50,10 +49,7 @@ __device__ __forceinline__ void bn_partial_sums(const float* __restrict__ st0, c
                 if (!ok) { x[u] = make_float4(0.f, 0.f, 0.f, 0.f); y[u] = make_float4(0.f, 0.f, 0.f, 0.f); }
             }
 #pragma unroll
-            for (int u = 0; u < 3; ++u) {
-                a[0] += x[u].x; a[1] += x[u].y; a[2] += x[u].z; a[3] += x[u].w;
-                b[0] += y[u].x; b[1] += y[u].y; b[2] += y[u].z; b[3] += y[u].w;
-            }
+            for (int u = 0; u < 3; ++u) { add4(a, x[u]); add4(b, y[u]); }
         }
     }
     // RG row groups -> NW (one per wave) via shuffles over the lanes sharing qd (lane bits 3..5), then LDS
@@ -75,6 +71,15 @@ __device__ __forceinline__ void bn_partial_sums(const float* __restrict__ st0, c
     }
 }
 
+// The finalize kernels' prologue: thread -> channel c; fin = the thread loads the channel's per-channel operands (BEFORE the partial-row sweep, so
+// their latency hides behind it).  Behind the sweep the same thread, tested as `rg == 0 && c < C`, receives the column sums and writes the
+// results.  A macro and those two spellings on purpose: with the prologue in an inline function, or the write block under `if (fin)`, the
+// compiler no longer merges the write block with the last LDS read of bn_partial_sums (one more exec region, 13 more instructions).
+#define FINALIZE_LANE(C)                                    \
+    const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5; \
+    const int c = blockIdx.x * 32 + cl;                     \
+    const bool fin = threadIdx.x < 32 && c < C
+
 template <int NTH>
 __global__ __launch_bounds__(NTH) void bn_finalize_kernel(
     const float* __restrict__ st0, const float* __restrict__ st1, int R, int C, float count,
@@ -82,32 +87,23 @@ __global__ __launch_bounds__(NTH) void bn_finalize_kernel(
     float* __restrict__ rmean, float* __restrict__ rvar, long long* __restrict__ nbt,
     float momentum, float eps,
     float* __restrict__ scale, float* __restrict__ shift, float* __restrict__ mean_out, float* __restrict__ invstd_out, int cumulative) {
-    __shared__ double red[2][32][33];
-    const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cl;
-    // per-channel parameters are fetched before the partial-row sweep so their latency hides behind it
-    const bool fin = threadIdx.x < 32 && c < C;
+    FINALIZE_LANE(C);
     const float gam = fin ? gamma[c] : 0.f, bet = fin ? beta[c] : 0.f;
     const float rm0 = (fin && rmean) ? rmean[c] : 0.f, rv0 = (fin && rmean) ? rvar[c] : 0.f;
     double a, b;
-    bn_partial_sums<NTH>(st0, st1, R, C, blockIdx.x * 32, red, a, b);
+    bn_partial_sums<NTH>(st0, st1, R, C, a, b);
     if (rg == 0 && c < C) {
-        const double mean = a / (double)count;
-        double var = b / (double)count - mean * mean;
-        if (var < 0.0) var = 0.0;
-        const float invstd = (float)(1.0 / sqrt(var + (double)eps));
-        const float sc = gam * invstd;
-        scale[c] = sc;
-        shift[c] = bet - (float)mean * sc;
-        mean_out[c] = (float)mean;
-        invstd_out[c] = invstd;
+        const BnStats s = bn_finalize(a, b, count, eps, gam, bet);
+        scale[c] = s.scale;
+        shift[c] = s.shift;
+        mean_out[c] = (float)s.mean;
+        invstd_out[c] = s.invstd;
         if (rmean) {
-            const double unbiased = count > 1.f ? var * (double)count / ((double)count - 1.0) : var;
-            // cumulative average (momentum=None): factor 1 / (n + 1) from the count BEFORE this batch -- nobody writes *nbt in this launch
-            // (tuber_bn_count_advance does, after the forward), so every workgroup reads the same n
-            const float m = cumulative ? (float)(1.0 / (double)(*nbt + 1)) : momentum;
-            rmean[c] = (1.f - m) * rm0 + m * (float)mean;
-            rvar[c] = (1.f - m) * rv0 + m * (float)unbiased;
+            // cumulative average (momentum=None): the count BEFORE this batch -- nobody writes *nbt in this launch (tuber_bn_count_advance
+            // does, after the forward), so every workgroup reads the same n
+            const BnRunning u = bn_running_update(s.mean, s.var, count, cumulative ? bn_cumulative_factor(*nbt) : momentum, rm0, rv0);
+            rmean[c] = u.mean;
+            rvar[c] = u.var;
         }
     }
     if (nbt && !cumulative && blockIdx.x == 0 && threadIdx.x == 0) *nbt += 1;
@@ -124,9 +120,9 @@ __global__ void bn_eval_affine_kernel(const float* __restrict__ gamma, const flo
                                       float* __restrict__ scale, float* __restrict__ shift, int C) {
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= C) return;
-    const float sc = gamma[c] / sqrtf(rvar[c] + eps);
-    scale[c] = sc;
-    shift[c] = beta[c] - rmean[c] * sc;
+    const BnAffine m = bn_eval_affine(gamma[c], beta[c], rmean[c], rvar[c], eps);
+    scale[c] = m.scale;
+    shift[c] = m.shift;
 }
 
 // the same for EVERY BatchNorm of a network in one launch (eval forward: 155 launches of the kernel above were 0.6 ms of a 5.5 ms forward):
@@ -136,14 +132,14 @@ __global__ void bn_eval_affine_multi_kernel(const BnAffineRow* __restrict__ tabl
     const BnAffineRow r = table[blockIdx.y];
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= r.C) return;
-    const float sc = r.gamma[c] / sqrtf(r.rvar[c] + eps);
-    r.scale[c] = sc;
-    r.shift[c] = r.beta[c] - r.rmean[c] * sc;
+    const BnAffine m = bn_eval_affine(r.gamma[c], r.beta[c], r.rmean[c], r.rvar[c], eps);
+    r.scale[c] = m.scale;
+    r.shift[c] = m.shift;
 }
 
 // FROZEN BatchNorm layers (module in eval mode inside a training step): the layer is the constant affine map of the eval path, and its
 // backward is dx = gamma * invstd * dz.  One launch per forward over a device table of the frozen layers only writes everything both
-// passes read: scale / shift (the expressions of bn_eval_affine_kernel, so bit-identical to it), mean = running_mean, invstd, and the
+// passes read: scale / shift (bn_eval_affine, so bit-identical to the eval path), mean = running_mean, invstd, and the
 // backward coefficients cA = gamma * invstd, cB = cC = 0 -- so every backward kernel that TAKES (cA, cB, cC) runs unchanged.
 struct BnFrozenRow { const float* gamma; const float* beta; const float* rmean; const float* rvar; float* scale; float* shift;
                      float* mean; float* invstd; float* cA; float* cB; float* cC; long C; };
@@ -152,12 +148,12 @@ __global__ void bn_frozen_affine_multi_kernel(const BnFrozenRow* __restrict__ ta
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c >= r.C) return;
     const float g = r.gamma[c], mu = r.rmean[c], v = r.rvar[c];
-    const float sc = g / sqrtf(v + eps);
-    r.scale[c] = sc;
-    r.shift[c] = r.beta[c] - mu * sc;
-    // invstd as the train-mode finalisation forms it (fp64, rounded once); scale above is the fp32 expression of the eval kernel, which bit identity
-    // with the eval path needs -- so the backward slope cA = g * inv and the forward slope sc may differ in the last fp32 bit (far below bf16)
-    const float inv = (float)(1.0 / sqrt((double)v + (double)eps));
+    const BnAffine m = bn_eval_affine(g, r.beta[c], mu, v, eps);
+    r.scale[c] = m.scale;
+    r.shift[c] = m.shift;
+    // invstd as the train-mode finalisation forms it (fp64, rounded once); scale above is the fp32 expression of the eval path, which bit identity
+    // with it needs -- so the backward slope cA = g * inv and the forward slope may differ in the last fp32 bit (far below bf16)
+    const float inv = bn_invstd((double)v, eps);
     r.mean[c] = mu;
     r.invstd[c] = inv;
     r.cA[c] = g * inv;
@@ -171,18 +167,15 @@ template <int NTH>
 __global__ __launch_bounds__(NTH) void bn_frozen_param_grads_kernel(
     const float* __restrict__ st0, const float* __restrict__ st1, int R, int C,
     const float* __restrict__ mean, const float* __restrict__ invstd, float* __restrict__ dgamma, float* __restrict__ dbeta) {
-    __shared__ double red[2][32][33];
-    const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cl;
-    const bool fin = threadIdx.x < 32 && c < C;
+    FINALIZE_LANE(C);
     const float mu_f = fin ? mean[c] : 0.f, r_f = fin ? invstd[c] : 0.f;
     const float dg0 = fin ? dgamma[c] : 0.f, db0 = fin ? dbeta[c] : 0.f;
     double a, b;
-    bn_partial_sums<NTH>(st0, st1, R, C, blockIdx.x * 32, red, a, b);
+    bn_partial_sums<NTH>(st0, st1, R, C, a, b);
     if (rg == 0 && c < C) {
-        const double mu = mu_f, r = r_f;
-        dgamma[c] = dg0 + (float)((b - mu * a) * r);
-        dbeta[c] = db0 + (float)a;
+        const BnBwd k = bn_bwd_coefs<true>(a, b, mu_f, r_f, 0.f, 0.f);      // (gamma only enters cA, which is not wanted here)
+        dgamma[c] = dg0 + k.dgamma;
+        dbeta[c] = db0 + k.dbeta;
     }
 }
 
@@ -193,24 +186,19 @@ __global__ __launch_bounds__(NTH) void bn_bwd_finalize_kernel(
     const float* __restrict__ gamma, const float* __restrict__ mean, const float* __restrict__ invstd,
     float* __restrict__ cA, float* __restrict__ cB, float* __restrict__ cC,
     float* __restrict__ dgamma, float* __restrict__ dbeta, int accumulate) {
-    __shared__ double red[2][32][33];
-    const int cl = threadIdx.x & 31, rg = threadIdx.x >> 5;
-    const int c = blockIdx.x * 32 + cl;
-    const bool fin = threadIdx.x < 32 && c < C;
+    FINALIZE_LANE(C);
     const float mu_f = fin ? mean[c] : 0.f, r_f = fin ? invstd[c] : 0.f, g_f = fin ? gamma[c] : 0.f;
     const float dg0 = (fin && dgamma && accumulate) ? dgamma[c] : 0.f, db0 = (fin && dgamma && accumulate) ? dbeta[c] : 0.f;
     double a, b;
-    bn_partial_sums<NTH>(st0, st1, R, C, blockIdx.x * 32, red, a, b);
+    bn_partial_sums<NTH>(st0, st1, R, C, a, b);
     if (rg == 0 && c < C) {
-        const double mu = mu_f, r = r_f, g = g_f;
-        const double sum_dz = a, sum_dz_xhat = (b - mu * a) * r;
-        const double m1 = sum_dz / count, m2 = sum_dz_xhat / count;
-        cA[c] = (float)(g * r);
-        cB[c] = (float)(-g * r * r * m2);
-        cC[c] = (float)(g * r * r * m2 * mu - g * r * m1);
+        const BnBwd k = bn_bwd_coefs(a, b, mu_f, r_f, g_f, count);
+        cA[c] = k.cA;
+        cB[c] = k.cB;
+        cC[c] = k.cC;
         if (dgamma) {
-            dgamma[c] = dg0 + (float)sum_dz_xhat;
-            dbeta[c] = db0 + (float)sum_dz;
+            dgamma[c] = dg0 + k.dgamma;
+            dbeta[c] = db0 + k.dbeta;
         }
     }
 }
@@ -223,56 +211,40 @@ __device__ __forceinline__ void load8f(const float* p, float (&v)[8]) {
     v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 
-// y = relu( c4*s4+h4 + (rs ? res*rs+rh : res) )     [block output; ir_CSN_152.py:84-90]
-__global__ __launch_bounds__(256) void block_out_fwd_kernel(
-    const bf16* __restrict__ c4, const float* __restrict__ s4, const float* __restrict__ h4,
-    const bf16* __restrict__ res, const float* __restrict__ rs, const float* __restrict__ rh,
-    bf16* __restrict__ y, uint8_t* __restrict__ ymask, long M, int C) {
-    const int tpr = C >> 3;
-    const int cg = threadIdx.x % tpr;
-    const long rpp = 256 / tpr;
-    float a4[8], b4[8], ar[8], br[8];
-    load8f(s4 + cg * 8, a4); load8f(h4 + cg * 8, b4);
-    if (rs) { load8f(rs + cg * 8, ar); load8f(rh + cg * 8, br); }
-    for (long row = (long)blockIdx.x * rpp + threadIdx.x / tpr; row < M; row += (long)gridDim.x * rpp) {
-        const long off = row * C + cg * 8;
-        const bf16x8 c = as_bf16x8(*(const uint4*)(c4 + off));
-        const bf16x8 r = as_bf16x8(*(const uint4*)(res + off));
-        bf16x8 o;
-        unsigned bits = 0;
-#pragma unroll
-        for (int e = 0; e < 8; ++e) {
-            float rv = bf2f(r[e]);
-            if (rs) rv = fmaf(rv, ar[e], br[e]);
-            o[e] = f2bf(fmaxf(fmaf(bf2f(c[e]), a4[e], b4[e]) + rv, 0.f));
-            bits |= (bf2f(o[e]) > 0.f ? 1u : 0u) << e;
-        }
-        *(uint4*)(y + off) = as_uint4(o);
-        // ReLU mask of the block output, one bit per element ([M][C / 8] bytes, bit e of byte (m, c / 8) = y[m][c + e] > 0): what the join
-        // backward of this block reads instead of the 16 x larger y (tuber_gemm_nt_join_mask, round 6)
-        if (ymask) ymask[row * tpr + cg] = (uint8_t)bits;
+// the row walk shared by these kernels: thread = channel group cg of row slot `slot`; one pass of the 256 threads covers rpp = 256 / tpr rows
+struct RowWalk {
+    int C, tpr, cg, slot, rpp;
+    __device__ __forceinline__ explicit RowWalk(int C_) : C(C_), tpr(C_ >> 3), cg(threadIdx.x % tpr), slot(threadIdx.x / tpr), rpp(256 / tpr) {}
+    // f(row, offset of this thread's 8 elements) for the rows first + slot, first + slot + step, ... below end
+    template <typename F>
+    __device__ __forceinline__ void rows(long first, long end, long step, F f) const {
+        for (long row = first + slot; row < end; row += step) f(row, row * C + cg * 8);
     }
-}
+    // all M rows, passes dealt round-robin over the grid
+    template <typename F>
+    __device__ __forceinline__ void grid_rows(long M, F f) const { rows((long)blockIdx.x * rpp, M, (long)gridDim.x * rpp, f); }
+};
 
-// the same join for the EVAL precision mode (round 6): the residual stream stays fp32 -- res32 = the previous block's fp32 output (identity
-// blocks) or the BatchNorm of the bf16 projection-shortcut conv output (res / rs / rh) -- and the block output is written twice: y32 (fp32,
-// the next block's residual input) and y (bf16, the operand of the next block's conv1 / projection GEMMs).  That is where the bf16-rounded
-// execution of the oracle (tests/parity_util.py) rounds: conv operands and results, never the stream between the blocks.
-__global__ __launch_bounds__(256) void block_out_fwd_f32_kernel(
+// y = relu( c4*s4+h4 + (rs ? res*rs+rh : res) )     [block output; ir_CSN_152.py:84-90]
+// F32 = false: also the ReLU mask of the block output when ymask is given, one bit per element ([M][C / 8] bytes, bit e of byte (m, c / 8) =
+// y[m][c + e] > 0): what the join backward of this block reads instead of the 16 x larger y (tuber_gemm_nt_join_mask, round 6).
+// F32 = true, the EVAL precision mode (round 6): the residual stream stays fp32 -- res32 = the previous block's fp32 output (identity
+// blocks) or, when NULL, the BatchNorm of the bf16 projection-shortcut conv output (res / rs / rh) -- and the block output is written twice:
+// y32 (fp32, the next block's residual input) and y (bf16, the operand of the next block's conv1 / projection GEMMs).  That is where the
+// bf16-rounded execution of the oracle (tests/parity_util.py) rounds: conv operands and results, never the stream between the blocks.
+template <bool F32>
+__device__ __forceinline__ void block_out_fwd_body(
     const bf16* __restrict__ c4, const float* __restrict__ s4, const float* __restrict__ h4,
     const bf16* __restrict__ res, const float* __restrict__ rs, const float* __restrict__ rh, const float* __restrict__ res32,
-    bf16* __restrict__ y, float* __restrict__ y32, long M, int C) {
-    const int tpr = C >> 3;
-    const int cg = threadIdx.x % tpr;
-    const long rpp = 256 / tpr;
+    bf16* __restrict__ y, uint8_t* __restrict__ ymask, float* __restrict__ y32, long M, int C) {
+    const RowWalk w(C);
     float a4[8], b4[8], ar[8], br[8];
-    load8f(s4 + cg * 8, a4); load8f(h4 + cg * 8, b4);
-    if (rs) { load8f(rs + cg * 8, ar); load8f(rh + cg * 8, br); }
-    for (long row = (long)blockIdx.x * rpp + threadIdx.x / tpr; row < M; row += (long)gridDim.x * rpp) {
-        const long off = row * C + cg * 8;
+    load8f(s4 + w.cg * 8, a4); load8f(h4 + w.cg * 8, b4);
+    if (rs) { load8f(rs + w.cg * 8, ar); load8f(rh + w.cg * 8, br); }
+    w.grid_rows(M, [&](long row, long off) {
         const bf16x8 c = as_bf16x8(*(const uint4*)(c4 + off));
         float rv[8];
-        if (res32) {
+        if (F32 && res32) {
             load8f(res32 + off, rv);
         } else {
             const bf16x8 r = as_bf16x8(*(const uint4*)(res + off));
@@ -281,15 +253,33 @@ __global__ __launch_bounds__(256) void block_out_fwd_f32_kernel(
         }
         bf16x8 o;
         float of[8];
+        unsigned bits = 0;
 #pragma unroll
         for (int e = 0; e < 8; ++e) {
             of[e] = fmaxf(fmaf(bf2f(c[e]), a4[e], b4[e]) + rv[e], 0.f);
             o[e] = f2bf(of[e]);
+            bits |= (bf2f(o[e]) > 0.f ? 1u : 0u) << e;
         }
         *(uint4*)(y + off) = as_uint4(o);
-        ((float4*)(y32 + off))[0] = make_float4(of[0], of[1], of[2], of[3]);
-        ((float4*)(y32 + off))[1] = make_float4(of[4], of[5], of[6], of[7]);
-    }
+        if constexpr (F32) {
+            ((float4*)(y32 + off))[0] = make_float4(of[0], of[1], of[2], of[3]);
+            ((float4*)(y32 + off))[1] = make_float4(of[4], of[5], of[6], of[7]);
+        } else if (ymask) {
+            ymask[row * w.tpr + w.cg] = (uint8_t)bits;
+        }
+    });
+}
+__global__ __launch_bounds__(256) void block_out_fwd_kernel(
+    const bf16* __restrict__ c4, const float* __restrict__ s4, const float* __restrict__ h4,
+    const bf16* __restrict__ res, const float* __restrict__ rs, const float* __restrict__ rh,
+    bf16* __restrict__ y, uint8_t* __restrict__ ymask, long M, int C) {
+    block_out_fwd_body<false>(c4, s4, h4, res, rs, rh, nullptr, y, ymask, nullptr, M, C);
+}
+__global__ __launch_bounds__(256) void block_out_fwd_f32_kernel(
+    const bf16* __restrict__ c4, const float* __restrict__ s4, const float* __restrict__ h4,
+    const bf16* __restrict__ res, const float* __restrict__ rs, const float* __restrict__ rh, const float* __restrict__ res32,
+    bf16* __restrict__ y, float* __restrict__ y32, long M, int C) {
+    block_out_fwd_body<true>(c4, s4, h4, res, rs, rh, res32, y, nullptr, y32, M, C);
 }
 
 // dz = dy * [y > 0]  (bf16 out) ; partial stats per block: sum dz, sum dz*c4, (sum dz*cds)
@@ -298,16 +288,13 @@ __global__ __launch_bounds__(256) void block_out_bwd_kernel(
     bf16* __restrict__ dz, float* __restrict__ st_dz, float* __restrict__ st_c4, float* __restrict__ st_ds,
     long M, int C, long rows_per_block) {
     __shared__ float red[3][256][8 + 1];
-    const int tpr = C >> 3;
-    const int cg = threadIdx.x % tpr, rs = threadIdx.x / tpr;
-    const int rpp = 256 / tpr;
+    const RowWalk w(C);
     float s0[8], s1[8], s2[8];
 #pragma unroll
     for (int e = 0; e < 8; ++e) { s0[e] = 0.f; s1[e] = 0.f; s2[e] = 0.f; }
     const long r0 = (long)blockIdx.x * rows_per_block;
     const long r1 = min(M, r0 + rows_per_block);
-    for (long row = r0 + rs; row < r1; row += rpp) {
-        const long off = row * C + cg * 8;
+    w.rows(r0, r1, w.rpp, [&](long, long off) {
         const bf16x8 g = as_bf16x8(*(const uint4*)(dy + off));
         const bf16x8 yy = as_bf16x8(*(const uint4*)(y + off));
         const bf16x8 c = as_bf16x8(*(const uint4*)(c4 + off));
@@ -322,7 +309,7 @@ __global__ __launch_bounds__(256) void block_out_bwd_kernel(
             if (cds) s2[e] += v * bf2f(d[e]);
         }
         *(uint4*)(dz + off) = as_uint4(o);
-    }
+    });
 #pragma unroll
     for (int e = 0; e < 8; ++e) { red[0][threadIdx.x][e] = s0[e]; red[1][threadIdx.x][e] = s1[e]; red[2][threadIdx.x][e] = s2[e]; }
     __syncthreads();
@@ -330,7 +317,7 @@ __global__ __launch_bounds__(256) void block_out_bwd_kernel(
     for (int ch = threadIdx.x; ch < C; ch += 256) {
         const int g8 = ch >> 3, e = ch & 7;
         float a = 0.f, b = 0.f, c = 0.f;
-        for (int s = 0; s < rpp; ++s) { const int t = s * tpr + g8; a += red[0][t][e]; b += red[1][t][e]; c += red[2][t][e]; }
+        for (int s = 0; s < w.rpp; ++s) { const int t = s * w.tpr + g8; a += red[0][t][e]; b += red[1][t][e]; c += red[2][t][e]; }
         st_dz[(long)blockIdx.x * C + ch] = a;
         st_c4[(long)blockIdx.x * C + ch] = b;
         if (st_ds) st_ds[(long)blockIdx.x * C + ch] = c;
@@ -341,20 +328,17 @@ __global__ __launch_bounds__(256) void block_out_bwd_kernel(
 __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(
     const bf16* __restrict__ dz, const bf16* __restrict__ x, const float* __restrict__ cA, const float* __restrict__ cB,
     const float* __restrict__ cC, bf16* __restrict__ dx, long M, int C) {
-    const int tpr = C >> 3;
-    const int cg = threadIdx.x % tpr;
-    const long rpp = 256 / tpr;
+    const RowWalk w(C);
     float a[8], b[8], c[8];
-    load8f(cA + cg * 8, a); load8f(cB + cg * 8, b); load8f(cC + cg * 8, c);
-    for (long row = (long)blockIdx.x * rpp + threadIdx.x / tpr; row < M; row += (long)gridDim.x * rpp) {
-        const long off = row * C + cg * 8;
+    load8f(cA + w.cg * 8, a); load8f(cB + w.cg * 8, b); load8f(cC + w.cg * 8, c);
+    w.grid_rows(M, [&](long, long off) {
         const bf16x8 d = as_bf16x8(*(const uint4*)(dz + off));
         const bf16x8 xx = as_bf16x8(*(const uint4*)(x + off));
         bf16x8 o;
 #pragma unroll
         for (int e = 0; e < 8; ++e) o[e] = f2bf(fmaf(a[e], bf2f(d[e]), fmaf(b[e], bf2f(xx[e]), c[e])));
         *(uint4*)(dx + off) = as_uint4(o);
-    }
+    });
 }
 
 
@@ -409,15 +393,11 @@ __global__ __launch_bounds__(256) void bn_bwd_fa_kernel(
 #pragma unroll
             for (int k = 0; k < 4; ++k) { u[k] = *(const float4*)(p0 + (long)(r + 8 * k) * C); v[k] = *(const float4*)(p1 + (long)(r + 8 * k) * C); }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                a[0] += u[k].x; a[1] += u[k].y; a[2] += u[k].z; a[3] += u[k].w;
-                b[0] += v[k].x; b[1] += v[k].y; b[2] += v[k].z; b[3] += v[k].w;
-            }
+            for (int k = 0; k < 4; ++k) { add4(a, u[k]); add4(b, v[k]); }
         }
         for (; r < R; r += 8) {
-            const float4 u = *(const float4*)(p0 + (long)r * C), v = *(const float4*)(p1 + (long)r * C);
-            a[0] += u.x; a[1] += u.y; a[2] += u.z; a[3] += u.w;
-            b[0] += v.x; b[1] += v.y; b[2] += v.z; b[3] += v.w;
+            add4(a, *(const float4*)(p0 + (long)r * C));
+            add4(b, *(const float4*)(p1 + (long)r * C));
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) { red[0][rg][q * 4 + e] = a[e]; red[1][rg][q * 4 + e] = b[e]; }
@@ -430,17 +410,12 @@ __global__ __launch_bounds__(256) void bn_bwd_fa_kernel(
             for (int k = 0; k < 8; ++k) { a += red[0][k][tid]; b += red[1][k][tid]; }
         }
         const int c = c0 + tid;
-        const double mu = mean[c], rr = invstd[c], g = gamma[c];
-        const double sum_dz = a, sum_dz_xhat = (b - mu * a) * rr;
-        coef[0][tid] = (float)(g * rr);
-        if constexpr (!FRZ) {
-            const double m1 = sum_dz / count, m2 = sum_dz_xhat / count;
-            coef[1][tid] = (float)(-g * rr * rr * m2);
-            coef[2][tid] = (float)(g * rr * rr * m2 * mu - g * rr * m1);
-        }
+        const BnBwd k = bn_bwd_coefs<FRZ>(a, b, mean[c], invstd[c], gamma[c], count);
+        coef[0][tid] = k.cA;
+        if constexpr (!FRZ) { coef[1][tid] = k.cB; coef[2][tid] = k.cC; }
         if (blockIdx.x == 0 && dgamma) {
-            dgamma[c] += (float)sum_dz_xhat;
-            dbeta[c] += (float)sum_dz;
+            dgamma[c] += k.dgamma;
+            dbeta[c] += k.dbeta;
         }
     }
     __syncthreads();
@@ -469,11 +444,61 @@ __global__ __launch_bounds__(256) void bn_bwd_fa_kernel(
     }
 }
 
+// the instantiation of kr rows per thread (fa_rows_per_thread)
+template <bool FRZ>
+static void fa_launch(int kr, const float* st0, const float* st1, int R, int C, float count, const float* gamma, const float* mean, const float* invstd,
+                      float* dgamma, float* dbeta, const void* dz, const void* x, void* dx, long M, hipStream_t stream) {
+#define FA_LAUNCH(KR) hipLaunchKernelGGL((bn_bwd_fa_kernel<KR, FRZ>), dim3(ceil_div(M, 16L * KR), C / FA_CS), dim3(256), 0, stream, st0, st1, R, C, \
+                                         count, gamma, mean, invstd, dgamma, dbeta, (const bf16*)dz, (const bf16*)x, (bf16*)dx, M)
+    if (kr == 4) FA_LAUNCH(4);
+    else if (kr == 11) FA_LAUNCH(11);
+    else FA_LAUNCH(8);
+#undef FA_LAUNCH
+}
+
 // ---------------------------------------------------------------------------------------------
 // LayerNorm(x + res) over the last dim E (256 or 2048), eps 1e-5, one wave per row.
 // reference: nn.LayerNorm in models/transformer/transformer.py:163-167,229-247 (post-norm).
 // ---------------------------------------------------------------------------------------------
-template <int EPL>   // elements per lane = E / 64 (4 for E=256, 32 for E=2048)
+// mean and rstd of the row whose elements the wave's lanes hold in v (EPL = elements per lane = E / 64: 4 for E=256, 32 for E=2048)
+template <int EPL>
+__device__ __forceinline__ void ln_row_stats(const float (&v)[EPL], float eps, float& mean, float& rstd) {
+    constexpr int E = EPL * 64;
+    float s = 0.f;
+#pragma unroll
+    for (int i = 0; i < EPL; ++i) s += v[i];
+    mean = wave_sum(s) * (1.f / E);
+    float q = 0.f;
+#pragma unroll
+    for (int i = 0; i < EPL; ++i) { const float d = v[i] - mean; q += d * d; }
+    rstd = rsqrtf(wave_sum(q) * (1.f / E) + eps);
+}
+// y = xhat * gamma + beta of that row as bf16 (yrow) and, where the pointer is not NULL, xhat as bf16 (xhat_row) and y as fp32 (y32_row)
+template <int EPL>
+__device__ __forceinline__ void ln_apply_store(const float (&v)[EPL], float mean, float rstd, const float* __restrict__ gamma,
+                                               const float* __restrict__ beta, int lane, bf16* __restrict__ yrow, bf16* __restrict__ xhat_row,
+                                               float* __restrict__ y32_row) {
+#pragma unroll
+    for (int i = 0; i < EPL / 4; ++i) {
+        const int col = (i * 64 + lane) * 4;
+        const float4 g = *(const float4*)(gamma + col), b = *(const float4*)(beta + col);
+        const float gg[4] = {g.x, g.y, g.z, g.w}, bb[4] = {b.x, b.y, b.z, b.w};
+        bf16x4 o, xh;
+        float of[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const float h = (v[i * 4 + e] - mean) * rstd;
+            xh[e] = f2bf(h);
+            of[e] = fmaf(h, gg[e], bb[e]);
+            o[e] = f2bf(of[e]);
+        }
+        *(uint2*)(yrow + col) = as_uint2(o);
+        if (xhat_row) *(uint2*)(xhat_row + col) = as_uint2(xh);
+        if (y32_row) *(float4*)(y32_row + col) = make_float4(of[0], of[1], of[2], of[3]);
+    }
+}
+
+template <int EPL>
 __global__ __launch_bounds__(256) void layernorm_fwd_kernel(
     const bf16* __restrict__ x, const bf16* __restrict__ res, const float* __restrict__ gamma, const float* __restrict__ beta,
     bf16* __restrict__ y, long ldy, bf16* __restrict__ xhat_out, float* __restrict__ rstd_out, int M, float eps,
@@ -500,29 +525,9 @@ __global__ __launch_bounds__(256) void layernorm_fwd_kernel(
             v[i * 4 + e] = xv + (res ? bf2f(r[e]) : 0.f);
         }
     }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) s += v[i];
-    const float mean = wave_sum(s) * (1.f / E);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) { const float d = v[i] - mean; q += d * d; }
-    const float rstd = rsqrtf(wave_sum(q) * (1.f / E) + eps);
-#pragma unroll
-    for (int i = 0; i < EPL / 4; ++i) {
-        const int col = (i * 64 + lane) * 4;
-        const float4 g = *(const float4*)(gamma + col), b = *(const float4*)(beta + col);
-        const float gg[4] = {g.x, g.y, g.z, g.w}, bb[4] = {b.x, b.y, b.z, b.w};
-        bf16x4 o, xh;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float h = (v[i * 4 + e] - mean) * rstd;
-            xh[e] = f2bf(h);
-            o[e] = f2bf(fmaf(h, gg[e], bb[e]));
-        }
-        *(uint2*)(y + (long)row * ldy + col) = as_uint2(o);
-        if (xhat_out) *(uint2*)(xhat_out + base + col) = as_uint2(xh);
-    }
+    float mean, rstd;
+    ln_row_stats<EPL>(v, eps, mean, rstd);
+    ln_apply_store<EPL>(v, mean, rstd, gamma, beta, lane, y + (long)row * ldy, xhat_out ? xhat_out + base : nullptr, nullptr);
     if (rstd_out && lane == 0) rstd_out[row] = rstd;
 }
 
@@ -550,29 +555,9 @@ __global__ __launch_bounds__(256) void layernorm_fwd_f32_kernel(
 #pragma unroll
         for (int e = 0; e < 4; ++e) v[i * 4 + e] = xv[e] + rv[e];
     }
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) s += v[i];
-    const float mean = wave_sum(s) * (1.f / E);
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < EPL; ++i) { const float d = v[i] - mean; q += d * d; }
-    const float rstd = rsqrtf(wave_sum(q) * (1.f / E) + eps);
-#pragma unroll
-    for (int i = 0; i < EPL / 4; ++i) {
-        const int col = (i * 64 + lane) * 4;
-        const float4 g = *(const float4*)(gamma + col), b = *(const float4*)(beta + col);
-        const float gg[4] = {g.x, g.y, g.z, g.w}, bb[4] = {b.x, b.y, b.z, b.w};
-        bf16x4 o;
-        float of[4];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            of[e] = fmaf((v[i * 4 + e] - mean) * rstd, gg[e], bb[e]);
-            o[e] = f2bf(of[e]);
-        }
-        *(uint2*)(y + (long)row * ldy + col) = as_uint2(o);
-        if (y32) *(float4*)(y32 + base + col) = make_float4(of[0], of[1], of[2], of[3]);
-    }
+    float mean, rstd;
+    ln_row_stats<EPL>(v, eps, mean, rstd);
+    ln_apply_store<EPL>(v, mean, rstd, gamma, beta, lane, y + (long)row * ldy, nullptr, y32 ? y32 + base : nullptr);
 }
 
 // dx = rstd * (g*dy - mean(g*dy) - xhat*mean(g*dy*xhat)); partial dgamma = sum dy*xhat, dbeta = sum dy
@@ -799,9 +784,8 @@ __global__ __launch_bounds__(256) void stat_rows_reduce_kernel(const float* __re
     float a[4] = {0.f, 0.f, 0.f, 0.f}, b[4] = {0.f, 0.f, 0.f, 0.f};
     if (cq < C) {
         for (int r = r0 + rl; r < r1; r += 32) {
-            const float4 x = *(const float4*)(st0 + (long)r * C + cq), y = *(const float4*)(st1 + (long)r * C + cq);
-            a[0] += x.x; a[1] += x.y; a[2] += x.z; a[3] += x.w;
-            b[0] += y.x; b[1] += y.y; b[2] += y.z; b[3] += y.w;
+            add4(a, *(const float4*)(st0 + (long)r * C + cq));
+            add4(b, *(const float4*)(st1 + (long)r * C + cq));
         }
     }
 #pragma unroll
@@ -815,6 +799,22 @@ __global__ __launch_bounds__(256) void stat_rows_reduce_kernel(const float* __re
         const int c = blockIdx.x * 32 + cl;
         if (c < C) (which ? o1 : o0)[(long)blockIdx.y * C + c] = v;
     }
+}
+
+// a finalize kernel over the partial rows st0 / st1 [R][C]: one workgroup per 32 channels, of 256 threads for the short lists and 1024 otherwise
+// (bn_partial_sums); k256 / k1024 = the kernel's two instantiations, args = its parameters behind (st0, st1, R, C)
+template <typename... P, typename... A>
+static void finalize_launch(void (*k256)(P...), void (*k1024)(P...), const float* st0, const float* st1, int R, int C, hipStream_t stream, A... args) {
+    if (R <= 128) hipLaunchKernelGGL(k256, dim3(ceil_div(C, 32)), dim3(256), 0, stream, st0, st1, R, C, args...);
+    else hipLaunchKernelGGL(k1024, dim3(ceil_div(C, 32)), dim3(1024), 0, stream, st0, st1, R, C, args...);
+}
+// a LayerNorm kernel in the instantiation of the row length E (k4: E = 256, k32: E = 2048); false = no kernel for this E, nothing launched
+template <typename... P, typename... A>
+static bool ln_launch(void (*k4)(P...), void (*k32)(P...), int E, dim3 grid, hipStream_t stream, A... args) {
+    if (E == 256) hipLaunchKernelGGL(k4, grid, dim3(256), 0, stream, args...);
+    else if (E == 2048) hipLaunchKernelGGL(k32, grid, dim3(256), 0, stream, args...);
+    else return false;
+    return true;
 }
 
 extern "C" {
@@ -836,12 +836,8 @@ static int bn_finalize_launch(const float* st0, const float* st1, int R, int C, 
                               float* running_mean, float* running_var, long long* num_batches_tracked, float momentum, float eps,
                               float* scale, float* shift, float* mean, float* invstd, int cumulative, hipStream_t stream) {
     if (R <= 0 || C <= 0) return TUBER_EINVAL;
-    if (R <= 128)
-        hipLaunchKernelGGL(bn_finalize_kernel<256>, dim3(ceil_div(C, 32)), dim3(256), 0, stream, st0, st1, R, C, count, gamma, beta,
-                           running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift, mean, invstd, cumulative);
-    else
-        hipLaunchKernelGGL(bn_finalize_kernel<1024>, dim3(ceil_div(C, 32)), dim3(1024), 0, stream, st0, st1, R, C, count, gamma, beta,
-                           running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift, mean, invstd, cumulative);
+    finalize_launch(bn_finalize_kernel<256>, bn_finalize_kernel<1024>, st0, st1, R, C, stream, count, gamma, beta, running_mean, running_var, num_batches_tracked, momentum, eps, scale, shift, mean,
+                    invstd, cumulative);
     TUBER_RETURN_LAUNCH();
 }
 
@@ -898,12 +894,7 @@ int tuber_bn_frozen_affine_multi(const void* table, int n, int cmax, float eps, 
 int tuber_bn_frozen_param_grads(const float* st0, const float* st1, int R, int C, const float* mean, const float* invstd,
                                 float* dgamma, float* dbeta, hipStream_t stream) {
     if (R <= 0 || C <= 0 || (C & 3) || !st0 || !st1 || !mean || !invstd || !dgamma || !dbeta) return TUBER_EINVAL;
-    if (R <= 128)
-        hipLaunchKernelGGL(bn_frozen_param_grads_kernel<256>, dim3(ceil_div(C, 32)), dim3(256), 0, stream, st0, st1, R, C, mean, invstd,
-                           dgamma, dbeta);
-    else
-        hipLaunchKernelGGL(bn_frozen_param_grads_kernel<1024>, dim3(ceil_div(C, 32)), dim3(1024), 0, stream, st0, st1, R, C, mean, invstd,
-                           dgamma, dbeta);
+    finalize_launch(bn_frozen_param_grads_kernel<256>, bn_frozen_param_grads_kernel<1024>, st0, st1, R, C, stream, mean, invstd, dgamma, dbeta);
     TUBER_RETURN_LAUNCH();
 }
 
@@ -911,12 +902,8 @@ int tuber_bn_bwd_finalize(const float* st0, const float* st1, int R, int C, floa
                           const float* invstd, float* cA, float* cB, float* cC, float* dgamma, float* dbeta, int accumulate,
                           hipStream_t stream) {
     if (R <= 0 || C <= 0) return TUBER_EINVAL;
-    if (R <= 128)
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel<256>, dim3(ceil_div(C, 32)), dim3(256), 0, stream, st0, st1, R, C, count, gamma, mean,
-                           invstd, cA, cB, cC, dgamma, dbeta, accumulate);
-    else
-        hipLaunchKernelGGL(bn_bwd_finalize_kernel<1024>, dim3(ceil_div(C, 32)), dim3(1024), 0, stream, st0, st1, R, C, count, gamma, mean,
-                           invstd, cA, cB, cC, dgamma, dbeta, accumulate);
+    finalize_launch(bn_bwd_finalize_kernel<256>, bn_bwd_finalize_kernel<1024>, st0, st1, R, C, stream, count, gamma, mean, invstd, cA, cB, cC, dgamma,
+                    dbeta, accumulate);
     TUBER_RETURN_LAUNCH();
 }
 
@@ -988,18 +975,13 @@ static int fa_rows_per_thread(long M, int C) {
 }
 int tuber_bn_bwd_fa_rows(long M, int C) { return 16 * fa_rows_per_thread(M, C); }
 static int g_fa_rows_forced = 0;     // test hook: rows per thread forced (0 = heuristic), so the kernel test covers every instantiation at every shape
+static int fa_rows_chosen(long M, int C) { return g_fa_rows_forced ? g_fa_rows_forced : fa_rows_per_thread(M, C); }
 int tuber_bn_bwd_fa_rows_set(int kr) { g_fa_rows_forced = kr; return 0; }
 int tuber_bn_bwd_fa(const float* st0, const float* st1, int R, int C, float count, const float* gamma, const float* mean,
                     const float* invstd, float* dgamma, float* dbeta, const void* dz, const void* x, void* dx, long M,
                     hipStream_t stream) {
     if (R <= 0 || R > 128 || C <= 0 || (C % FA_CS) || M <= 0) return TUBER_EINVAL;
-    const int kr = g_fa_rows_forced ? g_fa_rows_forced : fa_rows_per_thread(M, C);
-#define FA_LAUNCH(KR) hipLaunchKernelGGL(bn_bwd_fa_kernel<KR>, dim3(ceil_div(M, 16L * KR), C / FA_CS), dim3(256), 0, stream, st0, st1, R, C, \
-                                         count, gamma, mean, invstd, dgamma, dbeta, (const bf16*)dz, (const bf16*)x, (bf16*)dx, M)
-    if (kr == 4) FA_LAUNCH(4);
-    else if (kr == 11) FA_LAUNCH(11);
-    else FA_LAUNCH(8);
-#undef FA_LAUNCH
+    fa_launch<false>(fa_rows_chosen(M, C), st0, st1, R, C, count, gamma, mean, invstd, dgamma, dbeta, dz, x, dx, M, stream);
     TUBER_RETURN_LAUNCH();
 }
 
@@ -1009,13 +991,7 @@ int tuber_bn_bwd_fa_frozen(const float* st0, const float* st1, int R, int C, con
                            float* dgamma, float* dbeta, const void* dz, void* dx, long M, hipStream_t stream) {
     if (C <= 0 || (C % FA_CS) || M <= 0 || !gamma || !mean || !invstd || (dgamma == nullptr) != (dbeta == nullptr)) return TUBER_EINVAL;
     if (dgamma && (R <= 0 || R > 128 || !st0 || !st1)) return TUBER_EINVAL;
-    const int kr = g_fa_rows_forced ? g_fa_rows_forced : fa_rows_per_thread(M, C);
-#define FA_LAUNCH(KR) hipLaunchKernelGGL((bn_bwd_fa_kernel<KR, true>), dim3(ceil_div(M, 16L * KR), C / FA_CS), dim3(256), 0, stream, st0, st1, R, C, \
-                                         0.f, gamma, mean, invstd, dgamma, dbeta, (const bf16*)dz, (const bf16*)nullptr, (bf16*)dx, M)
-    if (kr == 4) FA_LAUNCH(4);
-    else if (kr == 11) FA_LAUNCH(11);
-    else FA_LAUNCH(8);
-#undef FA_LAUNCH
+    fa_launch<true>(fa_rows_chosen(M, C), st0, st1, R, C, 0.f, gamma, mean, invstd, dgamma, dbeta, dz, nullptr, dx, M, stream);
     TUBER_RETURN_LAUNCH();
 }
 
@@ -1032,15 +1008,11 @@ int tuber_bn_bwd_apply(const void* dz, const void* x, const float* cA, const flo
 int tuber_layernorm_fwd(const void* x, const void* res, const float* gamma, const float* beta, void* y, long ldy, void* xhat, float* rstd,
                         int M, int E, float eps, float p, const void* seed_ptr, unsigned long long salt, hipStream_t stream) {
     if (ldy < E || (ldy & 3) || p < 0.f || p >= 1.f) return TUBER_EINVAL;
-    dim3 grid(ceil_div(M, 4)), block(256);
     const uint32_t th = (uint32_t)((double)p * 4294967296.0);
     const float ik = dropout_inv_keep(p);
-#define LNF(EPL) hipLaunchKernelGGL(layernorm_fwd_kernel<EPL>, grid, block, 0, stream, (const bf16*)x, (const bf16*)res, gamma, beta, \
-                                    (bf16*)y, ldy, (bf16*)xhat, rstd, M, eps, th, ik, (const uint64_t*)seed_ptr, (uint64_t)salt)
-    if (E == 256) LNF(4);
-    else if (E == 2048) LNF(32);
-    else return TUBER_EINVAL;
-#undef LNF
+    if (!ln_launch(layernorm_fwd_kernel<4>, layernorm_fwd_kernel<32>, E, dim3(ceil_div(M, 4)), stream, (const bf16*)x, (const bf16*)res, gamma, beta,
+                   (bf16*)y, ldy, (bf16*)xhat, rstd, M, eps, th, ik, (const uint64_t*)seed_ptr, (uint64_t)salt))
+        return TUBER_EINVAL;
     TUBER_RETURN_LAUNCH();
 }
 
@@ -1049,13 +1021,9 @@ int tuber_layernorm_fwd(const void* x, const void* res, const float* gamma, cons
 int tuber_layernorm_fwd_f32(const void* x, const float* x32, const void* res, const float* res32, const float* gamma, const float* beta,
                             void* y, long ldy, float* y32, int M, int E, float eps, hipStream_t stream) {
     if (ldy < E || (ldy & 3) || (!x && !x32) || !y) return TUBER_EINVAL;
-    dim3 grid(ceil_div(M, 4)), block(256);
-#define LNF(EPL) hipLaunchKernelGGL(layernorm_fwd_f32_kernel<EPL>, grid, block, 0, stream, (const bf16*)x, x32, (const bf16*)res, res32, gamma, beta, \
-                                    (bf16*)y, ldy, y32, M, eps)
-    if (E == 256) LNF(4);
-    else if (E == 2048) LNF(32);
-    else return TUBER_EINVAL;
-#undef LNF
+    if (!ln_launch(layernorm_fwd_f32_kernel<4>, layernorm_fwd_f32_kernel<32>, E, dim3(ceil_div(M, 4)), stream, (const bf16*)x, x32, (const bf16*)res,
+                   res32, gamma, beta, (bf16*)y, ldy, y32, M, eps))
+        return TUBER_EINVAL;
     TUBER_RETURN_LAUNCH();
 }
 
@@ -1072,15 +1040,11 @@ int tuber_layernorm_bwd(const void* dy, long lddy, const void* xhat, const float
     const int nb = tuber_layernorm_bwd_blocks(M);
     int rpb = ceil_div(M, nb);
     rpb = ceil_div(rpb, 4) * 4;
-    dim3 grid(nb), block(256);
     const uint32_t th = (uint32_t)((double)p * 4294967296.0);
     const float ik = dropout_inv_keep(p);
-#define LNB(EPL) hipLaunchKernelGGL(layernorm_bwd_kernel<EPL>, grid, block, 0, stream, (const bf16*)dy, lddy, (const bf16*)xhat, rstd, gamma, \
-                                    (bf16*)dx, (bf16*)dxd, partial, M, rpb, th, ik, (const uint64_t*)seed_ptr, (uint64_t)salt)
-    if (E == 256) LNB(4);
-    else if (E == 2048) LNB(32);
-    else return TUBER_EINVAL;
-#undef LNB
+    if (!ln_launch(layernorm_bwd_kernel<4>, layernorm_bwd_kernel<32>, E, dim3(nb), stream, (const bf16*)dy, lddy, (const bf16*)xhat, rstd, gamma,
+                   (bf16*)dx, (bf16*)dxd, partial, M, rpb, th, ik, (const uint64_t*)seed_ptr, (uint64_t)salt))
+        return TUBER_EINVAL;
     if (accumulate == 2) {            // the caller reduces partial [nb][2E] later (tuber_multi_reduce)
     } else if (dbeta == dgamma + E) { // weight and bias adjacent in the flat gradient buffer: one reduction over [nb][2E]
         hipLaunchKernelGGL(reduce_rows_kernel, dim3(ceil_div(2 * E, 32)), dim3(1024), 0, stream, partial, dgamma, nb, 2 * E, accumulate, (long)2 * E);
